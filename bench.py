@@ -17,11 +17,18 @@ the timed region starts; the final latents stay on the device (VAE decode is out
 slot (static buffers, captured step, packed K/V, library workspace - DESIGN.md section 6), pulling the next generation
 from a shared queue.  Every generation is still ONE batch-1 image with its own inputs and results equal to the
 one-at-a-time results bit for bit; what changes is that the GPU interleaves two of them.  `value` / `ms_per_step` are
-total images / wall time (throughput); `one_generation_at_a_time` on the same line repeats the K generations with one in
-flight (`--in-flight 1` makes that the headline): its ms_per_generation is the latency of one image.  Leg order: one at a
-time, rooflines, cpu_baseline, then the generations in flight behind a stall watchdog (`--stall-seconds`).
+total images / wall time (throughput); `--in-flight 1` makes one generation at a time the headline.
 
-Extra objects on the JSON line:
+A plain run does only what the headline needs: set-up, `--warmup` generations per slot (which capture the slots' steps under
+the headline's launch rules), the K timed generations behind a stall watchdog (`--stall-seconds`), the outputs if
+`--dump-outputs DIR` is given, and the JSON line.  `--full` adds every other leg and check below; its leg order is: one at
+a time, rooflines, cpu_baseline, then the generations in flight.
+
+`--dump-outputs DIR`: after the timed generations, the final latents of the last timed generation (the pixels with
+`--decode`) are written as DIR/latents.npy (DIR/images.npy) in float32; with N ranks each rank writes its own images as
+DIR/<name>_rank<r>.npy.  Every input is seeded, so two builds run with the same arguments can be compared output for output.
+
+Extra objects on the JSON line (`--full` only):
   roofline     - the region cross-attention forward kernel (`xp_fwd`, L=4096 level of the same workload) timed live with
                  HIP events around graph-captured back-to-back launches on the stream they run on: algorithmic bytes
                  per launch / average launch duration vs the 8 TB/s HBM peak.  Algorithmic bytes per launch = 6.60 MB
@@ -30,7 +37,8 @@ Extra objects on the JSON line:
                  (4*L^2*C FLOPs per row).
   roofline_conv3x3   - the 3x3 convolution kernel (64x64, 320->320, the most frequent one) against the same peak
   roofline_at_8_images - the same three kernels at Bc = 16 (BASELINE configs[2]: 8 images per GPU): achieved / frac / launch time
-  one_generation_at_a_time - see above
+  one_generation_at_a_time - the same K generations with one in flight: its ms_per_generation is the latency of one image
+  coalesced_requests - serving mode: k concurrent batch-1 requests in one captured step (`--coalesce-sweep`)
   cpu_baseline - the oracle (oracle/unet_ref.py, torch fp32, op-for-op unfused like the reference) timed on this
                  box's host cores on a bounded sample of the same workload (rank 0, N=1 only); its
                  gpu_vs_cpu_on_the_sample = the product loop on the same sample against the oracle's latents.
@@ -97,7 +105,28 @@ def parse():
     ap.add_argument("--cpu-budget-s", type=float, default=300.0,
                     help="when the configs[0] single step predicts more than this for the cpu_baseline sample (few host cores), the "
                          "sample is cut to the steps that fit (>= 3) and labelled as extrapolated; 0 = no limit")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg and check beyond the headline: one generation at a time, the rooflines, the "
+                         "cpu_baseline, the slots-vs-alone and across-rank equality checks, the coalesced_requests sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed generation computed as DIR/<name>.npy (float32) after the timed region")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, name, t):
+    """t (a device tensor) as d/name.npy in float32; past DUMP_MAX_BYTES a fixed, seeded sample of its elements
+    (d/name_sample.npy) - the same elements on every run of the same arguments"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    x = t.detach().float().cpu().contiguous()
+    if x.numel() * 4 > DUMP_MAX_BYTES:
+        n = DUMP_MAX_BYTES // 4
+        idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+        x, name = x.reshape(-1)[idx], name + "_sample"
+    np.save(os.path.join(d, name + ".npy"), x.numpy())
 
 
 def synthetic_inputs(size, regions, S=77, ctx=768):
@@ -502,10 +531,13 @@ def main():
         return out
 
     out = None
-    ops.set_tuning_profile("latency" if a.tuning_profile == "auto" else a.tuning_profile)
     nfl = 1 if (a.decode or a.no_graph) else max(1, a.in_flight)     # slots exist for the captured denoising loop
     if nfl > 4:
         raise SystemExit("--in-flight: at most 4 generation slots (dsc_set_workspace_slot)")
+    # a plain run with generations in flight warms up (captures) the slots straight under the in-flight leg's launch rules;
+    # --full first runs one generation at a time under the latency rules and re-captures the slots before the in-flight leg
+    auto_profile = "throughput" if (nfl > 1 and not a.full) else "latency"
+    ops.set_tuning_profile(auto_profile if a.tuning_profile == "auto" else a.tuning_profile)
     streams = [torch.cuda.Stream() for _ in range(nfl)] if nfl > 1 else None
     if nfl > 1:
         torch.cuda.synchronize()
@@ -557,29 +589,37 @@ def main():
                 o = generate(0)
         return o
 
-    # Order: the one-at-a-time leg, the roofline / cpu_baseline legs, and only then the generations in flight - so that a
-    # complete line exists before the only leg in which two streams share the chip, and a stall there (never observed;
+    # Order (--full): the one-at-a-time leg, the roofline / cpu_baseline legs, and only then the generations in flight - so
+    # that a complete line exists before the only leg in which two streams share the chip, and a stall there (never observed;
     # hipBLASLt's stream-K kernels spin on each other's partial tiles) still ends with a valid line instead of a hung job.
-    dt_seq, out = timed(one_at_a_time)
-    rates_seq = per_rank()
-    finite = bool(torch.isfinite(out).all().item())
+    # A plain run times only the headline leg: one at a time when nfl == 1, else the generations in flight.
+    dt_seq, rates_seq, finite = None, None, True
+    if a.full or nfl == 1:
+        dt_seq, out = timed(one_at_a_time)
+        rates_seq = per_rank()
+        finite = bool(torch.isfinite(out).all().item())
     images = n_img * world * a.steps
     res = None
     if rank == 0:
         res = {
             "metric": ("512x512 images/sec, SD1.5 25-step DPM++2M Karras with region-biased cross-attention" if a.model == "sd15" and a.size == 512
                        else f"{a.size}x{a.size} images/sec, {a.model} UNet, 25-step DPM++2M Karras with region-biased cross-attention"),
-            "value": round(images / dt_seq, 4), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(dt_seq / a.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
+            "value": round(images / dt_seq, 4) if dt_seq else None, "unit": "images/s", "n_gpus": world, "steps": a.steps,
+            "warmup": a.warmup, "ms_per_step": round(dt_seq / a.steps * 1e3, 2) if dt_seq else None, "higher_is_better": True,
+            "scaling": "weak",
             "vs_baseline": None, "dtype": "f16", "data": "synthetic",
             "config": {"workload": f"{'SD1.5' if a.model == 'sd15' else 'SDXL-base-SHAPED UNet (configs[4] geometry)'} {a.size}x{a.size}, {a.denoise_steps}-step DPM++2M Karras, CFG 7.5, "
                                    f"{a.regions} region masks, {n_img} image(s) per generation, "
                                    f"1 generation(s) in flight per GPU",
                        "images_per_gpu": n_img, "parallelism": f"dp{world} (independent images, no per-step collective)",
-                       "per_rank_images_per_s": rates_seq, "max_over_ranks_s": round(dt_seq, 4),
+                       "per_rank_images_per_s": rates_seq, "max_over_ranks_s": round(dt_seq, 4) if dt_seq else None,
                        "generations_in_flight": 1, "images_per_generation": n_img, "slots_equal_one_at_a_time": None,
-                       "hip_graph": bool(ops.GRAPHS_ENABLED), "outputs_finite": finite, "vae_decode_in_timed_region": bool(a.decode)},
+                       "hip_graph": bool(ops.GRAPHS_ENABLED), "outputs_finite": finite, "vae_decode_in_timed_region": bool(a.decode),
+                       "full": bool(a.full)},
         }
+    if a.dump_outputs and nfl == 1:                             # the headline leg was the one just timed
+        dump_outputs(a.dump_outputs, ("images" if a.decode else "latents") + (f"_rank{rank}" if dist else ""), out)
+    if res is not None and a.full:
         res["roofline"] = roofline_region_xattn(dev, n_img)
         res["roofline_self_attn"] = roofline_self_attn(dev, n_img)
         res["roofline_conv3x3"] = roofline_conv3x3(dev, n_img)
@@ -623,7 +663,7 @@ def main():
     if res is not None:
         res["config"]["devices"] = names
     ranks_equal = True
-    if dist and not a.decode:
+    if dist and not a.decode and a.full:
         # per-image equality across ranks: every rank hashes the final latents of its images (one generation
         # at a time, latency rules); rank 0 generates EVERY rank's images itself and compares - the same bits are expected since
         # no kernel of the step is chosen per process any more (no library GEMM) and every kernel is bit-reproducible
@@ -639,10 +679,11 @@ def main():
             res["config"]["dist_backend"] = backend if backend == "nccl" else f"{backend} (NOT RCCL: a rehearsal, not a multi-GPU measurement)"
         td.barrier()
     if nfl > 1:
-        # the launch rules for generations that SHARE the chip (include/dsc_hip.h, dsc_set_tuning_profile): the legs above ran
-        # under "latency"; every slot re-captures its step under "throughput" here, outside the timed region
+        # the launch rules for generations that SHARE the chip (include/dsc_hip.h, dsc_set_tuning_profile): with --full the legs
+        # above ran under "latency"; every slot re-captures its step under "throughput" here, outside the timed region (a plain
+        # run captured them under "throughput" in its warm-up)
         ref_same_rules = out
-        if a.tuning_profile == "auto":
+        if a.tuning_profile == "auto" and a.full:
             ops.set_tuning_profile("throughput")
             if res is not None and "cpu_baseline" in res:
                 # the headline leg's launch rules against the oracle too (the check above ran under the latency rules)
@@ -657,7 +698,7 @@ def main():
                 if s_i == 0:
                     ref_same_rules = o_              # one generation alone on the chip under the in-flight leg's launch rules
         progress = [0, time.monotonic()]
-        outs, errs = [None] * nfl, []
+        outs, errs, last = [None] * nfl, [], [None]
         todo, todo_lock = iter(range(a.steps)), threading.Lock()
 
         def drive(s_i):
@@ -666,9 +707,12 @@ def main():
                 with torch.cuda.stream(streams[s_i]):
                     while True:                             # a.steps generations in total, whichever slot is free next
                         with todo_lock:
-                            if next(todo, None) is None:
-                                break
+                            i_ = next(todo, None)
+                        if i_ is None:
+                            break
                         outs[s_i] = generate(s_i)
+                        if i_ == a.steps - 1:
+                            last[0] = outs[s_i]             # the last timed generation: what --dump-outputs writes
                         progress[0] += 1
                         progress[1] = time.monotonic()
             except BaseException as e:                      # noqa: BLE001 - re-raised on the main thread
@@ -686,7 +730,7 @@ def main():
                     msg = f"stalled after {progress[0]} of {a.steps} generations with {nfl} in flight"
                     if res is not None:
                         res["status"] = "stalled"
-                        res["config"]["in_flight_leg"] = msg + "; value is the one-at-a-time figure"
+                        res["config"]["in_flight_leg"] = msg + ("; value is the one-at-a-time figure" if a.full else "; no value")
                         print(json.dumps(res), flush=True)
                     print(f"bench.py: rank {rank}: {msg}", file=sys.stderr, flush=True)
                     os._exit(3)          # a stall is a FAILURE (non-zero; under torchrun it takes the other ranks down too);
@@ -697,24 +741,31 @@ def main():
 
         dt, slot_outs = timed(in_flight)
         rates_fl = per_rank()
-        # every generation has the same inputs and every kernel is bit-reproducible: the slots' last results and the result of a
-        # generation that ran ALONE under the same launch rules must be EQUAL - a free check on every run that the generations in
-        # flight did not interfere.  (Against the one-at-a-time leg, which runs under the latency rules, the latents agree to
-        # rounding: the two profiles' own kernels give equal bytes, but a library GEMM may be run by another algorithm.)
-        slots_agree = all(torch.equal(o, ref_same_rules) for o in slot_outs)
-        prof_diff = max(float((o.float() - out.float()).abs().max().item()) for o in slot_outs)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, "latents" + (f"_rank{rank}" if dist else ""), last[0])
+        slots_agree, prof_diff = None, None
+        if a.full:
+            # every generation has the same inputs and every kernel is bit-reproducible: the slots' last results and the result of
+            # a generation that ran ALONE under the same launch rules must be EQUAL - a check that the generations in flight did
+            # not interfere.  (Against the one-at-a-time leg, which runs under the latency rules, the latents agree to rounding:
+            # the two profiles' own kernels give equal bytes, but a library GEMM may be run by another algorithm.)
+            slots_agree = all(torch.equal(o, ref_same_rules) for o in slot_outs)
+            prof_diff = round(max(float((o.float() - out.float()).abs().max().item()) for o in slot_outs), 6)
         if res is not None:
-            res["one_generation_at_a_time"] = {"value": res["value"], "unit": "images/s", "ms_per_generation": res["ms_per_step"],
-                                               "note": "the same K generations with one in flight (latency of one image)"}
+            if a.full:
+                res["one_generation_at_a_time"] = {"value": res["value"], "unit": "images/s", "ms_per_generation": res["ms_per_step"],
+                                                   "note": "the same K generations with one in flight (latency of one image)"}
             res["value"], res["ms_per_step"] = round(images / dt, 4), round(dt / a.steps * 1e3, 2)
             res["config"].update({"generations_in_flight": nfl, "slots_equal_one_at_a_time": slots_agree,
-                                  "max_abs_diff_between_the_profiles_latents": round(prof_diff, 6),
-                                  "tuning_profile": {"one_generation_at_a_time": "latency" if a.tuning_profile == "auto" else a.tuning_profile,
+                                  "max_abs_diff_between_the_profiles_latents": prof_diff,
+                                  "tuning_profile": {"one_generation_at_a_time": ("latency" if a.tuning_profile == "auto" else a.tuning_profile)
+                                                     if a.full else None,
                                                      "in_flight": ops.tuning_profile()},
                                   "per_rank_images_per_s": rates_fl, "max_over_ranks_s": round(dt, 4),
                                   "outputs_finite": finite and all(bool(torch.isfinite(o).all().item()) for o in slot_outs),
                                   "workload": res["config"]["workload"].replace("1 generation(s) in flight", f"{nfl} generation(s) in flight")})
-    if res is not None and world == 1 and n_img == 1 and not a.no_coalesced and not a.decode and not a.no_graph and a.model == "sd15":
+    if res is not None and a.full and world == 1 and n_img == 1 and not a.no_coalesced and not a.decode and not a.no_graph \
+            and a.model == "sd15":
         # Serving mode (not the headline, which stays BASELINE configs[1]: batch-1 generations): k CONCURRENT batch-1 requests of
         # the same workload - own start latent each, configs[1]'s prompt and masks - denoised by ONE captured step per sigma
         # (txt2img_coalesced: per-request std groups and tables, every kernel on k times the rows), f such generations in flight

@@ -619,6 +619,24 @@ def test_bench_refuses_a_gpus_world_size_mismatch_and_self_launches():
     assert "needs an MI355X" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_float32_and_a_fixed_sample_past_the_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: an output within the cap is written whole as float32; a larger one as a seeded sample of
+    its elements that is the same on every call, no larger than the cap"""
+    import numpy as np
+    import torch
+    import bench
+    x = torch.randn(1, 4, 64, 64, generator=torch.Generator().manual_seed(1)).half()
+    bench.dump_outputs(str(tmp_path / "a"), "latents", x)
+    got = np.load(tmp_path / "a" / "latents.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 4, 64, 64) and np.array_equal(got, x.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "latents", x)
+    s1, s2 = np.load(tmp_path / "b" / "latents_sample.npy"), np.load(tmp_path / "c" / "latents_sample.npy")
+    assert s1.dtype == np.float32 and s1.nbytes <= 4096 and s1.size == 1024 and np.array_equal(s1, s2)
+    assert np.isin(s1, x.float().numpy().reshape(-1)).all()
+
+
 def test_weight_func_key_is_by_value_where_the_callable_allows():
     """a fresh lambda per request (reference app.py:1004) must not force a re-capture: equal code + equal captured values ->
     equal key; different captured values -> different keys; unhashable captures -> object identity"""

@@ -24,7 +24,7 @@ def test_two_ranks_produce_the_single_process_latents():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--in-flight", "1",
-                        "--no-cpu-baseline", "--no-batched-roofline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--no-batched-roofline", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.lstrip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

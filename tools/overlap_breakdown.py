@@ -1,6 +1,6 @@
 """Two generations in flight: what each kernel family costs when two streams share the chip.
 
-    rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-batched-roofline
+    rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-batched-roofline --full
     python tools/overlap_breakdown.py OUT/*/*_kernel_trace.csv
 
 Takes the trace's last window in which two queues run sampler steps concurrently (the in-flight leg), and per family prints the

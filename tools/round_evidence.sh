@@ -14,7 +14,7 @@ if [ "$2" != "notests" ]; then
   timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $o/t.log 2>&1; echo "pytest rc=$?" >> $o/t.log; tail -3 $o/t.log
 fi
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/trace -- python3 $root/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-batched-roofline --no-coalesced --in-flight 1 > $o/bench_trace.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/trace -- python3 $root/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-batched-roofline --no-coalesced --in-flight 1 --full > $o/bench_trace.log 2>&1 || exit 1
 python3 $root/tools/step_breakdown.py -vv $o/trace/*/*_kernel_trace.csv > $o/step_breakdown.txt 2>&1
 python3 $root/tools/make_in_step.py $o/trace/*/*_kernel_trace.csv r04 > $o/make_in_step.log 2>&1 || { tail -3 $o/make_in_step.log; exit 1; }
 cp $o/trace/*/*_kernel_stats.csv $o/bench_kernel_stats.csv
@@ -27,7 +27,7 @@ python3 $root/tools/make_mfma_busy.py $o/pmc_sq/*/*counter_collection.csv r04 > 
 python3 $root/tools/summarize_pmc.py $o/pmc_sq/*/*counter_collection.csv > $o/pmc_sq_counters.csv
 rm -rf $o/pmc_f $o/pmc_w $o/pmc_sq
 cd $root
-DSC_DIST_BACKEND=gloo timeout -k 10 300 python3 bench.py --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline --no-batched-roofline --no-coalesced > $o/bench_line_2_ranks_gloo_rehearsal.json 2> $o/bench_2rank.err
+DSC_DIST_BACKEND=gloo timeout -k 10 300 python3 bench.py --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline --no-batched-roofline --no-coalesced --full > $o/bench_line_2_ranks_gloo_rehearsal.json 2> $o/bench_2rank.err
 echo "2-rank rc=$?"
 ls $o/stamped
 head -9 $o/step_breakdown.txt

@@ -8,7 +8,7 @@ cd $root
 for k in 1 2 4 8; do
   for f in 1 2; do
     n=$(( 24 / k )); [ $n -lt 4 ] && n=4
-    timeout -k 10 300 python3 bench.py --images-per-gpu $k --in-flight $f --steps $n --warmup 1 --no-cpu-baseline --no-batched-roofline --no-coalesced \
+    timeout -k 10 300 python3 bench.py --images-per-gpu $k --in-flight $f --steps $n --warmup 1 --no-cpu-baseline --no-batched-roofline --no-coalesced --full \
       > gpurun_out/$out/sweep_k${k}_f${f}.json 2> gpurun_out/$out/sweep_k${k}_f${f}.err || { echo "k=$k f=$f failed"; tail -3 gpurun_out/$out/sweep_k${k}_f${f}.err; exit 1; }
     python3 - <<PY
 import json
