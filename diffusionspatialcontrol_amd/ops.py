@@ -32,6 +32,18 @@ def _require_gpu(*ts):
             raise _lib.DscLibraryError("dsc ops run on the GPU only (no CPU fallback); got a CPU tensor")
 
 
+def _check_out(out, shape, like, what):
+    """an `out=` the caller supplied is written through its raw pointer as a [shape] fp16 tensor on `like`'s device: anything
+    smaller, of another dtype or on another device would be an out-of-bounds or foreign write, so refuse it before any launch"""
+    if out.dtype != torch.float16:
+        raise TypeError(f"{what}: out must be fp16, got {out.dtype}")
+    if out.device != like.device:
+        raise ValueError(f"{what}: out is on {out.device}, the operands on {like.device}")
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{what}: out has shape {tuple(out.shape)}, the kernel writes {tuple(shape)}")
+    return out
+
+
 def _workspace(device, nbytes):
     """fp64 scratch for one call, from torch's caching allocator.  Deliberately NOT cached across calls: inside a
     HIP-graph capture the allocation must belong to that graph's private pool, and a buffer remembered from an
@@ -94,6 +106,8 @@ def region_xattn(q, k, v, region=None, sigma=1.0, *, layout="bhld", n_std_groups
     vs, _ = _blhd_strides(v, lay)
     if out is None:
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    _check_out(out, q.shape, q, "region_xattn")
+    _drop_gn_partials(out)
     os_, _ = _blhd_strides(out, lay)
     Bw = 0
     rptr = None
@@ -138,8 +152,9 @@ def xattn_kv_pack(k, v, *, layout="blhd", out=None):
     nbytes = lib.dsc_xattn_kv_pack_bytes(Bc, H, S, d)
     if nbytes == 0:
         raise _lib.DscLibraryError(f"xattn_kv_pack: unsupported shape S={S}, d={d}")
-    if out is None or out.numel() * 2 != nbytes:
+    if out is None or out.numel() * 2 != nbytes or out.dtype != torch.float16 or out.device != k.device or not out.is_contiguous():
         out = torch.empty(nbytes // 2, dtype=torch.float16, device=k.device)
+    _drop_gn_partials(out)
     rc = lib.dsc_xattn_kv_pack(_p(k), _p(v), _p(out), Bc, H, S, d, _i64x3(*ks), _i64x3(*vs), 0, _stream_ptr(k))
     _lib.check(rc, "dsc_xattn_kv_pack")
     return out
@@ -199,6 +214,8 @@ def region_xattn_packed(q, packed_kv, S, region=None, sigma=1.0, *, n_std_groups
     qs, (Bc, H, L, d) = _blhd_strides(q, "blc")
     if out is None:
         out = torch.empty((Bc, L, H, d), dtype=q.dtype, device=q.device)
+    _check_out(out, (Bc, L, H, d), q, "region_xattn_packed")
+    _drop_gn_partials(out)
     os_, _ = _blhd_strides(out, "blc")
     ids = rows = None
     Bw = nrows = 0
@@ -259,7 +276,6 @@ def region_xattn_std(q, k, *, layout="bhld", n_std_groups=1, scale=None, ref_fp1
 def self_attention(q, k, v, scale=None, out=None):
     """softmax(q.k^T * scale) . v for q [B, L, H, d], k/v [B, S, H, d] (strided views allowed) -> [B, L, H, d]
     contiguous (dsc_self_attn_fwd: flash attention, scores never materialised)."""
-    _drop_gn_partials(out)
     _require_gpu(q, k, v)
     if q.dtype != torch.float16:
         raise TypeError("self_attention: fp16 only")
@@ -268,6 +284,8 @@ def self_attention(q, k, v, scale=None, out=None):
     vs, _ = _blhd_strides(v, "blc")
     if out is None:
         out = torch.empty((B, L, H, d), dtype=q.dtype, device=q.device)
+    _check_out(out, (B, L, H, d), q, "self_attention")
+    _drop_gn_partials(out)
     os_, _ = _blhd_strides(out, "blc")
     rc = _lib.load_library().dsc_self_attn_fwd(
         ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.data_ptr()),
@@ -879,12 +897,15 @@ def add_layernorm(x, a, weight, bias, eps=1e-5):
 def softmax_rows(scores, scale=1.0, out=None):
     """softmax(scale * scores, dim=-1) of an fp16 [rows, n] matrix (unit inner stride, 16-byte aligned rows) in fp32 arithmetic
     (dsc_softmax_rows_f16) - the middle step of the VAE's 512-channel attention head between its two GEMMs."""
-    _drop_gn_partials(out)
     _require_gpu(scores)
     if scores.dtype != torch.float16 or scores.dim() != 2 or scores.stride(1) != 1:
         raise TypeError("softmax_rows: a 2-D fp16 matrix with unit inner stride")
     if out is None:
         out = torch.empty_like(scores)
+    _check_out(out, scores.shape, scores, "softmax_rows")
+    if out.stride(1) != 1:
+        raise ValueError("softmax_rows: out needs unit inner stride")
+    _drop_gn_partials(out)
     rc = _lib.load_library().dsc_softmax_rows_f16(_p(scores), _p(out), scores.shape[0], scores.shape[1], scores.stride(0),
                                                   out.stride(0), float(scale), 0, _stream_ptr(scores))
     _lib.check(rc, "dsc_softmax_rows_f16")
@@ -908,34 +929,72 @@ GRAPHS_ENABLED = True      # the fused pipeline captures the UNet step into a HI
 PROTOCOL_GRAPH = os.environ.get("DSC_PROTOCOL_GRAPH", "1") != "0"   # protocol-mode model calls replay the same graph
 
 
-def _row_args(row):
+def _row_args(row, device):
     """(src, dst, halfs, copies) of the optional row broadcast of the sampler kernels: row = (src [n] fp16, dst [copies, n] fp16)"""
     if row is None:
         return None, None, 0, 0
     src, dst = row
     _require_gpu(src, dst)
     if src.dtype != torch.float16 or dst.dtype != torch.float16 or not dst.is_contiguous() or src.stride(-1) != 1 \
-            or dst.dim() != 2 or dst.shape[1] != src.numel():
+            or dst.dim() != 2 or dst.shape[1] != src.numel() or src.device != device or dst.device != device:
         raise ValueError("row broadcast: fp16 source [n] and contiguous destination [copies, n]")
+    _drop_gn_partials(dst)
     return _p(src), _p(dst), src.numel(), dst.shape[0]
+
+
+def _check_sampler_buffers(what, x, x_in, t_buf, sigma_buf, eps=None, old=None):
+    """the sampler kernels address fp16 x / old as [n_img, chw], eps / x_in as [2 n_img, chw] and fp32 t_buf as [2 n_img],
+    sigma_buf as [1] (include/dsc_hip.h) - all dense, on x's device; returns (n_img, chw).  Alignment is the C side's check."""
+    if x.dim() == 0 or x.shape[0] == 0:
+        raise ValueError(f"{what}: x needs a leading image dimension")
+    n_img = x.shape[0]
+    for name, t, rows in (("x", x, n_img), ("old", old, n_img), ("eps", eps, 2 * n_img), ("x_in", x_in, 2 * n_img)):
+        if t is None:
+            continue
+        if t.dtype != torch.float16:
+            raise TypeError(f"{what}: {name} must be fp16, got {t.dtype}")
+        if t.device != x.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, x on {x.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if t.dim() == 0 or t.shape[0] != rows or t.numel() != rows * (x.numel() // n_img):
+            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, need {rows} rows of {x.numel() // n_img}")
+    if old is not None and old.shape != x.shape:
+        raise ValueError(f"{what}: old has shape {tuple(old.shape)}, x {tuple(x.shape)}")
+    for name, t in (("t_buf", t_buf), ("sigma_buf", sigma_buf)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} must be fp32, got {t.dtype}")
+        if t.device != x.device or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a dense vector on {x.device}")
+    if t_buf.numel() != 2 * n_img:
+        raise ValueError(f"{what}: t_buf has {t_buf.numel()} elements, need 2 n_img = {2 * n_img}")
+    if sigma_buf.numel() < 1:
+        raise ValueError(f"{what}: sigma_buf is empty")
+    return n_img, x.numel() // n_img
 
 
 def prepare_unet_input(x, c_in, t, sigma, x_in, t_buf, sigma_buf, row=None):
     """x_in = [x; x] * c_in, t_buf[:] = t, sigma_buf[0] = sigma (dsc_prepare_unet_input); row: see _row_args."""
     _require_gpu(x, x_in, t_buf, sigma_buf)
-    n_img = x.shape[0]
-    rc = _lib.load_library().dsc_prepare_unet_input(_p(x), c_in, t, sigma, _p(x_in), _p(t_buf), _p(sigma_buf), n_img,
-                                                    x.numel() // n_img, 0, *_row_args(row), _stream_ptr(x))
+    n_img, chw = _check_sampler_buffers("prepare_unet_input", x, x_in, t_buf, sigma_buf)
+    rargs = _row_args(row, x.device)
+    _drop_gn_partials(x_in)
+    rc = _lib.load_library().dsc_prepare_unet_input(_p(x), c_in, t, sigma, _p(x_in), _p(t_buf), _p(sigma_buf), n_img, chw, 0,
+                                                    *rargs, _stream_ptr(x))
     _lib.check(rc, "dsc_prepare_unet_input")
 
 
 def cfg_dpmpp2m_step(x, eps, old, sigma, guidance, a, b, c, c_in_next, t_next, sigma_next, x_in, t_buf, sigma_buf, row=None):
     """One launch: CFG combine + eps->denoised + DPM++ 2M update (in place on x, old) + next UNet input (+ the row broadcast)."""
-    _require_gpu(x, eps, old, x_in)
-    n_img = x.shape[0]
+    _require_gpu(x, eps, old, x_in, t_buf, sigma_buf)
+    n_img, chw = _check_sampler_buffers("cfg_dpmpp2m_step", x, x_in, t_buf, sigma_buf, eps=eps, old=old)
+    rargs = _row_args(row, x.device)
+    _drop_gn_partials(x)
+    _drop_gn_partials(old)
+    _drop_gn_partials(x_in)
     rc = _lib.load_library().dsc_cfg_dpmpp2m_step(_p(x), _p(eps), _p(old), sigma, guidance, a, b, c, c_in_next, t_next,
-                                                  sigma_next, _p(x_in), _p(t_buf), _p(sigma_buf), n_img,
-                                                  x.numel() // n_img, 0, *_row_args(row), _stream_ptr(x))
+                                                  sigma_next, _p(x_in), _p(t_buf), _p(sigma_buf), n_img, chw, 0, *rargs,
+                                                  _stream_ptr(x))
     _lib.check(rc, "dsc_cfg_dpmpp2m_step")
 
 

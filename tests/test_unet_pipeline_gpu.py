@@ -737,7 +737,9 @@ def test_geglu(ops):
     assert torch.all((y - ref).abs() <= 2.5e-3 * ref.abs() + 1e-3) and (y - ref).abs().mean().item() < 3e-4
 
 
-def test_sampler_kernels(ops):
+def _sampler_launches_and_checks(ops, row_prepare=None, row_step=None):
+    """dsc_prepare_unet_input, then dsc_cfg_dpmpp2m_step, on seeded latents (each with an optional row broadcast): everything
+    each launch leaves in x_in / t_buf / sigma_buf, x and old against fp32 restatements; returns (x, eps, old, (a, b, c))"""
     g = torch.Generator().manual_seed(11)
     n, shp = 3, (3, 4, 16, 16)
     x = (torch.randn(shp, generator=g) * 10).half()
@@ -745,11 +747,11 @@ def test_sampler_kernels(ops):
     old = torch.randn(shp, generator=g).half()
     sigma, gs, a, b, c, cin, tn, sn = 3.17, 7.5, 0.8, 0.25, -0.05, 0.3, 412.5, 2.55
     xi, tb, sb = torch.zeros(2 * n, *shp[1:], dtype=torch.half).cuda(), torch.zeros(2 * n).cuda(), torch.zeros(1).cuda()
-    ops.prepare_unet_input(x.cuda(), 0.123, 999.0, 14.6, xi, tb, sb)
+    ops.prepare_unet_input(x.cuda(), 0.123, 999.0, 14.6, xi, tb, sb, row=row_prepare)
     assert (xi.float().cpu() - torch.cat([x, x]).float() * 0.123).abs().max() < 2e-3
     assert tb.tolist() == [999.0] * (2 * n) and abs(sb.item() - 14.6) < 1e-6
     xd, od = x.cuda().clone(), old.cuda().clone()
-    ops.cfg_dpmpp2m_step(xd, eps.cuda(), od, sigma, gs, a, b, c, cin, tn, sn, xi, tb, sb)
+    ops.cfg_dpmpp2m_step(xd, eps.cuda(), od, sigma, gs, a, b, c, cin, tn, sn, xi, tb, sb, row=row_step)
     eu, ec = eps.float().chunk(2)
     D = x.float() - sigma * (eu + gs * (ec - eu))
     xn = a * x.float() + b * D.half().float() + c * old.float()     # D is stored (and reused) as an fp16 tensor
@@ -758,10 +760,44 @@ def test_sampler_kernels(ops):
     assert close(xd, xn)
     assert close(xi, torch.cat([xn, xn]) * cin)
     assert tb.tolist() == [tn] * (2 * n) and abs(sb.item() - sn) < 1e-6
+    return x, eps, old, (a, b, c)
+
+
+def test_sampler_kernels(ops):
+    x, eps, old, (a, b, c) = _sampler_launches_and_checks(ops)
+    n = x.shape[0]
     out = ops.dpmpp2m_update(x.cuda(), eps[:n].cuda(), old.cuda(), a, b, c)
     assert (out.float().cpu() - (a * x.float() + b * eps[:n].float() + c * old.float())).abs().max() < 0.01
     out = ops.dpmpp2m_update(x.cuda(), eps[:n].cuda(), None, a, b, 0.0)
     assert (out.float().cpu() - (a * x.float() + b * eps[:n].float())).abs().max() < 0.01
+
+
+@pytest.mark.parametrize("copies", [1, 2, 6])
+@pytest.mark.parametrize("halfs", [8, 1280, 2560 + 8])
+def test_sampler_kernels_row_broadcast(ops, copies, halfs):
+    """row = (src, dst): the step's row of the per-schedule time-embedding table copied into every row of the static buffer
+    the captured step reads, in the same launch as the sampler arithmetic (which must come out as without it)"""
+    g = torch.Generator().manual_seed(copies * 10000 + halfs)
+    table = (torch.randn(3, halfs, generator=g) * 4).half().cuda()           # rows of a table, as the pipeline hands them
+    nan = torch.full((copies, halfs), float("nan"), dtype=torch.half, device="cuda")
+    dst_prepare, dst_step = nan.clone(), nan.clone()
+    _sampler_launches_and_checks(ops, row_prepare=(table[1], dst_prepare), row_step=(table[2], dst_step))
+    assert torch.equal(dst_prepare, table[1].expand(copies, halfs))
+    assert torch.equal(dst_step, table[2].expand(copies, halfs))
+
+
+def test_sampler_row_broadcast_refuses_ragged_rows(ops):
+    """a row of halfs % 8 != 0 is refused before the launch: neither the row nor the sampler buffers are written"""
+    x = torch.randn(1, 4, 8, 8).half().cuda()
+    x_in, tb, sb = torch.zeros(2, 4, 8, 8, dtype=torch.half, device="cuda"), torch.zeros(2, device="cuda"), torch.zeros(1, device="cuda")
+    src, dst = torch.ones(12, dtype=torch.half, device="cuda"), torch.zeros(2, 12, dtype=torch.half, device="cuda")
+    from diffusionspatialcontrol_amd import _lib
+    with pytest.raises(_lib.DscLibraryError):
+        ops.prepare_unet_input(x, 0.5, 10.0, 1.0, x_in, tb, sb, row=(src, dst))
+    with pytest.raises(_lib.DscLibraryError):
+        ops.cfg_dpmpp2m_step(x, x_in, x.clone(), 1.0, 7.5, 0.5, 0.5, 0.0, 1.0, 10.0, 1.0, x_in, tb, sb, row=(src, dst))
+    torch.cuda.synchronize()
+    assert not dst.any() and not x_in.any() and not tb.any() and not sb.any()
 
 
 def _tiny_setup(n_img=1, seed=0):
