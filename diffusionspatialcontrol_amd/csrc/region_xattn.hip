@@ -151,9 +151,10 @@ __global__ __launch_bounds__(kThreads, (NK <= 5 ? 2 : 1)) void xattn_fwd(XattnPa
     h8_t kr[C::CH], vr[C::CH];
     kv_load<NK, true>(p, b, h, kr, vr);
     double pa1 = 0.0, pa2 = 0.0;
-    if (need_std) group_partials(p, b - fdiv(b, p.fd_ngroups) * p.n_groups, pa1, pa2);
+    const int g = b - fdiv(b, p.fd_ngroups) * p.n_groups;
+    if (need_std) group_partials(p, g, pa1, pa2);
     float sig = 1.f;
-    if (need_std) sig = p.sigma_dev ? *p.sigma_dev : p.sigma_host;
+    if (need_std) sig = group_sigma(p, g);
 
     h8_t qf[NK];
     f4x_t wreg[kWCH];
@@ -352,6 +353,7 @@ extern "C" int dsc_region_xattn_fwd(const void* q, const void* k, const void* v,
     if (!aligned16(v) || !strides_ok(v_strides) || (reinterpret_cast<uintptr_t>(out) & 7) || !strides_ok(o_strides))
         return DSC_ERR_UNSUPPORTED;
     const bool need_stats = region != nullptr && !(flags & DSC_FLAG_BIAS_IS_FINAL);
+    if ((flags & DSC_FLAG_SIGMA_PER_GROUP) && !sigma_dev) return DSC_ERR_BAD_ARG;
     if (region) {
         if (Bw <= 0 || (Bc * H) % Bw != 0) return DSC_ERR_BAD_ARG;
         if (reinterpret_cast<uintptr_t>(region) & 3) return DSC_ERR_UNSUPPORTED;

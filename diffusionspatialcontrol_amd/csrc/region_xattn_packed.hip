@@ -256,8 +256,9 @@ __global__ __launch_bounds__(kThreads, (NK <= 5 ? 2 : 1)) void xp_fwd(XpParams p
     PartialLoads pl;
     float sd = 1.f, sig = 1.f;
     if (has_bias) {
-        pl.issue(p, b - fdiv(b, p.fd_ngroups) * p.n_groups);
-        sig = p.sigma_dev ? *p.sigma_dev : p.sigma_host;
+        const int g = b - fdiv(b, p.fd_ngroups) * p.n_groups;
+        pl.issue(p, g);
+        sig = group_sigma(p, g);
     }
     ImgCopy<P::KFR + P::VFR> imgc;
     imgc.load(pp.img + (long long)(b * p.H + h) * P::IMG);
@@ -505,8 +506,9 @@ __global__ __launch_bounds__(kThreads, (NK <= 5 ? 2 : 1)) void xp_fwd_long(XpPar
         if (has_bias) id = pp.ids[(long long)bw * p.L + row];
     }
     if (has_bias) {
-        const float sig = p.sigma_dev ? *p.sigma_dev : p.sigma_host;
-        const float sd = group_std(p, b - fdiv(b, p.fd_ngroups) * p.n_groups, red, false);        // contains __syncthreads()
+        const int g = b - fdiv(b, p.fd_ngroups) * p.n_groups;
+        const float sig = group_sigma(p, g);
+        const float sd = group_std(p, g, red, false);        // contains __syncthreads()
         for (int idx = threadIdx.x; idx < pp.NU * rs; idx += kThreads) {  // w * sigma * std, zero padded past each chunk's keys
             const int u = idx / rs, rem = idx - u * rs, kc = rem / kBP, s_ = rem - kc * kBP;
             const int key = kc * kSMax + s_;
@@ -703,6 +705,7 @@ extern "C" int dsc_region_xattn_fwd_packed(const void* q, const void* packed_kv,
         if (n_rows > kNUMax) return DSC_ERR_UNSUPPORTED;
         if ((flags & DSC_FLAG_ROWS_PADDED) && (nkc > 1 || !aligned16(region_rows))) return DSC_ERR_UNSUPPORTED;
     }
+    if ((flags & DSC_FLAG_SIGMA_PER_GROUP) && !sigma_dev) return DSC_ERR_BAD_ARG;
     XpParams pp{};
     XattnParams& p = pp.x;
     p.q = static_cast<const half_t*>(q); p.out = static_cast<half_t*>(out);

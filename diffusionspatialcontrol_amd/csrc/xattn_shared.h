@@ -32,6 +32,12 @@ struct XattnParams {
     FastDiv fd_nchunks, fd_ngroups, fd_rep;      // by nchunks, n_groups, (Bc H) / Bw (plan_tiles)
 };
 
+// sigma of std group g: one device float (sigma_dev[0]), or with DSC_FLAG_SIGMA_PER_GROUP one per group (serving: every
+// request of a continuous batch is at its own point of its own schedule), else the host value
+__device__ __forceinline__ float group_sigma(const XattnParams& p, int g) {
+    return p.sigma_dev ? p.sigma_dev[(p.flags & DSC_FLAG_SIGMA_PER_GROUP) ? g : 0] : p.sigma_host;
+}
+
 // grid = (8, H, Bc*nchunks/8) when Bc*nchunks % 8 == 0, else (1, H, Bc*nchunks).  The hardware deals linear workgroup
 // ids x + 8*(y + H*z) round-robin over the 8 XCDs, so the H heads (y) of one (b, row chunk) = (z, x) share an XCD and
 // re-read the same region rows / Q lines from that XCD's L2 - with no integer division except b = cg / nchunks (a multiply: FastDiv).

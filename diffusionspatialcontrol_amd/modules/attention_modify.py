@@ -8,6 +8,8 @@
                                     implementation here and differ only in which `scale` they honour
 Same call signature, same `region_prompt` contract:
     {"region_state": {L: FloatTensor[Bw, L, S]} | non-dict, "sigma": 0-dim tensor, "weight_func": callable}
+(plus, from the serving mode, "sigma_per_group": True with "sigma" an [n_std_groups] fp32 device tensor: one sigma per
+request of a continuous batch; the fused default-weight_func routes only, others raise NotImplementedError)
 
 What changes underneath:
   * the scores are never materialised: q.k^T, *scale, std(), w*sigma*std, repeat_interleave, +=, softmax, @v run
@@ -187,10 +189,17 @@ def _region_attention_masked(q, k, v, w, sigma, weight_func, layout, n_std_group
 
 
 def _region_attention(q, k, v, w, sigma, weight_func, layout, n_std_groups, scale=None, ref16=False, packed_kv=None,
-                      comp=None, mask=None):
+                      comp=None, mask=None, per_group_sigma=False):
     """comp: the caller's (ids, rows) of `w`, None = compress `w` here (cached per tensor version), False = `w` is a static
-    buffer whose CONTENTS change between replays of a captured step: read it densely, derive nothing from its values."""
+    buffer whose CONTENTS change between replays of a captured step: read it densely, derive nothing from its values.
+    per_group_sigma: `sigma` is an [n_std_groups] fp32 device tensor, one sigma per std group (continuous batching,
+    modules/serving.py) - only the fused default-weight_func kernels take it; every other route raises NotImplementedError."""
     S = k.shape[2 if layout == "bhld" else 1]
+    if per_group_sigma:
+        if mask is not None:
+            raise NotImplementedError("per-group sigma: attention masks are not supported")
+        if weight_func is not None and not weight_func_is_default(weight_func):
+            raise NotImplementedError("per-group sigma: a custom weight_func is not supported")
     if mask is not None:
         return _region_attention_masked(q, k, v, w, sigma, weight_func, layout, n_std_groups, scale, ref16, mask)
     if comp is False:
@@ -204,7 +213,10 @@ def _region_attention(q, k, v, w, sigma, weight_func, layout, n_std_groups, scal
                 comp = compressed_table(w, q.device)
             if comp is not None:
                 return ops.region_xattn_packed(q, packed_kv, S, comp, _sigma_arg(sigma, q.device), n_std_groups=n_std_groups,
-                                               scale=scale, ref_fp16_rounding=False)
+                                               scale=scale, ref_fp16_rounding=False, per_group_sigma=per_group_sigma)
+        if per_group_sigma:
+            raise NotImplementedError(f"per-group sigma: {S} text keys need the chunked prepared-operand kernels "
+                                      f"(<= {_KERNEL_MAX_KEYS_PACKED} keys, packed text K/V, compressible table)")
         return _region_attention_long(q, k, v, w, sigma, weight_func, layout, n_std_groups, scale)
     if weight_func is None or weight_func_is_default(weight_func):
         if packed_kv is not None and layout == "blhd":
@@ -212,10 +224,11 @@ def _region_attention(q, k, v, w, sigma, weight_func, layout, n_std_groups, scal
                 comp = compressed_table(w, q.device)
             if comp is not None:                 # prepared operands: packed text K/V + row-id region table
                 return ops.region_xattn_packed(q, packed_kv, k.shape[1], comp, _sigma_arg(sigma, q.device),
-                                               n_std_groups=n_std_groups, scale=scale, ref_fp16_rounding=ref16)
+                                               n_std_groups=n_std_groups, scale=scale, ref_fp16_rounding=ref16,
+                                               per_group_sigma=per_group_sigma)
         w_dev = resident_table(w, q.device)
         return ops.region_xattn(q, k, v, w_dev, _sigma_arg(sigma, q.device), layout=layout, n_std_groups=n_std_groups,
-                                scale=scale, ref_fp16_rounding=ref16)
+                                scale=scale, ref_fp16_rounding=ref16, per_group_sigma=per_group_sigma)
     w_dev = resident_table(w, q.device)
     # generic weight_func: evaluate it the way the reference does (attention_modify.py:90-95), then let the kernel
     # add its result (flag BIAS_IS_FINAL).  Slow path by construction - the scores are materialised once.
@@ -373,7 +386,8 @@ class _RegionProcessor:
                 # reference raises here - so does this (same exception type)
                 torch.zeros(L, S, dtype=q4.dtype, device=q4.device).add_(mask3.view(B, H, -1, S))
             out = _region_attention(q4, k4, v4, w, region_prompt["sigma"], region_prompt["weight_func"], "blhd",
-                                    groups, sc, ref16=self.ref_fp16_rounding, packed_kv=packed_kv, comp=comp, mask=mask3)
+                                    groups, sc, ref16=self.ref_fp16_rounding, packed_kv=packed_kv, comp=comp, mask=mask3,
+                                    per_group_sigma=bool(region_prompt.get("sigma_per_group", False)))
         elif mask3 is not None:
             # no region table: plain masked attention (:483-485 / :182-186) - the mask is the forward kernel's final bias when
             # the keys fit it, else the library's SDPA

@@ -532,6 +532,13 @@ class StableDiffusionPipeline:
             return latents_process
         return [self.latent_to_image(latents, output_type)]
 
+    def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77):
+        """Continuous-batching server (modules/serving.py): requests join a running batch at any step boundary, each at its own
+        point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
+        stats / warm)."""
+        from .serving import ServingBatcher
+        return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len)
+
     def txt2img_coalesced(self, requests, height: int = 512, width: int = 512, num_inference_steps: int = 50,
                           guidance_scale: float = 7.5, sampler_opt=None, output_type: Optional[str] = "latent",
                           weight_func=lambda w, sigma, qk: w * sigma * qk.std(), cross_attention_kwargs=None,
@@ -1270,7 +1277,8 @@ class StableDiffusionPipeline:
                     k, v = m.to_k(text), m.to_v(text)
                 B, S, C = k.shape
                 d = C // m.heads
-                # one entry per static text buffer (= per generation slot); the newest few are kept
+                # one entry per static text buffer (= per generation slot); the newest few are kept, and every entry a serving
+                # batcher pinned (its bucket graphs read those buffers for as long as the batcher lives, modules/serving.py)
                 slots = m.__dict__.setdefault("kv_caches", [])
                 c = next((e for e in slots if e["src"] is text and e["k"].shape == k.shape), None)
                 if c is not None:
@@ -1278,7 +1286,8 @@ class StableDiffusionPipeline:
                     c["v"].copy_(v)
                 else:
                     c = {"src": text, "k": k, "v": v, "packed": None}
-                    slots[:] = [e for e in slots if e["src"] is not text][-3:] + [c]
+                    others = [e for e in slots if e["src"] is not text]
+                    slots[:] = [e for e in others if e.get("pin")] + [e for e in others if not e.get("pin")][-3:] + [c]
                 m.kv_cache = c
                 # MFMA-fragment image of K / V^T for the fused kernel (rewritten in place: captured graphs keep reading it)
                 if S <= 384 and d % 8 == 0 and d <= 160:          # > 96 keys: one image per 96-key chunk (long prompts)

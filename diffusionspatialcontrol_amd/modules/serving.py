@@ -1,0 +1,516 @@
+"""Continuous batching for serving: requests join a running batch at any step boundary and leave when done.
+
+`txt2img_coalesced` runs k requests in lockstep (one schedule, one guidance scale, all start together).  Here every request
+keeps its own schedule, step count and guidance scale; what the batch shares is one captured UNet step per bucket.
+
+Slots and buckets.  A request takes the lowest free slot i (< max_batch) and keeps it until it finishes.  Slot i is latent row i
+of the batcher's x / old buffers and rows {i, n + i} of the UNet input of every bucket n > i ([u_0..u_{n-1}, c_0..c_{n-1}], the
+layout of txt2img_coalesced), i.e. std group i (`n_std_groups = n`).  Each step runs the captured graph of the smallest bucket
+that covers the highest occupied slot; empty slots below it are IDLE rows (zero input, zero text, zero tables).  Every bucket is
+captured once (`warm()`); joins, leaves and bucket switches only refresh static buffers in place (text rows, their packed K/V,
+the compressed region tables).
+
+Per step: ONE launch of dsc_cfg_dpmpp2m_step_rows takes the eps of the bucket that just ran and writes the next bucket's input -
+per slot its own sigma, guidance, DPM++ 2M coefficients (c = 0 on a request's first step), time-embedding row (of its own
+`temb_add_table`) and sigma of its std group (read by the region cross-attention under DSC_FLAG_SIGMA_PER_GROUP) - then the
+next bucket's graph replays.  No host<->device synchronisation per step: a request's completion is a CUDA event recorded after
+the copy of its final latent row, and futures resolve when those events are seen complete.
+
+The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
+request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
+"""
+import collections
+import concurrent.futures
+import threading
+import time
+
+import torch
+
+from .. import _lib, ops
+from . import sampling
+from .attention_modify import weight_func_is_default
+from .encode_region_map_function import encode_region_map
+
+MAX_TEXT_KEYS = 384                  # the chunked prepared-operand kernels (ops.region_xattn_packed)
+_UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter", "ip_adapter_image", "ip_adapter_image_embeds")
+
+
+class _Request:
+    __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
+                 "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done")
+
+
+class ServingBatcher:
+    """See the module docstring.  `executor` is the device side (default: the captured-graph executor on the pipeline's GPU);
+    the scheduling here is host logic only."""
+
+    def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None):
+        buckets = tuple(sorted(set(int(b) for b in buckets)))
+        if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
+            raise ValueError(f"serve: buckets {buckets} must cover max_batch={max_batch}")
+        if max_batch > ops.ROW_STEP_MAX_SLOTS:
+            raise ValueError(f"serve: at most {ops.ROW_STEP_MAX_SLOTS} slots (dsc_cfg_dpmpp2m_step_rows)")
+        if text_len > MAX_TEXT_KEYS:
+            raise ValueError(f"serve: at most {MAX_TEXT_KEYS} text keys")
+        self.pipe, self.height, self.width = pipe, int(height), int(width)
+        self.max_batch, self.slot, self.buckets, self.text_len = int(max_batch), int(slot), buckets, int(text_len)
+        self._lock = threading.RLock()
+        self._wake = threading.Condition(self._lock)
+        self._queue = collections.deque()
+        self._slots = [None] * self.max_batch
+        self._done = []                        # (request, handle) whose final row copy is in flight
+        self._n = None                         # bucket whose eps is pending (None: nothing ran yet / the batch drained)
+        self._members = {}                     # bucket -> per-slot request ids its static buffers were last refreshed for
+        self._next_id = 0
+        self._stats = collections.Counter(captures=0, joins=0, leaves=0, bucket_switches=0, steps=0, refreshes=0)
+        self._warm_captures = None
+        self._thread = None
+        self._stop = False
+        self.exec = executor if executor is not None else _GraphExecutor(self)
+
+    # ------------------------------------------------------------------ public interface
+    def warm(self):
+        """capture every bucket's step now (otherwise each is captured on first use)"""
+        with self._lock:
+            for n in self.buckets:
+                self._ensure(n)
+            self._warm_captures = self._stats["captures"]
+        return self
+
+    def submit(self, request):
+        """request: txt2img_coalesced's request dict plus its own `num_inference_steps` (default 25), `sampler_opt` (the
+        schedule: karras / exponential / ...), `guidance_scale` (> 1, default 7.5) and `latents` / `generator`; optional
+        `output_type` ("latent", default, or what latent_to_image takes).  Returns a Future of the final output."""
+        r = self._prepare(request)
+        with self._lock:
+            r.rid = self._next_id
+            self._next_id += 1
+            self._queue.append(r)
+            self._wake.notify_all()
+        return r.future
+
+    def step(self):
+        """advance every active request by one sigma (admitting queued requests into free slots first); False when idle"""
+        with self._lock:
+            self.exec.bind_thread()
+            self._poll()
+            ran = self._step_locked()
+            self._poll()
+            return ran
+
+    def run_until_idle(self):
+        """step until the queue is empty and every request has finished, then wait for the last rows and resolve their futures"""
+        while self.step():
+            pass
+        with self._lock:
+            self._poll(wait=True)
+
+    def start(self):
+        """drive the batcher from a background thread (one per batcher; two batchers on two slots = two batches in flight)"""
+        with self._lock:
+            if self._thread is not None:
+                return self
+            self._stop = False
+            self._thread = threading.Thread(target=self._drive, name=f"dsc-serve-{self.slot}", daemon=True)
+            self._thread.start()
+        return self
+
+    def stop(self):
+        """stop the driver thread after the step it is in (queued and active requests stay where they are)"""
+        with self._lock:
+            self._stop = True
+            self._wake.notify_all()
+            t = self._thread
+        if t is not None:
+            t.join()
+        with self._lock:
+            self._thread = None
+            self._poll(wait=True)
+
+    def stats(self):
+        with self._lock:
+            s = dict(self._stats)
+            s["captures_after_warm"] = None if self._warm_captures is None else s["captures"] - self._warm_captures
+            s["queued"] = len(self._queue)
+            s["active"] = sum(r is not None for r in self._slots)
+            s["bucket"] = self._n
+            return s
+
+    # ------------------------------------------------------------------ request preparation (caller's thread)
+    def _prepare(self, request):
+        pipe = self.pipe
+        if not isinstance(request, dict):
+            raise TypeError("serve: a request is a dict (txt2img_coalesced's request + num_inference_steps / sampler_opt / "
+                            "guidance_scale)")
+        if getattr(pipe, "v_prediction", False):
+            raise ValueError("serve: v-prediction models are not supported (the per-row step computes x - sigma * eps)")
+        if (request.get("height", self.height), request.get("width", self.width)) != (self.height, self.width):
+            raise ValueError(f"serve: this batcher runs {self.height}x{self.width} images, the request asks for "
+                             f"{request.get('height')}x{request.get('width')}")
+        g = float(request.get("guidance_scale", 7.5))
+        if g <= 1.0:
+            raise ValueError("serve: guidance_scale must be > 1 (classifier-free guidance rows u_i / c_i)")
+        wf = request.get("weight_func")
+        if wf is not None and not weight_func_is_default(wf):
+            raise ValueError("serve: a custom weight_func is not supported (use txt2img)")
+        for k in _UNSUPPORTED_KEYS:
+            if request.get(k) is not None:
+                raise ValueError(f"serve: `{k}` (ControlNet / T2I-Adapter / IP-Adapter) is not supported (use txt2img)")
+        pos, neg = request.get("prompt_embeds"), request.get("negative_prompt_embeds")
+        if pos is None or neg is None:
+            raise ValueError("serve: a request needs prompt_embeds and negative_prompt_embeds ([1, S, ctx] each)")
+        if pos.dim() != 3 or pos.shape[0] != 1 or neg.shape != pos.shape:
+            raise ValueError("serve: prompt_embeds / negative_prompt_embeds must both be [1, S, ctx]")
+        if pos.shape[1] > MAX_TEXT_KEYS:
+            raise ValueError(f"serve: {pos.shape[1]} text keys; the batcher's kernels take at most {MAX_TEXT_KEYS} (use txt2img)")
+        if pos.shape[1] != self.text_len:
+            raise ValueError(f"serve: this batcher runs {self.text_len} text keys, the request has {pos.shape[1]}")
+        r = _Request()
+        r.req = request
+        r.future = concurrent.futures.Future()
+        r.steps = int(request.get("num_inference_steps", 25))
+        if r.steps < 1:
+            raise ValueError("serve: num_inference_steps must be >= 1")
+        r.guidance = g
+        r.output_type = request.get("output_type", "latent")
+        dev, dt = self.exec.device, self.exec.dtype
+        r.sig_dev = pipe._schedule(r.steps, request.get("sampler_opt") or {}, dev, dt)      # txt2img's schedule, fp16-rounded
+        sig = getattr(r.sig_dev, "_dsc_host", None)
+        r.sig = sig if sig is not None else r.sig_dev.detach().float().cpu().tolist()
+        r.coeffs = sampling.dpmpp_2m_coefficients(r.sig)
+        kdm = pipe.k_diffusion_model
+        r.scal = []
+        for s_ in r.sig[:len(r.coeffs)]:
+            c_in, _, t = kdm.step_scalars(s_)
+            r.scal.append((c_in, float(t)))
+        ids = request.get("text_input_ids") or [None, None]
+        tabs = encode_region_map(pipe, request.get("region_map_state"), width=self.width, height=self.height,
+                                 num_images_per_prompt=1, text_ids=ids)
+        r.tables = self._request_tables(tabs)
+        if not self._tables_fit([r]):
+            raise ValueError(f"serve: the request's region tables (with the zero row of an idle slot) hold more than "
+                             f"{ops.MAX_REGION_ROWS} distinct rows at some level; run it through txt2img")
+        r.slot, r.i, r.t_done = None, 0, None
+        r.text = (neg, pos)
+        r.t_submit = time.perf_counter()
+        self.exec.prepare(r)
+        return r
+
+    def levels(self):
+        """{L: S} of the region tables at this image size (one level per down block, encode_region_map_function.py)"""
+        out = {}
+        sr = 8
+        for _ in self.pipe.unet.down_blocks:
+            w_r, h_r = -(-self.width // sr), -(-self.height // sr)
+            out[w_r * h_r] = self.text_len
+            sr *= 2
+        return out
+
+    def _request_tables(self, tabs):
+        lv = self.levels()
+        if not isinstance(tabs, dict) or not tabs:                  # no masks: the region path with zero tables (quirk q2)
+            return {L: torch.zeros(2, L, S) for L, S in lv.items()}
+        if sorted(tabs) != sorted(lv) or any(tuple(w.shape) != (2, L, lv[L]) for L, w in tabs.items()):
+            raise ValueError("serve: the request's region tables do not match this batcher's image size / text length")
+        return {L: w.float().cpu() for L, w in tabs.items()}
+
+    # ------------------------------------------------------------------ scheduling (host)
+    def _bucket_for(self, top):
+        return next(b for b in self.buckets if b > top)
+
+    def _tables_fit(self, members):
+        """the union of these requests' table rows compresses at every level (<= 32 distinct rows, zero rows of IDLE slots in)"""
+        for L in self.levels():
+            rows = [r.tables[L].reshape(-1, r.tables[L].shape[-1]) for r in members]
+            rows.append(torch.zeros(1, self.text_len))
+            if ops.compress_region_table(torch.cat(rows)[None]) is None:
+                return False
+        return True
+
+    def _step_locked(self):
+        slots = self._slots
+        active = [r for r in slots if r is not None]
+        stepping = [r for r in active if r.i < len(r.coeffs) and self._n is not None]
+        # admissions: FIFO, lowest free slot, while the union of the tables still compresses
+        joins = []
+        while self._queue:
+            free = next((i for i, r in enumerate(slots) if r is None), None)
+            if free is None:
+                break
+            head = self._queue[0]
+            if not self._tables_fit([r for r in slots if r is not None] + [head]):
+                break
+            self._queue.popleft()
+            head.slot, head.i = free, 0
+            slots[free] = head
+            joins.append(head)
+        if not stepping and not joins:
+            return False
+        # who leaves after this transition: a request whose last step is the one being applied now
+        leaving = [r for r in stepping if r.i + 1 == len(r.coeffs)]
+        staying = [r for r in slots if r is not None and r not in leaving]
+        n_src = self._n or 0
+        n_dst = self._bucket_for(max(r.slot for r in staying)) if staying else None
+        nd = n_dst if n_dst is not None else self.buckets[0]
+        n_slots = max(n_src, nd)
+        recs = []
+        for i in range(n_slots):
+            r = slots[i] if i < len(slots) else None
+            if r is not None and r in stepping:
+                a, b, c = r.coeffs[r.i]
+                rec = {"mode": ops.ROW_STEP, "sigma": r.sig[r.i], "guidance": r.guidance, "a": a, "b": b, "c": c}
+                if r in leaving:
+                    rec.update(c_in_next=0.0, t_next=0.0, sigma_next=1.0, temb_row=None, req=r, step=r.i, next_step=None)
+                else:
+                    j = r.i + 1
+                    rec.update(c_in_next=r.scal[j][0], t_next=r.scal[j][1], sigma_next=max(r.sig[j], 1e-10),
+                               temb_row=self.exec.temb_row(r, j), req=r, step=r.i, next_step=j)
+            elif r is not None and r in joins:
+                rec = {"mode": ops.ROW_JOIN, "c_in_next": r.scal[0][0], "t_next": r.scal[0][1], "sigma_next": r.sig[0],
+                       "temb_row": self.exec.temb_row(r, 0), "req": r, "step": None, "next_step": 0}
+            else:
+                rec = {"mode": ops.ROW_IDLE, "t_next": 0.0, "sigma_next": 1.0, "temb_row": None, "req": None}
+            recs.append(rec)
+        if n_dst is not None:
+            self._ensure(n_dst)
+        for r in joins:
+            self.exec.load_latent(r)
+        self._stats["joins"] += len(joins)
+        self.exec.transition(n_src, nd, recs)
+        for r in leaving:
+            slots[r.slot] = None
+            self._done.append((r, self.exec.finish(r)))
+            self._stats["leaves"] += 1
+        for r in stepping:
+            r.i += 1
+        if n_dst is not None:
+            rows = [slots[i] if i < len(slots) else None for i in range(n_dst)]      # (a bucket may exceed max_batch)
+            members = tuple(None if r is None else r.rid for r in rows)
+            if self._members.get(n_dst) != members:
+                self.exec.refresh(n_dst, rows)
+                self._members[n_dst] = members
+                self._stats["refreshes"] += 1
+            if self._n is not None and n_dst != self._n:
+                self._stats["bucket_switches"] += 1
+            self.exec.run(n_dst)
+            self._stats["steps"] += 1
+        self._n = n_dst
+        return True
+
+    def _ensure(self, n):
+        if self.exec.ensure(n):
+            self._stats["captures"] += 1
+
+    def _poll(self, wait=False):
+        """resolve the futures of requests whose final row copy has completed (in completion order)"""
+        keep = []
+        for r, h in self._done:
+            if wait or self.exec.ready(h):
+                out = self.exec.result(r, h)
+                r.t_done = time.perf_counter()
+                r.future.dsc_latency_s = r.t_done - r.t_submit        # submit -> resolved, for measurement tools
+                if not r.future.done():
+                    r.future.set_result(out)
+            else:
+                keep.append((r, h))
+        self._done = keep
+
+    def _drive(self):
+        self.exec.bind_thread()
+        while True:
+            with self._lock:
+                if self._stop:
+                    return
+                self._poll()
+                if self._step_locked():
+                    # bound how far the host runs ahead of the GPU (a join lands within a few steps, not after every
+                    # step already queued): wait for the step before last, never for the one just queued
+                    self.exec.throttle()
+                elif self._done:
+                    self._wake.wait(0.0005)              # rows in flight: look again soon
+                else:
+                    self._wake.wait()
+
+
+class _GraphExecutor:
+    """The device side on the pipeline's GPU: per-bucket static buffers + captured UNet step, the per-row sampler launch,
+    per-request start latents / time-embedding tables / output rows and completion events."""
+
+    def __init__(self, batcher):
+        self.b = batcher
+        pipe = batcher.pipe
+        self.pipe = pipe
+        unet = pipe.unet
+        self.device = pipe._execution_device
+        self.dtype = unet.dtype
+        if self.device.type != "cuda" or self.dtype != torch.float16:
+            raise NotImplementedError("serve: the batcher runs fp16 on the GPU")
+        if not (ops.USE_TEMB_HOIST and hasattr(unet, "temb_add_table")):
+            raise NotImplementedError("serve: needs the UNet's per-step time-embedding tables (temb_add_table)")
+        if not pipe._all_cross_attention_packable():
+            raise NotImplementedError("serve: every cross-attention head dim must run the prepared-operand kernels "
+                                      "(d % 8 == 0, d <= 160)")
+        c = unet.config.in_channels
+        self.lat_shape = (c, batcher.height // 8, batcher.width // 8)
+        self.ctx = unet.config.cross_attention_dim
+        self.tw = unet.temb_width()
+        mb = max(batcher.max_batch, batcher.buckets[-1])
+        self.stream = torch.cuda.Stream(device=self.device)
+        with torch.cuda.stream(self.stream):
+            self.x = torch.zeros((mb,) + self.lat_shape, device=self.device, dtype=self.dtype)
+            self.old = torch.zeros_like(self.x)
+        self.st = {}
+        self._inflight = collections.deque()
+
+    def bind_thread(self):
+        _lib.check(_lib.load_library().dsc_set_workspace_slot(self.b.slot), "dsc_set_workspace_slot")
+
+    def throttle(self, ahead=2):
+        ev = torch.cuda.Event()
+        ev.record(self.stream)
+        self._inflight.append(ev)
+        while len(self._inflight) > ahead:
+            self._inflight.popleft().synchronize()
+
+    # ---- per request
+    def prepare(self, r):
+        pipe, dev, dt = self.pipe, self.device, self.dtype
+        req = r.req
+        self.stream.wait_stream(torch.cuda.current_stream(dev))      # the caller's tensors were made on its own stream
+        with torch.cuda.stream(self.stream):
+            lat = pipe.prepare_latents(1, self.lat_shape[0], self.b.height, self.b.width, dt, dev, req.get("generator"),
+                                       req.get("latents"))
+            if tuple(lat.shape) != (1,) + self.lat_shape:
+                raise ValueError(f"serve: latents {tuple(lat.shape)}, this batcher needs {(1,) + self.lat_shape}")
+            r.lat = lat * (r.sig_dev[0] ** 2 + 1) ** 0.5                                       # txt2img's op (:1043)
+            ts = [t for _, t in r.scal]
+            r.temb = pipe.unet.temb_add_table(torch.tensor(ts, dtype=torch.float32, device=dev))
+            neg, pos = r.text
+            r.text = (neg.to(device=dev, dtype=dt), pos.to(device=dev, dtype=dt))
+
+    def temb_row(self, r, j):
+        return r.temb[j]
+
+    def load_latent(self, r):
+        with torch.cuda.stream(self.stream):
+            self.x[r.slot].copy_(r.lat[0])
+
+    def finish(self, r):
+        with torch.cuda.stream(self.stream):
+            out = self.x[r.slot:r.slot + 1].clone()
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        return out, ev
+
+    def ready(self, h):
+        return h[1].query()
+
+    def result(self, r, h):
+        out, ev = h
+        ev.synchronize()
+        if r.output_type == "latent":
+            return out
+        with torch.cuda.stream(self.stream):
+            return self.pipe.latent_to_image(out, r.output_type)
+
+    # ---- per bucket
+    def ensure(self, n):
+        """static buffers + captured step of bucket n; True when this call captured it"""
+        if n in self.st:
+            return False
+        from .model_k_diffusion import _CAPTURE_LOCK
+        with _CAPTURE_LOCK:
+            self.bind_thread()
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+            self._capture(n)
+        return True
+
+    def _capture(self, n):
+        pipe, dev, dt = self.pipe, self.device, self.dtype
+        rows = 2 * n
+        S = self.b.text_len
+        with torch.cuda.stream(self.stream):
+            st = {"x_in": torch.zeros((rows,) + self.lat_shape, device=dev, dtype=dt),
+                  "t": torch.zeros(rows, device=dev, dtype=torch.float32),
+                  "sigma": torch.ones(n, device=dev, dtype=torch.float32),
+                  "text": torch.zeros((rows, S, self.ctx), device=dev, dtype=dt),
+                  "tadd": torch.zeros((rows, self.tw), device=dev, dtype=dt)}
+            zero = {L: torch.zeros(rows, L, S_) for L, S_ in self.b.levels().items()}
+            comp = pipe._compress_tables(zero)
+            st["compressed"] = {L: (ids.to(dev), rws.to(dev)) for L, (ids, rws) in comp.items()}
+            st["dense"] = None
+            pipe._refresh_text_kv(st["text"])
+            self._pin_kv()
+        kw = {"region_prompt": {"region_state": zero, "compressed": st["compressed"], "sigma": st["sigma"], "weight_func": None,
+                                "n_std_groups": n, "sigma_per_group": True}}
+        unet = pipe.unet
+
+        def step():
+            return unet(st["x_in"], st["t"], encoder_hidden_states=st["text"], cross_attention_kwargs=kw,
+                        temb_adds=st["tadd"], cfg_shared_prefix=ops.USE_CFG_SHARED_PREFIX).sample
+
+        side = self.stream
+        with torch.cuda.stream(side):
+            for _ in range(2):                       # warm-up: workspaces, kernel selection
+                st["eps"] = step()
+        if ops.GRAPHS_ENABLED:
+            torch.cuda.current_stream(dev).wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                st["eps"] = step()
+            side.wait_stream(torch.cuda.current_stream(dev))
+            st["graph"] = g
+
+            def run():
+                g.replay()
+        else:
+            def run():
+                pipe._refresh_text_kv(st["text"])
+                st["eps"] = step()
+        st["run"] = run
+        self.st[n] = st
+
+    def _pin_kv(self):
+        from .u_net_condition_modify import Attention
+        for m in self.pipe.unet.modules():
+            if isinstance(m, Attention) and m.is_cross_attention and getattr(m, "kv_cache", None) is not None:
+                m.kv_cache["pin"] = True
+
+    def refresh(self, n, members):
+        """text rows, their packed K/V and the compressed tables of bucket n for these slot members (None = IDLE)"""
+        st = self.st[n]
+        S = self.b.text_len
+        with torch.cuda.stream(self.stream):
+            text = st["text"]
+            dense = {}
+            for L in self.b.levels():
+                dense[L] = torch.zeros(2 * n, L, S)
+            for i, r in enumerate(members):
+                if r is None:
+                    text[i].zero_()
+                    text[n + i].zero_()
+                    continue
+                text[i].copy_(r.text[0][0])
+                text[n + i].copy_(r.text[1][0])
+                for L, w in r.tables.items():
+                    dense[L][i] = w[0]
+                    dense[L][n + i] = w[1]
+            self.pipe._refresh_text_kv(text)
+            comp = self.pipe._compress_tables(dense)
+            if comp is None:
+                raise RuntimeError("serve: the admitted requests' tables do not compress (admission check bypassed)")
+            self.pipe._upload_tables(st, comp, dense)
+
+    def transition(self, n_src, n_dst, recs):
+        st_d = self.st.get(n_dst)
+        if st_d is None:
+            self.ensure(n_dst)
+            st_d = self.st[n_dst]
+        eps = self.st[n_src]["eps"] if n_src else None
+        with torch.cuda.stream(self.stream):
+            ops.cfg_dpmpp2m_step_rows(self.x, eps, self.old, n_src, st_d["x_in"], st_d["t"], st_d["sigma"], recs,
+                                      tadd=st_d["tadd"])
+
+    def run(self, n):
+        with torch.cuda.stream(self.stream):
+            self.st[n]["run"]()

@@ -12,6 +12,7 @@ FLAG_REF_FP16_ROUNDING = 1
 FLAG_BIAS_IS_FINAL = 2
 FLAG_REUSE_STATS = 4
 FLAG_ROWS_PADDED = 256
+FLAG_SIGMA_PER_GROUP = 512
 REGION_ROW_STRIDE = 100    # region_xattn_packed.hip kBP: the forward kernel's LDS bias-table row stride (floats)
 
 def _stream_ptr(t):
@@ -87,7 +88,8 @@ def _blhd_strides(t, layout):
 
 
 def region_xattn(q, k, v, region=None, sigma=1.0, *, layout="bhld", n_std_groups=1, scale=None,
-                 ref_fp16_rounding=True, bias_is_final=False, out=None, reuse_stats=False, debug_flags=0):
+                 ref_fp16_rounding=True, bias_is_final=False, out=None, reuse_stats=False, debug_flags=0,
+                 per_group_sigma=False):
     """softmax(scale*q.k^T + region*sigma*std) . v  on the GPU (dsc_region_xattn_fwd).
 
     layout 'bhld': q [Bc,H,L,d], k/v [Bc,H,S,d] -> out [Bc,H,L,d] (the shape of
@@ -95,6 +97,8 @@ def region_xattn(q, k, v, region=None, sigma=1.0, *, layout="bhld", n_std_groups
     layout 'blhd': q [Bc,L,H,d], k/v [Bc,S,H,d] (views of the projection outputs) -> out [Bc,L,H,d] contiguous,
                    i.e. already the [Bc, L, H*d] tensor `to_out[0]` consumes.
     region: fp32 [Bw,L,S] on the same device or None.  sigma: python float or a 0-dim/1-element fp32 CUDA tensor.
+    per_group_sigma: sigma is an [n_std_groups] fp32 CUDA tensor and batch row b uses sigma[b % n_std_groups]
+    (DSC_FLAG_SIGMA_PER_GROUP; continuous batching).  Never inferred from sigma's size.
     """
     _require_gpu(q, k, v, region)
     lib = _lib.load_library()
@@ -120,7 +124,9 @@ def region_xattn(q, k, v, region=None, sigma=1.0, *, layout="bhld", n_std_groups
         Bw = region.shape[0]
         rptr = ctypes.c_void_p(region.data_ptr())
     sig_host, sig_dev = 0.0, None
-    if isinstance(sigma, torch.Tensor):
+    if per_group_sigma:
+        sig_dev = _group_sigma_ptr(sigma, n_std_groups, q.device, "region_xattn")
+    elif isinstance(sigma, torch.Tensor):
         if sigma.is_cuda and sigma.dtype == torch.float32:
             sig_dev = ctypes.c_void_p(sigma.data_ptr())
         else:
@@ -128,7 +134,7 @@ def region_xattn(q, k, v, region=None, sigma=1.0, *, layout="bhld", n_std_groups
     else:
         sig_host = float(sigma)
     flags = (FLAG_REF_FP16_ROUNDING if ref_fp16_rounding else 0) | (FLAG_BIAS_IS_FINAL if bias_is_final else 0) \
-        | (FLAG_REUSE_STATS if reuse_stats else 0) | debug_flags
+        | (FLAG_REUSE_STATS if reuse_stats else 0) | (FLAG_SIGMA_PER_GROUP if per_group_sigma else 0) | debug_flags
     nbytes = lib.dsc_region_xattn_workspace_bytes(Bc, H, L, S, d, n_std_groups)
     ws = _workspace(q.device, nbytes)
     rc = lib.dsc_region_xattn_fwd(
@@ -139,6 +145,14 @@ def region_xattn(q, k, v, region=None, sigma=1.0, *, layout="bhld", n_std_groups
         ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, _stream_ptr(q))
     _lib.check(rc, "dsc_region_xattn_fwd")
     return out
+
+
+def _group_sigma_ptr(sigma, n_std_groups, device, what):
+    """per_group_sigma=True: one fp32 sigma per std group, dense on the attention's device"""
+    if not (isinstance(sigma, torch.Tensor) and sigma.is_cuda and sigma.dtype == torch.float32 and sigma.dim() == 1
+            and sigma.numel() == n_std_groups and sigma.is_contiguous() and sigma.device == device):
+        raise ValueError(f"{what}: per_group_sigma needs a dense [n_std_groups={n_std_groups}] fp32 tensor on {device}")
+    return ctypes.c_void_p(sigma.data_ptr())
 
 
 def xattn_kv_pack(k, v, *, layout="blhd", out=None):
@@ -206,9 +220,10 @@ def pad_region_rows(rows):
 
 
 def region_xattn_packed(q, packed_kv, S, region=None, sigma=1.0, *, n_std_groups=1, scale=None, ref_fp16_rounding=True,
-                        out=None, reuse_stats=False, debug_flags=0):
+                        out=None, reuse_stats=False, debug_flags=0, per_group_sigma=False):
     """dsc_region_xattn_fwd_packed: q [Bc,L,H,d] view, packed_kv from xattn_kv_pack, region = (ids, rows) from
-    compress_region_table (device tensors; rows optionally through pad_region_rows) or None -> out [Bc,L,H,d] contiguous."""
+    compress_region_table (device tensors; rows optionally through pad_region_rows) or None -> out [Bc,L,H,d] contiguous.
+    per_group_sigma: as region_xattn."""
     _require_gpu(q, packed_kv)
     lib = _lib.load_library()
     qs, (Bc, H, L, d) = _blhd_strides(q, "blc")
@@ -223,11 +238,14 @@ def region_xattn_packed(q, packed_kv, S, region=None, sigma=1.0, *, n_std_groups
         ids, rows = region
         Bw, nrows = ids.shape[0], rows.shape[0]
     sig_host, sig_dev = 0.0, None
-    if isinstance(sigma, torch.Tensor) and sigma.is_cuda and sigma.dtype == torch.float32:
+    if per_group_sigma:
+        sig_dev = _group_sigma_ptr(sigma, n_std_groups, q.device, "region_xattn_packed")
+    elif isinstance(sigma, torch.Tensor) and sigma.is_cuda and sigma.dtype == torch.float32:
         sig_dev = ctypes.c_void_p(sigma.data_ptr())
     else:
         sig_host = float(sigma)
-    flags = (FLAG_REF_FP16_ROUNDING if ref_fp16_rounding else 0) | (FLAG_REUSE_STATS if reuse_stats else 0) | debug_flags
+    flags = (FLAG_REF_FP16_ROUNDING if ref_fp16_rounding else 0) | (FLAG_REUSE_STATS if reuse_stats else 0) \
+        | (FLAG_SIGMA_PER_GROUP if per_group_sigma else 0) | debug_flags
     if rows is not None and rows.shape[1] == REGION_ROW_STRIDE and S <= 96:      # pad_region_rows() form ([NU, S] has S <= 96 columns)
         flags |= FLAG_ROWS_PADDED
     ws = _workspace(q.device, lib.dsc_region_xattn_workspace_bytes(Bc, H, L, S, d, n_std_groups))
@@ -996,6 +1014,61 @@ def cfg_dpmpp2m_step(x, eps, old, sigma, guidance, a, b, c, c_in_next, t_next, s
                                                   sigma_next, _p(x_in), _p(t_buf), _p(sigma_buf), n_img, chw, 0, *rargs,
                                                   _stream_ptr(x))
     _lib.check(rc, "dsc_cfg_dpmpp2m_step")
+
+
+ROW_STEP, ROW_JOIN, ROW_IDLE = 0, 1, 2
+ROW_STEP_MAX_SLOTS = 16
+
+
+class RowStep(ctypes.Structure):
+    """dsc_row_step (include/dsc_hip.h)"""
+    _fields_ = [("mode", ctypes.c_int), ("sigma", ctypes.c_float), ("guidance", ctypes.c_float), ("a", ctypes.c_float),
+                ("b", ctypes.c_float), ("c", ctypes.c_float), ("c_in_next", ctypes.c_float), ("t_next", ctypes.c_float),
+                ("sigma_next", ctypes.c_float), ("temb_row", ctypes.c_void_p)]
+
+
+def cfg_dpmpp2m_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=None):
+    """Per-request sampler step of a continuous batch (dsc_cfg_dpmpp2m_step_rows): slot i = latent row i of x / old, rows
+    {i, n_src + i} of eps (the bucket that just ran; eps may be None when no slot steps) and rows {i, n' + i} of x_in / t_buf /
+    tadd (the bucket that runs next, n' = t_buf.numel() // 2); sigma_groups [n'] fp32.  rows: one dict per slot with `mode`
+    (ROW_STEP / ROW_JOIN / ROW_IDLE), the scalars of dsc_row_step and `temb_row` (an fp16 [tadd width] tensor or None); at least
+    n' of them.  x / old hold at least len(rows) latent rows."""
+    _require_gpu(x, old, x_in, t_buf, sigma_groups)
+    n_dst = t_buf.numel() // 2
+    n_slots = len(rows)
+    if not 1 <= n_dst <= n_slots <= ROW_STEP_MAX_SLOTS:
+        raise ValueError(f"cfg_dpmpp2m_step_rows: {n_slots} records for a {n_dst}-row bucket (at most {ROW_STEP_MAX_SLOTS})")
+    if x.shape[0] < n_slots or old.shape != x.shape:
+        raise ValueError("cfg_dpmpp2m_step_rows: x / old need a latent row per slot")
+    chw = x.numel() // x.shape[0]
+    for name, t, nr in (("x", x, None), ("old", old, None), ("x_in", x_in, 2 * n_dst), ("eps", eps, 2 * n_src), ("tadd", tadd, 2 * n_dst)):
+        if t is None:
+            continue
+        if t.dtype != torch.float16 or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"cfg_dpmpp2m_step_rows: {name} must be dense fp16 on {x.device}")
+        if nr is not None and t.shape[0] != nr:
+            raise ValueError(f"cfg_dpmpp2m_step_rows: {name} has {t.shape[0]} rows, need {nr}")
+        if name in ("x_in", "eps") and t.numel() != nr * chw:
+            raise ValueError(f"cfg_dpmpp2m_step_rows: {name} rows are not [{chw}] latents")
+    for name, t, n in (("t_buf", t_buf, 2 * n_dst), ("sigma_groups", sigma_groups, n_dst)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device or t.numel() != n:
+            raise ValueError(f"cfg_dpmpp2m_step_rows: {name} must be a dense fp32 [{n}] on {x.device}")
+    recs = (RowStep * n_slots)()
+    for i, r in enumerate(rows):
+        tr = r.get("temb_row")
+        if tr is not None:
+            if tadd is None or tr.dtype != torch.float16 or tr.device != x.device or tr.stride(-1) != 1 \
+                    or tr.numel() != tadd.shape[1]:
+                raise ValueError("cfg_dpmpp2m_step_rows: temb_row must be an fp16 row of the tadd buffer's width")
+        recs[i] = RowStep(int(r["mode"]), *(float(r.get(f, 0.0)) for f in ("sigma", "guidance", "a", "b", "c", "c_in_next",
+                                                                             "t_next")),
+                          float(r.get("sigma_next", 1.0)), None if tr is None else tr.data_ptr())
+    for t in (x, old, x_in, t_buf, sigma_groups, tadd):
+        _drop_gn_partials(t)
+    rc = _lib.load_library().dsc_cfg_dpmpp2m_step_rows(
+        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
+        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), n_slots, chw, 0, _stream_ptr(x))
+    _lib.check(rc, "dsc_cfg_dpmpp2m_step_rows")
 
 
 def dpmpp2m_update(x, denoised, old, a, b, c):

@@ -43,6 +43,9 @@ extern "C" {
                                           of [n_rows][S]: the table goes to LDS as a flat 16-byte copy.  S <= 96 only. */
 #define DSC_FLAG_BIAS_IS_FINAL     2u  /* `region` already holds the additive bias (a custom weight_func was
                                           evaluated by the caller): add it as is, skip the statistics pass */
+#define DSC_FLAG_SIGMA_PER_GROUP 512u  /* dsc_region_xattn_fwd / _fwd_packed: `sigma_dev` points to n_std_groups floats and
+                                          batch row b uses sigma_dev[b % n_std_groups] (the row's std group; a continuous
+                                          batch of requests at different sigmas).  Needs sigma_dev. */
 
 /* ABI version of this header; bumped on any signature change. */
 int dsc_abi_version(void);
@@ -187,6 +190,32 @@ int dsc_cfg_dpmpp2m_step(void* x, const void* eps, void* old, float sigma, float
                          float a, float b, float c, float c_in_next, float t_next, float sigma_next,
                          void* x_in, float* t_buf, float* sigma_buf, int n_img, int chw, int dtype,
                          const void* row_src, void* row_dst, int row_halfs, int row_copies, void* stream);
+/*
+ * Per-request variant of dsc_cfg_dpmpp2m_step for continuous batching: request slot i is latent row i of x / old, rows
+ * {i, n_src + i} of eps (the bucket that just ran, [u_0..u_{n_src-1}, c_0..c_{n_src-1}]) and rows {i, n_dst + i} of x_in,
+ * t_buf and tadd (the bucket that runs next); sigma_groups[i] is its std group's sigma.  One record per slot, passed BY VALUE
+ * in the kernel arguments (at most DSC_ROW_STEP_MAX_SLOTS, 48 bytes each), so the host may reuse its record array at once.
+ *   DSC_ROW_STEP: the arithmetic and fp16 rounding points of dsc_cfg_dpmpp2m_step with this slot's scalars (i < n_src);
+ *                 the next-step values are those of the coming step (for a request that has just finished: any finite ones)
+ *   DSC_ROW_JOIN: x[i] already holds the start latent: x_in rows = x[i] * c_in_next, old[i] = 0 (dsc_prepare_unet_input's line)
+ *   DSC_ROW_IDLE: padding: x_in rows = 0, sigma_groups[i] = 1
+ * Every slot i < n_dst writes t_next into t_buf rows {i, n_dst + i}, its sigma (sigma_next; 1 for IDLE) into sigma_groups[i]
+ * and, when temb_row != NULL, copies temb_row (tadd_halfs fp16) into tadd rows {i, n_dst + i}.  Slots i >= n_dst write no
+ * destination row (only STEP or IDLE there).  n_slots >= n_dst records.  chw % 8 == 0, tadd_halfs % 8 == 0, 16-byte aligned.
+ */
+#define DSC_ROW_STEP 0
+#define DSC_ROW_JOIN 1
+#define DSC_ROW_IDLE 2
+#define DSC_ROW_STEP_MAX_SLOTS 16
+typedef struct {
+    int   mode;                                    /* DSC_ROW_STEP, DSC_ROW_JOIN, DSC_ROW_IDLE */
+    float sigma, guidance, a, b, c;                /* this step (STEP) */
+    float c_in_next, t_next, sigma_next;           /* what the coming UNet step reads */
+    const void* temb_row;                          /* fp16 time-embedding row for the coming step, or NULL */
+} dsc_row_step;
+int dsc_cfg_dpmpp2m_step_rows(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf, float* sigma_groups,
+                              void* tadd, int tadd_halfs, int n_dst, const dsc_row_step* rows /* host */, int n_slots,
+                              int chw, int dtype, void* stream);
 /* out = a*x + b*denoised + c*old  (old may be NULL when c == 0): the sampler update alone, for callers that keep
  * the reference's `sampler(model_fn, x, sigmas=...)` control flow.  n elements, n % 8 == 0. */
 int dsc_dpmpp2m_update(const void* x, const void* denoised, const void* old, float a, float b, float c,

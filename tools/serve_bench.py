@@ -1,0 +1,221 @@
+"""Continuous-batching serving measurements (modules/serving.py) on one GPU; one JSON line per leg.
+
+    python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0]
+
+Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
+latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
+  saturated   8 slots kept full, 25 steps each: images/s of the batcher (one and two batchers in flight) beside
+              txt2img_coalesced at k = 8 (one and two in flight) on the same requests in the same process
+  staggered   Poisson arrivals at each rate, mixed step counts (20/25/30) and guidance scales (5/7.5): images/s and p50/p95
+              request latency of the batcher against one-at-a-time txt2img and lockstep txt2img_coalesced batches of 8
+  join        the stall a join puts on the running rows: host ms of a step that admits a request (text K/V refresh, table
+              compression and upload) minus that of a plain step, with the GPU time of the refresh
+  stats       the batcher's counters; captures after warm() must be 0
+"""
+import argparse
+import json
+import os
+import random
+import sys
+import threading
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+
+from inputs import FakeTokenizer  # noqa: E402
+
+
+def emit(**kw):
+    print(json.dumps(kw), flush=True)
+
+
+def make_requests(n, seed):
+    tok = FakeTokenizer()
+    out = []
+    for i in range(n):
+        regions = (2, 1, 4)[i % 3]
+        words = [f"object{r}a object{r}b" for r in range(regions)]
+        ids = [49406, 320]
+        for w in words:
+            ids += tok(w).input_ids
+        ids = ids + [49407] * (77 - len(ids))
+        pos = np.array([ids], dtype=np.int64)
+        state = {}
+        for r, w in enumerate(words):
+            m = np.full((512, 512), 255, dtype=np.uint8)
+            x0, x1 = (r * 8) // regions, ((r + 1) * 8) // regions
+            m[128:384, x0 * 64:x1 * 64] = 0
+            state[w] = {"map": m, "weight": 0.5, "mask_outsides": 0.0}
+        emb = torch.randn(2, 77, 768, generator=torch.Generator().manual_seed(seed * 1000 + 70 + i)).half().cuda()
+        lat = torch.randn(1, 4, 64, 64, generator=torch.Generator().manual_seed(seed * 1000 + 1000 + i)).half().cuda()
+        out.append({"prompt_embeds": emb[1:2], "negative_prompt_embeds": emb[0:1], "text_input_ids": [pos.copy(), pos],
+                    "region_map_state": state, "latents": lat})
+    return out
+
+
+def pct(v, p):
+    return float(np.percentile(np.array(v), p)) if v else None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--requests", type=int, default=16)
+    ap.add_argument("--rates", default="2,6", help="Poisson arrival rates, requests/s")
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    from diffusionspatialcontrol_amd.modules.model_k_diffusion import SD15Scheduler, StableDiffusionPipeline
+    from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNet2DConditionModel, UNetConfig
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        unet = UNet2DConditionModel(UNetConfig.sd15())
+    pipe = StableDiffusionPipeline(None, None, FakeTokenizer(), unet.half().eval(), SD15Scheduler())
+    opt = {"scheduler": "karras"}
+    reqs = make_requests(a.requests, a.seed)
+    kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    # ---- saturated
+    b0 = pipe.serve(512, 512, max_batch=8, slot=0).warm()
+    b1 = pipe.serve(512, 512, max_batch=8, slot=1).warm()
+    b0.run_until_idle()
+    for r in reqs[:8]:                                   # one untimed pass (allocator, kernel selection at every bucket)
+        b0.submit(dict(r, **kw25))
+    b0.run_until_idle()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    futs = [b0.submit(dict(r, **kw25)) for r in reqs]
+    b0.run_until_idle()
+    torch.cuda.synchronize()
+    serve1 = len(reqs) / (time.perf_counter() - t0)
+    half = len(reqs) // 2
+    t0 = time.perf_counter()
+    b0.start()
+    b1.start()
+    futs = [b0.submit(dict(r, **kw25)) for r in reqs[:half]] + [b1.submit(dict(r, **kw25)) for r in reqs[half:]]
+    for f in futs:
+        f.result()
+    torch.cuda.synchronize()
+    serve2 = len(reqs) / (time.perf_counter() - t0)
+    b0.stop()
+    b1.stop()
+    groups = [reqs[i:i + 8] for i in range(0, len(reqs) - 7, 8)]
+    pipe.txt2img_coalesced(groups[0], height=512, width=512, output_type="latent", **kw25)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for g in groups:
+        pipe.txt2img_coalesced(g, height=512, width=512, output_type="latent", **kw25)
+    torch.cuda.synchronize()
+    co1 = 8 * len(groups) / (time.perf_counter() - t0)
+    co2 = None
+    if len(groups) >= 2:
+        pipe.txt2img_coalesced(groups[1], height=512, width=512, output_type="latent", slot=1, **kw25)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ths = [threading.Thread(target=lambda g_, s_: (torch.cuda.set_stream(torch.cuda.Stream()),
+                                                        pipe.txt2img_coalesced(g_, height=512, width=512, output_type="latent",
+                                                                               slot=s_, **kw25)), args=(g, i % 2))
+               for i, g in enumerate(groups[:2])]
+        for t in ths:
+            t.start()
+        for t in ths:
+            t.join()
+        torch.cuda.synchronize()
+        co2 = 16 / (time.perf_counter() - t0)
+    emit(leg="saturated", requests=len(reqs), steps=25, serve_one_in_flight_img_s=round(serve1, 2),
+         serve_two_in_flight_img_s=round(serve2, 2), coalesced_k8_one_in_flight_img_s=round(co1, 2),
+         coalesced_k8_two_in_flight_img_s=None if co2 is None else round(co2, 2))
+
+    # ---- staggered arrivals
+    rng = random.Random(a.seed)
+    mix = [dict(num_inference_steps=rng.choice((20, 25, 30)), guidance_scale=rng.choice((5.0, 7.5)), sampler_opt=opt)
+           for _ in reqs]
+    single_s = {}
+    for steps in (20, 25, 30):                          # one-at-a-time txt2img: service time per step count
+        r = reqs[0]
+        pipe.txt2img(None, height=512, width=512, sampler_name="sample_dpmpp_2m", latents=r["latents"],
+                     region_map_state=r["region_map_state"], prompt_embeds=r["prompt_embeds"],
+                     negative_prompt_embeds=r["negative_prompt_embeds"], text_input_ids=r["text_input_ids"],
+                     output_type="latent", num_inference_steps=steps, sampler_opt=opt)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pipe.txt2img(None, height=512, width=512, sampler_name="sample_dpmpp_2m", latents=r["latents"],
+                     region_map_state=r["region_map_state"], prompt_embeds=r["prompt_embeds"],
+                     negative_prompt_embeds=r["negative_prompt_embeds"], text_input_ids=r["text_input_ids"],
+                     output_type="latent", num_inference_steps=steps, sampler_opt=opt)
+        torch.cuda.synchronize()
+        single_s[steps] = time.perf_counter() - t0
+    co_batch_s = 8 / co1
+    for rate in (float(x) for x in a.rates.split(",")):
+        gaps = [rng.expovariate(rate) for _ in reqs]
+        arrive = list(np.cumsum(gaps))
+        b0.start()
+        t0 = time.perf_counter()
+        futs, sub_t = [], []
+        for r, m, at in zip(reqs, mix, arrive):
+            dt = t0 + at - time.perf_counter()
+            if dt > 0:
+                time.sleep(dt)
+            sub_t.append(time.perf_counter())
+            futs.append(b0.submit(dict(r, **m)))
+        lat = [f.result() is not None and f.dsc_latency_s for f in futs]       # submit -> future resolved (step-granular)
+        end = time.perf_counter()
+        b0.stop()
+        # one-at-a-time txt2img (a FIFO queue, service time measured above) and lockstep batches of 8 (a batch starts when
+        # 8 requests have arrived and the previous batch is done; all its requests share the batch's 25-step schedule)
+        free, sl = 0.0, []
+        for at, m in zip(arrive, mix):
+            s_ = max(free, at)
+            free = s_ + single_s[m["num_inference_steps"]]
+            sl.append(free - at)
+        free, cl = 0.0, []
+        for i in range(0, len(arrive) - 7, 8):
+            s_ = max(free, arrive[i + 7])
+            free = s_ + co_batch_s
+            cl += [free - at for at in arrive[i:i + 8]]
+        emit(leg="staggered", rate_req_s=rate, requests=len(reqs), serve_img_s=round(len(reqs) / (end - t0), 2),
+             serve_p50_s=pct(lat, 50), serve_p95_s=pct(lat, 95),
+             txt2img_serial_p50_s=pct(sl, 50), txt2img_serial_p95_s=pct(sl, 95),
+             coalesced_lockstep_p50_s=pct(cl, 50), coalesced_lockstep_p95_s=pct(cl, 95),
+             note="txt2img / coalesced latencies are queueing models over service times measured in this process")
+
+    # ---- join cost
+    b0.submit(dict(reqs[0], num_inference_steps=30, guidance_scale=7.5, sampler_opt=opt))
+    b0.step()
+    for _ in range(3):
+        b0.step()
+    torch.cuda.synchronize()
+    plain = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        b0.step()
+        plain.append(time.perf_counter() - t0)
+    torch.cuda.synchronize()
+    join = []
+    for r in reqs[1:4]:
+        b0.submit(dict(r, num_inference_steps=30, guidance_scale=7.5, sampler_opt=opt))
+        t0 = time.perf_counter()
+        b0.step()
+        join.append(time.perf_counter() - t0)
+        b0.step()
+    torch.cuda.synchronize()
+    members = [b0._slots[i] if i < len(b0._slots) else None for i in range(max(b0.exec.st))]
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.cuda.stream(b0.exec.stream):
+        e0.record()
+        b0.exec.refresh(max(b0.exec.st), members)
+        e1.record()
+    torch.cuda.synchronize()
+    b0.run_until_idle()
+    emit(leg="join", plain_step_host_ms=round(1e3 * float(np.median(plain)), 3),
+         join_step_host_ms=round(1e3 * float(np.median(join)), 3),
+         join_stall_host_ms=round(1e3 * (float(np.median(join)) - float(np.median(plain))), 3),
+         text_kv_table_refresh_gpu_ms=round(e0.elapsed_time(e1), 3), bucket=max(b0.exec.st))
+    emit(leg="stats", slot0=b0.stats(), slot1=b1.stats())
+
+
+if __name__ == "__main__":
+    main()
