@@ -183,6 +183,106 @@ __global__ __launch_bounds__(256) void step_rows_kernel(half_t* x, const half_t*
     }
 }
 
+// dsc_cfg_dpmpp2m_step_rows_known: step_rows_kernel plus, per slot, the known region of an inpainting request blended into the
+// model input (what the eager hook of `inpaiting` did per model call, reference model_k_diffusion.py:1599-1612).  A slot whose
+// record has no image runs step_rows_kernel's arithmetic unchanged (same bits); JOIN / IDLE slots never look at the record.
+struct RowKnowns { dsc_row_known r[DSC_ROW_STEP_MAX_SLOTS]; };
+
+__global__ __launch_bounds__(256) void step_rows_known_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
+                                                              float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
+                                                              int n_dst, int chw, const RowSteps rs, const RowKnowns ks) {
+    const int i = blockIdx.y;
+    const dsc_row_step& r = rs.r[i];
+    const dsc_row_known& kr = ks.r[i];
+    const bool dst = i < n_dst;
+    const long long v8 = chw / 8;
+    if (dst && r.temb_row) {
+        const int t8 = tadd_halfs / 8;
+        for (int j = blockIdx.x * 256 + threadIdx.x; j < 2 * t8; j += gridDim.x * 256) {
+            const int h = j >= t8, c = j - h * t8;
+            *reinterpret_cast<h8_t*>(tadd + ((long long)(h ? n_dst + i : i) * tadd_halfs) + c * 8) =
+                reinterpret_cast<const h8_t*>(r.temb_row)[c];
+        }
+    }
+    half_t* xi_u = x_in + (long long)i * chw;
+    half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
+    if (r.mode == DSC_ROW_STEP) {
+        const float sigma = r.sigma, g = r.guidance, a = r.a, b = r.b, c = r.c, c_in_next = r.c_in_next;
+        const float sigma_next = r.sigma_next;
+        const half_t* img = static_cast<const half_t*>(kr.image);
+        const half_t* nse = static_cast<const half_t*>(kr.noise);
+        const half_t* msk = static_cast<const half_t*>(kr.mask);
+        const bool now = img && kr.blend_now, next = img && kr.blend_next && dst;
+        half_t* xr = x + (long long)i * chw;
+        half_t* orow = old + (long long)i * chw;
+        const half_t* eur = eps + (long long)i * chw;
+        const half_t* ecr = eps + (long long)(n_src + i) * chw;
+        for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
+            float xv[8], eu[8], ec[8], ov[8], dn[8], xn[8], xi[8], im[8], nz[8], mk[8];
+            unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), xv);
+            unpack8(*reinterpret_cast<const h8_t*>(eur + k * 8), eu);
+            unpack8(*reinterpret_cast<const h8_t*>(ecr + k * 8), ec);
+            unpack8(*reinterpret_cast<const h8_t*>(orow + k * 8), ov);
+            if (now || next) {
+                unpack8(*reinterpret_cast<const h8_t*>(img + k * 8), im);
+                unpack8(*reinterpret_cast<const h8_t*>(nse + k * 8), nz);
+                unpack8(*reinterpret_cast<const h8_t*>(msk + k * 8), mk);
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                // step_rows_kernel's lines; the model input xh replaces x in D only - the sampler's own state stays unblended
+                const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
+                float xh = xv[j];
+                if (now) {
+                    const float kn = as_f32(__builtin_fmaf(sigma, nz[j], im[j]));          // known region at this sigma
+                    xh = as_f32(__builtin_fmaf(mk[j], xv[j], as_f32((1.0f - mk[j]) * kn)));
+                }
+                dn[j] = (float)(half_t)as_f32(__builtin_fmaf(-sigma, e, xh));
+                const float bd = as_f32(b * dn[j]);
+                xn[j] = (float)(half_t)as_f32(__builtin_fmaf(c, ov[j], as_f32(__builtin_fmaf(a, xv[j], bd))));
+                float xo = xn[j];
+                if (next) {
+                    const float kn = as_f32(__builtin_fmaf(sigma_next, nz[j], im[j]));     // ... and at the coming one
+                    xo = as_f32(__builtin_fmaf(mk[j], xn[j], as_f32((1.0f - mk[j]) * kn)));
+                }
+                xi[j] = as_f32(xo * c_in_next);
+            }
+            *reinterpret_cast<h8_t*>(orow + k * 8) = pack8(dn);
+            *reinterpret_cast<h8_t*>(xr + k * 8) = pack8(xn);
+            if (dst) {
+                const h8_t o = pack8(xi);
+                *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
+                *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+            }
+        }
+    } else if (dst) {
+        const bool join = r.mode == DSC_ROW_JOIN;
+        const float c_in = r.c_in_next;
+        const half_t* xr = x + (long long)i * chw;
+        half_t* orow = old + (long long)i * chw;
+        for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
+            h8_t o;
+            if (join) {                                            // a request's first model call is never blended
+                float f[8];
+                unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), f);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) f[j] = as_f32(f[j] * c_in);
+                o = pack8(f);
+                *reinterpret_cast<h8_t*>(orow + k * 8) = h8_t{};
+            } else {
+                o = h8_t{};
+            }
+            *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
+            *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+        }
+    }
+    if (dst && blockIdx.x == 0 && threadIdx.x == 0) {
+        t_buf[i] = r.t_next;
+        t_buf[n_dst + i] = r.t_next;
+        sigma_groups[i] = r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next;
+    }
+}
+
 int grid_for(long long n8) {
     long long g = (n8 + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
@@ -272,5 +372,49 @@ extern "C" int dsc_cfg_dpmpp2m_step_rows(void* x, const void* eps, void* old, in
     DSC_LAUNCH(step_rows_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
                static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
                static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs);
+    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+}
+
+extern "C" int dsc_cfg_dpmpp2m_step_rows_known(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
+                                               float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
+                                               const dsc_row_step* rows, const dsc_row_known* known, int n_slots, int chw,
+                                               int dtype, void* stream) {
+    if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || !known || n_src < 0 || n_dst <= 0 || chw <= 0)
+        return DSC_ERR_BAD_ARG;
+    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
+    if (dtype != DSC_F16 || chw % 8 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
+    RowSteps rs{};
+    RowKnowns ks{};
+    bool any_row = false;
+    for (int i = 0; i < n_slots; ++i) {
+        const dsc_row_step& r = rows[i];
+        if (r.mode == DSC_ROW_STEP) {
+            if (!eps || i >= n_src) return DSC_ERR_BAD_ARG;
+            const dsc_row_known& k = known[i];
+            const int set = (k.image != nullptr) + (k.noise != nullptr) + (k.mask != nullptr);
+            if (set != 0 && set != 3) return DSC_ERR_BAD_ARG;
+            if (set && (!al16(k.image) || !al16(k.noise) || !al16(k.mask))) return DSC_ERR_UNSUPPORTED;
+            ks.r[i] = k;
+        } else if (r.mode == DSC_ROW_JOIN) {
+            if (i >= n_dst) return DSC_ERR_BAD_ARG;
+        } else if (r.mode != DSC_ROW_IDLE) {
+            return DSC_ERR_BAD_ARG;
+        }
+        if (r.temb_row) {
+            if (!al16(r.temb_row)) return DSC_ERR_UNSUPPORTED;
+            any_row = true;
+        }
+        rs.r[i] = r;
+    }
+    if (any_row) {
+        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
+        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
+    }
+    const long long v8 = chw / 8;
+    long long gx = (v8 + 255) / 256;
+    gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
+    DSC_LAUNCH(step_rows_known_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
+               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
+               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs, ks);
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }

@@ -16,6 +16,12 @@ per slot its own sigma, guidance, DPM++ 2M coefficients (c = 0 on a request's fi
 next bucket's graph replays.  No host<->device synchronisation per step: a request's completion is a CUDA event recorded after
 the copy of its final latent row, and futures resolve when those events are seen complete.
 
+Image-conditioned requests.  A request with `image` is img2img (the last `strength` fraction of its schedule, started from
+`image_latents + noise * sqrt(sigma_0^2 + 1)`, the pipeline method's line); with `mask_image` too it is inpainting on the 4-channel
+UNet: its image latents, noise and mask rows stay on the device while it runs, and the per-row step blends the known region into
+the model input of every model call after its first (dsc_cfg_dpmpp2m_step_rows_known, what `inpaiting`'s eager hook does per
+call).  That launch replaces the plain one only for transitions in which an inpainting slot steps.
+
 The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
 request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
 """
@@ -35,9 +41,21 @@ MAX_TEXT_KEYS = 384                  # the chunked prepared-operand kernels (ops
 _UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter", "ip_adapter_image", "ip_adapter_image_embeds")
 
 
+def _spatial_size(image):
+    """(height, width) of a tensor (NCHW / CHW / HW), a numpy array (HW / HWC / NCHW) or a PIL image"""
+    if torch.is_tensor(image):
+        return tuple(int(v) for v in image.shape[-2:])
+    if hasattr(image, "size") and not hasattr(image, "shape"):              # PIL: (width, height)
+        return (int(image.size[1]), int(image.size[0]))
+    shape = tuple(getattr(image, "shape", ()))
+    if len(shape) == 3:
+        return (int(shape[0]), int(shape[1]))
+    return tuple(int(v) for v in shape[-2:])
+
+
 class _Request:
     __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
-                 "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done")
+                 "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known")
 
 
 class ServingBatcher:
@@ -171,12 +189,15 @@ class ServingBatcher:
         r.steps = int(request.get("num_inference_steps", 25))
         if r.steps < 1:
             raise ValueError("serve: num_inference_steps must be >= 1")
+        t_start = self._image_request(r)
         r.guidance = g
         r.output_type = request.get("output_type", "latent")
         dev, dt = self.exec.device, self.exec.dtype
         r.sig_dev = pipe._schedule(r.steps, request.get("sampler_opt") or {}, dev, dt)      # txt2img's schedule, fp16-rounded
         sig = getattr(r.sig_dev, "_dsc_host", None)
         r.sig = sig if sig is not None else r.sig_dev.detach().float().cpu().tolist()
+        if t_start:                                                  # img2img / inpaiting keep the schedule's tail (:637-647)
+            r.sig, r.sig_dev = r.sig[t_start:], r.sig_dev[t_start:]
         r.coeffs = sampling.dpmpp_2m_coefficients(r.sig)
         kdm = pipe.k_diffusion_model
         r.scal = []
@@ -193,8 +214,52 @@ class ServingBatcher:
         r.slot, r.i, r.t_done = None, 0, None
         r.text = (neg, pos)
         r.t_submit = time.perf_counter()
-        self.exec.prepare(r)
+        if r.kind == "txt2img":
+            self.exec.prepare(r)
+        else:
+            self.exec.prepare_image(r)
         return r
+
+    def _image_request(self, r):
+        """kind / strength of the request and the submit-time rejections of the image keys -> first index of its schedule"""
+        req, pipe = r.req, self.pipe
+        image, mask = req.get("image"), req.get("mask_image")
+        r.kind, r.strength, r.known = "txt2img", 1.0, None
+        if req.get("padding_mask_crop") is not None:
+            raise ValueError("serve: `padding_mask_crop` is not supported (use inpaiting)")
+        if req.get("upscale"):
+            raise ValueError("serve: `upscale` (the hires pass) is not supported (use the pipeline methods)")
+        if image is None:
+            if mask is not None:
+                raise ValueError("serve: `mask_image` needs `image`")
+            if req.get("strength") is not None:
+                raise ValueError("serve: `strength` needs `image` (txt2img starts from pure noise)")
+            return 0
+        r.kind = "img2img" if mask is None else "inpaint"
+        r.strength = float(req.get("strength", 1.0))
+        if not 0.0 < r.strength <= 1.0:
+            raise ValueError(f"serve: `strength` must be in (0, 1], got {r.strength}")
+        keep = min(int(r.steps * r.strength), r.steps)                                           # :637-638
+        if keep < 1:
+            raise ValueError(f"serve: `strength` {r.strength} leaves none of the {r.steps} steps")
+        h, w = self.height // 8, self.width // 8
+        size = _spatial_size(image)
+        latents_in = torch.is_tensor(image) and image.dim() == 4 and image.shape[1] == 4
+        if latents_in:
+            if tuple(image.shape) != (1, 4, h, w):
+                raise ValueError(f"serve: `image` latents {tuple(image.shape)}, this batcher needs {(1, 4, h, w)}")
+        else:
+            if size != (self.height, self.width) or (torch.is_tensor(image) and (image.dim() != 4 or image.shape[0] != 1)):
+                raise ValueError(f"serve: `image` is {size}, this batcher runs one {self.height}x{self.width} image per request")
+            if pipe.vae is None or not hasattr(pipe.vae, "encode"):
+                raise ValueError("serve: `image` given as pixels needs a VAE with an encoder; pass [1, 4, h, w] latents")
+        if mask is not None:
+            if pipe.unet.config.in_channels != 4:
+                raise ValueError("serve: `mask_image` on a 9-channel inpainting UNet is not supported (use inpaiting)")
+            if _spatial_size(mask) not in ((self.height, self.width), (h, w)):
+                raise ValueError(f"serve: `mask_image` is {_spatial_size(mask)}, this batcher needs {self.height}x{self.width} "
+                                 f"(or the latent size {h}x{w})")
+        return max(r.steps - keep, 0)
 
     def levels(self):
         """{L: S} of the region tables at this image size (one level per down block, encode_region_map_function.py)"""
@@ -271,15 +336,26 @@ class ServingBatcher:
             else:
                 rec = {"mode": ops.ROW_IDLE, "t_next": 0.0, "sigma_next": 1.0, "temb_row": None, "req": None}
             recs.append(rec)
+        # known region of inpainting slots that step now: the model call of request step k >= 1 saw a blended input, and the
+        # coming call is blended unless the request leaves (a JOIN is a request's first call: never blended)
+        known = [None] * n_slots
+        for i, rec in enumerate(recs):
+            r = rec["req"]
+            if rec["mode"] == ops.ROW_STEP and r.known is not None:
+                known[i] = dict(r.known, blend_now=r.i >= 1, blend_next=r not in leaving)
         if n_dst is not None:
             self._ensure(n_dst)
         for r in joins:
             self.exec.load_latent(r)
         self._stats["joins"] += len(joins)
-        self.exec.transition(n_src, nd, recs)
+        if any(k is not None for k in known):
+            self.exec.transition_known(n_src, nd, recs, known)
+        else:
+            self.exec.transition(n_src, nd, recs)
         for r in leaving:
             slots[r.slot] = None
             self._done.append((r, self.exec.finish(r)))
+            r.known = None                           # its image / noise / mask rows go back to the allocator (stream-ordered)
             self._stats["leaves"] += 1
         for r in stepping:
             r.i += 1
@@ -383,10 +459,46 @@ class _GraphExecutor:
             if tuple(lat.shape) != (1,) + self.lat_shape:
                 raise ValueError(f"serve: latents {tuple(lat.shape)}, this batcher needs {(1,) + self.lat_shape}")
             r.lat = lat * (r.sig_dev[0] ** 2 + 1) ** 0.5                                       # txt2img's op (:1043)
-            ts = [t for _, t in r.scal]
-            r.temb = pipe.unet.temb_add_table(torch.tensor(ts, dtype=torch.float32, device=dev))
-            neg, pos = r.text
-            r.text = (neg.to(device=dev, dtype=dt), pos.to(device=dev, dtype=dt))
+            self._tables_and_text(r)
+
+    def _tables_and_text(self, r):
+        dev, dt = self.device, self.dtype
+        ts = [t for _, t in r.scal]
+        r.temb = self.pipe.unet.temb_add_table(torch.tensor(ts, dtype=torch.float32, device=dev))
+        neg, pos = r.text
+        r.text = (neg.to(device=dev, dtype=dt), pos.to(device=dev, dtype=dt))
+
+    def prepare_image(self, r):
+        """img2img / inpainting: the start latent of the pipeline method, line for line, on the truncated schedule; for
+        inpainting also the image latents, noise and mask rows the per-row step blends from"""
+        pipe, dev, dt = self.pipe, self.device, self.dtype
+        req, H, W = r.req, self.b.height, self.b.width
+        gen, image = req.get("generator"), req["image"]
+        latents_in = torch.is_tensor(image) and image.shape[1] == 4
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self.stream):
+            if r.kind == "img2img":
+                lat = image if latents_in else pipe._encode_vae_image(pipe._image_tensor(image, H, W), gen)     # :600-606
+                lat = lat.to(dev, dtype=dt)
+                noise = req.get("latents")
+                noise = pipe._randn_like_ref(lat.shape, gen, dev, dt) if noise is None else noise.to(dev, dtype=dt)
+                if noise.shape != lat.shape:
+                    raise ValueError(f"serve: latents (the noise) {tuple(noise.shape)}, this batcher needs {tuple(lat.shape)}")
+                r.lat = lat + noise * (r.sig_dev[0] ** 2 + 1) ** 0.5                                                 # :647
+            else:
+                init = image.float() if latents_in else pipe._image_tensor(image, H, W)
+                r.lat, noise, img_lat = pipe.prepare_latents_inpating(
+                    1, 4, H, W, dt, dev, gen, req.get("latents"), image=init, sigma=r.sig_dev[0],
+                    is_strength_max=r.strength == 1.0, return_noise=True, return_image_latents=True)            # :1459-1478
+                mask = pipe._image_tensor(req["mask_image"], H, W, mask=True)
+                mask = torch.nn.functional.interpolate(mask, size=self.lat_shape[1:]).to(device=dev, dtype=dt)    # :1253-1257
+                # rows of the batcher's own (allocated on its stream, alive until the request leaves)
+                r.known = {"image": img_lat[0].to(dt).clone().contiguous(), "noise": noise[0].to(dt).clone().contiguous(),
+                           "mask": mask[0].expand(self.lat_shape).contiguous()}
+            if tuple(r.lat.shape) != (1,) + self.lat_shape:
+                raise ValueError(f"serve: start latent {tuple(r.lat.shape)}, this batcher needs {(1,) + self.lat_shape}")
+            r.lat = r.lat.to(dt)
+            self._tables_and_text(r)
 
     def temb_row(self, r, j):
         return r.temb[j]
@@ -510,6 +622,17 @@ class _GraphExecutor:
         with torch.cuda.stream(self.stream):
             ops.cfg_dpmpp2m_step_rows(self.x, eps, self.old, n_src, st_d["x_in"], st_d["t"], st_d["sigma"], recs,
                                       tadd=st_d["tadd"])
+
+    def transition_known(self, n_src, n_dst, recs, known):
+        """transition() for a step in which an inpainting slot steps: the same ONE launch, with the known-region records"""
+        st_d = self.st.get(n_dst)
+        if st_d is None:
+            self.ensure(n_dst)
+            st_d = self.st[n_dst]
+        eps = self.st[n_src]["eps"] if n_src else None
+        with torch.cuda.stream(self.stream):
+            ops.cfg_dpmpp2m_step_rows_known(self.x, eps, self.old, n_src, st_d["x_in"], st_d["t"], st_d["sigma"], recs, known,
+                                            tadd=st_d["tadd"])
 
     def run(self, n):
         with torch.cuda.stream(self.stream):

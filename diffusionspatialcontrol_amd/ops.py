@@ -1027,48 +1027,88 @@ class RowStep(ctypes.Structure):
                 ("sigma_next", ctypes.c_float), ("temb_row", ctypes.c_void_p)]
 
 
-def cfg_dpmpp2m_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=None):
-    """Per-request sampler step of a continuous batch (dsc_cfg_dpmpp2m_step_rows): slot i = latent row i of x / old, rows
-    {i, n_src + i} of eps (the bucket that just ran; eps may be None when no slot steps) and rows {i, n' + i} of x_in / t_buf /
-    tadd (the bucket that runs next, n' = t_buf.numel() // 2); sigma_groups [n'] fp32.  rows: one dict per slot with `mode`
-    (ROW_STEP / ROW_JOIN / ROW_IDLE), the scalars of dsc_row_step and `temb_row` (an fp16 [tadd width] tensor or None); at least
-    n' of them.  x / old hold at least len(rows) latent rows."""
+def _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd):
+    """shape / dtype / device validation shared by the per-row sampler steps -> (n_dst, n_slots, chw, dsc_row_step array)"""
     _require_gpu(x, old, x_in, t_buf, sigma_groups)
     n_dst = t_buf.numel() // 2
     n_slots = len(rows)
     if not 1 <= n_dst <= n_slots <= ROW_STEP_MAX_SLOTS:
-        raise ValueError(f"cfg_dpmpp2m_step_rows: {n_slots} records for a {n_dst}-row bucket (at most {ROW_STEP_MAX_SLOTS})")
+        raise ValueError(f"{what}: {n_slots} records for a {n_dst}-row bucket (at most {ROW_STEP_MAX_SLOTS})")
     if x.shape[0] < n_slots or old.shape != x.shape:
-        raise ValueError("cfg_dpmpp2m_step_rows: x / old need a latent row per slot")
+        raise ValueError(f"{what}: x / old need a latent row per slot")
     chw = x.numel() // x.shape[0]
     for name, t, nr in (("x", x, None), ("old", old, None), ("x_in", x_in, 2 * n_dst), ("eps", eps, 2 * n_src), ("tadd", tadd, 2 * n_dst)):
         if t is None:
             continue
         if t.dtype != torch.float16 or not t.is_contiguous() or t.device != x.device:
-            raise ValueError(f"cfg_dpmpp2m_step_rows: {name} must be dense fp16 on {x.device}")
+            raise ValueError(f"{what}: {name} must be dense fp16 on {x.device}")
         if nr is not None and t.shape[0] != nr:
-            raise ValueError(f"cfg_dpmpp2m_step_rows: {name} has {t.shape[0]} rows, need {nr}")
+            raise ValueError(f"{what}: {name} has {t.shape[0]} rows, need {nr}")
         if name in ("x_in", "eps") and t.numel() != nr * chw:
-            raise ValueError(f"cfg_dpmpp2m_step_rows: {name} rows are not [{chw}] latents")
+            raise ValueError(f"{what}: {name} rows are not [{chw}] latents")
     for name, t, n in (("t_buf", t_buf, 2 * n_dst), ("sigma_groups", sigma_groups, n_dst)):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device or t.numel() != n:
-            raise ValueError(f"cfg_dpmpp2m_step_rows: {name} must be a dense fp32 [{n}] on {x.device}")
+            raise ValueError(f"{what}: {name} must be a dense fp32 [{n}] on {x.device}")
     recs = (RowStep * n_slots)()
     for i, r in enumerate(rows):
         tr = r.get("temb_row")
         if tr is not None:
             if tadd is None or tr.dtype != torch.float16 or tr.device != x.device or tr.stride(-1) != 1 \
                     or tr.numel() != tadd.shape[1]:
-                raise ValueError("cfg_dpmpp2m_step_rows: temb_row must be an fp16 row of the tadd buffer's width")
+                raise ValueError(f"{what}: temb_row must be an fp16 row of the tadd buffer's width")
         recs[i] = RowStep(int(r["mode"]), *(float(r.get(f, 0.0)) for f in ("sigma", "guidance", "a", "b", "c", "c_in_next",
                                                                              "t_next")),
                           float(r.get("sigma_next", 1.0)), None if tr is None else tr.data_ptr())
     for t in (x, old, x_in, t_buf, sigma_groups, tadd):
         _drop_gn_partials(t)
+    return n_dst, n_slots, chw, recs
+
+
+def cfg_dpmpp2m_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=None):
+    """Per-request sampler step of a continuous batch (dsc_cfg_dpmpp2m_step_rows): slot i = latent row i of x / old, rows
+    {i, n_src + i} of eps (the bucket that just ran; eps may be None when no slot steps) and rows {i, n' + i} of x_in / t_buf /
+    tadd (the bucket that runs next, n' = t_buf.numel() // 2); sigma_groups [n'] fp32.  rows: one dict per slot with `mode`
+    (ROW_STEP / ROW_JOIN / ROW_IDLE), the scalars of dsc_row_step and `temb_row` (an fp16 [tadd width] tensor or None); at least
+    n' of them.  x / old hold at least len(rows) latent rows."""
+    n_dst, n_slots, chw, recs = _step_rows_args("cfg_dpmpp2m_step_rows", x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd)
     rc = _lib.load_library().dsc_cfg_dpmpp2m_step_rows(
         _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
         0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), n_slots, chw, 0, _stream_ptr(x))
     _lib.check(rc, "dsc_cfg_dpmpp2m_step_rows")
+
+
+class RowKnown(ctypes.Structure):
+    """dsc_row_known (include/dsc_hip.h)"""
+    _fields_ = [("image", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("blend_now", ctypes.c_int), ("blend_next", ctypes.c_int)]
+
+
+def cfg_dpmpp2m_step_rows_known(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, known, tadd=None):
+    """cfg_dpmpp2m_step_rows with the known region of inpainting slots blended into the model input
+    (dsc_cfg_dpmpp2m_step_rows_known).  known: one entry per record of `rows` - None (the slot has no known region: the plain
+    op's bits) or a dict with `image` / `noise` / `mask` (fp16 [chw] rows on x's device, mask 1 = repaint, 0 = keep) and the
+    flags `blend_now` / `blend_next`.  A row given as None inside a dict is passed as NULL: the library refuses a record with
+    only some of the three, and rows that are not 16-byte aligned."""
+    what = "cfg_dpmpp2m_step_rows_known"
+    n_dst, n_slots, chw, recs = _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd)
+    if len(known) != n_slots:
+        raise ValueError(f"{what}: {len(known)} known-region records for {n_slots} slots")
+    kn = (RowKnown * n_slots)()
+    for i, k in enumerate(known):
+        if k is None:
+            continue
+        ptrs = []
+        for name in ("image", "noise", "mask"):
+            t = k.get(name)
+            if t is not None and (t.dtype != torch.float16 or t.device != x.device or not t.is_contiguous() or t.numel() != chw):
+                raise ValueError(f"{what}: known[{i}][{name!r}] must be a dense fp16 [{chw}] row on {x.device}")
+            ptrs.append(None if t is None else t.data_ptr())
+        kn[i] = RowKnown(*ptrs, int(bool(k.get("blend_now"))), int(bool(k.get("blend_next"))))
+    rc = _lib.load_library().dsc_cfg_dpmpp2m_step_rows_known(
+        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
+        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), ctypes.cast(kn, ctypes.c_void_p),
+        n_slots, chw, 0, _stream_ptr(x))
+    _lib.check(rc, what)
 
 
 def dpmpp2m_update(x, denoised, old, a, b, c):

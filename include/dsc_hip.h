@@ -216,6 +216,33 @@ typedef struct {
 int dsc_cfg_dpmpp2m_step_rows(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf, float* sigma_groups,
                               void* tadd, int tadd_halfs, int n_dst, const dsc_row_step* rows /* host */, int n_slots,
                               int chw, int dtype, void* stream);
+/*
+ * dsc_cfg_dpmpp2m_step_rows with a known region per slot: the 4-channel inpainting branch re-imposes the known part of the image
+ * on the model input before every model call after a request's first (reference model_k_diffusion.py:1599-1612,
+ * `((1 - mask) * (alpha_t * image + sigma_t * noise) + mask * x / rate) * rate`, rate = sqrt(sigma^2 + 1), i.e.
+ * alpha_t * rate = 1 and sigma_t * rate = sigma) - five or six eager elementwise launches and a host read of sigma per model
+ * call there.  One more record per slot, also passed by value (32 bytes each).  For a DSC_ROW_STEP slot with image != NULL,
+ * all fp32, fp16 rounding where marked:
+ *   kn(s) = fma(s, noise, image)                                   the known region at noise level s
+ *   xh    = blend_now ? fma(mask, x, (1 - mask) * kn(sigma)) : x   the input the model call of this step saw
+ *   D     = fp16(fma(-sigma, e, xh))                               e = CFG combine as in dsc_cfg_dpmpp2m_step_rows; old = D
+ *   x'    = fp16(fma(c, old, fma(a, x, b * D)))                    x: the sampler's own, unblended state
+ *   xh'   = blend_next ? fma(mask, x', (1 - mask) * kn(sigma_next)) : x'
+ *   x_in rows {i, n_dst + i} = fp16(xh' * c_in_next)
+ * A STEP slot with image == NULL computes dsc_cfg_dpmpp2m_step_rows' bits; JOIN (a request's first model call is not blended)
+ * and IDLE slots ignore their record.  image / noise / mask: all three set or all NULL, fp16 [chw], 16-byte aligned.
+ */
+typedef struct {
+    const void* image;      /* fp16 [chw] image latents of this slot, or NULL: slot has no known region */
+    const void* noise;      /* fp16 [chw] the request's noise */
+    const void* mask;       /* fp16 [chw] 1 = repaint, 0 = keep (already broadcast over the channels) */
+    int blend_now;          /* the x of THIS step's model call was blended (request step index >= 1) */
+    int blend_next;         /* blend the input of the coming model call */
+} dsc_row_known;
+int dsc_cfg_dpmpp2m_step_rows_known(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
+                                    float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
+                                    const dsc_row_step* rows /* host */, const dsc_row_known* known /* host */, int n_slots,
+                                    int chw, int dtype, void* stream);
 /* out = a*x + b*denoised + c*old  (old may be NULL when c == 0): the sampler update alone, for callers that keep
  * the reference's `sampler(model_fn, x, sigmas=...)` control flow.  n elements, n % 8 == 0. */
 int dsc_dpmpp2m_update(const void* x, const void* denoised, const void* old, float a, float b, float c,

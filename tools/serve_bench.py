@@ -1,6 +1,6 @@
 """Continuous-batching serving measurements (modules/serving.py) on one GPU; one JSON line per leg.
 
-    python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0]
+    python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -11,6 +11,9 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
   join        the stall a join puts on the running rows: host ms of a step that admits a request (text K/V refresh, table
               compression and upload) minus that of a plain step, with the GPU time of the refresh
   stats       the batcher's counters; captures after warm() must be 0
+  mix         (--mix: this leg and the saturated txt2img figure only) 8 slots kept full with one third each txt2img / img2img at
+              strength 0.6 / inpainting at strength 1.0 (4-channel latents as `image`, distinct prompts and masks per request):
+              images/s and sampler steps/s beside the same figures of the all-txt2img batch in the same process
 """
 import argparse
 import json
@@ -58,6 +61,38 @@ def make_requests(n, seed):
     return out
 
 
+def make_mixed(reqs, seed):
+    """request i: txt2img / img2img at strength 0.6 / inpainting (i % 3), its own image latents and its own mask"""
+    out = []
+    for i, r in enumerate(reqs):
+        g = torch.Generator().manual_seed(seed * 1000 + 2000 + i)
+        img = (torch.randn(1, 4, 64, 64, generator=g) * 0.8).half().cuda()
+        if i % 3 == 0:
+            out.append(dict(r))
+        elif i % 3 == 1:
+            out.append(dict(r, image=img, strength=0.6))
+        else:
+            m = torch.zeros(1, 1, 512, 512)
+            x0 = 64 * (i % 7)
+            m[..., x0:x0 + 192] = 1.0                       # repaint a 192-pixel column band, elsewhere keep the image
+            out.append(dict(r, image=img, mask_image=m, strength=1.0))
+    return out
+
+
+def run_full(b, reqs, kw):
+    """(images/s, sampler steps/s) of one batcher with its slots kept full by these requests"""
+    torch.cuda.synchronize()
+    s0 = b.stats()["steps"]
+    t0 = time.perf_counter()
+    futs = [b.submit(dict(r, **kw)) for r in reqs]
+    b.run_until_idle()
+    for f in futs:
+        f.result()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    return len(reqs) / dt, (b.stats()["steps"] - s0) / dt
+
+
 def pct(v, p):
     return float(np.percentile(np.array(v), p)) if v else None
 
@@ -67,6 +102,7 @@ def main():
     ap.add_argument("--requests", type=int, default=16)
     ap.add_argument("--rates", default="2,6", help="Poisson arrival rates, requests/s")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--mix", action="store_true", help="only the mixed txt2img / img2img / inpainting leg")
     a = ap.parse_args()
     from diffusionspatialcontrol_amd.modules.model_k_diffusion import SD15Scheduler, StableDiffusionPipeline
     from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNet2DConditionModel, UNetConfig
@@ -77,6 +113,22 @@ def main():
     opt = {"scheduler": "karras"}
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    if a.mix:
+        b = pipe.serve(512, 512, max_batch=8, slot=0).warm()
+        mixed = make_mixed(reqs, a.seed)
+        for group in (reqs[:8], mixed[:8]):               # one untimed pass each (allocator, kernel selection at every bucket)
+            run_full(b, group, kw25)
+        runs = []
+        for _ in range(3):                                # alternating, so that a drift of the box hits both alike
+            runs.append((run_full(b, reqs, kw25), run_full(b, mixed, kw25)))
+        emit(leg="mix", requests=len(reqs), steps=25, mix="1/3 txt2img, 1/3 img2img strength 0.6 (15 steps), 1/3 inpainting",
+             txt2img_img_s=[round(t[0], 2) for t, _ in runs], txt2img_steps_s=[round(t[1], 1) for t, _ in runs],
+             mixed_img_s=[round(m[0], 2) for _, m in runs], mixed_steps_s=[round(m[1], 1) for _, m in runs],
+             note="steps/s = captured UNet steps of the batch per second; a step of the mixed batch carries one "
+                  "dsc_cfg_dpmpp2m_step_rows_known launch instead of the plain one while an inpainting slot steps")
+        emit(leg="stats", slot0=b.stats())
+        return
 
     # ---- saturated
     b0 = pipe.serve(512, 512, max_batch=8, slot=0).warm()
