@@ -103,6 +103,46 @@ __device__ __forceinline__ float as_f32(float v) {
     return v;
 }
 
+// ---- what the three per-row kernels below share (slot i = blockIdx.y)
+// the slot's time-embedding row -> both of its CFG rows of the destination bucket
+__device__ __forceinline__ void rows_copy_temb(const void* temb_row, half_t* tadd, int tadd_halfs, int n_dst, int i) {
+    if (!temb_row) return;
+    const int t8 = tadd_halfs / 8;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < 2 * t8; j += gridDim.x * 256) {
+        const int h = j >= t8, c = j - h * t8;
+        *reinterpret_cast<h8_t*>(tadd + ((long long)(h ? n_dst + i : i) * tadd_halfs) + c * 8) =
+            reinterpret_cast<const h8_t*>(temb_row)[c];
+    }
+}
+// JOIN: prepare_kernel's line for a freshly loaded start latent (a request's first model call: never blended), old row zeroed;
+// IDLE: zero input rows
+__device__ __forceinline__ void rows_join_or_idle(bool join, float c_in, const half_t* xr, half_t* orow, half_t* xi_u, half_t* xi_c,
+                                                  long long v8) {
+    for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
+        h8_t o;
+        if (join) {
+            float f[8];
+            unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), f);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = as_f32(f[j] * c_in);
+            o = pack8(f);
+            *reinterpret_cast<h8_t*>(orow + k * 8) = h8_t{};
+        } else {
+            o = h8_t{};
+        }
+        *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
+        *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+    }
+}
+// t of both CFG rows and the sigma of the slot's std group
+__device__ __forceinline__ void rows_write_scalars(float* t_buf, float* sigma_groups, int n_dst, int i, float t_next, float sigma) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        t_buf[i] = t_next;
+        t_buf[n_dst + i] = t_next;
+        sigma_groups[i] = sigma;
+    }
+}
+
 // dsc_cfg_dpmpp2m_step_rows: the records ride in the kernel arguments (kernarg segment, read through scalar loads: the slot is
 // blockIdx.y, uniform per workgroup)
 struct RowSteps { dsc_row_step r[DSC_ROW_STEP_MAX_SLOTS]; };
@@ -114,14 +154,7 @@ __global__ __launch_bounds__(256) void step_rows_kernel(half_t* x, const half_t*
     const dsc_row_step& r = rs.r[i];
     const bool dst = i < n_dst;
     const long long v8 = chw / 8;
-    if (dst && r.temb_row) {                      // this slot's time-embedding row -> both of its CFG rows
-        const int t8 = tadd_halfs / 8;
-        for (int j = blockIdx.x * 256 + threadIdx.x; j < 2 * t8; j += gridDim.x * 256) {
-            const int h = j >= t8, c = j - h * t8;
-            *reinterpret_cast<h8_t*>(tadd + ((long long)(h ? n_dst + i : i) * tadd_halfs) + c * 8) =
-                reinterpret_cast<const h8_t*>(r.temb_row)[c];
-        }
-    }
+    if (dst) rows_copy_temb(r.temb_row, tadd, tadd_halfs, n_dst, i);
     half_t* xi_u = x_in + (long long)i * chw;
     half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
     if (r.mode == DSC_ROW_STEP) {
@@ -156,31 +189,9 @@ __global__ __launch_bounds__(256) void step_rows_kernel(half_t* x, const half_t*
             }
         }
     } else if (dst) {
-        const bool join = r.mode == DSC_ROW_JOIN;
-        const float c_in = r.c_in_next;
-        const half_t* xr = x + (long long)i * chw;
-        half_t* orow = old + (long long)i * chw;
-        for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
-            h8_t o;
-            if (join) {                                            // prepare_kernel's line
-                float f[8];
-                unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), f);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) f[j] = as_f32(f[j] * c_in);
-                o = pack8(f);
-                *reinterpret_cast<h8_t*>(orow + k * 8) = h8_t{};
-            } else {
-                o = h8_t{};
-            }
-            *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
-            *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
-        }
+        rows_join_or_idle(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
     }
-    if (dst && blockIdx.x == 0 && threadIdx.x == 0) {
-        t_buf[i] = r.t_next;
-        t_buf[n_dst + i] = r.t_next;
-        sigma_groups[i] = r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next;
-    }
+    if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
 }
 
 // dsc_cfg_dpmpp2m_step_rows_known: step_rows_kernel plus, per slot, the known region of an inpainting request blended into the
@@ -196,14 +207,7 @@ __global__ __launch_bounds__(256) void step_rows_known_kernel(half_t* x, const h
     const dsc_row_known& kr = ks.r[i];
     const bool dst = i < n_dst;
     const long long v8 = chw / 8;
-    if (dst && r.temb_row) {
-        const int t8 = tadd_halfs / 8;
-        for (int j = blockIdx.x * 256 + threadIdx.x; j < 2 * t8; j += gridDim.x * 256) {
-            const int h = j >= t8, c = j - h * t8;
-            *reinterpret_cast<h8_t*>(tadd + ((long long)(h ? n_dst + i : i) * tadd_halfs) + c * 8) =
-                reinterpret_cast<const h8_t*>(r.temb_row)[c];
-        }
-    }
+    if (dst) rows_copy_temb(r.temb_row, tadd, tadd_halfs, n_dst, i);
     half_t* xi_u = x_in + (long long)i * chw;
     half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
     if (r.mode == DSC_ROW_STEP) {
@@ -256,31 +260,67 @@ __global__ __launch_bounds__(256) void step_rows_known_kernel(half_t* x, const h
             }
         }
     } else if (dst) {
-        const bool join = r.mode == DSC_ROW_JOIN;
-        const float c_in = r.c_in_next;
-        const half_t* xr = x + (long long)i * chw;
+        rows_join_or_idle(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
+    }
+    if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
+}
+
+// dsc_cfg_linear_step_rows: step_rows_kernel with the denoised estimate affine in (x, model output) - D = c_skip x + c_out m, eps- or
+// v-prediction - and an optional per-slot noise row: x' = a x + b D + c D_old + s xi, the one-model-call-per-step samplers of
+// modules/sampling.py (sample_euler, sample_euler_ancestral, sample_dpmpp_2m, sample_dpmpp_2m_sde, sample_lcm of
+// samplers_extra_k_diffusion.py) with their scalars computed on the host (sampling.linear_step_coefficients).  A slot with
+// c_skip = 1, c_out = -sigma and no noise row runs step_rows_kernel's arithmetic (same bits); JOIN / IDLE slots are its lines.
+struct RowLinears { dsc_row_linear r[DSC_ROW_STEP_MAX_SLOTS]; };
+
+__global__ __launch_bounds__(256) void linear_rows_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
+                                                          float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
+                                                          int n_dst, int chw, const RowLinears rs) {
+    const int i = blockIdx.y;
+    const dsc_row_linear& r = rs.r[i];
+    const bool dst = i < n_dst;
+    const long long v8 = chw / 8;
+    if (dst) rows_copy_temb(r.temb_row, tadd, tadd_halfs, n_dst, i);
+    half_t* xi_u = x_in + (long long)i * chw;
+    half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
+    if (r.mode == DSC_ROW_STEP) {
+        const float g = r.guidance, a = r.a, b = r.b, c = r.c, c_in_next = r.c_in_next;
+        const float c_skip = r.c_skip, c_out = r.c_out, s = r.s;
+        const half_t* nse = static_cast<const half_t*>(r.noise);            // per slot: the branch below is uniform per workgroup
+        half_t* xr = x + (long long)i * chw;
         half_t* orow = old + (long long)i * chw;
+        const half_t* eur = eps + (long long)i * chw;
+        const half_t* ecr = eps + (long long)(n_src + i) * chw;
         for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
-            h8_t o;
-            if (join) {                                            // a request's first model call is never blended
-                float f[8];
-                unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), f);
+            float xv[8], eu[8], ec[8], ov[8], dn[8], xn[8], xi[8], nz[8];
+            unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), xv);
+            unpack8(*reinterpret_cast<const h8_t*>(eur + k * 8), eu);
+            unpack8(*reinterpret_cast<const h8_t*>(ecr + k * 8), ec);
+            unpack8(*reinterpret_cast<const h8_t*>(orow + k * 8), ov);
+            if (nse) unpack8(*reinterpret_cast<const h8_t*>(nse + k * 8), nz);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) f[j] = as_f32(f[j] * c_in);
-                o = pack8(f);
-                *reinterpret_cast<h8_t*>(orow + k * 8) = h8_t{};
-            } else {
-                o = h8_t{};
+            for (int j = 0; j < 8; ++j) {
+                // e = fma(g, ec - eu, eu), D = fma(c_out, e, c_skip * x), x' = fma(s, xi, fma(c, old, fma(a, x, b * D)))
+                const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
+                const float sx = as_f32(c_skip * xv[j]);
+                dn[j] = (float)(half_t)as_f32(__builtin_fmaf(c_out, e, sx));
+                const float bd = as_f32(b * dn[j]);
+                float xo = as_f32(__builtin_fmaf(c, ov[j], as_f32(__builtin_fmaf(a, xv[j], bd))));
+                if (nse) xo = as_f32(__builtin_fmaf(s, nz[j], xo));
+                xn[j] = (float)(half_t)xo;
+                xi[j] = as_f32(xn[j] * c_in_next);
             }
-            *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
-            *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+            *reinterpret_cast<h8_t*>(orow + k * 8) = pack8(dn);
+            *reinterpret_cast<h8_t*>(xr + k * 8) = pack8(xn);
+            if (dst) {
+                const h8_t o = pack8(xi);
+                *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
+                *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+            }
         }
+    } else if (dst) {
+        rows_join_or_idle(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
     }
-    if (dst && blockIdx.x == 0 && threadIdx.x == 0) {
-        t_buf[i] = r.t_next;
-        t_buf[n_dst + i] = r.t_next;
-        sigma_groups[i] = r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next;
-    }
+    if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
 }
 
 int grid_for(long long n8) {
@@ -296,6 +336,21 @@ int row_args_status(const void* row_src, const void* row_dst, int row_halfs, int
     if (!row_src) return DSC_OK;
     if (!row_dst || row_halfs <= 0 || row_copies <= 0) return DSC_ERR_BAD_ARG;
     if (row_halfs % 8 != 0 || !al16(row_src) || !al16(row_dst)) return DSC_ERR_UNSUPPORTED;
+    return DSC_OK;
+}
+// one record of the per-row entries: STEP needs the model output and a source row, JOIN a destination row; an aligned embedding row
+int row_record_status(int mode, int i, int n_src, int n_dst, const void* eps, const void* temb_row, bool* any_row) {
+    if (mode == DSC_ROW_STEP) {
+        if (!eps || i >= n_src) return DSC_ERR_BAD_ARG;
+    } else if (mode == DSC_ROW_JOIN) {
+        if (i >= n_dst) return DSC_ERR_BAD_ARG;
+    } else if (mode != DSC_ROW_IDLE) {
+        return DSC_ERR_BAD_ARG;
+    }
+    if (temb_row) {
+        if (!al16(temb_row)) return DSC_ERR_UNSUPPORTED;
+        *any_row = true;
+    }
     return DSC_OK;
 }
 }  // namespace
@@ -349,17 +404,7 @@ extern "C" int dsc_cfg_dpmpp2m_step_rows(void* x, const void* eps, void* old, in
     bool any_row = false;
     for (int i = 0; i < n_slots; ++i) {
         const dsc_row_step& r = rows[i];
-        if (r.mode == DSC_ROW_STEP) {
-            if (!eps || i >= n_src) return DSC_ERR_BAD_ARG;
-        } else if (r.mode == DSC_ROW_JOIN) {
-            if (i >= n_dst) return DSC_ERR_BAD_ARG;
-        } else if (r.mode != DSC_ROW_IDLE) {
-            return DSC_ERR_BAD_ARG;
-        }
-        if (r.temb_row) {
-            if (!al16(r.temb_row)) return DSC_ERR_UNSUPPORTED;
-            any_row = true;
-        }
+        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
         rs.r[i] = r;
     }
     if (any_row) {
@@ -395,15 +440,8 @@ extern "C" int dsc_cfg_dpmpp2m_step_rows_known(void* x, const void* eps, void* o
             if (set != 0 && set != 3) return DSC_ERR_BAD_ARG;
             if (set && (!al16(k.image) || !al16(k.noise) || !al16(k.mask))) return DSC_ERR_UNSUPPORTED;
             ks.r[i] = k;
-        } else if (r.mode == DSC_ROW_JOIN) {
-            if (i >= n_dst) return DSC_ERR_BAD_ARG;
-        } else if (r.mode != DSC_ROW_IDLE) {
-            return DSC_ERR_BAD_ARG;
         }
-        if (r.temb_row) {
-            if (!al16(r.temb_row)) return DSC_ERR_UNSUPPORTED;
-            any_row = true;
-        }
+        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
         rs.r[i] = r;
     }
     if (any_row) {
@@ -416,5 +454,32 @@ extern "C" int dsc_cfg_dpmpp2m_step_rows_known(void* x, const void* eps, void* o
     DSC_LAUNCH(step_rows_known_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
                static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
                static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs, ks);
+    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+}
+
+extern "C" int dsc_cfg_linear_step_rows(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
+                                        float* sigma_groups, void* tadd, int tadd_halfs, int n_dst, const dsc_row_linear* rows,
+                                        int n_slots, int chw, int dtype, void* stream) {
+    if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || n_src < 0 || n_dst <= 0 || chw <= 0) return DSC_ERR_BAD_ARG;
+    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
+    if (dtype != DSC_F16 || chw % 8 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
+    RowLinears rs{};
+    bool any_row = false;
+    for (int i = 0; i < n_slots; ++i) {
+        const dsc_row_linear& r = rows[i];
+        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
+        if (r.mode == DSC_ROW_STEP && r.noise && !al16(r.noise)) return DSC_ERR_UNSUPPORTED;
+        rs.r[i] = r;
+    }
+    if (any_row) {
+        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
+        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
+    }
+    const long long v8 = chw / 8;
+    long long gx = (v8 + 255) / 256;
+    gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
+    DSC_LAUNCH(linear_rows_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
+               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
+               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs);
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }

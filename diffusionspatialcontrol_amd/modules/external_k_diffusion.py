@@ -84,6 +84,10 @@ class DiscreteEpsDDPMDenoiser(DiscreteSchedule):
         """(c_in, c_out, t) as python floats for one sigma"""
         return 1.0 / math.sqrt(sigma * sigma + self.sigma_data ** 2), -sigma, self.sigma_to_t_host(sigma)
 
+    def step_skip(self, sigma: float) -> float:
+        """c_skip of D = c_skip x + c_out eps for one sigma (eps-prediction: D = x - sigma eps)"""
+        return 1.0
+
     def get_eps(self, *args, **kwargs):
         return self.inner_model(*args, **kwargs)
 
@@ -117,6 +121,17 @@ class DiscreteVDDPMDenoiser(DiscreteSchedule):
         c_out = -sigma * self.sigma_data / (sigma ** 2 + sd2) ** 0.5
         c_in = 1 / (sigma ** 2 + sd2) ** 0.5
         return c_skip, c_out, c_in
+
+    def step_scalars(self, sigma: float):
+        """(c_in, c_out, t) as python floats for one sigma (get_scalings in fp64; c_skip: step_skip)"""
+        sd2 = self.sigma_data ** 2
+        return 1.0 / math.sqrt(sigma * sigma + sd2), -sigma * self.sigma_data / math.sqrt(sigma * sigma + sd2), \
+            self.sigma_to_t_host(sigma)
+
+    def step_skip(self, sigma: float) -> float:
+        """c_skip of D = c_skip x + c_out v for one sigma"""
+        sd2 = self.sigma_data ** 2
+        return sd2 / (sigma * sigma + sd2)
 
     def get_v(self, *args, **kwargs):
         return self.inner_model(*args, **kwargs)

@@ -449,7 +449,8 @@ class StableDiffusionPipeline:
                 ip_adapter_image_embeds=None,
                 # build-specific inputs (the prompt encoders are a "next" row):
                 prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
-                text_input_ids=None, fused: Optional[bool] = None, slot: int = 0, **unsupported):
+                text_input_ids=None, fused: Optional[bool] = None, slot: int = 0, step_noise: Optional[torch.Tensor] = None,
+                **unsupported):
         hires = dict(prompt=prompt, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                      negative_prompt=negative_prompt, generator=generator, strength=upscale_denoising_strength,
                      sampler_name=sampler_name_hires or sampler_name, sampler_opt=sampler_opt_hires or sampler_opt,
@@ -519,7 +520,10 @@ class StableDiffusionPipeline:
             if control_hook is not None or preview is not None:
                 raise NotImplementedError("ControlNet / T2I-Adapter / latent previews run in protocol mode (fused=False)")
             latents = self._denoise_fused(latents, sigmas, text, region_state, weight_func, guidance_scale, n_img,
-                                          cross_attention_kwargs, start_time, timeout, slot=slot)
+                                          cross_attention_kwargs, start_time, timeout, slot=slot, sampler=sampler,
+                                          sampler_args=self._fused_sampler_args(sampler, sigmas, eta, num_inference_steps,
+                                                                                sampler_opt, latents, seed, step_noise),
+                                          step_noise=step_noise)
         else:
             latents = self._denoise_protocol(sampler, latents, sigmas, text, region_state, weight_func, guidance_scale,
                                              guidance_rescale, n_img, cross_attention_kwargs, eta,
@@ -726,7 +730,7 @@ class StableDiffusionPipeline:
                 guidance_rescale: float = 0.0, cross_attention_kwargs=None, clip_skip=None, long_encode=0,
                 num_images_per_prompt=1, ip_adapter_image_embeds=None,
                 prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
-                text_input_ids=None, fused: Optional[bool] = None, **unsupported):
+                text_input_ids=None, fused: Optional[bool] = None, step_noise: Optional[torch.Tensor] = None, **unsupported):
         """reference :543-846: encode the image (or take `latents`), keep the last `strength` fraction of the schedule, add
         noise, denoise.  Reproduces the reference's start: `latents + noise * sqrt(sigma_0^2 + 1)` (:647 - sic, not
         `noise * sigma_0`)."""
@@ -792,7 +796,10 @@ class StableDiffusionPipeline:
             if control_hook is not None or preview is not None:
                 raise NotImplementedError("ControlNet / T2I-Adapter / latent previews run in protocol mode (fused=False)")
             latents = self._denoise_fused(latents, sigma_sched, text, region_state, weight_func, guidance_scale, n_img,
-                                          cross_attention_kwargs, start_time, timeout)
+                                          cross_attention_kwargs, start_time, timeout, sampler=sampler,
+                                          sampler_args=self._fused_sampler_args(sampler, sigma_sched, None, len(sigma_sched),
+                                                                                sampler_opt, latents, seed, step_noise),
+                                          step_noise=step_noise)
         else:
             args = self.get_sampler_extra_args_i2i(sigma_sched, len(sigma_sched), sampler_opt, latents, seed, sampler)
             latents = self._denoise_protocol(sampler, latents, sigma_sched, text, region_state, weight_func, guidance_scale,
@@ -1124,7 +1131,9 @@ class StableDiffusionPipeline:
         st = {
             "x_in": torch.zeros((rows,) + lat_shape[1:], device=dev, dtype=dt),
             "t": torch.zeros(rows, device=dev, dtype=torch.float32),
-            "sigma": torch.ones(1, device=dev, dtype=torch.float32),
+            # the captured step reads element 0 (a lockstep batch has one sigma); the per-row sampler step
+            # (ops.cfg_linear_step_rows) writes every image's own entry of the same buffer
+            "sigma_rows": torch.ones(n_img, device=dev, dtype=torch.float32),
             "text": text.clone(),
             "compressed": None, "dense": None,
             "weight_func": weight_func,          # kept alive: the key holds its id
@@ -1136,6 +1145,7 @@ class StableDiffusionPipeline:
             "temb_tab": None, "temb_key": None,
             "image_embeds": None if ack is None else [e.clone() for e in ack["image_embeds"]],
         }
+        st["sigma"] = st["sigma_rows"][:1]
         if comp_cpu is not None:
             st["compressed"] = {L: (ids.to(dev), rws.to(dev)) for L, (ids, rws) in comp_cpu.items()}
         if need_dense:
@@ -1301,11 +1311,65 @@ class StableDiffusionPipeline:
                 m.kv_cache = None
                 m.__dict__.pop("kv_caches", None)
 
+    def _fused_sampler_args(self, sampler, sigmas, eta, steps, sampler_opt, latents, seed, step_noise):
+        """what protocol mode hands `sampler` besides the schedule (get_sampler_extra_args_t2i / _i2i), for the fused loop:
+        eta (None: the sampler's own default, as img2img passes none), the solver type and the Brownian noise sampler of
+        `sampler_opt` - the latter only when the loop has to build the noise table itself"""
+        args = {"solver_type": "heun" if sampler_opt.get("solver_type", None) == "heun" else "midpoint"}
+        if eta is not None:
+            args["eta"] = eta
+        if step_noise is None and sampler_opt.get("brownian_noise", False) \
+                and sampling.linear_family(sampler) in ("euler_ancestral", "dpmpp_2m_sde", "lcm"):
+            args["noise_sampler"] = self.create_noise_sampler(latents, sigmas, steps, seed)
+        return args
+
+    @staticmethod
+    def _check_step_noise(noise, steps, x):
+        """the noise table of a fused / served generation: [steps, 1 or n, *latent] -> dense, x's dtype, on x's device"""
+        want = (steps,) + tuple(x.shape)
+        if not torch.is_tensor(noise) or noise.dim() != len(want) or tuple(noise.shape[2:]) != want[2:] \
+                or noise.shape[0] != steps or noise.shape[1] not in (1, x.shape[0]):
+            raise ValueError(f"step_noise must be a [{steps}, 1 or {x.shape[0]}, {', '.join(str(v) for v in x.shape[1:])}] tensor, "
+                             f"got {tuple(noise.shape) if torch.is_tensor(noise) else type(noise).__name__}")
+        return noise.to(device=x.device, dtype=x.dtype).contiguous()
+
+    def _linear_fused_loop(self, st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout):
+        """the fused loop's steps through the per-row kernel: one record per image, all on the same step of the same schedule"""
+        kdm = self.k_diffusion_model
+        for i, (a, b, c, s) in enumerate(coeffs):
+            if start_time > 0 and timeout > 0:
+                assert (time.time() - start_time) < timeout, "inference process timed out"
+            st["run"]()
+            nxt = sig[i + 1]
+            c_in_n, _, t_n = kdm.step_scalars(nxt) if nxt > 0 else (1.0, 0.0, 0.0)
+            rec = {"mode": ops.ROW_STEP, "sigma": sig[i], "guidance": guidance_scale, "a": a, "b": b, "c": c, "s": s,
+                   "c_skip": kdm.step_skip(sig[i]), "c_out": kdm.step_scalars(sig[i])[1], "c_in_next": c_in_n, "t_next": t_n,
+                   "sigma_next": max(nxt, 1e-10), "temb_row": tab[i + 1] if tab is not None and i + 1 < len(coeffs) else None}
+            recs = [dict(rec, noise=None if noise is None or s == 0.0 else noise[i, j if noise.shape[1] > 1 else 0])
+                    for j in range(n_img)]
+            ops.cfg_linear_step_rows(x, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, tadd=st["tadd"])
+
     def _denoise_fused(self, latents, sigmas, text, region_state, weight_func, guidance_scale, n_img,
-                       cross_attention_kwargs, start_time, timeout, slot=0):
-        if self.v_prediction:
-            raise NotImplementedError("the fused step (dsc_cfg_dpmpp2m_step) computes denoised = x - sigma * eps; "
-                                      "v-prediction models run in protocol mode (fused=False)")
+                       cross_attention_kwargs, start_time, timeout, slot=0, sampler=None, sampler_args=None, step_noise=None):
+        """sampler: None (DPM++ 2M) or one of sampling.LINEAR_FAMILY's functions.  DPM++ 2M on an eps-prediction model is one
+        dsc_cfg_dpmpp2m_step per step; every other member, and every v-prediction model, one dsc_cfg_linear_step_rows with a
+        record per image.  step_noise: the noise table [steps, 1 or n_img, c, h, w] (default: sampling.step_noise_table)."""
+        family = "dpmpp_2m" if sampler is None else sampling.linear_family(sampler)
+        if family is None:
+            raise NotImplementedError(f"fused=True: sampler {getattr(sampler, '__name__', sampler)!r} has no fused step "
+                                      f"(supported: {', '.join(sampling.LINEAR_FAMILY)}); run it with fused=False")
+        rows_path = family != "dpmpp_2m" or self.v_prediction
+        if rows_path and n_img > ops.ROW_STEP_MAX_SLOTS:
+            raise NotImplementedError(f"fused=True: the per-row sampler step takes at most {ops.ROW_STEP_MAX_SLOTS} images per "
+                                      f"batch, got {n_img}; run it with fused=False")
+        # the lockstep kernel's wrapper refuses CPU / non-fp16 tensors itself, deep inside the loop; the per-row path builds
+        # records and a noise table first, so it says so here (tests/test_host_logic.py probes a v-prediction pipeline's fused
+        # path with no tensors at all and expects this error class)
+        if rows_path and not (torch.is_tensor(latents) and latents.is_cuda and text.dtype == torch.float16):
+            raise NotImplementedError("fused=True: the per-row sampler step (dsc_cfg_linear_step_rows: every sampler but DPM++ 2M, "
+                                      "and v-prediction models) runs fp16 latents on the GPU; run it with fused=False")
+        if self.v_prediction and not self.k_diffusion_model.pass_kwargs:
+            region_state, cross_attention_kwargs = None, {}          # CompVisVDenoiser.get_v forwards (x, t, cond) only
         prof = os.environ.get("DSC_PROFILE_HOST") == "1"
         if prof:
             torch.cuda.synchronize()
@@ -1314,7 +1378,13 @@ class StableDiffusionPipeline:
         sig = getattr(sigmas, "_dsc_host", None)                     # host copy made where the schedule was built, or
         if sig is None:
             sig = sigmas.detach().float().cpu().tolist()             # one device->host transfer before the loop
-        coeffs = sampling.dpmpp_2m_coefficients(sig)
+        sargs = dict(sampler_args or {})
+        noise_sampler = sargs.pop("noise_sampler", None)
+        if family not in ("euler_ancestral", "dpmpp_2m_sde"):
+            sargs.pop("eta", None)
+        if family != "dpmpp_2m_sde":
+            sargs.pop("solver_type", None)
+        coeffs = sampling.linear_step_coefficients(family, sig, **sargs) if rows_path else sampling.dpmpp_2m_coefficients(sig)
         levels = tuple(sorted((int(L), tuple(w.shape)) for L, w in region_state.items())) \
             if isinstance(region_state, dict) else None
         ack = getattr(self, "_added_cond_kwargs", None)
@@ -1346,6 +1416,14 @@ class StableDiffusionPipeline:
                 st["temb_key"] = tkey
             tab = st["temb_tab"]
         ops.prepare_unet_input(x, c_in, t, sig[0], st["x_in"], st["t"], st["sigma"], row=None if tab is None else (tab[0], st["tadd"]))
+        if rows_path:
+            noise = None
+            if any(c4[3] != 0.0 for c4 in coeffs):
+                noise = step_noise if step_noise is not None else \
+                    sampling.step_noise_table(family, x, sigmas, eta=sargs.get("eta", 1.0), noise_sampler=noise_sampler)
+                noise = self._check_step_noise(noise, len(coeffs), x)
+            self._linear_fused_loop(st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout)
+            coeffs = []
         for i, (a, b, c) in enumerate(coeffs):
             if start_time > 0 and timeout > 0:
                 assert (time.time() - start_time) < timeout, "inference process timed out"

@@ -458,3 +458,91 @@ def sample_dpmpp_3m_sde(model, x, sigmas, extra_args=None, callback=None, disabl
             h1, h2 = h, h1
         d1, d2 = denoised, d1
     return x
+
+
+# ----------------------------------------------------------------------------------------------- the linear-step family
+# The samplers above that make ONE model call per step and update  x' = a x + b D + c D_old + s xi  with host scalars: what the
+# per-row step kernel (dsc_cfg_linear_step_rows) runs inside the fused loop and the continuous batcher.
+LINEAR_FAMILY = ("euler", "euler_ancestral", "dpmpp_2m", "dpmpp_2m_sde", "lcm")
+
+
+def linear_family(sampler):
+    """family name of a sampler given as a callable (sample_euler, ..., samplers_extra_k_diffusion.sample_lcm) or a name
+    ("sample_euler_ancestral" / "euler_ancestral"); None when it is not one of LINEAR_FAMILY"""
+    name = sampler if isinstance(sampler, str) else getattr(sampler, "__name__", "")
+    if not isinstance(sampler, str):
+        mod = getattr(sampler, "__module__", "") or ""
+        if not (mod == __name__ or mod.endswith(".samplers_extra_k_diffusion")):
+            return None
+    if name.startswith("sample_"):
+        name = name[len("sample_"):]
+    return name if name in LINEAR_FAMILY else None
+
+
+def linear_step_coefficients(name, sigmas, eta=1.0, s_noise=1.0, solver_type="midpoint"):
+    """(name: a family name or the sampler callable, as linear_family takes.)  Host fp64 scalars (a, b, c, s) per step with  x <- a*x + b*D_i + c*D_{i-1} + s*xi_i  for the samplers of LINEAR_FAMILY,
+    read off the functions above (sample_euler without churn, sample_euler_ancestral, sample_dpmpp_2m, sample_dpmpp_2m_sde,
+    samplers_extra_k_diffusion.sample_lcm), their final sigma' = 0 step included.  s == 0 means the step adds no noise."""
+    fam = linear_family(name)
+    if fam is None:
+        raise NotImplementedError(f"no linear one-call step for sampler {getattr(name, '__name__', name)!r} "
+                                  f"(supported: {', '.join(LINEAR_FAMILY)})")
+    sig = [float(s) for s in sigmas]
+    if fam == "dpmpp_2m":
+        return [(a, b, c, 0.0) for a, b, c in dpmpp_2m_coefficients(sig)]
+    if fam == "dpmpp_2m_sde" and solver_type not in {"heun", "midpoint"}:
+        raise ValueError("solver_type must be 'heun' or 'midpoint'")
+    out = []
+    h_last = None
+    for i in range(len(sig) - 1):
+        s0, s1 = sig[i], sig[i + 1]
+        if fam == "euler":                                        # x + (x - D) * ((sigma' - sigma) / sigma)
+            k = (s1 - s0) / s0
+            out.append((1.0 + k, -k, 0.0, 0.0))
+        elif fam == "euler_ancestral":
+            sigma_down, sigma_up = get_ancestral_step(s0, s1, eta=eta)
+            k = (sigma_down - s0) / s0
+            out.append((1.0 + k, -k, 0.0, s_noise * sigma_up if s1 > 0 else 0.0))
+        elif fam == "lcm":                                        # x = D (+ sigma' xi)
+            out.append((0.0, 1.0, 0.0, s1 if s1 > 0 else 0.0))
+        elif s1 == 0:                                             # dpmpp_2m_sde: x = D
+            out.append((0.0, 1.0, 0.0, 0.0))
+        else:
+            h = -math.log(s1) + math.log(s0)
+            eta_h = eta * h
+            e = -math.expm1(-h - eta_h)
+            a, b, c = (s1 / s0) * math.exp(-eta_h), e, 0.0
+            if i > 0:
+                r = h_last / h
+                k = (e / (-h - eta_h) + 1) * (1 / r) if solver_type == "heun" else 0.5 * e * (1 / r)
+                b, c = b + k, -k
+            out.append((a, b, c, s1 * math.sqrt(-math.expm1(-2 * eta_h)) * s_noise if eta else 0.0))
+            h_last = h
+    return out
+
+
+def step_noise_table(name, x, sigmas, eta=1.0, noise_sampler=None):
+    """The unit noise every step of sampler `name` would draw for latent `x` over `sigmas`, as ONE table [steps, *x.shape] of
+    x's dtype on x's device, built before the loop - the same calls in the same order as the sampler itself makes:
+    sample_euler_ancestral and sample_lcm ask `noise_sampler(sigmas[i], sigmas[i + 1])` (default: torch.randn_like(x)) on every
+    step with sigma' > 0; sample_dpmpp_2m_sde asks its BrownianTreeNoiseSampler (default seed) for consecutive intervals when
+    eta != 0.  Rows of steps that draw nothing are zero.  None for the samplers without a noise term."""
+    fam = linear_family(name)
+    if fam is None:
+        raise NotImplementedError(f"no linear one-call step for sampler {getattr(name, '__name__', name)!r} "
+                                  f"(supported: {', '.join(LINEAR_FAMILY)})")
+    if fam in ("euler", "dpmpp_2m") or (fam == "dpmpp_2m_sde" and not eta):
+        return None
+    sig = _steps(sigmas) if torch.is_tensor(sigmas) else [float(s) for s in sigmas]
+    if noise_sampler is None:
+        noise_sampler = BrownianTreeNoiseSampler(x, min(v for v in sig if v > 0), max(sig)) if fam == "dpmpp_2m_sde" \
+            else default_noise_sampler(x)
+    rows = []
+    for i in range(len(sig) - 1):
+        if not sig[i + 1] > 0:
+            rows.append(torch.zeros_like(x))
+        elif fam == "dpmpp_2m_sde" or not torch.is_tensor(sigmas):
+            rows.append(noise_sampler(sig[i], sig[i + 1]).to(x.dtype))
+        else:
+            rows.append(noise_sampler(sigmas[i], sigmas[i + 1]).to(x.dtype))
+    return torch.stack(rows)

@@ -10,7 +10,7 @@ that covers the highest occupied slot; empty slots below it are IDLE rows (zero 
 captured once (`warm()`); joins, leaves and bucket switches only refresh static buffers in place (text rows, their packed K/V,
 the compressed region tables).
 
-Per step: ONE launch of dsc_cfg_dpmpp2m_step_rows takes the eps of the bucket that just ran and writes the next bucket's input -
+Per step: ONE launch of the per-row sampler step takes the eps of the bucket that just ran and writes the next bucket's input -
 per slot its own sigma, guidance, DPM++ 2M coefficients (c = 0 on a request's first step), time-embedding row (of its own
 `temb_add_table`) and sigma of its std group (read by the region cross-attention under DSC_FLAG_SIGMA_PER_GROUP) - then the
 next bucket's graph replays.  No host<->device synchronisation per step: a request's completion is a CUDA event recorded after
@@ -21,6 +21,16 @@ Image-conditioned requests.  A request with `image` is img2img (the last `streng
 UNet: its image latents, noise and mask rows stay on the device while it runs, and the per-row step blends the known region into
 the model input of every model call after its first (dsc_cfg_dpmpp2m_step_rows_known, what `inpaiting`'s eager hook does per
 call).  That launch replaces the plain one only for transitions in which an inpainting slot steps.
+
+Samplers and parameterisation.  A request names its sampler (`sampler_name`: one of sampling.LINEAR_FAMILY - Euler, Euler a,
+DPM++ 2M (default), DPM++ 2M SDE, LCM - by name or as the callable) with `eta` / `s_noise` / `solver_type`; the noise of all its
+steps is one table on the device from submit until it leaves (`step_noise`, or sampling.step_noise_table from `seed` /
+`generator`), and its record for step j points at row j.  A transition in which every stepping slot is DPM++ 2M on an
+eps-prediction model launches dsc_cfg_dpmpp2m_step_rows as before; any other launches dsc_cfg_linear_step_rows for all slots
+(DPM++ 2M slots ride in it with the same bits).  On a v-prediction pipeline every slot carries CompVisVDenoiser's scalars (and,
+with `pass_kwargs = False`, zero region tables: the reference's v-prediction path never sees the region prompt).  The
+known-region launch of inpainting carries DPM++ 2M records only, so an inpainting request and a request of another sampler never
+share a batch: the later one waits in the queue until the others have left.
 
 The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
 request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
@@ -36,6 +46,7 @@ from .. import _lib, ops
 from . import sampling
 from .attention_modify import weight_func_is_default
 from .encode_region_map_function import encode_region_map
+from .external_k_diffusion import DiscreteVDDPMDenoiser
 
 MAX_TEXT_KEYS = 384                  # the chunked prepared-operand kernels (ops.region_xattn_packed)
 _UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter", "ip_adapter_image", "ip_adapter_image_embeds")
@@ -55,7 +66,8 @@ def _spatial_size(image):
 
 class _Request:
     __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
-                 "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known")
+                 "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known",
+                 "family", "snoise", "skipout", "noise")
 
 
 class ServingBatcher:
@@ -80,7 +92,8 @@ class ServingBatcher:
         self._n = None                         # bucket whose eps is pending (None: nothing ran yet / the batch drained)
         self._members = {}                     # bucket -> per-slot request ids its static buffers were last refreshed for
         self._next_id = 0
-        self._stats = collections.Counter(captures=0, joins=0, leaves=0, bucket_switches=0, steps=0, refreshes=0)
+        self._stats = collections.Counter(captures=0, joins=0, leaves=0, bucket_switches=0, steps=0, refreshes=0,
+                                          linear_transitions=0)
         self._warm_captures = None
         self._thread = None
         self._stop = False
@@ -98,7 +111,9 @@ class ServingBatcher:
     def submit(self, request):
         """request: txt2img_coalesced's request dict plus its own `num_inference_steps` (default 25), `sampler_opt` (the
         schedule: karras / exponential / ...), `guidance_scale` (> 1, default 7.5) and `latents` / `generator`; optional
-        `output_type` ("latent", default, or what latent_to_image takes).  Returns a Future of the final output."""
+        `output_type` ("latent", default, or what latent_to_image takes), `sampler_name` (sampling.LINEAR_FAMILY, default
+        DPM++ 2M) with `eta` / `s_noise` / `solver_type`, and `step_noise` ([steps, 1, 4, h, w]: the noise of every step;
+        default: drawn as the sampler itself would, from `seed` / `generator`).  Returns a Future of the final output."""
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -160,8 +175,21 @@ class ServingBatcher:
         if not isinstance(request, dict):
             raise TypeError("serve: a request is a dict (txt2img_coalesced's request + num_inference_steps / sampler_opt / "
                             "guidance_scale)")
-        if getattr(pipe, "v_prediction", False):
-            raise ValueError("serve: v-prediction models are not supported (the per-row step computes x - sigma * eps)")
+        v_pred = bool(getattr(pipe, "v_prediction", False))
+        # the v scalars (step_skip, c_out) come from the denoiser object, the choice of launch from the flag: setup_unet sets
+        # both from the scheduler; a flag flipped by hand on an eps-prediction pipeline (tests/test_serving_host.py does that to
+        # probe the former v-prediction rejection) would otherwise be served with eps scalars
+        if v_pred != isinstance(pipe.k_diffusion_model, DiscreteVDDPMDenoiser):
+            raise ValueError("serve: pipe.v_prediction and the denoiser disagree: a v-prediction pipeline needs CompVisVDenoiser's "
+                             "scalars (setup_unet builds both from the scheduler's prediction_type; do not set the flag alone)")
+        sampler = request.get("sampler_name") or "dpmpp_2m"
+        family = sampling.linear_family(sampler)
+        if family is None:
+            raise ValueError(f"serve: `sampler_name` {getattr(sampler, '__name__', sampler)!r} has no per-row step (supported: "
+                             f"{', '.join(sampling.LINEAR_FAMILY)}; use txt2img)")
+        if request.get("mask_image") is not None and (family != "dpmpp_2m" or v_pred):
+            raise ValueError("serve: `mask_image` (inpainting) runs DPM++ 2M on an eps-prediction model only (the known-region "
+                             "step, dsc_cfg_dpmpp2m_step_rows_known); drop `sampler_name` or use inpaiting")
         if (request.get("height", self.height), request.get("width", self.width)) != (self.height, self.width):
             raise ValueError(f"serve: this batcher runs {self.height}x{self.width} images, the request asks for "
                              f"{request.get('height')}x{request.get('width')}")
@@ -198,12 +226,34 @@ class ServingBatcher:
         r.sig = sig if sig is not None else r.sig_dev.detach().float().cpu().tolist()
         if t_start:                                                  # img2img / inpaiting keep the schedule's tail (:637-647)
             r.sig, r.sig_dev = r.sig[t_start:], r.sig_dev[t_start:]
-        r.coeffs = sampling.dpmpp_2m_coefficients(r.sig)
+        r.family = family
+        eta = float(request.get("eta", 1.0))
+        args = {}
+        if family in ("euler_ancestral", "dpmpp_2m_sde"):
+            args.update(eta=eta, s_noise=float(request.get("s_noise", 1.0)))
+        if family == "dpmpp_2m_sde":
+            args["solver_type"] = request.get("solver_type") or "midpoint"
+            if args["solver_type"] not in ("midpoint", "heun"):
+                raise ValueError(f"serve: `solver_type` must be 'midpoint' or 'heun', got {args['solver_type']!r}")
+        abcs = sampling.linear_step_coefficients(family, r.sig, **args)
+        r.coeffs = [c4[:3] for c4 in abcs]
+        r.snoise = [c4[3] for c4 in abcs]
         kdm = pipe.k_diffusion_model
         r.scal = []
+        # None: DPM++ 2M's own launch serves the request (c_skip = 1, c_out = -sigma)
+        r.skipout = [] if family != "dpmpp_2m" or v_pred else None
         for s_ in r.sig[:len(r.coeffs)]:
-            c_in, _, t = kdm.step_scalars(s_)
+            c_in, c_out, t = kdm.step_scalars(s_)
             r.scal.append((c_in, float(t)))
+            if r.skipout is not None:
+                r.skipout.append((kdm.step_skip(s_), c_out))
+        r.noise = None
+        table = request.get("step_noise")
+        if table is not None:
+            want = (len(r.coeffs), 1, 4, self.height // 8, self.width // 8)
+            if not torch.is_tensor(table) or tuple(table.shape) != want:
+                raise ValueError(f"serve: `step_noise` must be a {list(want)} tensor (one unit-noise row per step), got "
+                                 f"{list(table.shape) if torch.is_tensor(table) else type(table).__name__}")
         ids = request.get("text_input_ids") or [None, None]
         tabs = encode_region_map(pipe, request.get("region_map_state"), width=self.width, height=self.height,
                                  num_images_per_prompt=1, text_ids=ids)
@@ -218,6 +268,8 @@ class ServingBatcher:
             self.exec.prepare(r)
         else:
             self.exec.prepare_image(r)
+        if any(v != 0.0 for v in r.snoise):
+            self.exec.prepare_noise(r, eta)
         return r
 
     def _image_request(self, r):
@@ -273,6 +325,8 @@ class ServingBatcher:
 
     def _request_tables(self, tabs):
         lv = self.levels()
+        if getattr(self.pipe, "v_prediction", False) and not self.pipe.k_diffusion_model.pass_kwargs:
+            tabs = None                                             # CompVisVDenoiser.get_v drops the region prompt
         if not isinstance(tabs, dict) or not tabs:                  # no masks: the region path with zero tables (quirk q2)
             return {L: torch.zeros(2, L, S) for L, S in lv.items()}
         if sorted(tabs) != sorted(lv) or any(tuple(w.shape) != (2, L, lv[L]) for L, w in tabs.items()):
@@ -292,6 +346,17 @@ class ServingBatcher:
                 return False
         return True
 
+    @staticmethod
+    def _launch_compatible(head, members):
+        """One launch serves every stepping slot of a transition, and the known-region launch (inpainting) carries DPM++ 2M /
+        eps-prediction records only: it has no c_skip / c_out / noise fields.  So an inpainting request and a request of another
+        sampler never share a batch - whichever comes second waits at the head of the queue (FIFO) until the others have left."""
+        if head.kind == "inpaint":
+            return all(r.skipout is None for r in members)
+        if head.skipout is not None:
+            return all(r.kind != "inpaint" for r in members)
+        return True
+
     def _step_locked(self):
         slots = self._slots
         active = [r for r in slots if r is not None]
@@ -304,6 +369,8 @@ class ServingBatcher:
                 break
             head = self._queue[0]
             if not self._tables_fit([r for r in slots if r is not None] + [head]):
+                break
+            if not self._launch_compatible(head, [r for r in slots if r is not None]):
                 break
             self._queue.popleft()
             head.slot, head.i = free, 0
@@ -324,6 +391,9 @@ class ServingBatcher:
             if r is not None and r in stepping:
                 a, b, c = r.coeffs[r.i]
                 rec = {"mode": ops.ROW_STEP, "sigma": r.sig[r.i], "guidance": r.guidance, "a": a, "b": b, "c": c}
+                if r.skipout is not None:
+                    rec.update(c_skip=r.skipout[r.i][0], c_out=r.skipout[r.i][1], s=r.snoise[r.i],
+                               noise=self.exec.noise_row(r, r.i) if r.snoise[r.i] != 0.0 else None)
                 if r in leaving:
                     rec.update(c_in_next=0.0, t_next=0.0, sigma_next=1.0, temb_row=None, req=r, step=r.i, next_step=None)
                 else:
@@ -349,13 +419,19 @@ class ServingBatcher:
             self.exec.load_latent(r)
         self._stats["joins"] += len(joins)
         if any(k is not None for k in known):
+            if any(rec["mode"] == ops.ROW_STEP and rec["req"].skipout is not None for rec in recs):
+                raise RuntimeError("serve: an inpainting slot and a slot of another sampler step together (admission check bypassed)")
             self.exec.transition_known(n_src, nd, recs, known)
+        elif any(rec["mode"] == ops.ROW_STEP and rec["req"].skipout is not None for rec in recs):
+            self.exec.transition_linear(n_src, nd, recs)           # a slot steps another sampler / a v-prediction model
+            self._stats["linear_transitions"] += 1
         else:
             self.exec.transition(n_src, nd, recs)
         for r in leaving:
             slots[r.slot] = None
             self._done.append((r, self.exec.finish(r)))
             r.known = None                           # its image / noise / mask rows go back to the allocator (stream-ordered)
+            r.noise = None                           # ... and its noise table
             self._stats["leaves"] += 1
         for r in stepping:
             r.i += 1
@@ -500,6 +576,27 @@ class _GraphExecutor:
             r.lat = r.lat.to(dt)
             self._tables_and_text(r)
 
+    def prepare_noise(self, r, eta):
+        """the request's noise table on the device, [steps, 1, c, h, w]: `step_noise`, or the draws its sampler would make"""
+        req, dev, dt = r.req, self.device, self.dtype
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self.stream):
+            table = req.get("step_noise")
+            if table is None:
+                like = torch.empty((1,) + self.lat_shape, device=dev, dtype=dt)
+                ns = None
+                if r.family == "dpmpp_2m_sde":
+                    if req.get("seed") is not None:              # protocol mode's `brownian_noise` sampler, seeded per request
+                        ns = self.pipe.create_noise_sampler(like, r.sig_dev, len(r.coeffs), int(req["seed"]))
+                elif req.get("generator") is not None:
+                    gen = req["generator"]
+                    ns = lambda *_: torch.randn(like.shape, generator=gen, device=gen.device, dtype=dt).to(dev)   # noqa: E731
+                table = sampling.step_noise_table(r.family, like, r.sig_dev, eta=eta, noise_sampler=ns)
+            r.noise = table.to(device=dev, dtype=dt).contiguous()
+
+    def noise_row(self, r, j):
+        return r.noise[j, 0]
+
     def temb_row(self, r, j):
         return r.temb[j]
 
@@ -622,6 +719,17 @@ class _GraphExecutor:
         with torch.cuda.stream(self.stream):
             ops.cfg_dpmpp2m_step_rows(self.x, eps, self.old, n_src, st_d["x_in"], st_d["t"], st_d["sigma"], recs,
                                       tadd=st_d["tadd"])
+
+    def transition_linear(self, n_src, n_dst, recs):
+        """transition() for a step in which a slot steps a sampler other than DPM++ 2M, or a v-prediction model: the same ONE
+        launch through dsc_cfg_linear_step_rows (records without c_skip / c_out are DPM++ 2M's: same bits)"""
+        st_d = self.st.get(n_dst)
+        if st_d is None:
+            self.ensure(n_dst)
+            st_d = self.st[n_dst]
+        eps = self.st[n_src]["eps"] if n_src else None
+        with torch.cuda.stream(self.stream):
+            ops.cfg_linear_step_rows(self.x, eps, self.old, n_src, st_d["x_in"], st_d["t"], st_d["sigma"], recs, tadd=st_d["tadd"])
 
     def transition_known(self, n_src, n_dst, recs, known):
         """transition() for a step in which an inpainting slot steps: the same ONE launch, with the known-region records"""

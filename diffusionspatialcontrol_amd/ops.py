@@ -1027,8 +1027,15 @@ class RowStep(ctypes.Structure):
                 ("sigma_next", ctypes.c_float), ("temb_row", ctypes.c_void_p)]
 
 
-def _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd):
-    """shape / dtype / device validation shared by the per-row sampler steps -> (n_dst, n_slots, chw, dsc_row_step array)"""
+class RowLinear(ctypes.Structure):
+    """dsc_row_linear (include/dsc_hip.h)"""
+    _fields_ = RowStep._fields_[:-1] + [("c_skip", ctypes.c_float), ("c_out", ctypes.c_float), ("s", ctypes.c_float),
+                                        ("temb_row", ctypes.c_void_p), ("noise", ctypes.c_void_p)]
+
+
+def _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=False):
+    """shape / dtype / device validation shared by the per-row sampler steps -> (n_dst, n_slots, chw, dsc_row_step array, or
+    dsc_row_linear array with linear=True)"""
     _require_gpu(x, old, x_in, t_buf, sigma_groups)
     n_dst = t_buf.numel() // 2
     n_slots = len(rows)
@@ -1049,16 +1056,24 @@ def _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, t
     for name, t, n in (("t_buf", t_buf, 2 * n_dst), ("sigma_groups", sigma_groups, n_dst)):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device or t.numel() != n:
             raise ValueError(f"{what}: {name} must be a dense fp32 [{n}] on {x.device}")
-    recs = (RowStep * n_slots)()
+    recs = ((RowLinear if linear else RowStep) * n_slots)()
     for i, r in enumerate(rows):
         tr = r.get("temb_row")
         if tr is not None:
             if tadd is None or tr.dtype != torch.float16 or tr.device != x.device or tr.stride(-1) != 1 \
                     or tr.numel() != tadd.shape[1]:
                 raise ValueError(f"{what}: temb_row must be an fp16 row of the tadd buffer's width")
-        recs[i] = RowStep(int(r["mode"]), *(float(r.get(f, 0.0)) for f in ("sigma", "guidance", "a", "b", "c", "c_in_next",
-                                                                             "t_next")),
-                          float(r.get("sigma_next", 1.0)), None if tr is None else tr.data_ptr())
+        head = (int(r["mode"]), *(float(r.get(f, 0.0)) for f in ("sigma", "guidance", "a", "b", "c", "c_in_next", "t_next")),
+                float(r.get("sigma_next", 1.0)))
+        if not linear:
+            recs[i] = RowStep(*head, None if tr is None else tr.data_ptr())
+            continue
+        nz = r.get("noise")
+        if nz is not None and (nz.dtype != torch.float16 or nz.device != x.device or not nz.is_contiguous() or nz.numel() != chw):
+            raise ValueError(f"{what}: rows[{i}]['noise'] must be a dense fp16 [{chw}] row on {x.device}")
+        # eps-prediction unless the record says otherwise: D = x - sigma * e
+        recs[i] = RowLinear(*head, float(r.get("c_skip", 1.0)), float(r.get("c_out", -float(r.get("sigma", 0.0)))),
+                            float(r.get("s", 0.0)), None if tr is None else tr.data_ptr(), None if nz is None else nz.data_ptr())
     for t in (x, old, x_in, t_buf, sigma_groups, tadd):
         _drop_gn_partials(t)
     return n_dst, n_slots, chw, recs
@@ -1075,6 +1090,19 @@ def cfg_dpmpp2m_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, t
         _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
         0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), n_slots, chw, 0, _stream_ptr(x))
     _lib.check(rc, "dsc_cfg_dpmpp2m_step_rows")
+
+
+def cfg_linear_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=None):
+    """cfg_dpmpp2m_step_rows for every sampler of sampling.LINEAR_FAMILY and both parameterisations (dsc_cfg_linear_step_rows):
+    D = c_skip x + c_out e, x' = a x + b D + c D_old + s noise.  rows: cfg_dpmpp2m_step_rows' dicts plus `c_skip` / `c_out`
+    (default 1 / -sigma: eps-prediction), `s` and `noise` (this step's fp16 [chw] unit noise row on x's device, or None: no noise
+    term).  A record without them gives cfg_dpmpp2m_step_rows' bits."""
+    what = "cfg_linear_step_rows"
+    n_dst, n_slots, chw, recs = _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=True)
+    rc = _lib.load_library().dsc_cfg_linear_step_rows(
+        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
+        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), n_slots, chw, 0, _stream_ptr(x))
+    _lib.check(rc, what)
 
 
 class RowKnown(ctypes.Structure):

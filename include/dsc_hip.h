@@ -243,6 +243,34 @@ int dsc_cfg_dpmpp2m_step_rows_known(void* x, const void* eps, void* old, int n_s
                                     float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
                                     const dsc_row_step* rows /* host */, const dsc_row_known* known /* host */, int n_slots,
                                     int chw, int dtype, void* stream);
+/*
+ * dsc_cfg_dpmpp2m_step_rows generalised to the one-model-call-per-step samplers and to v-prediction: per slot, host scalars
+ * (modules/sampling.py linear_step_coefficients) select the update of sample_euler (a = sigma'/sigma, b = 1 - a),
+ * sample_euler_ancestral (the same to sigma_down, s = s_noise * sigma_up), sample_dpmpp_2m (s = 0), sample_dpmpp_2m_sde
+ * (midpoint / heun; s = sigma' sqrt(-expm1(-2 eta h)) s_noise) and sample_lcm (a = 0, b = 1, s = sigma'), and (c_skip, c_out)
+ * the parameterisation: eps-prediction c_skip = 1, c_out = -sigma; v-prediction CompVisVDenoiser.get_scalings.  Same launch
+ * contract as dsc_cfg_dpmpp2m_step_rows (slot = row, STEP / JOIN / IDLE, separate source and destination buckets, t_buf / tadd /
+ * sigma_groups written per slot); one 64-byte record per slot passed by value.  For a DSC_ROW_STEP slot, all fp32, every
+ * intermediate rounded to fp32 before the next operation, fp16 rounding where marked:
+ *   e  = fma(guidance, m_c - m_u, m_u)                                the model output (eps or v) rows {i, n_src + i}
+ *   D  = fp16(fma(c_out, e, c_skip * x))                              old = D
+ *   x' = fp16(noise ? fma(s, noise, fma(c, old, fma(a, x, b * D))) : fma(c, old, fma(a, x, b * D)))
+ *   x_in rows {i, n_dst + i} = fp16(x' * c_in_next)
+ * With c_skip = 1, c_out = -sigma and noise == NULL these are dsc_cfg_dpmpp2m_step_rows' bits.  JOIN / IDLE as there.
+ * noise: this step's unit noise row of the slot, fp16 [chw], 16-byte aligned, or NULL (no noise term; s is ignored).
+ * The inpainting known-region blend stays with dsc_cfg_dpmpp2m_step_rows_known.
+ */
+typedef struct {
+    int   mode;                                    /* DSC_ROW_STEP, DSC_ROW_JOIN, DSC_ROW_IDLE */
+    float sigma, guidance, a, b, c;                /* this step (STEP); sigma is informative: D reads c_skip / c_out */
+    float c_in_next, t_next, sigma_next;           /* what the coming UNet step reads */
+    float c_skip, c_out, s;                        /* D = c_skip x + c_out e; s scales the noise row */
+    const void* temb_row;                          /* fp16 time-embedding row for the coming step, or NULL */
+    const void* noise;                             /* fp16 [chw] unit noise of this step, or NULL */
+} dsc_row_linear;
+int dsc_cfg_linear_step_rows(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf, float* sigma_groups,
+                             void* tadd, int tadd_halfs, int n_dst, const dsc_row_linear* rows /* host */, int n_slots,
+                             int chw, int dtype, void* stream);
 /* out = a*x + b*denoised + c*old  (old may be NULL when c == 0): the sampler update alone, for callers that keep
  * the reference's `sampler(model_fn, x, sigmas=...)` control flow.  n elements, n % 8 == 0. */
 int dsc_dpmpp2m_update(const void* x, const void* denoised, const void* old, float a, float b, float c,
