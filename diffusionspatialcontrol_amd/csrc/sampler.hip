@@ -103,12 +103,13 @@ __device__ __forceinline__ float as_f32(float v) {
     return v;
 }
 
-// ---- what the three per-row kernels below share (slot i = blockIdx.y)
+// ---- what the per-row kernels below share (slot i = blockIdx.y; T: the workgroup size, 256 for the first three)
 // the slot's time-embedding row -> both of its CFG rows of the destination bucket
+template <int T = 256>
 __device__ __forceinline__ void rows_copy_temb(const void* temb_row, half_t* tadd, int tadd_halfs, int n_dst, int i) {
     if (!temb_row) return;
     const int t8 = tadd_halfs / 8;
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < 2 * t8; j += gridDim.x * 256) {
+    for (int j = blockIdx.x * T + threadIdx.x; j < 2 * t8; j += gridDim.x * T) {
         const int h = j >= t8, c = j - h * t8;
         *reinterpret_cast<h8_t*>(tadd + ((long long)(h ? n_dst + i : i) * tadd_halfs) + c * 8) =
             reinterpret_cast<const h8_t*>(temb_row)[c];
@@ -116,9 +117,10 @@ __device__ __forceinline__ void rows_copy_temb(const void* temb_row, half_t* tad
 }
 // JOIN: prepare_kernel's line for a freshly loaded start latent (a request's first model call: never blended), old row zeroed;
 // IDLE: zero input rows
+template <int T = 256>
 __device__ __forceinline__ void rows_join_or_idle(bool join, float c_in, const half_t* xr, half_t* orow, half_t* xi_u, half_t* xi_c,
                                                   long long v8) {
-    for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
+    for (long long k = blockIdx.x * (long long)T + threadIdx.x; k < v8; k += (long long)gridDim.x * T) {
         h8_t o;
         if (join) {
             float f[8];
@@ -323,6 +325,124 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(half_t* x, const half_
     if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
 }
 
+// dsc_cfg_linear_step_rows_rescale: linear_rows_kernel with the guidance rescale of arXiv 2305.08891 sec. 3.4 per slot, applied
+// - as the reference does - to the denoised estimate: D' = K D, K = phi sqrt(SSD(D_c) / SSD(D)) + (1 - phi), the two sums of
+// squared deviations taken over the slot's whole row.  x is updated in place, so a slot with phi > 0 belongs to ONE workgroup
+// (blockIdx.x == 0; the slot's other workgroups leave once the embedding row is copied): it reads x / m_u / m_c for the four
+// sums, meets at the workgroup barrier of the across-wave sum - after which no thread reads the old x of an element it does
+// not own - and then updates the row, every thread the elements it alone reads and writes.  Slots with phi == 0 and JOIN /
+// IDLE slots keep linear_rows_kernel's striding over gridDim.x and its bits.  No atomics, nothing crosses workgroups.
+// The sums have one fixed order: per thread over k = tid, tid + T, ... (8 halfs in order each), a 6-stage xor butterfly in the
+// wave (32, 16, .. 1: every lane ends with the same value), then waves 0 .. T/64 - 1 in order out of LDS.
+#ifndef DSC_RESCALE_THREADS
+#define DSC_RESCALE_THREADS 1024
+#endif
+struct RowRescales { float phi[DSC_ROW_STEP_MAX_SLOTS]; };
+
+template <int T>
+__global__ __launch_bounds__(T) void linear_rows_rescale_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
+                                                                float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
+                                                                int n_dst, int chw, const RowLinears rs, const RowRescales ps) {
+    static_assert(T % 64 == 0 && T <= 1024, "whole waves");
+    __shared__ double red[T / 64][4];
+    const int i = blockIdx.y;
+    const dsc_row_linear& r = rs.r[i];
+    const bool dst = i < n_dst;
+    const long long v8 = chw / 8;
+    if (dst) rows_copy_temb<T>(r.temb_row, tadd, tadd_halfs, n_dst, i);
+    half_t* xi_u = x_in + (long long)i * chw;
+    half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
+    if (r.mode == DSC_ROW_STEP) {
+        const float phi = ps.phi[i];
+        const bool owned = phi > 0.0f;                                      // per slot: uniform per workgroup
+        if (owned && blockIdx.x != 0) return;
+        const float g = r.guidance, a = r.a, b = r.b, c = r.c, c_in_next = r.c_in_next;
+        const float c_skip = r.c_skip, c_out = r.c_out, s = r.s;
+        const half_t* nse = static_cast<const half_t*>(r.noise);
+        half_t* xr = x + (long long)i * chw;
+        half_t* orow = old + (long long)i * chw;
+        const half_t* eur = eps + (long long)i * chw;
+        const half_t* ecr = eps + (long long)(n_src + i) * chw;
+        float K = 1.0f;
+        if (owned) {
+            double sc = 0.0, qc = 0.0, sg = 0.0, qg = 0.0;                   // sum Dc, sum Dc^2, sum Dg, sum Dg^2
+            for (long long k = threadIdx.x; k < v8; k += T) {
+                float xv[8], eu[8], ec[8];
+                unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), xv);
+                unpack8(*reinterpret_cast<const h8_t*>(eur + k * 8), eu);
+                unpack8(*reinterpret_cast<const h8_t*>(ecr + k * 8), ec);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
+                    const float sx = as_f32(c_skip * xv[j]);
+                    const double dc = (double)as_f32(__builtin_fmaf(c_out, ec[j], sx));
+                    const double dg = (double)as_f32(__builtin_fmaf(c_out, e, sx));
+                    sc += dc;
+                    qc = __builtin_fma(dc, dc, qc);
+                    sg += dg;
+                    qg = __builtin_fma(dg, dg, qg);
+                }
+            }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+                sc += __shfl_xor(sc, m);
+                qc += __shfl_xor(qc, m);
+                sg += __shfl_xor(sg, m);
+                qg += __shfl_xor(qg, m);
+            }
+            if ((threadIdx.x & 63) == 0) {
+                double* w = red[threadIdx.x >> 6];
+                w[0] = sc, w[1] = qc, w[2] = sg, w[3] = qg;
+            }
+            __syncthreads();                                                // also: every read of the old x row is done
+            sc = qc = sg = qg = 0.0;
+            for (int w = 0; w < T / 64; ++w) {
+                sc += red[w][0];
+                qc += red[w][1];
+                sg += red[w][2];
+                qg += red[w][3];
+            }
+            const double n = (double)chw;
+            const double ssd_c = qc - sc * sc / n, ssd_g = qg - sg * sg / n;   // (the n - 1 of both stds cancels)
+            K = (float)((double)phi * __builtin_sqrt(ssd_c / ssd_g) + (1.0 - (double)phi));
+        }
+        const long long k0 = owned ? threadIdx.x : blockIdx.x * (long long)T + threadIdx.x;
+        const long long dk = owned ? T : (long long)gridDim.x * T;
+        for (long long k = k0; k < v8; k += dk) {
+            float xv[8], eu[8], ec[8], ov[8], dn[8], xn[8], xi[8], nz[8];
+            unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), xv);
+            unpack8(*reinterpret_cast<const h8_t*>(eur + k * 8), eu);
+            unpack8(*reinterpret_cast<const h8_t*>(ecr + k * 8), ec);
+            unpack8(*reinterpret_cast<const h8_t*>(orow + k * 8), ov);
+            if (nse) unpack8(*reinterpret_cast<const h8_t*>(nse + k * 8), nz);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                // linear_rows_kernel's lines, D scaled by K before its fp16 rounding in an owned slot
+                const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
+                const float sx = as_f32(c_skip * xv[j]);
+                float dg = as_f32(__builtin_fmaf(c_out, e, sx));
+                if (owned) dg = as_f32(K * dg);
+                dn[j] = (float)(half_t)dg;
+                const float bd = as_f32(b * dn[j]);
+                float xo = as_f32(__builtin_fmaf(c, ov[j], as_f32(__builtin_fmaf(a, xv[j], bd))));
+                if (nse) xo = as_f32(__builtin_fmaf(s, nz[j], xo));
+                xn[j] = (float)(half_t)xo;
+                xi[j] = as_f32(xn[j] * c_in_next);
+            }
+            *reinterpret_cast<h8_t*>(orow + k * 8) = pack8(dn);
+            *reinterpret_cast<h8_t*>(xr + k * 8) = pack8(xn);
+            if (dst) {
+                const h8_t o = pack8(xi);
+                *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
+                *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+            }
+        }
+    } else if (dst) {
+        rows_join_or_idle<T>(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
+    }
+    if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
+}
+
 int grid_for(long long n8) {
     long long g = (n8 + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
@@ -481,5 +601,40 @@ extern "C" int dsc_cfg_linear_step_rows(void* x, const void* eps, void* old, int
     DSC_LAUNCH(linear_rows_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
                static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
                static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs);
+    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+}
+
+extern "C" int dsc_cfg_linear_step_rows_rescale(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
+                                                float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
+                                                const dsc_row_linear* rows, const float* rescale, int n_slots, int chw, int dtype,
+                                                void* stream) {
+    if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || !rescale || n_src < 0 || n_dst <= 0 || chw <= 0)
+        return DSC_ERR_BAD_ARG;
+    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
+    if (dtype != DSC_F16 || chw % 8 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
+    RowLinears rs{};
+    RowRescales ps{};
+    bool any_row = false;
+    for (int i = 0; i < n_slots; ++i) {
+        const dsc_row_linear& r = rows[i];
+        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
+        if (r.mode == DSC_ROW_STEP) {
+            if (r.noise && !al16(r.noise)) return DSC_ERR_UNSUPPORTED;
+            if (!(rescale[i] >= 0.0f && rescale[i] <= 1.0f)) return DSC_ERR_BAD_ARG;      // (NaN lands here too)
+            ps.phi[i] = rescale[i];
+        }
+        rs.r[i] = r;
+    }
+    if (any_row) {
+        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
+        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
+    }
+    constexpr int T = DSC_RESCALE_THREADS;
+    const long long v8 = chw / 8;
+    long long gx = (v8 + T - 1) / T;
+    gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
+    DSC_LAUNCH(linear_rows_rescale_kernel<T>, dim3((unsigned)gx, (unsigned)n_slots), dim3(T), 0, static_cast<hipStream_t>(stream),
+               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
+               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs, ps);
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }

@@ -523,7 +523,7 @@ class StableDiffusionPipeline:
                                           cross_attention_kwargs, start_time, timeout, slot=slot, sampler=sampler,
                                           sampler_args=self._fused_sampler_args(sampler, sigmas, eta, num_inference_steps,
                                                                                 sampler_opt, latents, seed, step_noise),
-                                          step_noise=step_noise)
+                                          step_noise=step_noise, guidance_rescale=guidance_rescale)
         else:
             latents = self._denoise_protocol(sampler, latents, sigmas, text, region_state, weight_func, guidance_scale,
                                              guidance_rescale, n_img, cross_attention_kwargs, eta,
@@ -799,7 +799,7 @@ class StableDiffusionPipeline:
                                           cross_attention_kwargs, start_time, timeout, sampler=sampler,
                                           sampler_args=self._fused_sampler_args(sampler, sigma_sched, None, len(sigma_sched),
                                                                                 sampler_opt, latents, seed, step_noise),
-                                          step_noise=step_noise)
+                                          step_noise=step_noise, guidance_rescale=guidance_rescale)
         else:
             args = self.get_sampler_extra_args_i2i(sigma_sched, len(sigma_sched), sampler_opt, latents, seed, sampler)
             latents = self._denoise_protocol(sampler, latents, sigma_sched, text, region_state, weight_func, guidance_scale,
@@ -1333,8 +1333,9 @@ class StableDiffusionPipeline:
                              f"got {tuple(noise.shape) if torch.is_tensor(noise) else type(noise).__name__}")
         return noise.to(device=x.device, dtype=x.dtype).contiguous()
 
-    def _linear_fused_loop(self, st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout):
-        """the fused loop's steps through the per-row kernel: one record per image, all on the same step of the same schedule"""
+    def _linear_fused_loop(self, st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout, rescale=0.0):
+        """the fused loop's steps through the per-row kernel: one record per image, all on the same step of the same schedule;
+        rescale > 0: every record carries it (ops.cfg_linear_step_rows then issues the rescale launch)"""
         kdm = self.k_diffusion_model
         for i, (a, b, c, s) in enumerate(coeffs):
             if start_time > 0 and timeout > 0:
@@ -1345,20 +1346,29 @@ class StableDiffusionPipeline:
             rec = {"mode": ops.ROW_STEP, "sigma": sig[i], "guidance": guidance_scale, "a": a, "b": b, "c": c, "s": s,
                    "c_skip": kdm.step_skip(sig[i]), "c_out": kdm.step_scalars(sig[i])[1], "c_in_next": c_in_n, "t_next": t_n,
                    "sigma_next": max(nxt, 1e-10), "temb_row": tab[i + 1] if tab is not None and i + 1 < len(coeffs) else None}
+            if rescale > 0.0:
+                rec["rescale"] = rescale
             recs = [dict(rec, noise=None if noise is None or s == 0.0 else noise[i, j if noise.shape[1] > 1 else 0])
                     for j in range(n_img)]
             ops.cfg_linear_step_rows(x, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, tadd=st["tadd"])
 
     def _denoise_fused(self, latents, sigmas, text, region_state, weight_func, guidance_scale, n_img,
-                       cross_attention_kwargs, start_time, timeout, slot=0, sampler=None, sampler_args=None, step_noise=None):
+                       cross_attention_kwargs, start_time, timeout, slot=0, sampler=None, sampler_args=None, step_noise=None,
+                       guidance_rescale=0.0):
         """sampler: None (DPM++ 2M) or one of sampling.LINEAR_FAMILY's functions.  DPM++ 2M on an eps-prediction model is one
         dsc_cfg_dpmpp2m_step per step; every other member, and every v-prediction model, one dsc_cfg_linear_step_rows with a
-        record per image.  step_noise: the noise table [steps, 1 or n_img, c, h, w] (default: sampling.step_noise_table)."""
+        record per image.  step_noise: the noise table [steps, 1 or n_img, c, h, w] (default: sampling.step_noise_table).
+        guidance_rescale (phi, arXiv 2305.08891 sec. 3.4) > 0: every family member, DPM++ 2M on an eps model included, takes the
+        per-row path and its records carry phi - the statistics of rescale_noise_cfg are taken inside the sampler launch
+        (dsc_cfg_linear_step_rows_rescale), on the denoised estimate as protocol mode's model_fn does."""
+        guidance_rescale = float(guidance_rescale)
+        if not 0.0 <= guidance_rescale <= 1.0:
+            raise ValueError(f"fused=True: guidance_rescale must be in [0, 1], got {guidance_rescale}")
         family = "dpmpp_2m" if sampler is None else sampling.linear_family(sampler)
         if family is None:
             raise NotImplementedError(f"fused=True: sampler {getattr(sampler, '__name__', sampler)!r} has no fused step "
                                       f"(supported: {', '.join(sampling.LINEAR_FAMILY)}); run it with fused=False")
-        rows_path = family != "dpmpp_2m" or self.v_prediction
+        rows_path = family != "dpmpp_2m" or self.v_prediction or guidance_rescale > 0.0
         if rows_path and n_img > ops.ROW_STEP_MAX_SLOTS:
             raise NotImplementedError(f"fused=True: the per-row sampler step takes at most {ops.ROW_STEP_MAX_SLOTS} images per "
                                       f"batch, got {n_img}; run it with fused=False")
@@ -1367,7 +1377,8 @@ class StableDiffusionPipeline:
         # path with no tensors at all and expects this error class)
         if rows_path and not (torch.is_tensor(latents) and latents.is_cuda and text.dtype == torch.float16):
             raise NotImplementedError("fused=True: the per-row sampler step (dsc_cfg_linear_step_rows: every sampler but DPM++ 2M, "
-                                      "and v-prediction models) runs fp16 latents on the GPU; run it with fused=False")
+                                      "v-prediction models, and guidance_rescale) runs fp16 latents on the GPU; run it with "
+                                      "fused=False")
         if self.v_prediction and not self.k_diffusion_model.pass_kwargs:
             region_state, cross_attention_kwargs = None, {}          # CompVisVDenoiser.get_v forwards (x, t, cond) only
         prof = os.environ.get("DSC_PROFILE_HOST") == "1"
@@ -1422,7 +1433,8 @@ class StableDiffusionPipeline:
                 noise = step_noise if step_noise is not None else \
                     sampling.step_noise_table(family, x, sigmas, eta=sargs.get("eta", 1.0), noise_sampler=noise_sampler)
                 noise = self._check_step_noise(noise, len(coeffs), x)
-            self._linear_fused_loop(st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout)
+            self._linear_fused_loop(st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout,
+                                    rescale=guidance_rescale)
             coeffs = []
         for i, (a, b, c) in enumerate(coeffs):
             if start_time > 0 and timeout > 0:

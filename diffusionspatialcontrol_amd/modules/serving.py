@@ -32,6 +32,11 @@ with `pass_kwargs = False`, zero region tables: the reference's v-prediction pat
 known-region launch of inpainting carries DPM++ 2M records only, so an inpainting request and a request of another sampler never
 share a batch: the later one waits in the queue until the others have left.
 
+Guidance rescale.  A request may carry `guidance_rescale` (phi in [0, 1], arXiv 2305.08891 sec. 3.4; the usual companion of
+v-prediction models).  Its STEP records carry `rescale` and, DPM++ 2M on an eps-prediction model included, (c_skip, c_out); a
+transition in which such a slot steps launches dsc_cfg_linear_step_rows_rescale for all slots (ops.cfg_linear_step_rows picks it
+from the records), every other transition the launch it had.  Inpainting with rescale is refused at submit.
+
 The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
 request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
 """
@@ -67,7 +72,7 @@ def _spatial_size(image):
 class _Request:
     __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
                  "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known",
-                 "family", "snoise", "skipout", "noise")
+                 "family", "snoise", "skipout", "noise", "rescale")
 
 
 class ServingBatcher:
@@ -112,8 +117,9 @@ class ServingBatcher:
         """request: txt2img_coalesced's request dict plus its own `num_inference_steps` (default 25), `sampler_opt` (the
         schedule: karras / exponential / ...), `guidance_scale` (> 1, default 7.5) and `latents` / `generator`; optional
         `output_type` ("latent", default, or what latent_to_image takes), `sampler_name` (sampling.LINEAR_FAMILY, default
-        DPM++ 2M) with `eta` / `s_noise` / `solver_type`, and `step_noise` ([steps, 1, 4, h, w]: the noise of every step;
-        default: drawn as the sampler itself would, from `seed` / `generator`).  Returns a Future of the final output."""
+        DPM++ 2M) with `eta` / `s_noise` / `solver_type`, `step_noise` ([steps, 1, 4, h, w]: the noise of every step;
+        default: drawn as the sampler itself would, from `seed` / `generator`) and `guidance_rescale` (in [0, 1], default 0; not
+        with `mask_image`).  Returns a Future of the final output."""
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -190,6 +196,15 @@ class ServingBatcher:
         if request.get("mask_image") is not None and (family != "dpmpp_2m" or v_pred):
             raise ValueError("serve: `mask_image` (inpainting) runs DPM++ 2M on an eps-prediction model only (the known-region "
                              "step, dsc_cfg_dpmpp2m_step_rows_known); drop `sampler_name` or use inpaiting")
+        phi = request.get("guidance_rescale", 0.0)
+        if phi is None:
+            phi = 0.0
+        if isinstance(phi, bool) or not isinstance(phi, (int, float)) or not 0.0 <= phi <= 1.0:      # (NaN fails the range)
+            raise ValueError(f"serve: `guidance_rescale` must be a number in [0, 1], got {phi!r}")
+        phi = float(phi)
+        if request.get("mask_image") is not None and phi > 0.0:
+            raise ValueError("serve: `mask_image` (inpainting) with `guidance_rescale` > 0 is not served (the known-region step "
+                             "has no rescale); use inpaiting")
         if (request.get("height", self.height), request.get("width", self.width)) != (self.height, self.width):
             raise ValueError(f"serve: this batcher runs {self.height}x{self.width} images, the request asks for "
                              f"{request.get('height')}x{request.get('width')}")
@@ -227,6 +242,7 @@ class ServingBatcher:
         if t_start:                                                  # img2img / inpaiting keep the schedule's tail (:637-647)
             r.sig, r.sig_dev = r.sig[t_start:], r.sig_dev[t_start:]
         r.family = family
+        r.rescale = phi
         eta = float(request.get("eta", 1.0))
         args = {}
         if family in ("euler_ancestral", "dpmpp_2m_sde"):
@@ -240,8 +256,9 @@ class ServingBatcher:
         r.snoise = [c4[3] for c4 in abcs]
         kdm = pipe.k_diffusion_model
         r.scal = []
-        # None: DPM++ 2M's own launch serves the request (c_skip = 1, c_out = -sigma)
-        r.skipout = [] if family != "dpmpp_2m" or v_pred else None
+        # None: DPM++ 2M's own launch serves the request (c_skip = 1, c_out = -sigma); with a rescale it needs the linear family's
+        # launch, so its (1, -sigma) are spelled out like any other member's
+        r.skipout = [] if family != "dpmpp_2m" or v_pred or phi > 0.0 else None
         for s_ in r.sig[:len(r.coeffs)]:
             c_in, c_out, t = kdm.step_scalars(s_)
             r.scal.append((c_in, float(t)))
@@ -394,6 +411,8 @@ class ServingBatcher:
                 if r.skipout is not None:
                     rec.update(c_skip=r.skipout[r.i][0], c_out=r.skipout[r.i][1], s=r.snoise[r.i],
                                noise=self.exec.noise_row(r, r.i) if r.snoise[r.i] != 0.0 else None)
+                    if r.rescale > 0.0:
+                        rec["rescale"] = r.rescale
                 if r in leaving:
                     rec.update(c_in_next=0.0, t_next=0.0, sigma_next=1.0, temb_row=None, req=r, step=r.i, next_step=None)
                 else:
@@ -722,7 +741,8 @@ class _GraphExecutor:
 
     def transition_linear(self, n_src, n_dst, recs):
         """transition() for a step in which a slot steps a sampler other than DPM++ 2M, or a v-prediction model: the same ONE
-        launch through dsc_cfg_linear_step_rows (records without c_skip / c_out are DPM++ 2M's: same bits)"""
+        launch through dsc_cfg_linear_step_rows (records without c_skip / c_out are DPM++ 2M's: same bits), or through
+        dsc_cfg_linear_step_rows_rescale when a stepping record carries `rescale` (the wrapper chooses)"""
         st_d = self.st.get(n_dst)
         if st_d is None:
             self.ensure(n_dst)

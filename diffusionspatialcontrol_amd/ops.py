@@ -1096,12 +1096,41 @@ def cfg_linear_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, ta
     """cfg_dpmpp2m_step_rows for every sampler of sampling.LINEAR_FAMILY and both parameterisations (dsc_cfg_linear_step_rows):
     D = c_skip x + c_out e, x' = a x + b D + c D_old + s noise.  rows: cfg_dpmpp2m_step_rows' dicts plus `c_skip` / `c_out`
     (default 1 / -sigma: eps-prediction), `s` and `noise` (this step's fp16 [chw] unit noise row on x's device, or None: no noise
-    term).  A record without them gives cfg_dpmpp2m_step_rows' bits."""
+    term).  A record without them gives cfg_dpmpp2m_step_rows' bits.  A STEP record may carry `rescale` (guidance_rescale, phi
+    in [0, 1], default 0): when any does with phi > 0 the launch is cfg_linear_step_rows_rescale's, otherwise this one's as ever."""
     what = "cfg_linear_step_rows"
+    if any(phi > 0.0 for phi in _row_rescales(what, rows)):
+        return cfg_linear_step_rows_rescale(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=tadd)
     n_dst, n_slots, chw, recs = _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=True)
     rc = _lib.load_library().dsc_cfg_linear_step_rows(
         _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
         0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), n_slots, chw, 0, _stream_ptr(x))
+    _lib.check(rc, what)
+
+
+def _row_rescales(what, rows):
+    """phi of every record (0 where it is not a STEP record or has no `rescale`), validated"""
+    out = []
+    for i, r in enumerate(rows):
+        phi = r.get("rescale", 0.0) if int(r["mode"]) == ROW_STEP else 0.0
+        if isinstance(phi, bool) or not isinstance(phi, (int, float)) or not 0.0 <= phi <= 1.0:       # (NaN fails the range)
+            raise ValueError(f"{what}: rows[{i}]['rescale'] (guidance_rescale) must be a number in [0, 1], got {phi!r}")
+        out.append(float(phi))
+    return out
+
+
+def cfg_linear_step_rows_rescale(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=None):
+    """cfg_linear_step_rows with the guidance rescale of each STEP record's `rescale` (dsc_cfg_linear_step_rows_rescale): the
+    denoised estimate of a slot with phi > 0 is scaled by K = phi * std(D_c) / std(D) + 1 - phi, the stds taken over the slot's
+    whole row inside the same launch; a slot with phi == 0 carries cfg_linear_step_rows' bits."""
+    what = "cfg_linear_step_rows_rescale"
+    phis = _row_rescales(what, rows)
+    n_dst, n_slots, chw, recs = _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=True)
+    phi = (ctypes.c_float * n_slots)(*phis)
+    rc = _lib.load_library().dsc_cfg_linear_step_rows_rescale(
+        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
+        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), ctypes.cast(phi, ctypes.c_void_p),
+        n_slots, chw, 0, _stream_ptr(x))
     _lib.check(rc, what)
 
 

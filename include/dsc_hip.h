@@ -271,6 +271,28 @@ typedef struct {
 int dsc_cfg_linear_step_rows(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf, float* sigma_groups,
                              void* tadd, int tadd_halfs, int n_dst, const dsc_row_linear* rows /* host */, int n_slots,
                              int chw, int dtype, void* stream);
+/*
+ * dsc_cfg_linear_step_rows with the guidance rescale of arXiv 2305.08891 sec. 3.4 per slot (`guidance_rescale`, phi).  The
+ * k-diffusion pipelines of the reference rescale what their model call returns, which is the DENOISED estimate and not eps
+ * (reference model_k_diffusion.py:71-82 applied at :781 / :1168 / :1694; modules/model_k_diffusion.py rescale_noise_cfg), and so
+ * does this entry.  rescale: one phi per slot on the host, read at the call like the records (0 = off).  For a DSC_ROW_STEP
+ * slot with phi > 0, all fp32 with every intermediate rounded to fp32 unless marked:
+ *   e   = fma(guidance, m_c - m_u, m_u)      sx = c_skip * x
+ *   Dc  = fma(c_out, m_c, sx)                Dg = fma(c_out, e, sx)                 (fp32, not yet rounded to fp16)
+ *   the sums of Dc, Dc^2, Dg, Dg^2 over the slot's whole row (n = chw elements) in fp64, in one fixed order
+ *   SSD(v) = sum v^2 - (sum v)^2 / n         K = (float)(phi * sqrt(SSD(Dc) / SSD(Dg)) + (1 - phi))     (fp64 until the cast)
+ *   D   = fp16(K * Dg)                       old = D
+ *   x', x_in rows exactly as dsc_cfg_linear_step_rows from here on (noise row included)
+ * (std(Dc) / std(Dg) of the reference: both run over the same n, the unbiased n - 1 cancels.)  SSD(Dg) == 0 - a constant
+ * guided estimate - is NOT guarded: K is inf or NaN there, as the reference's division is.  Two launches on the same inputs
+ * give the same bits.  A STEP slot with phi == 0 and every JOIN / IDLE slot compute dsc_cfg_linear_step_rows' bits, and t_buf /
+ * sigma_groups / tadd are written as there.  Status: what dsc_cfg_linear_step_rows checks; rescale == NULL, or a phi outside
+ * [0, 1] (NaN included) in a STEP slot: DSC_ERR_BAD_ARG.  The known-region blend of inpainting is not part of this entry.
+ */
+int dsc_cfg_linear_step_rows_rescale(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
+                                     float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
+                                     const dsc_row_linear* rows /* host */, const float* rescale /* host, n_slots */, int n_slots,
+                                     int chw, int dtype, void* stream);
 /* out = a*x + b*denoised + c*old  (old may be NULL when c == 0): the sampler update alone, for callers that keep
  * the reference's `sampler(model_fn, x, sigmas=...)` control flow.  n elements, n % 8 == 0. */
 int dsc_dpmpp2m_update(const void* x, const void* denoised, const void* old, float a, float b, float c,

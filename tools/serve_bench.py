@@ -1,6 +1,6 @@
 """Continuous-batching serving measurements (modules/serving.py) on one GPU; one JSON line per leg.
 
-    python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME]
+    python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -17,6 +17,9 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
   sampler     (--sampler NAME, one of sampling.LINEAR_FAMILY: this leg only) 8 slots kept full, every other request running NAME
               (its step goes through dsc_cfg_linear_step_rows, with a noise table per request) beside the all-DPM++ 2M batch in
               the same process, three alternating runs; then one-at-a-time txt2img with NAME, fused against protocol mode
+  rescale     (--guidance-rescale PHI, alone or with --sampler: this leg only) the same leg with `guidance_rescale` = PHI on
+              every other request (its step goes through dsc_cfg_linear_step_rows_rescale; DPM++ 2M unless --sampler names
+              another), and one-at-a-time txt2img with PHI, fused against protocol mode
 """
 import argparse
 import json
@@ -108,6 +111,8 @@ def main():
     ap.add_argument("--mix", action="store_true", help="only the mixed txt2img / img2img / inpainting leg")
     ap.add_argument("--sampler", default=None, help="only the saturated leg with every other request on this sampler "
                                                     "(sample_euler, sample_euler_ancestral, sample_dpmpp_2m_sde, sample_lcm)")
+    ap.add_argument("--guidance-rescale", type=float, default=None, metavar="PHI",
+                    help="only the saturated leg with guidance_rescale = PHI (in (0, 1]) on every other request")
     a = ap.parse_args()
     from diffusionspatialcontrol_amd.modules.model_k_diffusion import SD15Scheduler, StableDiffusionPipeline
     from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNet2DConditionModel, UNetConfig
@@ -119,15 +124,20 @@ def main():
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
 
-    if a.sampler:
+    if a.sampler or a.guidance_rescale is not None:
         b = pipe.serve(512, 512, max_batch=8, slot=0).warm()
-        named = [dict(r, sampler_name=a.sampler, seed=i) if i % 2 else dict(r) for i, r in enumerate(reqs)]
+        keys = {} if a.guidance_rescale is None else {"guidance_rescale": a.guidance_rescale}
+        if a.sampler:
+            keys["sampler_name"] = a.sampler
+        a.sampler = a.sampler or "sample_dpmpp_2m"
+        named = [dict(r, seed=i, **keys) if i % 2 else dict(r) for i, r in enumerate(reqs)]
         for group in (reqs[:8], named[:8]):
             run_full(b, group, kw25)
         runs = []
         for _ in range(3):
             runs.append((run_full(b, reqs, kw25), run_full(b, named, kw25)))
-        emit(leg="sampler", sampler=a.sampler, requests=len(reqs), steps=25, mix="every other request on the named sampler",
+        emit(leg="sampler" if a.guidance_rescale is None else "rescale", sampler=a.sampler, guidance_rescale=a.guidance_rescale,
+             requests=len(reqs), steps=25, mix="every other request on the named sampler / with the rescale",
              dpmpp_2m_img_s=[round(t[0], 2) for t, _ in runs], mixed_img_s=[round(m[0], 2) for _, m in runs],
              linear_transitions=b.stats()["linear_transitions"], captures_after_warm=b.stats()["captures_after_warm"])
         from diffusionspatialcontrol_amd.modules import sampling, samplers_extra_k_diffusion as sx
@@ -136,6 +146,8 @@ def main():
         one = dict(height=512, width=512, sampler_name=fn, latents=r["latents"], region_map_state=r["region_map_state"],
                    prompt_embeds=r["prompt_embeds"], negative_prompt_embeds=r["negative_prompt_embeds"], eta=1.0,
                    text_input_ids=r["text_input_ids"], output_type="latent", **kw25)
+        if a.guidance_rescale is not None:
+            one["guidance_rescale"] = a.guidance_rescale
         rate = {}
         for mode in (True, False):
             pipe.txt2img(None, fused=mode, **one)
@@ -145,7 +157,7 @@ def main():
                 pipe.txt2img(None, fused=mode, **one)
             torch.cuda.synchronize()
             rate[mode] = 4 / (time.perf_counter() - t0)
-        emit(leg="sampler_one_at_a_time", sampler=a.sampler, steps=25, fused_img_s=round(rate[True], 2),
+        emit(leg="sampler_one_at_a_time", sampler=a.sampler, guidance_rescale=a.guidance_rescale, steps=25, fused_img_s=round(rate[True], 2),
              protocol_img_s=round(rate[False], 2))
         return
 
