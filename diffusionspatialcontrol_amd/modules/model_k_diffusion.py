@@ -543,6 +543,34 @@ class StableDiffusionPipeline:
         from .serving import ServingBatcher
         return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len)
 
+    def serve_hires(self, height: int = 512, width: int = 512, upscale_x: float = 1.25, max_batch: int = 8, buckets=(1, 2, 4, 8),
+                    text_len: int = 77, slots=(0, 1)):
+        """Continuous-batching server for requests with a hires pass (reference :1176-1228): a batcher at `height` x `width`
+        chained to one at the target size of `upscale_x` (_hires_pass's expression), on two workspace slots.  A request with
+        `upscale=True` runs its first pass on the one, is enlarged and re-noised on the device (dsc_latent_resample_noise) and
+        finishes on the other; requests without it are served at the base size as by `serve`.  Returns a `HiresPair` with the
+        batcher's surface (submit / step / run_until_idle / start / stop / stats / warm)."""
+        from .latent_resample import hires_target_size
+        from .serving import HiresPair, ServingBatcher
+        th, tw = hires_target_size(height, width, upscale_x, self.vae_scale_factor)
+        if th < height or tw < width:
+            raise ValueError(f"serve_hires: upscale_x {upscale_x} shrinks {height}x{width} to {th}x{tw}; only enlarging is served "
+                             "(use txt2img / img2img with upscale=True)")
+        if len(slots) != 2:
+            raise ValueError("serve_hires: `slots` names two workspace slots, one per batcher")
+        # OPEN GAP against the reference: its UNet hands the skip connection's size to each upsampler (`upsample_size`,
+        # u_net_condition_modify.py:1116-1300) and so runs any latent size; this package's Upsample2D doubles (the fused
+        # upsampling convolution), so latents must be a multiple of 2^(downsamplings).  The app's default factor 1.2 at 512x512
+        # (608x608, 76-row latents) is therefore not servable yet, as txt2img(upscale=True) fails there; hence the default 1.25
+        m = 2 ** (len(self.unet.down_blocks) - 1)
+        if (th // 8) % m or (tw // 8) % m:
+            raise ValueError(f"serve_hires: a {th}x{tw} hires pass has {th // 8}x{tw // 8} latents; this package's UNet does not yet "
+                             f"forward the skip sizes to its upsamplers (the reference's `upsample_size`), so latents must be "
+                             f"multiples of {m} (txt2img(upscale=True) has the same limit).  Choose an upscale_x whose target is a "
+                             f"multiple of {8 * m} pixels, e.g. 1.25 or 1.5 at 512")
+        kw = dict(max_batch=max_batch, buckets=buckets, text_len=text_len)
+        return HiresPair(ServingBatcher(self, height, width, slot=slots[0], **kw), ServingBatcher(self, th, tw, slot=slots[1], **kw))
+
     def txt2img_coalesced(self, requests, height: int = 512, width: int = 512, num_inference_steps: int = 50,
                           guidance_scale: float = 7.5, sampler_opt=None, output_type: Optional[str] = "latent",
                           weight_func=lambda w, sigma, qk: w * sigma * qk.std(), cross_attention_kwargs=None,

@@ -37,6 +37,16 @@ v-prediction models).  Its STEP records carry `rescale` and, DPM++ 2M on an eps-
 transition in which such a slot steps launches dsc_cfg_linear_step_rows_rescale for all slots (ops.cfg_linear_step_rows picks it
 from the records), every other transition the launch it had.  Inpainting with rescale is refused at submit.
 
+Hires requests.  A batcher is built for one image size, so the reference's "Hires fix" (generate at the base size, enlarge the
+final latents, img2img at the target size; model_k_diffusion.py:1176-1228) runs on a chained PAIR of batchers on two workspace
+slots (`pipe.serve_hires`, or `base.chain_hires(hi)`).  A request with `upscale=True` is validated and prepared for BOTH passes at
+submit (the second pass with its own sampler, schedule tail, coefficients, time-embedding table, region tables at the target
+size and noise).  When it leaves the first batcher, ONE launch of dsc_latent_resample_noise on that batcher's stream reads its
+final row of x and writes the second pass's start latent (the enlarged row + noise * fp16 sqrt(sigma_0^2 + 1), img2img's line)
+into a tensor of the second-pass record; an event is recorded, the record joins the second batcher's queue, and that batcher's
+stream waits on the event before it loads the row.  Only the first batcher ever takes the second's lock (no cycle); the caller's
+one Future resolves with the second pass's output.  No host synchronisation between the passes.
+
 The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
 request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
 """
@@ -49,6 +59,7 @@ import torch
 
 from .. import _lib, ops
 from . import sampling
+from .latent_resample import MODES as _RESAMPLE_MODES, device_taps, hires_target_size
 from .attention_modify import weight_func_is_default
 from .encode_region_map_function import encode_region_map
 from .external_k_diffusion import DiscreteVDDPMDenoiser
@@ -72,7 +83,7 @@ def _spatial_size(image):
 class _Request:
     __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
                  "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known",
-                 "family", "snoise", "skipout", "noise", "rescale")
+                 "family", "snoise", "skipout", "noise", "rescale", "eta", "hires", "second", "ready", "hnoise", "t_handoff")
 
 
 class ServingBatcher:
@@ -98,7 +109,8 @@ class ServingBatcher:
         self._members = {}                     # bucket -> per-slot request ids its static buffers were last refreshed for
         self._next_id = 0
         self._stats = collections.Counter(captures=0, joins=0, leaves=0, bucket_switches=0, steps=0, refreshes=0,
-                                          linear_transitions=0)
+                                          linear_transitions=0, handoffs=0)
+        self._hires = None                     # the chained batcher of the hires pass (chain_hires)
         self._warm_captures = None
         self._thread = None
         self._stop = False
@@ -113,13 +125,35 @@ class ServingBatcher:
             self._warm_captures = self._stats["captures"]
         return self
 
+    def chain_hires(self, hi):
+        """requests with `upscale=True` run their second pass on `hi`, a batcher of the target size on another workspace slot
+        (see the module docstring); `hi` keeps serving ordinary requests of its size.  Returns self."""
+        if not isinstance(hi, ServingBatcher):
+            raise TypeError("serve: chain_hires takes the ServingBatcher of the hires pass")
+        if hi is self:
+            raise ValueError("serve: a batcher cannot be chained to itself (the hires pass runs at another image size)")
+        if hi.slot == self.slot:
+            raise ValueError(f"serve: both batchers of a hires pair sit on workspace slot {self.slot}; give the second its own")
+        if hi.pipe is not self.pipe:
+            raise ValueError("serve: both batchers of a hires pair serve the same pipeline")
+        if hi.height < self.height or hi.width < self.width:
+            raise ValueError(f"serve: the hires batcher runs {hi.height}x{hi.width}, smaller than this one's "
+                             f"{self.height}x{self.width} (only enlarging is served)")
+        with self._lock:
+            self._hires = hi
+        return self
+
     def submit(self, request):
         """request: txt2img_coalesced's request dict plus its own `num_inference_steps` (default 25), `sampler_opt` (the
         schedule: karras / exponential / ...), `guidance_scale` (> 1, default 7.5) and `latents` / `generator`; optional
         `output_type` ("latent", default, or what latent_to_image takes), `sampler_name` (sampling.LINEAR_FAMILY, default
         DPM++ 2M) with `eta` / `s_noise` / `solver_type`, `step_noise` ([steps, 1, 4, h, w]: the noise of every step;
         default: drawn as the sampler itself would, from `seed` / `generator`) and `guidance_rescale` (in [0, 1], default 0; not
-        with `mask_image`).  Returns a Future of the final output."""
+        with `mask_image`).  On a chained pair (chain_hires) `upscale=True` adds the hires pass: `upscale_x` (2.0), `upscale_method`
+        ("bicubic"), `upscale_antialias`, `upscale_denoising_strength` (0.7), `sampler_name_hires`, `sampler_opt_hires` (default:
+        the first pass's), `hires_latents` ([1, 4, H/8, W/8] unit noise of the second pass; default: drawn from `generator` after
+        the first pass's draws) and `region_map_state_hires` (default: `region_map_state`; None: no region condition in the second
+        pass).  Returns a Future of the final output."""
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -176,11 +210,15 @@ class ServingBatcher:
             return s
 
     # ------------------------------------------------------------------ request preparation (caller's thread)
-    def _prepare(self, request):
+    def _prepare(self, request, second=False, device=True):
+        """validate a request and build its record; `second`: the record of a hires request's second pass on this batcher (its
+        start latent comes from the hand-off); `device=False` leaves the device half (_prepare_device) to the caller"""
         pipe = self.pipe
         if not isinstance(request, dict):
             raise TypeError("serve: a request is a dict (txt2img_coalesced's request + num_inference_steps / sampler_opt / "
                             "guidance_scale)")
+        if request.get("upscale") and not second:
+            return self._prepare_hires_pair(request)
         v_pred = bool(getattr(pipe, "v_prediction", False))
         # the v scalars (step_skip, c_out) come from the denoiser object, the choice of launch from the flag: setup_unet sets
         # both from the scheduler; a flag flipped by hand on an eps-prediction pipeline (tests/test_serving_host.py does that to
@@ -232,6 +270,7 @@ class ServingBatcher:
         r.steps = int(request.get("num_inference_steps", 25))
         if r.steps < 1:
             raise ValueError("serve: num_inference_steps must be >= 1")
+        r.second, r.hires, r.ready, r.hnoise, r.t_handoff = second, None, None, None, None
         t_start = self._image_request(r)
         r.guidance = g
         r.output_type = request.get("output_type", "latent")
@@ -243,7 +282,7 @@ class ServingBatcher:
             r.sig, r.sig_dev = r.sig[t_start:], r.sig_dev[t_start:]
         r.family = family
         r.rescale = phi
-        eta = float(request.get("eta", 1.0))
+        eta = r.eta = float(request.get("eta", 1.0))
         args = {}
         if family in ("euler_ancestral", "dpmpp_2m_sde"):
             args.update(eta=eta, s_noise=float(request.get("s_noise", 1.0)))
@@ -281,12 +320,65 @@ class ServingBatcher:
         r.slot, r.i, r.t_done = None, 0, None
         r.text = (neg, pos)
         r.t_submit = time.perf_counter()
-        if r.kind == "txt2img":
+        if device:
+            self._prepare_device(r)
+        return r
+
+    def _prepare_device(self, r):
+        """the device half of _prepare, in the order the pipeline's one generator is consumed: start latent, then step noise"""
+        if r.second:
+            self.exec.prepare_hires(r)
+        elif r.kind == "txt2img":
             self.exec.prepare(r)
         else:
             self.exec.prepare_image(r)
         if any(v != 0.0 for v in r.snoise):
-            self.exec.prepare_noise(r, eta)
+            self.exec.prepare_noise(r, r.eta)
+
+    def _prepare_hires_pair(self, request):
+        """a request with `upscale=True`: both passes validated first, then prepared (first pass, then second: the order in which
+        txt2img / img2img and _hires_pass draw from the request's generator) -> the first-pass record, its `.hires` the second's"""
+        hi = self._hires
+        if hi is None:
+            raise ValueError("serve: `upscale` (the hires pass) needs a chained pair of batchers (pipe.serve_hires, or chain_hires "
+                             "on two batchers); this one is not chained (or use the pipeline methods)")
+        if request.get("mask_image") is not None:
+            raise ValueError("serve: `mask_image` with `upscale` is not supported (inpaiting refuses the hires pass too)")
+        x = request.get("upscale_x", 2.0)
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not x > 0:
+            raise ValueError(f"serve: `upscale_x` must be a positive number, got {x!r}")
+        th, tw = hires_target_size(self.height, self.width, x, self.pipe.vae_scale_factor)
+        if th < self.height or tw < self.width:
+            raise ValueError(f"serve: `upscale_x` {x} shrinks {self.height}x{self.width} to {th}x{tw}; only enlarging is served "
+                             "(use txt2img / img2img with upscale=True)")
+        if (th, tw) != (hi.height, hi.width):
+            raise ValueError(f"serve: `upscale_x` {x} asks for a {th}x{tw} hires pass, the chained batcher runs "
+                             f"{hi.height}x{hi.width}")
+        method = request.get("upscale_method", "bicubic")
+        if method not in _RESAMPLE_MODES:
+            raise ValueError(f"serve: `upscale_method` {method!r} is not one of {', '.join(_RESAMPLE_MODES)}")
+        name2 = request.get("sampler_name_hires") or request.get("sampler_name") or "dpmpp_2m"
+        if sampling.linear_family(name2) is None:
+            raise ValueError(f"serve: `sampler_name_hires` {getattr(name2, '__name__', name2)!r} has no per-row step (supported: "
+                             f"{', '.join(sampling.LINEAR_FAMILY)}; use txt2img)")
+        noise = request.get("hires_latents")
+        want = (1, 4, th // 8, tw // 8)
+        if noise is not None and (not torch.is_tensor(noise) or tuple(noise.shape) != want):
+            raise ValueError(f"serve: `hires_latents` (the unit noise of the hires pass) must be a {list(want)} tensor, got "
+                             f"{list(noise.shape) if torch.is_tensor(noise) else type(noise).__name__}")
+        drop = ("upscale", "image", "strength", "latents", "step_noise", "height", "width", "output_type")
+        first = {k: v for k, v in request.items() if k not in ("upscale", "output_type")}
+        second = {k: v for k, v in request.items() if k not in drop}
+        second.update(sampler_name=name2, sampler_opt=request.get("sampler_opt_hires") or request.get("sampler_opt") or {},
+                      strength=request.get("upscale_denoising_strength", 0.7), output_type=request.get("output_type", "latent"))
+        if "region_map_state_hires" in request:
+            second["region_map_state"] = request["region_map_state_hires"]
+        r = self._prepare(first, device=False)
+        r2 = hi._prepare(second, second=True, device=False)
+        r2.future, r2.t_submit = r.future, r.t_submit
+        r.hires = r2
+        self._prepare_device(r)
+        hi._prepare_device(r2)
         return r
 
     def _image_request(self, r):
@@ -296,8 +388,14 @@ class ServingBatcher:
         r.kind, r.strength, r.known = "txt2img", 1.0, None
         if req.get("padding_mask_crop") is not None:
             raise ValueError("serve: `padding_mask_crop` is not supported (use inpaiting)")
-        if req.get("upscale"):
-            raise ValueError("serve: `upscale` (the hires pass) is not supported (use the pipeline methods)")
+        if r.second:                             # the hires pass: img2img from the latent the hand-off writes
+            r.kind = "img2img"
+            r.strength = float(req.get("strength", 0.7))
+            keep = min(int(r.steps * r.strength), r.steps) if 0.0 < r.strength <= 1.0 else 0               # :637-638
+            if keep < 1:
+                raise ValueError(f"serve: `upscale_denoising_strength` {r.strength} leaves none of the {r.steps} steps of the "
+                                 "hires pass (it must be in (0, 1])")
+            return max(r.steps - keep, 0)
         if image is None:
             if mask is not None:
                 raise ValueError("serve: `mask_image` needs `image`")
@@ -448,7 +546,11 @@ class ServingBatcher:
             self.exec.transition(n_src, nd, recs)
         for r in leaving:
             slots[r.slot] = None
-            self._done.append((r, self.exec.finish(r)))
+            if r.hires is not None:
+                self._hand_off(r)
+            else:
+                self._done.append((r, self.exec.finish(r)))
+            r.hnoise = None                          # (a second-pass record: its start noise was read before it joined)
             r.known = None                           # its image / noise / mask rows go back to the allocator (stream-ordered)
             r.noise = None                           # ... and its noise table
             self._stats["leaves"] += 1
@@ -467,6 +569,21 @@ class ServingBatcher:
             self._stats["steps"] += 1
         self._n = n_dst
         return True
+
+    def _hand_off(self, r):
+        """r leaves this batcher for its hires pass: the resample + noise launch on this batcher's stream, then the second-pass
+        record joins the chained batcher's queue (the only place one batcher takes another's lock)"""
+        hi, r2 = self._hires, r.hires
+        r2.ready = self.exec.hand_off(r, r2)
+        r2.t_handoff = time.perf_counter()
+        r.future.dsc_first_pass_s = r2.t_handoff - r.t_submit    # submit -> handed off (host clock), for measurement tools
+        r.hires = None
+        self._stats["handoffs"] += 1
+        with hi._lock:
+            r2.rid = hi._next_id
+            hi._next_id += 1
+            hi._queue.append(r2)
+            hi._wake.notify_all()
 
     def _ensure(self, n):
         if self.exec.ensure(n):
@@ -613,6 +730,44 @@ class _GraphExecutor:
                 table = sampling.step_noise_table(r.family, like, r.sig_dev, eta=eta, noise_sampler=ns)
             r.noise = table.to(device=dev, dtype=dt).contiguous()
 
+    def prepare_hires(self, r):
+        """second pass of a hires request (this executor is the target-size batcher's): its unit noise and the tensor the
+        hand-off writes its start latent into, both alive until the request leaves"""
+        req, dev, dt = r.req, self.device, self.dtype
+        shape = (1,) + self.lat_shape
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self.stream):
+            noise = req.get("hires_latents")
+            noise = self.pipe._randn_like_ref(shape, req.get("generator"), dev, dt) if noise is None else noise.to(dev, dtype=dt)
+            # both are allocated on THIS (the second) batcher's stream and used once by the first batcher's stream in hand_off,
+            # ordered by events only (no record_stream): that is safe because they are freed only when the request leaves this
+            # batcher, after this stream has waited on the hand-off's event - keep that lifetime
+            r.hnoise = noise.contiguous()
+            r.lat = torch.empty(shape, device=dev, dtype=dt)
+            self._tables_and_text(r)
+            r.ready = torch.cuda.Event()
+            r.ready.record(self.stream)              # the first batcher's stream waits for these allocations and copies
+
+    def hand_off(self, r, r2):
+        """one launch on THIS (the first) batcher's stream: x[r.slot] enlarged + r2's noise * fp16 sqrt(sigma_0^2 + 1) -> r2.lat;
+        returns the event the second batcher's stream waits on before it loads the row"""
+        req = r2.req
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_event(r2.ready)
+            ops.latent_resample_noise(self.x[r.slot:r.slot + 1], r2.lat.shape[-2:], req.get("upscale_method", "bicubic"),
+                                      bool(req.get("upscale_antialias", False)), noise=r2.hnoise, sigma0=r2.sig[0], out=r2.lat)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        return ev
+
+    def warm_hand_off(self, hi_exec):
+        """every mode's tap tables for this pair of sizes on the device now (otherwise on a mode's first hand-off)"""
+        (h, w), (H, W) = self.lat_shape[1:], hi_exec.lat_shape[1:]
+        for mode in _RESAMPLE_MODES:
+            for aa in ((False, True) if mode in ("bilinear", "bicubic") else (False,)):
+                device_taps(h, H, mode, aa, self.device)
+                device_taps(w, W, mode, aa, self.device)
+
     def noise_row(self, r, j):
         return r.noise[j, 0]
 
@@ -621,6 +776,8 @@ class _GraphExecutor:
 
     def load_latent(self, r):
         with torch.cuda.stream(self.stream):
+            if r.ready is not None:                  # a hires second pass: its start latent is written on another stream
+                self.stream.wait_event(r.ready)
             self.x[r.slot].copy_(r.lat[0])
 
     def finish(self, r):
@@ -765,3 +922,47 @@ class _GraphExecutor:
     def run(self, n):
         with torch.cuda.stream(self.stream):
             self.st[n]["run"]()
+
+
+class HiresPair:
+    """Two chained batchers (pipe.serve_hires): `base` at the request's size, `hires` at the target size, with the batcher's own
+    public surface.  Requests go to `base`; those with `upscale=True` continue on `hires` (which also takes ordinary requests of
+    its size through `pair.hires.submit`)."""
+
+    def __init__(self, base, hires):
+        self.base, self.hires = base.chain_hires(hires), hires
+
+    def warm(self):
+        self.base.warm()
+        self.hires.warm()
+        if hasattr(self.base.exec, "warm_hand_off"):
+            self.base.exec.warm_hand_off(self.hires.exec)
+        return self
+
+    def submit(self, request):
+        return self.base.submit(request)
+
+    def step(self):
+        """advance both batchers by one step each; False when both are idle"""
+        a = self.base.step()
+        b = self.hires.step()
+        return a or b
+
+    def run_until_idle(self):
+        while self.step():
+            pass
+        self.base.run_until_idle()
+        self.hires.run_until_idle()
+
+    def start(self):
+        self.base.start()
+        self.hires.start()
+        return self
+
+    def stop(self):
+        self.base.stop()
+        self.hires.stop()
+
+    def stats(self):
+        b = self.base.stats()
+        return {"base": b, "hires": self.hires.stats(), "handoffs": b["handoffs"]}

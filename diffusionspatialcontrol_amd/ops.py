@@ -1181,3 +1181,8 @@ def dpmpp2m_update(x, denoised, old, a, b, c):
                                                 _p(out), x.numel(), 0, _stream_ptr(x))
     _lib.check(rc, "dsc_dpmpp2m_update")
     return out
+
+
+# The hires pass's resample + noise launch (dsc_latent_resample_noise).  Its wrapper lives beside the tap tables it is made of;
+# like every writer here it drops GroupNorm partial sums from its destination (tests/test_hires_gpu.py).
+from .modules.latent_resample import latent_resample_noise, noise_scale_f16  # noqa: E402,F401

@@ -565,6 +565,25 @@ int dsc_linear_splitk_f16(const void* x, const void* w, const void* bias, const 
 int dsc_softmax_rows_f16(const void* scores, void* probs, int64_t rows, int n, int64_t ld_scores, int64_t ld_probs,
                          float scale, int dtype, void* stream);
 
+/*
+ * The step between the two passes of a hires request: enlarge the final latent rows of the base pass and add the start noise of
+ * the second pass, one launch.  Replaces modules/model_k_diffusion.py:1179-1191 (`F.interpolate(latents.float(), size, mode
+ * [, antialias]).to(fp16)`) and :647 (`latents + noise * (sigma_0 ** 2 + 1) ** 0.5` on fp16 tensors) of the reference.
+ * src [n, C, h, w], noise (NULL: resample only) and dst [n, C, H, W]: fp16, contiguous, H >= h, W >= w; dst must not be src.
+ * idx_* / w_* are the separable tap tables of the mode (modules/latent_resample.py): [H, 4] / [W, 4], int32 source indices
+ * (clamped into the plane by the kernel) and fp32 weights, 16-byte aligned; unused taps carry weight 0.  Per output element
+ *     r   = fp16( sum_i w_y[y, i] * ( sum_j w_x[x, j] * float(src[c, idx_y[y, i], idx_x[x, j]]) ) )   fp32, each sum in tap
+ *           order: the first product, then one fma per further tap (the order of torch's CPU kernels)
+ *     out = fp16( float(r) + float(fp16( float(noise) * s )) )                                      s = noise_scale_f16_value
+ * with s the fp16-rounded sqrt(sigma_0^2 + 1) passed as a float.  16-byte stores when W % 8 == 0 and dst / noise are 16-byte
+ * aligned, 2-byte stores otherwise (chosen per launch).  No allocation, no synchronisation: safe under graph capture.
+ * DSC_ERR_BAD_ARG: null src / dst / table, n, C, h, w < 1, H < h, W < w, dst == src.  DSC_ERR_UNSUPPORTED: misaligned tables,
+ * 2^31 elements or more.
+ */
+int dsc_latent_resample_noise(const void* src, const void* noise, void* dst, int n, int C, int h, int w, int H, int W,
+                              const int* idx_y, const float* w_y, const int* idx_x, const float* w_x,
+                              float noise_scale_f16_value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """Continuous-batching serving measurements (modules/serving.py) on one GPU; one JSON line per leg.
 
     python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
+                                [--hires X]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -20,6 +21,9 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
   rescale     (--guidance-rescale PHI, alone or with --sampler: this leg only) the same leg with `guidance_rescale` = PHI on
               every other request (its step goes through dsc_cfg_linear_step_rows_rescale; DPM++ 2M unless --sampler names
               another), and one-at-a-time txt2img with PHI, fused against protocol mode
+  hires       (--hires X: this leg only) a chained pair of batchers (pipe.serve_hires(512, 512, X)) driven by its two threads,
+              every other request with `upscale=True, upscale_x=X` (bicubic, strength 0.7): images/s, and the latency of the
+              hires requests split by pass (submit -> handed off on the host clock, handed off -> resolved) beside the plain ones
 """
 import argparse
 import json
@@ -113,6 +117,8 @@ def main():
                                                     "(sample_euler, sample_euler_ancestral, sample_dpmpp_2m_sde, sample_lcm)")
     ap.add_argument("--guidance-rescale", type=float, default=None, metavar="PHI",
                     help="only the saturated leg with guidance_rescale = PHI (in (0, 1]) on every other request")
+    ap.add_argument("--hires", type=float, default=None, metavar="X",
+                    help="only the hires leg: a chained pair, every other request with upscale_x = X (1.0 .. 2.0)")
     a = ap.parse_args()
     from diffusionspatialcontrol_amd.modules.model_k_diffusion import SD15Scheduler, StableDiffusionPipeline
     from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNet2DConditionModel, UNetConfig
@@ -123,6 +129,32 @@ def main():
     opt = {"scheduler": "karras"}
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    if a.hires is not None:
+        pair = pipe.serve_hires(512, 512, a.hires, max_batch=8).warm()
+        mixed = [dict(r, upscale=True, upscale_x=a.hires, seed=i) if i % 2 else dict(r) for i, r in enumerate(reqs)]
+
+        def leg():
+            pair.start()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            futs = [pair.submit(dict(r, **kw25)) for r in mixed]
+            for f in futs:
+                f.result()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            pair.stop()
+            return len(mixed) / dt, futs
+        leg()                                             # one untimed pass (allocator, kernel selection at every bucket)
+        rate, futs = leg()
+        hi = [f for i, f in enumerate(futs) if i % 2]
+        emit(leg="hires", upscale_x=a.hires, target=[pair.hires.height, pair.hires.width], requests=len(mixed), steps=25,
+             mix="every other request with the hires pass (bicubic, strength 0.7: 17 steps at the target size)",
+             img_s=round(rate, 2), plain_p50_s=pct([f.dsc_latency_s for i, f in enumerate(futs) if not i % 2], 50),
+             hires_p50_s=pct([f.dsc_latency_s for f in hi], 50), hires_first_pass_p50_s=pct([f.dsc_first_pass_s for f in hi], 50),
+             hires_second_pass_p50_s=pct([f.dsc_latency_s - f.dsc_first_pass_s for f in hi], 50))
+        emit(leg="stats", **pair.stats())
+        return
 
     if a.sampler or a.guidance_rescale is not None:
         b = pipe.serve(512, 512, max_batch=8, slot=0).warm()
