@@ -47,11 +47,14 @@ constexpr unsigned kOob = 0x80000000u;           // buffer offset beyond any sup
 struct ConvParams {
     const half_t* x; const half_t* w; const half_t* bias; const half_t* res; half_t* out; float* ws;
     int B, H, W, Cin, Cout;
-    int up;                       // 1: x is [B, H/2, W/2, Cin] and is read through a nearest-neighbour 2x upsampling
+    int up;                       // 1: x is [B, sh, sw, Cin] and is read through a nearest-neighbour upsampling to H x W: source
+    int sh, sw;                   // pixel = destination >> 1 (sh = H/2: the 2x upsampling; sh = (H+1)/2: H is 2 sh or 2 sh - 1, the
+                                  // size of the UNet skip tensor the result meets - torch's `nearest` index is the same shift there)
     int nchw;                     // 1: out is [B, Cout, H, W] (the UNet's conv_out: 4 channels back to the sampler's layout)
-    int sub2;                     // 1 / 2: only the even / odd pixels are kept: out is [B, H/2, W/2, Cout] = the stride-2
-                                  // convolution with pad 1 (UNet Downsample2D) / with pad (0,1,0,1) (VAE encoder)
-    long long onpix;              // output pixels (npix, or npix / 4 with sub2)
+    int sub2;                     // 1 / 2: only the even / odd pixels are kept: out is [B, oh, ow, Cout] = the stride-2
+    int oh, ow;                   // convolution with pad 1 (UNet Downsample2D; oh = (H+1)/2: odd sides keep their last pixel) /
+                                  // with pad (0,1,0,1) (VAE encoder; even sides only)
+    long long onpix;              // output pixels (npix, or B * oh * ow with sub2)
     long long ldx, ldr, ldo;      // pixel strides (elements)
     int nc, splits, cps;          // 64-channel slices, split count, slices per split
     int order;                    // workgroup order within an XCD (see the kernel)
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
             const int y = (NSB == 1 ? oy[0] : (sb ? oy[NSB - 1] : oy[0])) - 1 + hy;
             const int x = (NSB == 1 ? ox[0] : (sb ? ox[NSB - 1] : ox[0])) - 1 + hx;
             if (b >= 0 && y >= 0 && y < p.H && x >= 0 && x < p.W) {
-                const int px = p.up ? (b * (p.H >> 1) + (y >> 1)) * (p.W >> 1) + (x >> 1) : (b * p.H + y) * p.W + x;
+                const int px = p.up ? (b * p.sh + (y >> 1)) * p.sw + (x >> 1) : (b * p.H + y) * p.W + x;
                 off = ((unsigned)px * (unsigned)p.ldx + (((lane & 7) ^ halo_swz<TW>(hy, hx)) << 3)) * 2u;
             }
         }
@@ -380,7 +383,7 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
             const int yy = (NSB == 1 ? oy[0] : (sb ? oy[NSB - 1] : oy[0])) + py, xx = (NSB == 1 ? ox[0] : (sb ? ox[NSB - 1] : ox[0])) + pxl;
             long long gp = ((long long)b * p.H + yy) * p.W + xx;
             bool live = b >= 0 && yy < p.H && xx < p.W && n0 + ch * 8 + 8 <= p.Cout;
-            if (p.sub2) { live = live && (p.sub2 == 1 ? !((yy | xx) & 1) : (yy & xx & 1) != 0); gp = ((long long)b * (p.H >> 1) + (yy >> 1)) * (p.W >> 1) + (xx >> 1); }
+            if (p.sub2) { live = live && (p.sub2 == 1 ? !((yy | xx) & 1) : (yy & xx & 1) != 0); gp = ((long long)b * p.oh + (yy >> 1)) * p.ow + (xx >> 1); }
             if (live) rpre[cidx] = *reinterpret_cast<const h8_t*>(p.res + gp * p.ldr + n0 + ch * 8);
         }
     }
@@ -407,7 +410,7 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
         long long gp = ((long long)b * p.H + yy) * p.W + xx;
         if (p.sub2) {                                                // stride 2 = the even (odd) pixels of the stride-1 result
             if (p.sub2 == 1 ? ((yy | xx) & 1) != 0 : (yy & xx & 1) == 0) continue;
-            gp = ((long long)b * (p.H >> 1) + (yy >> 1)) * (p.W >> 1) + (xx >> 1);
+            gp = ((long long)b * p.oh + (yy >> 1)) * p.ow + (xx >> 1);
         }
         const float* sp_ = stage + m * kEpiStride + ch * 8;
         if (p.splits > 1) {
@@ -599,6 +602,7 @@ extern "C" int dsc_conv3x3_gn_rows(int B, int H, int W, int Cin, int Cout, int g
     // 2 <= channels per group <= 64: gn_tile_partials writes at most 32 group slots per 64-channel tile (gn_partials.h)
     if (B <= 0 || H <= 0 || W <= 0 || groups <= 0 || Cout % BN != 0 || Cout % groups != 0 || Cout / groups > 64 || Cout / groups < 2) return 0;
     if (resample == DSC_CONV_STRIDE2 || resample == DSC_CONV_STRIDE2_PAD_BR) return 0;   // (the kept pixels are a quarter of a tile's)
+    if (resample < 0 || resample > DSC_CONV_UPSAMPLE_CEIL) return 0;
     if (plan(B, Hc, Wc, Cin, Cout, 0, &p) != 16 || p.splits != 1 || p.bpi > 128) return 0;
     return p.bpi;
 }
@@ -641,14 +645,16 @@ int conv_impl(const void* x, const void* w, const void* bias, const void* residu
     // activation-heavy shapes (the 64x64 level): a pixel tile's halo is fetched into one L2 for all of its channel blocks
     // (640->320 @64x64 66.8 -> 61.5 us in the step); weight-heavy ones keep sharing the weight slab
     p.order = g_conv_order >= 0 ? g_conv_order : (p.npix >= 2ll * Cout ? 1 : 0);
-    if (resample < 0 || resample > 3 || ((resample == DSC_CONV_STRIDE2 || resample == DSC_CONV_STRIDE2_PAD_BR) && out_nchw)) return DSC_ERR_UNSUPPORTED;
-    if ((resample == DSC_CONV_STRIDE2 || resample == DSC_CONV_STRIDE2_PAD_BR) && ((H | W) & 1)) return DSC_ERR_UNSUPPORTED;
-    p.up = resample == DSC_CONV_UPSAMPLE2X ? 1 : 0;
+    if (resample < 0 || resample > 4 || ((resample == DSC_CONV_STRIDE2 || resample == DSC_CONV_STRIDE2_PAD_BR) && out_nchw)) return DSC_ERR_UNSUPPORTED;
+    if (resample == DSC_CONV_STRIDE2_PAD_BR && ((H | W) & 1)) return DSC_ERR_UNSUPPORTED;
+    p.up = resample == DSC_CONV_UPSAMPLE2X || resample == DSC_CONV_UPSAMPLE_CEIL ? 1 : 0;
+    p.sh = resample == DSC_CONV_UPSAMPLE_CEIL ? (H + 1) / 2 : H / 2; p.sw = resample == DSC_CONV_UPSAMPLE_CEIL ? (W + 1) / 2 : W / 2;
     p.sub2 = resample == DSC_CONV_STRIDE2 ? 1 : (resample == DSC_CONV_STRIDE2_PAD_BR ? 2 : 0);
-    p.onpix = p.sub2 ? p.npix / 4 : p.npix;
+    p.oh = (H + 1) / 2; p.ow = (W + 1) / 2;          // pad 1 keeps pixel 0, 2, ..: ceil; the VAE's code has even sides
+    p.onpix = p.sub2 ? (long long)B * p.oh * p.ow : p.npix;
     p.nchw = out_nchw ? 1 : 0;
     {
-        const long long in_pix = p.up ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W;
+        const long long in_pix = p.up ? (long long)B * p.sh * p.sw : (long long)B * H * W;
         p.x_bytes = (unsigned)(((in_pix - 1) * ldx + Cin) * 2);
         p.w_bytes = (unsigned)(9ll * Cin * Cout * 2);
     }

@@ -17,6 +17,25 @@ __device__ __forceinline__ h8_t pack8(const float (&f)[8]) {
     return v;
 }
 
+// V halfs per access: 8 (16 bytes) where a latent row holds a multiple of 8 halfs, else 4 - rows of 4 h w halfs with h w odd (the
+// 19 x 19 latents of a 152 x 152 image) are only 8-byte aligned.  The arithmetic per element is the same: equal bits.
+template <int V> struct hv_sel;
+template <> struct hv_sel<8> { typedef h8_t type; };
+template <> struct hv_sel<4> { typedef h4_t type; };
+template <int V> using hv_t = typename hv_sel<V>::type;
+template <int V>
+__device__ __forceinline__ void unpackv(const hv_t<V> v, float (&f)[V]) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) f[j] = (float)v[j];
+}
+template <int V>
+__device__ __forceinline__ hv_t<V> packv(const float (&f)[V]) {
+    hv_t<V> v;
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = (half_t)f[j];
+    return v;
+}
+
 // the step's row of a per-generation table (the time-embedding projections of every ResNet block for this step's timestep,
 // computed for all steps before the loop) copied to every row of the static buffer the captured UNet step reads
 __device__ __forceinline__ void copy_row(const half_t* src, half_t* dst, int halfs, int copies) {
@@ -28,20 +47,21 @@ __device__ __forceinline__ void copy_row(const half_t* src, half_t* dst, int hal
     }
 }
 
+template <int V>
 __global__ __launch_bounds__(256) void prepare_kernel(const half_t* x, float c_in, float t, float sigma, half_t* x_in,
                                                       float* t_buf, float* sigma_buf, int n_img, int chw,
                                                       const half_t* row_src, half_t* row_dst, int row_halfs, int row_copies) {
     copy_row(row_src, row_dst, row_halfs, row_copies);
-    const long long n8 = (long long)n_img * chw / 8;
+    const long long n8 = (long long)n_img * chw / V;
     const long long half_elems = (long long)n_img * chw;
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-        float f[8];
-        unpack8(*reinterpret_cast<const h8_t*>(x + i * 8), f);
+        float f[V];
+        unpackv<V>(*reinterpret_cast<const hv_t<V>*>(x + i * V), f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] *= c_in;
-        const h8_t o = pack8(f);
-        *reinterpret_cast<h8_t*>(x_in + i * 8) = o;
-        *reinterpret_cast<h8_t*>(x_in + half_elems + i * 8) = o;
+        for (int j = 0; j < V; ++j) f[j] *= c_in;
+        const hv_t<V> o = packv<V>(f);
+        *reinterpret_cast<hv_t<V>*>(x_in + i * V) = o;
+        *reinterpret_cast<hv_t<V>*>(x_in + half_elems + i * V) = o;
     }
     if (blockIdx.x == 0) {
         if (threadIdx.x < 2 * n_img) t_buf[threadIdx.x] = t;
@@ -50,6 +70,7 @@ __global__ __launch_bounds__(256) void prepare_kernel(const half_t* x, float c_i
     }
 }
 
+template <int V>
 __global__ __launch_bounds__(256) void step_kernel(half_t* x, const half_t* eps, half_t* old, float sigma, float g,
                                                    float a, float b, float c, float c_in_next, float t_next,
                                                    float sigma_next, half_t* x_in, float* t_buf, float* sigma_buf,
@@ -57,25 +78,25 @@ __global__ __launch_bounds__(256) void step_kernel(half_t* x, const half_t* eps,
                                                    const half_t* row_src, half_t* row_dst, int row_halfs, int row_copies) {
     copy_row(row_src, row_dst, row_halfs, row_copies);
     const long long half_elems = (long long)n_img * chw;
-    const long long n8 = half_elems / 8;
+    const long long n8 = half_elems / V;
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-        float xv[8], eu[8], ec[8], ov[8], dn[8], xn[8], xi[8];
-        unpack8(*reinterpret_cast<const h8_t*>(x + i * 8), xv);
-        unpack8(*reinterpret_cast<const h8_t*>(eps + i * 8), eu);
-        unpack8(*reinterpret_cast<const h8_t*>(eps + half_elems + i * 8), ec);
-        unpack8(*reinterpret_cast<const h8_t*>(old + i * 8), ov);
+        float xv[V], eu[V], ec[V], ov[V], dn[V], xn[V], xi[V];
+        unpackv<V>(*reinterpret_cast<const hv_t<V>*>(x + i * V), xv);
+        unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eps + i * V), eu);
+        unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eps + half_elems + i * V), ec);
+        unpackv<V>(*reinterpret_cast<const hv_t<V>*>(old + i * V), ov);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < V; ++j) {
             const float e = eu[j] + g * (ec[j] - eu[j]);          // model_k_diffusion.py:1162-1166 (affine in eps)
             dn[j] = (float)(half_t)(xv[j] - sigma * e);           // external_k_diffusion.py:114, stored as fp16
             xn[j] = (float)(half_t)(a * xv[j] + b * dn[j] + c * ov[j]);
             xi[j] = xn[j] * c_in_next;
         }
-        *reinterpret_cast<h8_t*>(old + i * 8) = pack8(dn);
-        *reinterpret_cast<h8_t*>(x + i * 8) = pack8(xn);
-        const h8_t o = pack8(xi);
-        *reinterpret_cast<h8_t*>(x_in + i * 8) = o;
-        *reinterpret_cast<h8_t*>(x_in + half_elems + i * 8) = o;
+        *reinterpret_cast<hv_t<V>*>(old + i * V) = packv<V>(dn);
+        *reinterpret_cast<hv_t<V>*>(x + i * V) = packv<V>(xn);
+        const hv_t<V> o = packv<V>(xi);
+        *reinterpret_cast<hv_t<V>*>(x_in + i * V) = o;
+        *reinterpret_cast<hv_t<V>*>(x_in + half_elems + i * V) = o;
     }
     if (blockIdx.x == 0) {
         for (int i = threadIdx.x; i < 2 * n_img; i += 256) t_buf[i] = t_next;
@@ -83,16 +104,17 @@ __global__ __launch_bounds__(256) void step_kernel(half_t* x, const half_t* eps,
     }
 }
 
+template <int V>
 __global__ __launch_bounds__(256) void update_kernel(const half_t* x, const half_t* den, const half_t* old, float a,
                                                      float b, float c, half_t* out, long long n8) {
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-        float xv[8], dv[8], ov[8], r[8];
-        unpack8(*reinterpret_cast<const h8_t*>(x + i * 8), xv);
-        unpack8(*reinterpret_cast<const h8_t*>(den + i * 8), dv);
-        if (old) unpack8(*reinterpret_cast<const h8_t*>(old + i * 8), ov);
+        float xv[V], dv[V], ov[V], r[V];
+        unpackv<V>(*reinterpret_cast<const hv_t<V>*>(x + i * V), xv);
+        unpackv<V>(*reinterpret_cast<const hv_t<V>*>(den + i * V), dv);
+        if (old) unpackv<V>(*reinterpret_cast<const hv_t<V>*>(old + i * V), ov);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = a * xv[j] + b * dv[j] + (old ? c * ov[j] : 0.f);
-        *reinterpret_cast<h8_t*>(out + i * 8) = pack8(r);
+        for (int j = 0; j < V; ++j) r[j] = a * xv[j] + b * dv[j] + (old ? c * ov[j] : 0.f);
+        *reinterpret_cast<hv_t<V>*>(out + i * V) = packv<V>(r);
     }
 }
 
@@ -117,23 +139,23 @@ __device__ __forceinline__ void rows_copy_temb(const void* temb_row, half_t* tad
 }
 // JOIN: prepare_kernel's line for a freshly loaded start latent (a request's first model call: never blended), old row zeroed;
 // IDLE: zero input rows
-template <int T = 256>
+template <int T = 256, int V = 8>
 __device__ __forceinline__ void rows_join_or_idle(bool join, float c_in, const half_t* xr, half_t* orow, half_t* xi_u, half_t* xi_c,
                                                   long long v8) {
     for (long long k = blockIdx.x * (long long)T + threadIdx.x; k < v8; k += (long long)gridDim.x * T) {
-        h8_t o;
+        hv_t<V> o;
         if (join) {
-            float f[8];
-            unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), f);
+            float f[V];
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(xr + k * V), f);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = as_f32(f[j] * c_in);
-            o = pack8(f);
-            *reinterpret_cast<h8_t*>(orow + k * 8) = h8_t{};
+            for (int j = 0; j < V; ++j) f[j] = as_f32(f[j] * c_in);
+            o = packv<V>(f);
+            *reinterpret_cast<hv_t<V>*>(orow + k * V) = hv_t<V>{};
         } else {
-            o = h8_t{};
+            o = hv_t<V>{};
         }
-        *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
-        *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+        *reinterpret_cast<hv_t<V>*>(xi_u + k * V) = o;
+        *reinterpret_cast<hv_t<V>*>(xi_c + k * V) = o;
     }
 }
 // t of both CFG rows and the sigma of the slot's std group
@@ -149,13 +171,14 @@ __device__ __forceinline__ void rows_write_scalars(float* t_buf, float* sigma_gr
 // blockIdx.y, uniform per workgroup)
 struct RowSteps { dsc_row_step r[DSC_ROW_STEP_MAX_SLOTS]; };
 
+template <int V>
 __global__ __launch_bounds__(256) void step_rows_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
                                                         float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
                                                         int n_dst, int chw, const RowSteps rs) {
     const int i = blockIdx.y;
     const dsc_row_step& r = rs.r[i];
     const bool dst = i < n_dst;
-    const long long v8 = chw / 8;
+    const long long v8 = chw / V;
     if (dst) rows_copy_temb(r.temb_row, tadd, tadd_halfs, n_dst, i);
     half_t* xi_u = x_in + (long long)i * chw;
     half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
@@ -166,13 +189,13 @@ __global__ __launch_bounds__(256) void step_rows_kernel(half_t* x, const half_t*
         const half_t* eur = eps + (long long)i * chw;
         const half_t* ecr = eps + (long long)(n_src + i) * chw;
         for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
-            float xv[8], eu[8], ec[8], ov[8], dn[8], xn[8], xi[8];
-            unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), xv);
-            unpack8(*reinterpret_cast<const h8_t*>(eur + k * 8), eu);
-            unpack8(*reinterpret_cast<const h8_t*>(ecr + k * 8), ec);
-            unpack8(*reinterpret_cast<const h8_t*>(orow + k * 8), ov);
+            float xv[V], eu[V], ec[V], ov[V], dn[V], xn[V], xi[V];
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(xr + k * V), xv);
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eur + k * V), eu);
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(ecr + k * V), ec);
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(orow + k * V), ov);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
+            for (int j = 0; j < V; ++j) {
                 // step_kernel's arithmetic with the fused multiply-adds it compiles to, spelled out (the contraction of a
                 // plain expression depends on the surrounding code, and the per-row step must give the same bits):
                 // e = fma(g, ec - eu, eu), D = fma(-sigma, e, x), x' = fma(c, old, fma(a, x, b * D))
@@ -182,16 +205,16 @@ __global__ __launch_bounds__(256) void step_rows_kernel(half_t* x, const half_t*
                 xn[j] = (float)(half_t)as_f32(__builtin_fmaf(c, ov[j], as_f32(__builtin_fmaf(a, xv[j], bd))));
                 xi[j] = as_f32(xn[j] * c_in_next);
             }
-            *reinterpret_cast<h8_t*>(orow + k * 8) = pack8(dn);
-            *reinterpret_cast<h8_t*>(xr + k * 8) = pack8(xn);
+            *reinterpret_cast<hv_t<V>*>(orow + k * V) = packv<V>(dn);
+            *reinterpret_cast<hv_t<V>*>(xr + k * V) = packv<V>(xn);
             if (dst) {
-                const h8_t o = pack8(xi);
-                *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
-                *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+                const hv_t<V> o = packv<V>(xi);
+                *reinterpret_cast<hv_t<V>*>(xi_u + k * V) = o;
+                *reinterpret_cast<hv_t<V>*>(xi_c + k * V) = o;
             }
         }
     } else if (dst) {
-        rows_join_or_idle(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
+        rows_join_or_idle<256, V>(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
     }
     if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
 }
@@ -201,6 +224,7 @@ __global__ __launch_bounds__(256) void step_rows_kernel(half_t* x, const half_t*
 // record has no image runs step_rows_kernel's arithmetic unchanged (same bits); JOIN / IDLE slots never look at the record.
 struct RowKnowns { dsc_row_known r[DSC_ROW_STEP_MAX_SLOTS]; };
 
+template <int V>
 __global__ __launch_bounds__(256) void step_rows_known_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
                                                               float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
                                                               int n_dst, int chw, const RowSteps rs, const RowKnowns ks) {
@@ -208,7 +232,7 @@ __global__ __launch_bounds__(256) void step_rows_known_kernel(half_t* x, const h
     const dsc_row_step& r = rs.r[i];
     const dsc_row_known& kr = ks.r[i];
     const bool dst = i < n_dst;
-    const long long v8 = chw / 8;
+    const long long v8 = chw / V;
     if (dst) rows_copy_temb(r.temb_row, tadd, tadd_halfs, n_dst, i);
     half_t* xi_u = x_in + (long long)i * chw;
     half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
@@ -224,18 +248,18 @@ __global__ __launch_bounds__(256) void step_rows_known_kernel(half_t* x, const h
         const half_t* eur = eps + (long long)i * chw;
         const half_t* ecr = eps + (long long)(n_src + i) * chw;
         for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
-            float xv[8], eu[8], ec[8], ov[8], dn[8], xn[8], xi[8], im[8], nz[8], mk[8];
-            unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), xv);
-            unpack8(*reinterpret_cast<const h8_t*>(eur + k * 8), eu);
-            unpack8(*reinterpret_cast<const h8_t*>(ecr + k * 8), ec);
-            unpack8(*reinterpret_cast<const h8_t*>(orow + k * 8), ov);
+            float xv[V], eu[V], ec[V], ov[V], dn[V], xn[V], xi[V], im[V], nz[V], mk[V];
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(xr + k * V), xv);
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eur + k * V), eu);
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(ecr + k * V), ec);
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(orow + k * V), ov);
             if (now || next) {
-                unpack8(*reinterpret_cast<const h8_t*>(img + k * 8), im);
-                unpack8(*reinterpret_cast<const h8_t*>(nse + k * 8), nz);
-                unpack8(*reinterpret_cast<const h8_t*>(msk + k * 8), mk);
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(img + k * V), im);
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(nse + k * V), nz);
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(msk + k * V), mk);
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
+            for (int j = 0; j < V; ++j) {
                 // step_rows_kernel's lines; the model input xh replaces x in D only - the sampler's own state stays unblended
                 const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
                 float xh = xv[j];
@@ -253,16 +277,16 @@ __global__ __launch_bounds__(256) void step_rows_known_kernel(half_t* x, const h
                 }
                 xi[j] = as_f32(xo * c_in_next);
             }
-            *reinterpret_cast<h8_t*>(orow + k * 8) = pack8(dn);
-            *reinterpret_cast<h8_t*>(xr + k * 8) = pack8(xn);
+            *reinterpret_cast<hv_t<V>*>(orow + k * V) = packv<V>(dn);
+            *reinterpret_cast<hv_t<V>*>(xr + k * V) = packv<V>(xn);
             if (dst) {
-                const h8_t o = pack8(xi);
-                *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
-                *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+                const hv_t<V> o = packv<V>(xi);
+                *reinterpret_cast<hv_t<V>*>(xi_u + k * V) = o;
+                *reinterpret_cast<hv_t<V>*>(xi_c + k * V) = o;
             }
         }
     } else if (dst) {
-        rows_join_or_idle(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
+        rows_join_or_idle<256, V>(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
     }
     if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
 }
@@ -479,12 +503,15 @@ extern "C" int dsc_prepare_unet_input(const void* x, float c_in, float t, float 
                                       float* sigma_buf, int n_img, int chw, int dtype,
                                       const void* row_src, void* row_dst, int row_halfs, int row_copies, void* stream) {
     if (!x || !x_in || !t_buf || !sigma_buf || n_img <= 0 || chw <= 0) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16 || chw % 8 != 0 || !al16(x) || !al16(x_in)) return DSC_ERR_UNSUPPORTED;
+    if (dtype != DSC_F16 || chw % 4 != 0 || !al16(x) || !al16(x_in)) return DSC_ERR_UNSUPPORTED;
     if (const int rs = row_args_status(row_src, row_dst, row_halfs, row_copies)) return rs;
-    const long long n8 = (long long)n_img * chw / 8;
-    DSC_LAUNCH(prepare_kernel, dim3(grid_for(n8)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const half_t*>(x), c_in, t, sigma, static_cast<half_t*>(x_in), t_buf, sigma_buf,
-                       n_img, chw, static_cast<const half_t*>(row_src), static_cast<half_t*>(row_dst), row_halfs, row_copies);
+    const int V = chw % 8 == 0 ? 8 : 4;               // (4: latent rows of 4 h w halfs with h w odd)
+    const long long n8 = (long long)n_img * chw / V;
+#define DSC_PREPARE(VV) DSC_LAUNCH(prepare_kernel<VV>, dim3(grid_for(n8)), dim3(256), 0, static_cast<hipStream_t>(stream), \
+                       static_cast<const half_t*>(x), c_in, t, sigma, static_cast<half_t*>(x_in), t_buf, sigma_buf, \
+                       n_img, chw, static_cast<const half_t*>(row_src), static_cast<half_t*>(row_dst), row_halfs, row_copies)
+    if (V == 8) DSC_PREPARE(8); else DSC_PREPARE(4);
+#undef DSC_PREPARE
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }
 
@@ -493,24 +520,29 @@ extern "C" int dsc_cfg_dpmpp2m_step(void* x, const void* eps, void* old, float s
                                     float* sigma_buf, int n_img, int chw, int dtype,
                                     const void* row_src, void* row_dst, int row_halfs, int row_copies, void* stream) {
     if (!x || !eps || !old || !x_in || !t_buf || !sigma_buf || n_img <= 0 || chw <= 0) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16 || chw % 8 != 0 || !al16(x) || !al16(eps) || !al16(old) || !al16(x_in)) return DSC_ERR_UNSUPPORTED;
+    if (dtype != DSC_F16 || chw % 4 != 0 || !al16(x) || !al16(eps) || !al16(old) || !al16(x_in)) return DSC_ERR_UNSUPPORTED;
     if (const int rs = row_args_status(row_src, row_dst, row_halfs, row_copies)) return rs;
-    const long long n8 = (long long)n_img * chw / 8;
-    DSC_LAUNCH(step_kernel, dim3(grid_for(n8)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), sigma,
-                       guidance, a, b, c, c_in_next, t_next, sigma_next, static_cast<half_t*>(x_in), t_buf, sigma_buf,
-                       n_img, chw, static_cast<const half_t*>(row_src), static_cast<half_t*>(row_dst), row_halfs, row_copies);
+    const int V = chw % 8 == 0 ? 8 : 4;
+    const long long n8 = (long long)n_img * chw / V;
+#define DSC_STEP(VV) DSC_LAUNCH(step_kernel<VV>, dim3(grid_for(n8)), dim3(256), 0, static_cast<hipStream_t>(stream), \
+                       static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), sigma, \
+                       guidance, a, b, c, c_in_next, t_next, sigma_next, static_cast<half_t*>(x_in), t_buf, sigma_buf, \
+                       n_img, chw, static_cast<const half_t*>(row_src), static_cast<half_t*>(row_dst), row_halfs, row_copies)
+    if (V == 8) DSC_STEP(8); else DSC_STEP(4);
+#undef DSC_STEP
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }
 
 extern "C" int dsc_dpmpp2m_update(const void* x, const void* denoised, const void* old, float a, float b, float c,
                                   void* out, int64_t n, int dtype, void* stream) {
     if (!x || !denoised || !out || n <= 0 || (!old && c != 0.f)) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16 || n % 8 != 0 || !al16(x) || !al16(denoised) || !al16(out) || (old && !al16(old)))
+    if (dtype != DSC_F16 || n % 4 != 0 || !al16(x) || !al16(denoised) || !al16(out) || (old && !al16(old)))
         return DSC_ERR_UNSUPPORTED;
-    DSC_LAUNCH(update_kernel, dim3(grid_for(n / 8)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const half_t*>(x), static_cast<const half_t*>(denoised),
-                       static_cast<const half_t*>(old), a, b, c, static_cast<half_t*>(out), (long long)(n / 8));
+#define DSC_UPDATE(VV) DSC_LAUNCH(update_kernel<VV>, dim3(grid_for(n / VV)), dim3(256), 0, static_cast<hipStream_t>(stream), \
+                       static_cast<const half_t*>(x), static_cast<const half_t*>(denoised), \
+                       static_cast<const half_t*>(old), a, b, c, static_cast<half_t*>(out), (long long)(n / VV))
+    if (n % 8 == 0) DSC_UPDATE(8); else DSC_UPDATE(4);
+#undef DSC_UPDATE
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }
 
@@ -519,7 +551,7 @@ extern "C" int dsc_cfg_dpmpp2m_step_rows(void* x, const void* eps, void* old, in
                                          int n_slots, int chw, int dtype, void* stream) {
     if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || n_src < 0 || n_dst <= 0 || chw <= 0) return DSC_ERR_BAD_ARG;
     if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16 || chw % 8 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
+    if (dtype != DSC_F16 || chw % 4 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
     RowSteps rs{};
     bool any_row = false;
     for (int i = 0; i < n_slots; ++i) {
@@ -531,12 +563,15 @@ extern "C" int dsc_cfg_dpmpp2m_step_rows(void* x, const void* eps, void* old, in
         if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
         if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
     }
-    const long long v8 = chw / 8;
+    const int V = chw % 8 == 0 ? 8 : 4;
+    const long long v8 = chw / V;
     long long gx = (v8 + 255) / 256;
     gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-    DSC_LAUNCH(step_rows_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
-               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
-               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs);
+#define DSC_STEP_ROWS(VV) DSC_LAUNCH(step_rows_kernel<VV>, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream), \
+               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src, \
+               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs)
+    if (V == 8) DSC_STEP_ROWS(8); else DSC_STEP_ROWS(4);
+#undef DSC_STEP_ROWS
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }
 
@@ -547,7 +582,7 @@ extern "C" int dsc_cfg_dpmpp2m_step_rows_known(void* x, const void* eps, void* o
     if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || !known || n_src < 0 || n_dst <= 0 || chw <= 0)
         return DSC_ERR_BAD_ARG;
     if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16 || chw % 8 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
+    if (dtype != DSC_F16 || chw % 4 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
     RowSteps rs{};
     RowKnowns ks{};
     bool any_row = false;
@@ -568,12 +603,15 @@ extern "C" int dsc_cfg_dpmpp2m_step_rows_known(void* x, const void* eps, void* o
         if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
         if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
     }
-    const long long v8 = chw / 8;
+    const int V = chw % 8 == 0 ? 8 : 4;
+    const long long v8 = chw / V;
     long long gx = (v8 + 255) / 256;
     gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-    DSC_LAUNCH(step_rows_known_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
-               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
-               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs, ks);
+#define DSC_STEP_KNOWN(VV) DSC_LAUNCH(step_rows_known_kernel<VV>, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream), \
+               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src, \
+               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs, ks)
+    if (V == 8) DSC_STEP_KNOWN(8); else DSC_STEP_KNOWN(4);
+#undef DSC_STEP_KNOWN
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }
 

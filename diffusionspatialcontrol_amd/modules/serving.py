@@ -246,6 +246,12 @@ class ServingBatcher:
         if (request.get("height", self.height), request.get("width", self.width)) != (self.height, self.width):
             raise ValueError(f"serve: this batcher runs {self.height}x{self.width} images, the request asks for "
                              f"{request.get('height')}x{request.get('width')}")
+        # dsc_cfg_linear_step_rows and its rescale form move 8 halfs per lane; refused here, before the request can reach a step
+        # that other requests share (DPM++ 2M's own per-row step takes the 4 * odd halfs of a latent with both sides odd)
+        if (family != "dpmpp_2m" or v_pred or phi > 0.0) and (4 * (self.height // 8) * (self.width // 8)) % 8 != 0:
+            raise ValueError(f"serve: this batcher's {self.height // 8}x{self.width // 8} latent has both sides odd; the linear "
+                             f"per-row step (every sampler but DPM++ 2M, v-prediction models, `guidance_rescale` > 0) needs a "
+                             f"multiple of 8 halfs per latent: drop `sampler_name` / `guidance_rescale`, or use txt2img")
         g = float(request.get("guidance_scale", 7.5))
         if g <= 1.0:
             raise ValueError("serve: guidance_scale must be > 1 (classifier-free guidance rows u_i / c_i)")

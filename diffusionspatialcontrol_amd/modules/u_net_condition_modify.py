@@ -610,8 +610,9 @@ class Downsample2D(nn.Module):
         self.conv = nn.Conv2d(c, c, 3, stride=2, padding=1)
 
     def forward(self, x):
-        if x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0 and ops.conv3x3_supported(x, self.conv.weight):
-            return ops.conv3x3(x, self.conv.weight, self.conv.bias, stride2=True)      # even pixels of the stride-1 taps
+        if ops.conv3x3_supported(x, self.conv.weight):
+            # even pixels of the stride-1 taps; an odd side n keeps its last pixel: ceil(n / 2), as the stride-2 / pad-1 convolution does
+            return ops.conv3x3(x, self.conv.weight, self.conv.bias, stride2_ceil=True)
         return self.conv(x)
 
 
@@ -620,10 +621,18 @@ class Upsample2D(nn.Module):
         super().__init__()
         self.conv = nn.Conv2d(c, c, 3, padding=1)
 
-    def forward(self, x):
-        if ops.conv3x3_supported(x, self.conv.weight, upsample=True):      # the upsampling happens in the halo gather
-            return ops.conv3x3(x, self.conv.weight, self.conv.bias, upsample=True)
-        return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))
+    def forward(self, x, output_size=None):
+        """output_size: the (H, W) of the skip tensor the result meets (reference :1281-1300 `upsample_size`) when the latent
+        sides are not multiples of the UNet's overall factor - 2s or 2s-1 of the source sides; None: double"""
+        if output_size is None:
+            if ops.conv3x3_supported(x, self.conv.weight, upsample=True):      # the upsampling happens in the halo gather
+                return ops.conv3x3(x, self.conv.weight, self.conv.bias, upsample=True)
+            return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))
+        output_size = tuple(int(v) for v in output_size)
+        if all(t in (2 * s_, 2 * s_ - 1) for t, s_ in zip(output_size, x.shape[2:])) \
+                and ops.conv3x3_supported(x, self.conv.weight, upsample_size=output_size):
+            return ops.conv3x3(x, self.conv.weight, self.conv.bias, upsample_size=output_size)   # same gather, skip-sized extent
+        return self.conv(F.interpolate(x, size=output_size, mode="nearest"))
 
 
 class _Block(nn.Module):
@@ -712,7 +721,7 @@ class _EncoderHalf:
     def _conv_in(self, sample):
         ci = self.conv_in
         if (sample.is_cuda and sample.dtype == torch.float16 and ci.in_channels <= 16 and ci.out_channels % 8 == 0
-                and ci.out_channels <= 512 and sample.shape[-1] % 8 == 0 and ops.USE_DSC_CONV):
+                and ci.out_channels <= 512 and ops.USE_DSC_CONV):
             wt = _derived(self, "conv_in_t", (ci.weight,), lambda: ci.weight.reshape(ci.out_channels, -1).t().contiguous())
             return ops.conv3x3_fewcin(sample, wt, ci.bias, ci.out_channels)   # NCHW latents -> NHWC features, one launch
         return ci(sample.contiguous()).contiguous(memory_format=torch.channels_last)
@@ -920,13 +929,18 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
         x = self._run_mid(x, temb_act, tadd, encoder_hidden_states, cross_attention_kwargs)
         if mid_block_additional_residual is not None:            # reference :1269-1270
             x = x + mid_block_additional_residual
+        # reference :1110-1123, 1281-1300: when a latent side is not a multiple of 2 ** (number of upsamplers) the down path's
+        # ceil(n / 2) sizes are not what doubling gives back, and every upsampler is told the size of the skip tensor its result
+        # is concatenated with.  Sides that divide: nothing is forwarded and the upsamplers double, as before.
+        factor = 2 ** sum(1 for blk in self.up_blocks if hasattr(blk, "upsamplers"))
+        forward_size = any(int(d) % factor != 0 for d in sample.shape[-2:])
         for blk in self.up_blocks:
             for j, res in enumerate(blk.resnets):
                 x = res((x, skips.pop()), temb_act, tadd[res])
                 if blk.has_attn:
                     x = blk.attentions[j](x, encoder_hidden_states, cross_attention_kwargs)
             if hasattr(blk, "upsamplers"):
-                x = blk.upsamplers[0](x)
+                x = blk.upsamplers[0](x, skips[-1].shape[2:]) if forward_size else blk.upsamplers[0](x)
         h = self.conv_norm_out(x)                                            # reference :1304-1307
         co = self.conv_out
         wcl = _derived(self, "conv_out_cl", (co.weight,), lambda: co.weight.contiguous(memory_format=torch.channels_last))

@@ -425,18 +425,23 @@ def groupnorm_apply_nhwc(x, part, groups, weight, bias, eps, act):
     return y
 
 
-def conv3x3_gn_rows(x, weight, groups, upsample=False):
-    """pixel tiles per image when dsc_conv3x3_gn_nhwc_f16 covers this convolution (and GroupNorm grouping of its output), else 0"""
-    if not (USE_GN_FUSE and conv3x3_supported(x, weight, upsample=upsample)):
+def conv3x3_gn_rows(x, weight, groups, upsample=False, upsample_size=None):
+    """pixel tiles per image when dsc_conv3x3_gn_nhwc_f16 covers this convolution (and GroupNorm grouping of its output), else 0;
+    upsample_size as in conv3x3"""
+    size = _upsample_target(x, upsample, upsample_size)
+    if not (USE_GN_FUSE and conv3x3_supported(x, weight, upsample=upsample, upsample_size=upsample_size)):
         return 0
     B, C, H, W = x.shape
+    if size is not None:
+        return int(_lib.load_library().dsc_conv3x3_gn_rows(B, size[0], size[1], C, weight.shape[0], groups, 4))
     f = 2 if upsample else 1
     return int(_lib.load_library().dsc_conv3x3_gn_rows(B, H * f, W * f, C, weight.shape[0], groups, 1 if upsample else 0))
 
 
-def conv3x3_gn(x, weight, groups, bias=None, add=None, residual=None, upsample=False):
+def conv3x3_gn(x, weight, groups, bias=None, add=None, residual=None, upsample=False, upsample_size=None):
     """conv3x3 (+ bias) (+ per-image bias row add [B, Cout]) (+ residual), channels_last; the returned tensor carries the
     GroupNorm partial sums of what was stored (gn_partials_of) - call only when conv3x3_gn_rows() > 0"""
+    size = _upsample_target(x, upsample, upsample_size)
     _require_gpu(x, weight)
     lib = _lib.load_library()
     cl = torch.channels_last
@@ -447,8 +452,11 @@ def conv3x3_gn(x, weight, groups, bias=None, add=None, residual=None, upsample=F
     B, Cin, H, W = x.shape
     if upsample:
         H, W = 2 * H, 2 * W
+    if size is not None:
+        H, W = size
+    resample = 4 if size is not None else (1 if upsample else 0)
     Cout = weight.shape[0]
-    rows = int(lib.dsc_conv3x3_gn_rows(B, H, W, Cin, Cout, groups, 1 if upsample else 0))
+    rows = int(lib.dsc_conv3x3_gn_rows(B, H, W, Cin, Cout, groups, resample))
     if rows <= 0:
         raise ValueError("conv3x3_gn: shape not covered (ask conv3x3_gn_rows first)")
     out = torch.empty((B, Cout, H, W), dtype=x.dtype, device=x.device, memory_format=cl)
@@ -466,7 +474,7 @@ def conv3x3_gn(x, weight, groups, bias=None, add=None, residual=None, upsample=F
         add_ld = add.stride(0)
     part = torch.empty((B, rows, groups, 2, 2), dtype=torch.float32, device=x.device)
     rc = lib.dsc_conv3x3_gn_nhwc_f16(_p(x), _p(weight), _p(bias), _p(add), add_ld, _p(residual), _p(out), B, H, W, Cin, Cout, Cin,
-                                     ldr, Cout, 1 if upsample else 0, _p(part), groups, 0, _stream_ptr(x))
+                                     ldr, Cout, resample, _p(part), groups, 0, _stream_ptr(x))
     _lib.check(rc, "dsc_conv3x3_gn_nhwc_f16")
     return attach_gn_partials(out, GnPartials(part, rows, groups, Cout, B, H * W))
 
@@ -788,25 +796,54 @@ def linear(x, weight, bias=None, residual=None, geglu=False, prefer_kernel=False
 USE_DSC_CONV = True        # route qualifying 3x3 convolutions to dsc_conv3x3_nhwc_f16 (False: always MIOpen through torch)
 
 
-def conv3x3_supported(x, weight, upsample=False):
+def _upsample_target(x, upsample, upsample_size, stride2=False, stride2_pad_br=False):
+    """the (H, W) a convolution with upsample_size runs at, or None without one; ValueError for a size the gather cannot serve"""
+    if upsample_size is None:
+        return None
+    if upsample or stride2 or stride2_pad_br:
+        raise ValueError("conv3x3: upsample_size, upsample, stride2 and stride2_pad_br exclude each other")
+    if x.dim() != 4 or len(upsample_size) != 2:
+        raise ValueError("conv3x3: upsample_size is the (H, W) of the upsampled [B, C, H, W] image")
+    size = (int(upsample_size[0]), int(upsample_size[1]))
+    for t, s in zip(size, x.shape[2:]):
+        # the only targets whose nearest-neighbour source index is dst >> 1 (and the only ones a UNet skip tensor demands)
+        if t not in (2 * s, 2 * s - 1) or t < 1:
+            raise ValueError(f"conv3x3: upsample_size {size} is not 2s or 2s-1 of the source sides {tuple(x.shape[2:])}")
+    return size
+
+
+def conv3x3_supported(x, weight, upsample=False, upsample_size=None):
     """True when dsc_conv3x3_nhwc_f16 covers this [B, Cin, H, W] channels_last fp16 input / [Cout, Cin, 3, 3] weight
-    (upsample: the convolution runs on the 2x nearest-upsampled image)."""
+    (upsample: the convolution runs on the 2x nearest-upsampled image; upsample_size=(H', W'): on the image upsampled to that
+    size, each side 2s or 2s-1 of the source side - ValueError otherwise)."""
+    size = _upsample_target(x, upsample, upsample_size)
     if not (USE_DSC_CONV and x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16 and x.dim() == 4
             and tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] == x.shape[1]):
         return False
     B, C, H, W = x.shape
     f = 2 if upsample else 1
+    if size is not None:
+        return bool(_lib.load_library().dsc_conv3x3_supported(B, size[0], size[1], C, weight.shape[0]))
     return bool(_lib.load_library().dsc_conv3x3_supported(B, H * f, W * f, C, weight.shape[0]))
 
 
-def conv3x3(x, weight, bias=None, residual=None, splits=0, upsample=False, out_nchw=False, stride2=False, stride2_pad_br=False):
+def conv3x3(x, weight, bias=None, residual=None, splits=0, upsample=False, out_nchw=False, stride2=False, stride2_pad_br=False,
+            upsample_size=None, stride2_ceil=False):
     """3x3 / stride 1 / pad 1 convolution (+ bias) (+ residual) of a channels_last fp16 [B, Cin, H, W] tensor with a
     [Cout, Cin, 3, 3] weight held in channels_last memory format (dsc_conv3x3_nhwc_f16); returns channels_last
     [B, Cout, H, W], or a plain contiguous (NCHW) tensor with out_nchw=True.  upsample=True convolves the 2x
-    nearest-neighbour upsampling of x (output [B, Cout, 2H, 2W]) without materialising it; stride2=True is the
-    stride-2 / pad-1 convolution (output [B, Cout, H/2, W/2], H and W even); stride2_pad_br=True the stride-2 convolution with
-    zero padding on the bottom / right only (`F.pad(x, (0, 1, 0, 1))` + stride-2 / pad-0 conv: AutoencoderKL encoder).  Raises
-    on an unsupported shape - ask conv3x3_supported() first."""
+    nearest-neighbour upsampling of x (output [B, Cout, 2H, 2W]) without materialising it; upsample_size=(H', W') convolves
+    `F.interpolate(x, size=(H', W'), mode="nearest")`, each side 2s or 2s-1 of the source side (the UNet's upsampling to the
+    size of a skip tensor; ValueError for any other size); stride2_ceil=True is the stride-2 / pad-1 convolution (output
+    [B, Cout, ceil(H/2), ceil(W/2)], any H and W: UNet Downsample2D); stride2=True the same launch behind its older even-sides-only
+    rule (ValueError for an odd side: tests/test_unet_pipeline_gpu.py::test_conv3x3_unsupported pins that refusal, so the rule
+    stays under this name until that assertion goes); stride2_pad_br=True the stride-2 convolution with zero padding on the bottom / right only
+    (`F.pad(x, (0, 1, 0, 1))` + stride-2 / pad-0 conv: AutoencoderKL encoder; H and W even).  Raises on an unsupported shape - ask
+    conv3x3_supported() first."""
+    size = _upsample_target(x, upsample, upsample_size, stride2 or stride2_ceil, stride2_pad_br)
+    if stride2 and (x.shape[-1] % 2 or x.shape[-2] % 2):
+        raise ValueError("conv3x3: stride2=True keeps its even-sides rule; stride2_ceil=True takes any side")
+    stride2 = bool(stride2) or bool(stride2_ceil)
     _require_gpu(x, weight)
     lib = _lib.load_library()
     cl = torch.channels_last
@@ -817,10 +854,12 @@ def conv3x3(x, weight, bias=None, residual=None, splits=0, upsample=False, out_n
     B, Cin, H, W = x.shape
     if upsample:
         H, W = 2 * H, 2 * W
+    if size is not None:
+        H, W = size
     Cout = weight.shape[0]
     if int(bool(upsample)) + int(bool(stride2)) + int(bool(stride2_pad_br)) > 1:
         raise ValueError("conv3x3: upsample, stride2 and stride2_pad_br exclude each other")
-    oh, ow = (H // 2, W // 2) if (stride2 or stride2_pad_br) else (H, W)
+    oh, ow = ((H + 1) // 2, (W + 1) // 2) if stride2 else ((H // 2, W // 2) if stride2_pad_br else (H, W))
     if out_nchw:
         out = torch.empty((B, Cout, oh, ow), dtype=x.dtype, device=x.device)
     else:
@@ -835,7 +874,7 @@ def conv3x3(x, weight, bias=None, residual=None, splits=0, upsample=False, out_n
     nbytes = lib.dsc_conv3x3_workspace_bytes(B, H, W, Cin, Cout, splits)
     ws = _workspace(x.device, nbytes) if nbytes else None
     rc = lib.dsc_conv3x3_nhwc_f16(_p(x), _p(weight), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, Cin, ldr, Cout,
-                                  3 if stride2_pad_br else (2 if stride2 else (1 if upsample else 0)), 1 if out_nchw else 0, splits, 0, _p(ws),
+                                  3 if stride2_pad_br else (2 if stride2 else (1 if upsample else (4 if size is not None else 0))), 1 if out_nchw else 0, splits, 0, _p(ws),
                                   ws.numel() * 8 if ws is not None else 0, _stream_ptr(x))
     _lib.check(rc, "dsc_conv3x3_nhwc_f16")
     return out

@@ -177,7 +177,8 @@ int dsc_self_attn_fwd(const void* q, const void* k, const void* v, void* out,
  *   x_in   = [x; x] * c_in_next ;  t_buf[0 .. 2 n_img) = t_next ;  sigma_buf[0] = sigma_next
  *
  * x, old: fp16 [n_img, chw]; eps, x_in: fp16 [2 n_img, chw]; t_buf fp32 [2 n_img]; sigma_buf fp32 [1].
- * dsc_prepare_unet_input does only the last line (before the first step).  chw % 8 == 0, 16-byte aligned pointers.
+ * dsc_prepare_unet_input does only the last line (before the first step).  chw % 4 == 0 (8-byte accesses unless chw % 8 == 0:
+ * 4 h w halfs with h w odd, the 19 x 19 latents of a 152 x 152 image), 16-byte aligned pointers.
  */
 /* row_src (optional, NULL = none): row_halfs fp16 values copied to each of the row_copies rows of row_dst in the same launch -
  * the pipeline keeps the per-ResNet time-embedding projections of ALL steps in a table computed once per schedule (they depend on
@@ -201,7 +202,8 @@ int dsc_cfg_dpmpp2m_step(void* x, const void* eps, void* old, float sigma, float
  *   DSC_ROW_IDLE: padding: x_in rows = 0, sigma_groups[i] = 1
  * Every slot i < n_dst writes t_next into t_buf rows {i, n_dst + i}, its sigma (sigma_next; 1 for IDLE) into sigma_groups[i]
  * and, when temb_row != NULL, copies temb_row (tadd_halfs fp16) into tadd rows {i, n_dst + i}.  Slots i >= n_dst write no
- * destination row (only STEP or IDLE there).  n_slots >= n_dst records.  chw % 8 == 0, tadd_halfs % 8 == 0, 16-byte aligned.
+ * destination row (only STEP or IDLE there).  n_slots >= n_dst records.  chw % 4 == 0 (as above; dsc_cfg_dpmpp2m_step_rows_known
+ * too - dsc_cfg_linear_step_rows and its rescale form keep chw % 8 == 0), tadd_halfs % 8 == 0, 16-byte aligned.
  */
 #define DSC_ROW_STEP 0
 #define DSC_ROW_JOIN 1
@@ -294,7 +296,7 @@ int dsc_cfg_linear_step_rows_rescale(void* x, const void* eps, void* old, int n_
                                      const dsc_row_linear* rows /* host */, const float* rescale /* host, n_slots */, int n_slots,
                                      int chw, int dtype, void* stream);
 /* out = a*x + b*denoised + c*old  (old may be NULL when c == 0): the sampler update alone, for callers that keep
- * the reference's `sampler(model_fn, x, sigmas=...)` control flow.  n elements, n % 8 == 0. */
+ * the reference's `sampler(model_fn, x, sigmas=...)` control flow.  n elements, n % 4 == 0 (8-byte accesses unless n % 8 == 0). */
 int dsc_dpmpp2m_update(const void* x, const void* denoised, const void* old, float a, float b, float c,
                        void* out, int64_t n, int dtype, void* stream);
 
@@ -370,8 +372,15 @@ int dsc_linear_f16(const void* x, const void* w, const void* bias, const void* r
  * format), residual / out [B,H,W,Cout] with pixel strides ldr / ldo.  fp32 accumulation, one fp16 rounding.
  * resample == DSC_CONV_UPSAMPLE2X: x is [B,H/2,W/2,Cin] and the convolution reads it through a nearest-neighbour 2x
  * upsampling (diffusers Upsample2D = F.interpolate(scale_factor=2, mode="nearest") + conv) without materialising the image.
- * resample == DSC_CONV_STRIDE2: only the even pixels are stored, out is [B,H/2,W/2,Cout] - the stride-2 / pad-1 convolution of
- * diffusers Downsample2D (3 per UNet step).  The taps still run at H x W (4x the necessary MFMA work); it is nevertheless
+ * resample == DSC_CONV_UPSAMPLE_CEIL: x is [B,(H+1)/2,(W+1)/2,Cin] and is read through F.interpolate(x, size=(H, W),
+ * mode="nearest") - the upsampling to the size of the skip tensor the result is concatenated with (the reference UNet's
+ * `upsample_size`, u_net_condition_modify.py:1114-1123, 1281-1300), which lets latents whose sides are not multiples of 8 through
+ * the UNet.  Each side is 2s or 2s-1 of its source side s, and for both torch's source index is dst >> 1: exactly,
+ * floor(dst * s / (2s-1)) = floor(dst/2 + dst / (2 (2s-1))) and the second term is below 1/2 for dst <= 2s-2; torch computes the
+ * index in fp32, and tests/test_any_size_host.py compares it with the shift for every s in 1..1099.  So the gather is the 2x
+ * one with another source extent, and for even H, W the result has the bytes of DSC_CONV_UPSAMPLE2X.
+ * resample == DSC_CONV_STRIDE2: only the even pixels are stored, out is [B,(H+1)/2,(W+1)/2,Cout] - the stride-2 / pad-1 convolution
+ * of diffusers Downsample2D (3 per UNet step), odd sides included (their last pixel is an even one).  The taps still run at H x W (4x the necessary MFMA work); it is nevertheless
  * faster than MIOpen's stride-2 kernels here (24-27 us vs 31-37 us) and, unlike their atomic split-K, bit-reproducible.
  * out_nchw != 0: out is [B,Cout,H,W] (channel-major; the UNet's 4-channel conv_out hands its result back in the sampler's
  * layout).  Cout need not be a multiple of 64: a ragged last channel tile reads zero weight rows through the buffer bounds.
@@ -384,7 +393,9 @@ int dsc_linear_f16(const void* x, const void* w, const void* bias, const void* r
 #define DSC_CONV_UPSAMPLE2X 1
 #define DSC_CONV_STRIDE2 2
 #define DSC_CONV_STRIDE2_PAD_BR 3   /* stride 2 with zero padding on the bottom / right only (F.pad (0,1,0,1) + stride-2 conv of
-                                     * the AutoencoderKL encoder's Downsample2D): the ODD pixels of the stride-1 / pad-1 taps */
+                                     * the AutoencoderKL encoder's Downsample2D): the ODD pixels of the stride-1 / pad-1 taps;
+                                     * even H, W only (image sides are multiples of 8) */
+#define DSC_CONV_UPSAMPLE_CEIL 4
 int dsc_conv3x3_supported(int B, int H, int W, int Cin, int Cout);
 /* diagnostics: 8 x int64 per workgroup (start / loop start / loop end / end in 100 MHz ticks, the three segment lengths in
  * shader clocks, XCC and HW ids) of every following dsc_conv3x3_nhwc_f16 call go to `device_buffer`; NULL switches it off */
@@ -441,7 +452,7 @@ int dsc_linear_qkv_f16(const void* x, const void* w, const void* bias, void* q_o
  * 3x3 / pad 1 convolution with few input channels (<= 16) - the UNet's `conv_in` (4 -> 320; reference
  * u_net_condition_modify.py:352-356,1187): x [B,Cin,H,W] channel-major fp16 (the sampler's latent layout),
  * w_t [9*Cin, Cout] = weight.reshape(Cout, Cin*9).t() (k = (ci*3 + dy)*3 + dx), out [B,H,W,Cout] channels-last, bias fused.
- * Cout % 8 == 0, Cout <= 512, W % 8 == 0.
+ * Cout % 8 == 0, Cout <= 512; any H, W >= 1 (a workgroup computes 8 pixels of a row; the last one of a ragged row stores fewer).
  */
 int dsc_conv3x3_fewcin_f16(const void* x_nchw, const void* w_t, const void* bias, void* out_nhwc,
                            int B, int Cin, int H, int W, int Cout, int dtype, void* stream);

@@ -1,0 +1,194 @@
+"""Latents of any size (image sides multiples of 8, not of 64) - the parts that need no GPU: the index identity the skip-sized
+upsampling gather rests on, the sized restatement of the oracle's UNet pinned to the oracle, the sizes of the levels, and the
+argument checks of ops.conv3x3(upsample_size=...)."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import any_size_ref as ar
+from oracle import unet_ref
+
+
+def test_nearest_source_index_is_a_shift_for_the_two_skip_targets():
+    """F.interpolate(size=2n-1 | 2n, mode="nearest") reads source index dst >> 1: torch computes floor(dst * (n / out)) in fp32,
+    exact arithmetic gives floor(dst / 2 + dst / (2 (2n - 1))) with the second term below 1/2 for dst <= 2n - 2.  Checked over
+    every source side the UNet can meet (1..1099: beyond a 8192-pixel image's first level)"""
+    for n in range(1, 1100):
+        src = torch.arange(n, dtype=torch.float32).view(1, 1, 1, n)
+        for out in (2 * n - 1, 2 * n):
+            got = F.interpolate(src, size=(1, out), mode="nearest").view(-1).long()
+            assert torch.equal(got, torch.arange(out) >> 1), (n, out)
+    # ... and along the other axis of a small image, both axes at once
+    img = torch.arange(3 * 5, dtype=torch.float32).view(1, 1, 3, 5)
+    got = F.interpolate(img, size=(5, 10), mode="nearest")[0, 0]
+    want = img[0, 0][(torch.arange(5) >> 1)[:, None], (torch.arange(10) >> 1)[None, :]]
+    assert torch.equal(got, want)
+
+
+def _tiny_cpu(seed=0):
+    from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNet2DConditionModel, UNetConfig
+    torch.manual_seed(seed)
+    cfg = UNetConfig.tiny()
+    sd = {k: v.clone() for k, v in UNet2DConditionModel(cfg).half().state_dict().items()}
+    g = torch.Generator().manual_seed(7)
+    text = torch.randn(2, 77, cfg.cross_attention_dim, generator=g).half().float()
+    return cfg, sd, text
+
+
+def test_sized_restatement_is_the_oracle_where_sides_divide():
+    cfg, sd, text = _tiny_cpu()
+    x = torch.randn(2, 4, 16, 16, generator=torch.Generator().manual_seed(5)).half().float()
+    t = torch.tensor([731.25, 731.25])
+    assert torch.equal(ar.sized_unet_forward(sd, cfg, x, t, text), unet_ref.unet_forward(sd, cfg, x, t, text))
+    # ... and it runs where the oracle cannot: 19 -> 10 -> 5 -> 3 on the way down, 6 against 5 on the way up
+    x19 = torch.randn(2, 4, 19, 19, generator=torch.Generator().manual_seed(6)).half().float()
+    with pytest.raises(RuntimeError):
+        unet_ref.unet_forward(sd, cfg, x19, t, text)
+    out = ar.sized_unet_forward(sd, cfg, x19, t, text)
+    assert out.shape == (2, 4, 19, 19) and torch.isfinite(out).all()
+    assert unet_ref.unet_forward is not ar.sized_unet_forward            # the stand-in of sized_denoise_loop does not leak
+
+
+@pytest.mark.parametrize("hw,levels", [((19, 19), [(19, 19), (10, 10), (5, 5), (3, 3)]),
+                                       ((19, 22), [(19, 22), (10, 11), (5, 6), (3, 3)]),
+                                       ((76, 76), [(76, 76), (38, 38), (19, 19), (10, 10)]),
+                                       ((90, 135), [(90, 135), (45, 68), (23, 34), (12, 17)])])
+def test_skip_size_sequence(hw, levels):
+    """three downsamplings (SD1.5): the stride-2 / pad-1 convolution's own output sizes on the way down; every upsampler is asked
+    for the level above it, and each such target side is 2s or 2s - 1 of the side it starts from - the two cases of the gather"""
+    down, up = ar.skip_sizes(*hw, 3)
+    assert down == levels
+    x = torch.zeros(1, 1, *hw)
+    for size in levels[1:]:
+        x = F.conv2d(x, torch.zeros(1, 1, 3, 3), stride=2, padding=1)
+        assert tuple(x.shape[2:]) == size
+    assert up == list(reversed(levels[:-1]))
+    for src, dst in zip(reversed(levels[1:]), up):
+        assert all(d in (2 * s, 2 * s - 1) for s, d in zip(src, dst)), (src, dst)
+    # the reference's rule: sizes are forwarded exactly when a side is not a multiple of 2 ** 3
+    assert any(v % 8 for v in hw)
+
+
+def test_upsample_size_argument_refusals():
+    """every refusal is raised from the arguments alone, before the device is asked for"""
+    from diffusionspatialcontrol_amd import ops
+    x = torch.zeros(1, 64, 3, 5, dtype=torch.float16)
+    w = torch.zeros(64, 64, 3, 3, dtype=torch.float16)
+    for bad in ((7, 9), (5, 11), (4, 9), (5, 8), (3, 5), (0, 9)):
+        with pytest.raises(ValueError):
+            ops.conv3x3(x, w, upsample_size=bad)
+        with pytest.raises(ValueError):
+            ops.conv3x3_supported(x, w, upsample_size=bad)
+        with pytest.raises(ValueError):
+            ops.conv3x3_gn_rows(x, w, 32, upsample_size=bad)
+        with pytest.raises(ValueError):
+            ops.conv3x3_gn(x, w, 32, upsample_size=bad)
+    with pytest.raises(ValueError):
+        ops.conv3x3(x, w, upsample_size=(5, 9, 1))
+    for other in ("upsample", "stride2", "stride2_ceil", "stride2_pad_br"):
+        with pytest.raises(ValueError):
+            ops.conv3x3(x, w, upsample_size=(5, 9), **{other: True})
+    with pytest.raises(ValueError):
+        ops.conv3x3_supported(x, w, upsample=True, upsample_size=(5, 9))
+    # good sizes pass the argument checks: on a CPU tensor the answer is "not covered" / the no-CPU-fallback error
+    from diffusionspatialcontrol_amd import _lib
+    for good in ((5, 9), (6, 9), (5, 10), (6, 10)):
+        assert ops.conv3x3_supported(x, w, upsample_size=good) is False
+        with pytest.raises(_lib.DscLibraryError):
+            ops.conv3x3(x, w, upsample_size=good)
+    # stride2 keeps its even-sides refusal (pinned by an older test); stride2_ceil is the form that takes any side
+    with pytest.raises(ValueError):
+        ops.conv3x3(x, w, stride2=True)
+    with pytest.raises(_lib.DscLibraryError):
+        ops.conv3x3(x, w, stride2_ceil=True)
+
+
+def test_sized_denoise_loop_is_the_oracle_loop_where_sides_divide():
+    """sized_denoise_loop swaps `unet_ref.unet_forward` for the sized restatement while unet_ref.denoise_loop runs, which rests on
+    the loop resolving that name in its module at call time.  Two things pin the assumption: the stand-in is really called (an
+    odd-sided latent, which unet_ref's own forward cannot run, goes through), and at 16 x 16 the result is the oracle loop's"""
+    cfg, sd, text = _tiny_cpu()
+    sig = [4.0, 1.5, 0.0]
+    lat = torch.randn(1, 4, 16, 16, generator=torch.Generator().manual_seed(8)).half().float() * (sig[0] ** 2 + 1) ** 0.5
+    calls = []
+    saved = ar.sized_unet_forward
+
+    def counted(*a, **k):
+        calls.append(1)
+        return saved(*a, **k)
+
+    ar.sized_unet_forward = counted
+    try:
+        got = ar.sized_denoise_loop(sd, cfg, lat, sig, text, None, 7.5)
+    finally:
+        ar.sized_unet_forward = saved
+    assert len(calls) == 2                                               # one model call per step: the stand-in was the callee
+    assert unet_ref.unet_forward is not counted and unet_ref.unet_forward is not saved
+    assert torch.equal(got, unet_ref.denoise_loop(sd, cfg, lat, sig, text, None, 7.5))
+    lat19 = torch.randn(1, 4, 19, 19, generator=torch.Generator().manual_seed(9)).half().float() * (sig[0] ** 2 + 1) ** 0.5
+    with pytest.raises(RuntimeError):
+        unet_ref.denoise_loop(sd, cfg, lat19, sig, text, None, 7.5)
+    out = ar.sized_denoise_loop(sd, cfg, lat19, sig, text, None, 7.5)
+    assert out.shape == (1, 4, 19, 19) and torch.isfinite(out).all()
+
+
+# ----------------------------------------------------------------------------- the batcher's admission at odd x odd latents
+@pytest.fixture(scope="module")
+def pipe():
+    from inputs import FakeTokenizer
+    from diffusionspatialcontrol_amd.modules.model_k_diffusion import SD15Scheduler, StableDiffusionPipeline
+    from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNet2DConditionModel, UNetConfig
+    torch.manual_seed(0)
+    unet = UNet2DConditionModel(UNetConfig.tiny()).half()
+    return StableDiffusionPipeline(None, None, FakeTokenizer(), unet, SD15Scheduler())
+
+
+def _serve_request(h, w, **kw):
+    emb = torch.randn(2, 77, 64, generator=torch.Generator().manual_seed(3))
+    r = {"name": "r", "prompt_embeds": emb[1:2].half(), "negative_prompt_embeds": emb[0:1].half(), "num_inference_steps": 3,
+         "guidance_scale": 7.5, "sampler_opt": {"scheduler": "karras"}, "latents": torch.zeros(1, 4, h, w).half()}
+    r.update(kw)
+    return r
+
+
+def _fake_exec():
+    from test_serving_host import FakeExec
+
+    class Exec(FakeExec):
+        def prepare_noise(self, r, eta):                                 # (the ancestral / SDE members draw their step noise)
+            pass
+    return Exec()
+
+
+LINEAR_STEP_REQUESTS = [{"sampler_name": "sample_euler"}, {"sampler_name": "sample_euler_ancestral"},
+                        {"sampler_name": "sample_dpmpp_2m_sde"}, {"sampler_name": "sample_lcm"}, {"guidance_rescale": 0.7},
+                        {"sampler_name": "sample_dpmpp_2m", "guidance_rescale": 0.3}]
+
+
+@pytest.mark.parametrize("size", [(152, 152), (600, 600)])
+def test_batcher_refuses_linear_step_requests_at_odd_by_odd_latents(pipe, size):
+    """a latent with both sides odd holds 4 * odd halfs; dsc_cfg_linear_step_rows (and its rescale form) move 8 per lane.  Such
+    a request is refused when it is submitted - admitted, it would fail inside step(), under the other requests of the batch -
+    and leaves the batcher as it was; DPM++ 2M (its own per-row step takes 4 * odd) is served"""
+    from diffusionspatialcontrol_amd.modules import sampling
+    from diffusionspatialcontrol_amd.modules.serving import ServingBatcher
+    H, W = size
+    b = ServingBatcher(pipe, H, W, executor=_fake_exec(), max_batch=2, buckets=(1, 2))
+    for kw in LINEAR_STEP_REQUESTS:
+        assert kw.get("guidance_rescale") or sampling.linear_family(kw["sampler_name"]) not in (None, "dpmpp_2m")
+        with pytest.raises(ValueError, match="both sides odd"):
+            b.submit(_serve_request(H // 8, W // 8, **kw))
+    assert b.stats()["queued"] == 0 and not b.step()
+    fut = b.submit(_serve_request(H // 8, W // 8))
+    b.run_until_idle()
+    assert fut.done() and fut.exception() is None
+
+
+def test_batcher_serves_linear_step_requests_when_one_latent_side_is_even(pipe):
+    """19 x 22 latents (176 x 152 pixels) hold 1672 = 8 * 209 halfs: every sampler and guidance_rescale are admitted
+    (admission only: the fake executor of the host tests has no linear step)"""
+    from diffusionspatialcontrol_amd.modules.serving import ServingBatcher
+    b = ServingBatcher(pipe, 152, 176, executor=_fake_exec(), max_batch=2, buckets=(1, 2))
+    for n, kw in enumerate(LINEAR_STEP_REQUESTS):
+        b.submit(_serve_request(19, 22, **kw))
+        assert b.stats()["queued"] == n + 1, kw
