@@ -41,6 +41,11 @@ constexpr int kRingOff = 0;
 constexpr int a_off(int S) { return S * kBStageBytes; }
 constexpr int pad_off(int S) { return a_off(S) + 2 * kABytes; }
 constexpr int lds_bytes(int S) { return pad_off(S) + 1024; }   // S = 3: 76800 B
+// The phase form of the 2x-upsampled convolution (NT = 4 taps per slice, see conv3x3_body) runs a ring of FOUR weight tiles
+// (a tile's stage is its tap).  Its 16-wide kernel cuts the halo buffers to the 23 pieces its 180 slots need: 32 + 2 x 23 + 1 =
+// 79 KiB, two workgroups per CU as with the three-stage ring; the 8-wide one (200 slots) keeps 25 pieces: 83 KiB, one per CU.
+constexpr int a_bytes(int NT, int TW) { return NT == 4 && TW == 16 ? 23 * 1024 : kABytes; }
+constexpr int lds_bytes_up2x(int TW) { return a_off(4) + 2 * a_bytes(4, TW) + 1024; }
 constexpr int kEpiStride = BN + 4;
 constexpr unsigned kOob = 0x80000000u;           // buffer offset beyond any supported tensor: the load returns zeros
 
@@ -88,24 +93,25 @@ __device__ __forceinline__ void wait_vm() {
 // DMA instructions a wave issues after weight tile j+1 (the last thing step j+1-S issued) up to step j-1, for step j at
 // tap t: steps j-1 .. j-(S-2), 9 for a tap-0 step (7 halo pieces + 2 weight pieces), else 2.  The next slice's halo is
 // issued first in the tap-0 step, i.e. before the tile the tap-8 step waits for (S <= 9): no extra condition.
-template <int S>
+// (NT taps per slice: the same count with "tap 0" every NT steps; the halo argument needs S <= NT.)
+template <int S, int NT>
 constexpr int younger_dmas(int t) {
     int n = 0;
-    for (int i = 1; i <= S - 2; ++i) n += ((t - i) % 9 + 9) % 9 == 0 ? 9 : 2;
+    for (int i = 1; i <= S - 2; ++i) n += ((t - i) % NT + NT) % NT == 0 ? 9 : 2;
     return n;
 }
-template <int S>
+template <int S, int NT>
 __device__ __forceinline__ void wait_step(int t) {
     switch (t) {                                                  // t is a compile-time constant after unrolling
-        case 0: wait_vm<younger_dmas<S>(0)>(); break;
-        case 1: wait_vm<younger_dmas<S>(1)>(); break;
-        case 2: wait_vm<younger_dmas<S>(2)>(); break;
-        case 3: wait_vm<younger_dmas<S>(3)>(); break;
-        case 4: wait_vm<younger_dmas<S>(4)>(); break;
-        case 5: wait_vm<younger_dmas<S>(5)>(); break;
-        case 6: wait_vm<younger_dmas<S>(6)>(); break;
-        case 7: wait_vm<younger_dmas<S>(7)>(); break;
-        default: wait_vm<younger_dmas<S>(8)>(); break;
+        case 0: wait_vm<younger_dmas<S, NT>(0)>(); break;
+        case 1: wait_vm<younger_dmas<S, NT>(1)>(); break;
+        case 2: wait_vm<younger_dmas<S, NT>(2)>(); break;
+        case 3: wait_vm<younger_dmas<S, NT>(3)>(); break;
+        case 4: wait_vm<younger_dmas<S, NT>(4)>(); break;
+        case 5: wait_vm<younger_dmas<S, NT>(5)>(); break;
+        case 6: wait_vm<younger_dmas<S, NT>(6)>(); break;
+        case 7: wait_vm<younger_dmas<S, NT>(7)>(); break;
+        default: wait_vm<younger_dmas<S, NT>(8)>(); break;
     }
 }
 
@@ -128,12 +134,24 @@ __device__ __forceinline__ h8_t lds_read(unsigned byte_addr) {
 // registers fit the 512 of a SIMD, but only with ONE workgroup per CU - the kernel of the <= 256-workgroup grids under the
 // latency profile).  A DMA instruction holds its wave's issue port for 60-200 cycles; in the plain kernel the 2.8 of them per
 // step sit between the 8 MFMAs of the wave that also has to feed the matrix pipe.
-template <int TW, int S, int NLOAD = 0>
-__global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void conv3x3_kernel(ConvParams p) {
-    static_assert(S == 3 || S == 9, "the ring depth must divide the 9 taps");
+//
+// NT = 4: the PHASE FORM of "nearest-neighbour 2x upsampling, then this convolution" (dsc_conv3x3_up2x_nhwc_f16).  Output pixel
+// (2i+py, 2j+px) sees the source through a 2x2 neighbourhood only, x[i+py+a-1][j+px+b-1] for a, b in {0, 1}, with the weights
+// of the 3x3 taps that land on the same source pixel added up front (conv3x3_up2x_pack).  A tile is 128 SOURCE positions of ONE
+// phase (p.H x p.W is the source image; tile index = phase * source tiles + source tile, so neighbouring ids share a weight slab),
+// the halo is the plain stride-1 halo of the source, the four taps sit at halo offsets {py, py+1} x {px, px+1}, the weights
+// are [phase][Cout][tap][Cin], and the pixel stored is (2y+py, 2x+px) of the [B, 2H, 2W, Cout] output: 4 steps per slice, not 9.
+// (The body is a device function so that the nine-tap kernels keep the names profiles/ and the tools know them by.)
+template <int TW, int S, int NLOAD, int NT>
+__device__ __forceinline__ void conv3x3_body(const ConvParams& p) {
+    static_assert(NT == 9 || NT == 4, "nine taps, or the four of a phase of the 2x-upsampled form");
+    static_assert(NT % S == 0, "the ring depth must divide the taps of a slice (a tile's stage is its tap % S)");
     static_assert(NLOAD == 0 || NLOAD == 4, "loader waves mirror the four computing waves' DMA shares");
+    static_assert(NT == 9 || NLOAD == 0, "the phase form has no loader-wave variant");
     constexpr bool LOADER = NLOAD > 0;
-    constexpr int kAOff = a_off(S), kPadOff = pad_off(S);
+    constexpr bool UP = NT == 4;
+    constexpr int kAB = a_bytes(NT, TW);                      // one halo buffer
+    constexpr int kAOff = a_off(S), kPadOff = kAOff + 2 * kAB;
     constexpr int NSB = 16 / TW;                 // sub-blocks of 8 x TW pixels per tile
     constexpr int HWD = TW + 2;                  // halo row width (even)
     constexpr int HS = 10 * HWD;                 // halo slots per sub-block
@@ -141,7 +159,7 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
     constexpr int NPIECE = (NSLOT + 7) / 8;      // DMA pieces (8 slots x 128 B) per halo buffer
     constexpr int NPAR = TW == 16 ? 1 : 2;       // halo-row parities the swizzle distinguishes
     constexpr int MT1 = (32 / TW) * HWD * 128;   // byte distance of the wave's second 32-pixel fragment in the halo
-    static_assert(NPIECE <= kAPiecesMax && NPIECE <= 28, "halo does not fit");
+    static_assert(NPIECE * 1024 <= kAB && NPIECE <= 28, "halo does not fit");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -171,7 +189,14 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
     }
     const int n0 = bn * BN;
     const int cb = sp * p.cps, ce = min(p.nc, cb + p.cps);
-    const int ns = (ce - cb) * 9;
+    const int ns = (ce - cb) * NT;
+    int phase = 0;                                           // wave-uniform
+    if constexpr (UP) {
+        const int mts = p.mt >> 2;                           // source tiles
+        phase = (bm >= mts) + (bm >= 2 * mts) + (bm >= 3 * mts);
+        bm -= phase * mts;
+    }
+    const int PY = phase >> 1, PX = phase & 1;
 
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.x), 0, p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.w), 0, p.w_bytes, 0x00020000);
@@ -183,7 +208,7 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
     for (int pc = 0; pc < 2; ++pc) {
         const int row = (pc * 4 + wave) * 8 + (lane >> 3);
         const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-        wvoff[pc] = ((unsigned)(n0 + row) * 9u * (unsigned)p.Cin + chunk * 8) * 2u;
+        wvoff[pc] = ((unsigned)(phase * p.Cout + n0 + row) * (unsigned)NT * (unsigned)p.Cin + chunk * 8) * 2u;
     }
     auto issue_b = [&](unsigned soff, int stage) {
 #pragma unroll
@@ -195,7 +220,7 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
     const bool dma_wave = !LOADER || is_loader;              // this wave issues DMA
     if (dma_wave) {
 #pragma unroll
-        for (int k = 0; k < S; ++k) issue_b(tile_soff(cb, k), k);      // ns >= 9 >= S
+        for (int k = 0; k < S; ++k) issue_b(tile_soff(cb, k), k);      // ns >= NT >= S
     }
 
     // ---- sub-block origins (wave-uniform: at most two per tile, so the runtime divisions run once, not per lane)
@@ -229,21 +254,23 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
     }
     auto issue_a = [&](int i, int c, int ab) {
         const int piece = i * 4 + wave;
-        const unsigned dst = piece < NPIECE ? kAOff + ab * kABytes + piece * 1024 : kPadOff;
+        const unsigned dst = piece < NPIECE ? kAOff + ab * kAB + piece * 1024 : kPadOff;
         dma16(xr, aoff[i], (unsigned)c * (BK * 2), dst);
     };
     // ---- MFMA operand addresses (bytes).  Fragment 0 of this wave covers pixels wm*64 + r, fragment 1 the 32 pixels
     // after them: the same halo column, 2 (TW = 16) or 4 (TW = 8) halo rows below -> a constant byte distance.
     // xaddr[par][dx][ks]: top-left tap (dy = dx = -1) slot + dx, chunk (2 ks + hh) ^ swizzle; a tap adds dy * pitch.
-    unsigned xaddr[NPAR][3][4], waddr[4], waddr_hi[4];
+    // Phase form: the "top-left tap" is halo offset (PY, PX), dx runs over the two columns, par over the two rows.
+    constexpr int NDX = UP ? 2 : 3;
+    unsigned xaddr[NPAR][NDX][4], waddr[4], waddr_hi[4];
     {
         const int m = wm * 64 + r;
-        const int sb = m / (8 * TW), py = (m % (8 * TW)) / TW, pxl = m % TW;
+        const int sb = m / (8 * TW), py = (m % (8 * TW)) / TW + PY, pxl = m % TW + PX;
         const int slot00 = sb * HS + py * HWD + pxl;             // halo slot of tap (-1, -1)
 #pragma unroll
         for (int par = 0; par < NPAR; ++par)
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
+            for (int dx = 0; dx < NDX; ++dx) {
                 const int sw = halo_swz<TW>(py + par, pxl + dx);   // par = parity offset of the tap row (dy index & 1)
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) xaddr[par][dx][ks] = (unsigned)(kAOff + (slot00 + dx) * 128 + (((2 * ks + hh) ^ sw) << 4));
@@ -257,8 +284,8 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
     }
     // fragments of step (halo buffer ab, tap t, ring stage t % 3)
     auto load_frags = [&](Frags& f, int ab, int t) {
-        const int dy = t / 3, dx = t % 3;
-        const unsigned abase = ab * kABytes + dy * HWD * 128;          // kAOff is folded into xaddr (16-bit ds_read immediates)
+        const int dy = t / NDX, dx = t % NDX;
+        const unsigned abase = ab * kAB + dy * HWD * 128;          // kAOff is folded into xaddr (16-bit ds_read immediates)
         const int stg = t % S;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -284,19 +311,19 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
         if (is_loader) {
             // the loop's DMA with the plain kernel's cadence: per step a counted wait, the step's barrier, the step's issues
             for (int c = cb; c < ce; ++c) {
-                const int jb = (c - cb) * 9;
+                const int jb = (c - cb) * NT;
                 const int cn = c + 1 < ce ? c + 1 : c;
                 const int P = (c - cb) & 1;
 #pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    wait_step<S>(t);
+                for (int t = 0; t < NT; ++t) {
+                    wait_step<S, NT>(t);
                     __builtin_amdgcn_s_barrier();
                     if (t == 0) {
 #pragma unroll
                         for (int i = 0; i < 7; ++i) issue_a(i, cn, P ^ 1);
                     }
                     const bool more = jb + t + S < ns;
-                    const int c3 = t + S >= 9 ? c + 1 : c, t3 = (t + S) % 9;
+                    const int c3 = t + S >= NT ? c + 1 : c, t3 = (t + S) % NT;
                     issue_b(more ? tile_soff(c3, t3) : tile_soff(c, t), t % S);
                 }
             }
@@ -318,13 +345,14 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
     // The slice body is instantiated for both parities of the slice index: 9 steps flip which register set is "current".
     auto slice = [&](auto parity, int c) {
         constexpr int P = decltype(parity)::value;               // halo buffer of this slice; f[P] holds tap 0's fragments
-        const int jb = (c - cb) * 9;
+        constexpr int FP = (NT & 1) ? P : 0;                     // (four steps: every slice starts on register set 0)
+        const int jb = (c - cb) * NT;
         const int cn = c + 1 < ce ? c + 1 : c;
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            Frags& cur = f[(P + t) & 1];
-            Frags& nxt = f[(P + t + 1) & 1];
-            if (!LOADER) wait_step<S>(t);
+        for (int t = 0; t < NT; ++t) {
+            Frags& cur = f[(FP + t) & 1];
+            Frags& nxt = f[(FP + t + 1) & 1];
+            if (!LOADER) wait_step<S, NT>(t);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // step j's fragments are in registers
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);                       // keep step j+1's MFMAs out of step j (they would wait on their reads)
@@ -334,10 +362,10 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
                     for (int i = 0; i < 7; ++i) issue_a(i, cn, P ^ 1);
                 }
                 const bool more = jb + t + S < ns;
-                const int c3 = t + S >= 9 ? c + 1 : c, t3 = (t + S) % 9;
+                const int c3 = t + S >= NT ? c + 1 : c, t3 = (t + S) % NT;
                 issue_b(more ? tile_soff(c3, t3) : tile_soff(c, t), t % S);
             }
-            if (t < 8) load_frags(nxt, P, t + 1);
+            if (t < NT - 1) load_frags(nxt, P, t + 1);
             else load_frags(nxt, P ^ 1, 0);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
@@ -408,6 +436,7 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
         const int yy = (NSB == 1 ? oy[0] : (sb ? oy[NSB - 1] : oy[0])) + py, xx = (NSB == 1 ? ox[0] : (sb ? ox[NSB - 1] : ox[0])) + pxl;
         if (yy >= p.H || xx >= p.W) continue;                        // overhang of a ragged image side
         long long gp = ((long long)b * p.H + yy) * p.W + xx;
+        if constexpr (UP) gp = ((long long)b * (2 * p.H) + (2 * yy + PY)) * (2 * p.W) + (2 * xx + PX);   // this phase's pixel of the doubled image
         if (p.sub2) {                                                // stride 2 = the even (odd) pixels of the stride-1 result
             if (p.sub2 == 1 ? ((yy | xx) & 1) != 0 : (yy & xx & 1) == 0) continue;
             gp = ((long long)b * p.oh + (yy >> 1)) * p.ow + (xx >> 1);
@@ -461,6 +490,17 @@ __global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void con
         o[0] = st0; o[1] = st1; o[2] = st2; o[3] = __builtin_amdgcn_s_memrealtime();
         o[4] = sc1 - sc0; o[5] = sc2 - sc1; o[6] = __builtin_amdgcn_s_memtime() - sc2; o[7] = ((long long)xcc << 32) | hwid;
     }
+}
+
+template <int TW, int S, int NLOAD = 0>
+__global__ __launch_bounds__(T + 64 * NLOAD, (S == 3 || NLOAD ? 2 : 1)) void conv3x3_kernel(ConvParams p) {
+    conv3x3_body<TW, S, NLOAD, 9>(p);
+}
+
+// the phase form: four taps, four-stage ring; two workgroups per CU with 16-wide tiles (79 KiB), one with 8-wide ones (83 KiB)
+template <int TW>
+__global__ __launch_bounds__(T, (TW == 16 ? 2 : 1)) void conv3x3_kernel_up2x(ConvParams p) {
+    conv3x3_body<TW, 4, 0, 4>(p);
 }
 
 // out = sum over splits (in split order) + bias + residual, one fp16 rounding
@@ -518,22 +558,32 @@ int g_conv_order = -1;             // dsc_debug_set_conv_ring(300 / 301): pixel 
 // fewer partial sums through the L2 - work, which counts when two streams share the chip - and with the nine-stage ring and the
 // loader waves the one-workgroup-per-CU launches are no slower for the stream that owns them
 double g_conv_small_step = 0.14;
-int auto_splits(int tiles, int nc, long long npix, int cout) {
+// `taps`: steps per slice - 9, or 4 for the phase form of the 2x-upsampled convolution (a step is one weight tile, 8 MFMAs per
+// wave and one barrier in both).  `per_cu`: workgroups of the kernel a CU holds (2; 1 for the phase form's 8-wide kernel, whose
+// grids beyond 256 workgroups therefore run in rounds).  g_up2x_small_step: what the phase form's grids of <= 256 workgroups are
+// charged per step.  Its own time says 0.35 (1280->1280 from 8x8, 80 workgroups x 80 steps: 33.2 us unsplit, 22.9 + 4.9 in two
+// splits - no deep ring, no loader waves here), but like g_conv_small_step it is chosen on images/s (tools/ab_bench.sh, one
+// box, ten interleaved runs): 0.35 / 0.14 -> 11.65 +- 0.09 / 11.70 +- 0.05 two in flight, 8.263 / 8.256 one at a time.
+double g_up2x_small_step = 0.14;   // dsc_debug_set_conv_ring(500 + hundredths)
+int auto_splits(int tiles, int nc, long long npix, int cout, int taps, int per_cu) {
     int best = 1;
     double best_t = 1e30;
     for (int s = 1; s <= nc; ++s) {
         if (nc % s != 0) continue;
         const long long wgs = (long long)tiles * s;
         if (s > 1 && wgs > 1024) break;
-        const double load = wgs <= 256 ? g_conv_small_step / 0.26 : (wgs <= 512 ? 1.15 : 1.15 * (double)wgs / 512.0);
-        double t = 9.0 * nc / s * 0.26 * load + 5.0;
+        const double small = (taps == 4 ? g_up2x_small_step : g_conv_small_step) / 0.26;
+        const double load = wgs <= 256 ? small : (per_cu == 1 ? small * (double)((wgs + 255) / 256)
+                                                              : (wgs <= 512 ? 1.15 : 1.15 * (double)wgs / 512.0));
+        double t = (double)taps * nc / s * 0.26 * load + 5.0;
         if (s > 1) t += 4.0 + (double)s * (double)npix * cout * 8.0 / 3.0e6;
         if (t < best_t) { best_t = t; best = s; }
     }
     return best;
 }
 
-int plan(int B, int H, int W, int Cin, int Cout, int splits, ConvParams* p) {
+// taps = 4 (phase form): H x W is the SOURCE image, the tiles are its tiles x 4 phases, the output has 4 B H W pixels
+int plan(int B, int H, int W, int Cin, int Cout, int splits, ConvParams* p, int taps = 9) {
     const int tw = tile_width(H, W);
     if (!tw || Cin % BK != 0 || Cout <= 0) return 0;
     p->B = B; p->H = H; p->W = W; p->Cin = Cin; p->Cout = Cout;
@@ -542,8 +592,10 @@ int plan(int B, int H, int W, int Cin, int Cout, int splits, ConvParams* p) {
     const int nsb = 16 / tw;
     p->mt = (p->nblk + nsb - 1) / nsb; p->nt = (Cout + BN - 1) / BN;    // a ragged last tile reads zero weight rows (buffer bounds)
     p->npix = (long long)B * H * W;
+    p->onpix = p->npix;
+    if (taps == 4) { p->mt *= 4; p->onpix = 4 * p->npix; }
     if (Cout % BN != 0) splits = 1;                                      // the partial-sum layout assumes whole tiles
-    if (splits <= 0) splits = auto_splits(p->mt * p->nt, p->nc, p->npix, Cout);
+    if (splits <= 0) splits = auto_splits(p->mt * p->nt, p->nc, p->onpix, Cout, taps, taps == 4 && tw == 8 ? 1 : 2);
     if (splits > p->nc) splits = p->nc;
     p->cps = (p->nc + splits - 1) / splits;
     p->splits = (p->nc + p->cps - 1) / p->cps;
@@ -558,7 +610,8 @@ int plan(int B, int H, int W, int Cin, int Cout, int splits, ConvParams* p) {
 extern "C" void dsc_debug_set_conv_stamps(void* device_buffer) { g_conv_stamps = static_cast<long long*>(device_buffer); }
 
 extern "C" void dsc_debug_set_conv_ring(int stages) {
-    if (stages >= 400) g_conv_loaders = stages - 400;
+    if (stages >= 500) g_up2x_small_step = (stages - 500) / 100.0;
+    else if (stages >= 400) g_conv_loaders = stages - 400;
     else if (stages >= 300) g_conv_order = stages - 300;
     else if (stages >= 200) g_conv_small_step = (stages - 200) / 100.0;
     else g_conv_ring = stages;
@@ -705,3 +758,112 @@ int conv_impl(const void* x, const void* w, const void* bias, const void* residu
     return DSC_OK;
 }
 }  // namespace
+
+// ---- the phase form of Upsample2D's convolution (see conv3x3_body, NT = 4) ------------------------------------------------
+
+namespace {
+
+// packed[phase = 2 py + px][n][tap = 2 a + b][c] = sum_{dy in R(py, a)} sum_{dx in R(px, b)} w[n][dy][dx][c], R(0,0) = {0}, R(0,1) =
+// {1, 2}, R(1,0) = {0, 1}, R(1,1) = {2}: the 3x3 taps that read the same source pixel through the nearest-neighbour doubling.
+// Added in fp32 in this order - dy ascending (outer), dx ascending (inner) - and rounded once.
+__global__ __launch_bounds__(256) void conv3x3_up2x_pack_kernel(const half_t* __restrict__ w, half_t* __restrict__ packed, int Cin, int Cout) {
+    const int cv = Cin >> 3;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;          // one 8-channel vector of the packed tensor
+    if (idx >= 16ll * Cout * cv) return;
+    const int c = (int)(idx % cv) * 8;
+    const int tap = (int)(idx / cv) & 3;
+    const long long pn = idx / cv / 4;
+    const int n = (int)(pn % Cout), phase = (int)(pn / Cout);
+    const int py = phase >> 1, px = phase & 1, a = tap >> 1, b = tap & 1;
+    const int dy0 = py + a == 0 ? 0 : (py + a == 2 ? 2 : 1 - py), dy1 = py + a == 1 ? dy0 + 1 : dy0;   // R(py, a) = dy0 .. dy1
+    const int dx0 = px + b == 0 ? 0 : (px + b == 2 ? 2 : 1 - px), dx1 = px + b == 1 ? dx0 + 1 : dx0;
+    float s[8];
+    bool first = true;
+    for (int dy = dy0; dy <= dy1; ++dy)
+        for (int dx = dx0; dx <= dx1; ++dx) {
+            const h8_t v = *reinterpret_cast<const h8_t*>(w + ((long long)(n * 3 + dy) * 3 + dx) * Cin + c);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s[j] = first ? (float)v[j] : s[j] + (float)v[j];
+            first = false;
+        }
+    h8_t o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (half_t)s[j];
+    *reinterpret_cast<h8_t*>(packed + idx * 8) = o;
+}
+
+bool up2x_shape_ok(int B, int h, int w, int Cin, int Cout) {
+    if (B <= 0 || h <= 0 || w <= 0 || Cin <= 0 || Cout <= 0 || Cin % BK != 0 || Cout % BN != 0) return false;
+    // 32-bit byte offsets: the output has 4 B h w pixels, the packed weights 16 Cin Cout elements
+    return 4ll * B * h * w * (long long)(Cin > Cout ? Cin : Cout) < (1ll << 30) && 16ll * Cin * Cout < (1ll << 30);
+}
+
+}  // namespace
+
+extern "C" int dsc_conv3x3_up2x_pack_f16(const void* w, void* packed, int Cin, int Cout, void* stream) {
+    if (!w || !packed || Cin <= 0 || Cout <= 0) return DSC_ERR_BAD_ARG;
+    if (Cin % BK != 0 || 16ll * Cin * Cout >= (1ll << 30) || !al16(w) || !al16(packed)) return DSC_ERR_UNSUPPORTED;
+    const long long n = 16ll * Cout * (Cin / 8);
+    DSC_LAUNCH(conv3x3_up2x_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+               static_cast<const half_t*>(w), static_cast<half_t*>(packed), Cin, Cout);
+    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+}
+
+extern "C" int dsc_conv3x3_up2x_supported(int B, int h, int w, int Cin, int Cout) {
+    ConvParams p{};
+    return up2x_shape_ok(B, h, w, Cin, Cout) && plan(B, h, w, Cin, Cout, 0, &p, 4) ? 1 : 0;
+}
+
+extern "C" size_t dsc_conv3x3_up2x_workspace_bytes(int B, int h, int w, int Cin, int Cout, int splits) {
+    ConvParams p{};
+    if (!up2x_shape_ok(B, h, w, Cin, Cout) || !plan(B, h, w, Cin, Cout, splits, &p, 4)) return 0;
+    return p.splits > 1 ? (size_t)p.splits * p.onpix * Cout * sizeof(float) : 0;
+}
+
+extern "C" int dsc_conv3x3_up2x_nhwc_f16(const void* x, const void* w_packed, const void* bias, void* out, int B, int h, int w,
+                                         int Cin, int Cout, int splits, void* workspace, size_t workspace_bytes, int64_t ldx,
+                                         int64_t ldo, int dtype, void* stream) {
+    if (!x || !w_packed || !out || B <= 0 || h <= 0 || w <= 0 || Cin <= 0 || Cout <= 0) return DSC_ERR_BAD_ARG;
+    if (dtype != DSC_F16) return DSC_ERR_UNSUPPORTED;
+    if (ldx < Cin || ldo < Cout) return DSC_ERR_BAD_ARG;
+    if (ldx % 8 != 0 || ldo % 8 != 0) return DSC_ERR_UNSUPPORTED;
+    if (!al16(x) || !al16(w_packed) || !al16(out) || (bias && !al16(bias))) return DSC_ERR_UNSUPPORTED;
+    if (!up2x_shape_ok(B, h, w, Cin, Cout) || 4ll * B * h * w * (ldx > ldo ? ldx : ldo) >= (1ll << 30)) return DSC_ERR_UNSUPPORTED;
+    ConvParams p{};
+    const int tw = plan(B, h, w, Cin, Cout, splits, &p, 4);
+    if (!tw) return DSC_ERR_UNSUPPORTED;
+    p.x = static_cast<const half_t*>(x); p.w = static_cast<const half_t*>(w_packed);
+    p.bias = static_cast<const half_t*>(bias); p.out = static_cast<half_t*>(out); p.ws = static_cast<float*>(workspace);
+    p.ldx = ldx; p.ldo = ldo;
+    p.stamps = g_conv_stamps;
+    p.order = g_conv_order >= 0 ? g_conv_order : (p.onpix >= 2ll * Cout ? 1 : 0);     // the rule of the gather form it replaces
+    p.x_bytes = (unsigned)(((p.npix - 1) * ldx + Cin) * 2);
+    p.w_bytes = (unsigned)(16ll * Cin * Cout * 2);
+    if (p.splits > 1) {
+        const size_t need = (size_t)p.splits * p.onpix * Cout * sizeof(float);
+        if (!workspace || workspace_bytes < need || !al16(workspace)) return DSC_ERR_WORKSPACE;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel_up2x<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel_up2x<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    // One kernel per tile width under both tuning profiles and every dsc_debug_set_conv_ring setting: a four-stage ring, whose
+    // stage index is the tap.  A deeper ring (8) would have to issue the next slice's halo a slice earlier to keep its depth
+    // through the last tap's wait (the counted wait of tap 3 must cover the halo issued at tap 0: at most 6 DMAs may stay in
+    // flight there, whatever the ring holds), and the loader waves exist for that deep ring only: neither is built for this entry.
+    const int total = p.mt * p.nt * p.splits;
+    const dim3 grid(((total + 7) / 8) * 8), block(T);
+    if (tw == 16) DSC_LAUNCH((conv3x3_kernel_up2x<16>), grid, block, (size_t)lds_bytes_up2x(16), st, p);
+    else DSC_LAUNCH((conv3x3_kernel_up2x<8>), grid, block, (size_t)lds_bytes_up2x(8), st, p);
+    if (hipGetLastError() != hipSuccess) return DSC_ERR_LAUNCH;
+    if (p.splits > 1) {
+        const long long n = p.onpix * (Cout / 8);
+        p.fd_cv = make_fastdiv(Cout / 8, n + 256);
+        DSC_LAUNCH(conv3x3_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
+        if (hipGetLastError() != hipSuccess) return DSC_ERR_LAUNCH;
+    }
+    return DSC_OK;
+}

@@ -623,12 +623,21 @@ class Upsample2D(nn.Module):
 
     def forward(self, x, output_size=None):
         """output_size: the (H, W) of the skip tensor the result meets (reference :1281-1300 `upsample_size`) when the latent
-        sides are not multiples of the UNet's overall factor - 2s or 2s-1 of the source sides; None: double"""
+        sides are not multiples of the UNet's overall factor - 2s or 2s-1 of the source sides; None: double.
+        The exact doubling (None, or (2h, 2w)) runs as four 2x2 phase convolutions of the source with pre-summed weights
+        (ops.conv3x3_up2x: 4 taps instead of 9; the weights are packed once per weight and re-packed after an in-place write).  An
+        odd skip-sized side 2s-1 cannot: its last row / column has a tap on the zero padding whose twin lies inside the image, so
+        the summed weight is wrong there - those targets keep the gather form."""
+        if output_size is not None:
+            output_size = tuple(int(v) for v in output_size)
+        if output_size is None or output_size == (2 * x.shape[2], 2 * x.shape[3]):
+            w = self.conv.weight
+            if ops.USE_UP2X_PHASES and ops.conv3x3_up2x_supported(x, w):
+                return ops.conv3x3_up2x(x, _derived(self, "up2x", (w,), lambda: ops.conv3x3_up2x_pack(w)), self.conv.bias)
         if output_size is None:
             if ops.conv3x3_supported(x, self.conv.weight, upsample=True):      # the upsampling happens in the halo gather
                 return ops.conv3x3(x, self.conv.weight, self.conv.bias, upsample=True)
             return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))
-        output_size = tuple(int(v) for v in output_size)
         if all(t in (2 * s_, 2 * s_ - 1) for t, s_ in zip(output_size, x.shape[2:])) \
                 and ops.conv3x3_supported(x, self.conv.weight, upsample_size=output_size):
             return ops.conv3x3(x, self.conv.weight, self.conv.bias, upsample_size=output_size)   # same gather, skip-sized extent

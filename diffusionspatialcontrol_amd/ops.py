@@ -880,6 +880,70 @@ def conv3x3(x, weight, bias=None, residual=None, splits=0, upsample=False, out_n
     return out
 
 
+# Upsample2D (exact 2x): four 2x2 phase convolutions of the source with pre-summed weights (dsc_conv3x3_up2x_nhwc_f16) instead of
+# the 3x3 taps over the gathered image.  "0": the gather form, conv3x3(upsample=True) - an A/B switch like DSC_LN_FOLD
+USE_UP2X_PHASES = os.environ.get("DSC_UP2X_PHASES", "1") != "0"
+
+
+def conv3x3_up2x_pack(weight):
+    """[Cout, Cin, 3, 3] fp16 conv weight -> the [4, Cout, 4, Cin] fp16 phase weights of conv3x3_up2x (dsc_conv3x3_up2x_pack_f16):
+    packed[2*py+px, n, 2*a+b, c] = sum of weight[n, c, dy, dx] over dy in R(py, a), dx in R(px, b), R(0,0) = {0}, R(0,1) = {1, 2},
+    R(1,0) = {0, 1}, R(1,1) = {2}; added in fp32 (dy ascending, then dx ascending) and rounded once.  Depends on the weight only."""
+    _require_gpu(weight)
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.dtype != torch.float16:
+        raise ValueError("conv3x3_up2x_pack: weight must be a [Cout, Cin, 3, 3] fp16 tensor")
+    Cout, Cin = weight.shape[:2]
+    if Cin % 64 != 0:
+        raise ValueError("conv3x3_up2x_pack: Cin must be a multiple of 64")
+    cl = torch.channels_last
+    if not weight.is_contiguous(memory_format=cl):
+        weight = weight.contiguous(memory_format=cl)
+    packed = torch.empty((4, Cout, 4, Cin), dtype=torch.float16, device=weight.device)
+    rc = _lib.load_library().dsc_conv3x3_up2x_pack_f16(_p(weight), _p(packed), Cin, Cout, _stream_ptr(weight))
+    _lib.check(rc, "dsc_conv3x3_up2x_pack_f16")
+    return packed
+
+
+def conv3x3_up2x_supported(x, weight):
+    """True when dsc_conv3x3_up2x_nhwc_f16 covers the exact 2x upsampling + 3x3 convolution of this [B, Cin, h, w] channels_last
+    fp16 input with this [Cout, Cin, 3, 3] weight (Cin and Cout multiples of 64)"""
+    if not (USE_DSC_CONV and x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16 and x.dim() == 4
+            and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] == x.shape[1]):
+        return False
+    B, C, h, w = x.shape
+    return bool(_lib.load_library().dsc_conv3x3_up2x_supported(B, h, w, C, weight.shape[0]))
+
+
+def conv3x3_up2x(x, packed, bias=None, splits=0):
+    """`F.conv2d(F.interpolate(x, scale_factor=2.0, mode="nearest"), weight, bias, padding=1)` of a channels_last fp16
+    [B, Cin, h, w] tensor as four 2x2 phase convolutions of x itself with packed = conv3x3_up2x_pack(weight); returns channels_last
+    [B, Cout, 2h, 2w].  Only the exact 2x target: for the skip-sized 2s-1 targets the last row / column has a tap on the zero padding
+    whose twin is inside the image, which the summed weights cannot express - those keep conv3x3(upsample_size=...).  The result
+    differs from conv3x3(upsample=True) by the one fp16 rounding of the summed weights.  Raises on an unsupported shape."""
+    if x.dim() != 4 or x.dtype != torch.float16:
+        raise ValueError("conv3x3_up2x: x must be a [B, Cin, h, w] fp16 tensor")
+    B, Cin, h, w = x.shape
+    if (packed.dim() != 4 or packed.shape[0] != 4 or packed.shape[2] != 4 or packed.shape[3] != Cin
+            or packed.dtype != torch.float16 or not packed.is_contiguous()):
+        raise ValueError(f"conv3x3_up2x: packed must be the contiguous fp16 [4, Cout, 4, {Cin}] tensor of conv3x3_up2x_pack, "
+                         f"not {tuple(packed.shape)}")
+    Cout = packed.shape[1]
+    if bias is not None and (bias.dtype != torch.float16 or bias.numel() != Cout or not bias.is_contiguous()):
+        raise ValueError("conv3x3_up2x: bias must be a contiguous fp16 [Cout] tensor")
+    _require_gpu(x, packed)
+    lib = _lib.load_library()
+    cl = torch.channels_last
+    if not x.is_contiguous(memory_format=cl):
+        x = x.contiguous(memory_format=cl)
+    out = torch.empty((B, Cout, 2 * h, 2 * w), dtype=x.dtype, device=x.device, memory_format=cl)
+    nbytes = lib.dsc_conv3x3_up2x_workspace_bytes(B, h, w, Cin, Cout, splits)
+    ws = _workspace(x.device, nbytes) if nbytes else None
+    rc = lib.dsc_conv3x3_up2x_nhwc_f16(_p(x), _p(packed), _p(bias), _p(out), B, h, w, Cin, Cout, splits, _p(ws),
+                                       ws.numel() * 8 if ws is not None else 0, Cin, Cout, 0, _stream_ptr(x))
+    _lib.check(rc, "dsc_conv3x3_up2x_nhwc_f16")
+    return out
+
+
 def conv3x3_fewcin(x, weight_t, bias, cout):
     """3x3 / pad 1 convolution of a plain (NCHW) fp16 [B, Cin <= 16, H, W] tensor -> channels_last [B, cout, H, W]
     (dsc_conv3x3_fewcin_f16); weight_t is weight.reshape(cout, Cin * 9).t().contiguous()."""

@@ -402,13 +402,39 @@ int dsc_conv3x3_supported(int B, int H, int W, int Cin, int Cout);
 void dsc_debug_set_conv_stamps(void* device_buffer);
 /* diagnostics: 3 / 9 = force the weight-tile ring depth, 0 = by grid size and tuning profile; 200 + n = the split-count
  * model's per-step time for grids of <= 256 workgroups (n / 100 us); 300 / 301 = pixel tiles / channel blocks fastest
- * within an XCD (default: by shape); 400 / 401 / 402 = the nine-stage kernels without DMA-only loader waves / by rule / always */
+ * within an XCD (default: by shape); 400 / 401 / 402 = the nine-stage kernels without DMA-only loader waves / by rule / always;
+ * 500 + n = the same per-step time for dsc_conv3x3_up2x_nhwc_f16's grids of <= 256 workgroups (n / 100 us) */
 void dsc_debug_set_conv_ring(int stages);
 size_t dsc_conv3x3_workspace_bytes(int B, int H, int W, int Cin, int Cout, int splits);
 int dsc_conv3x3_nhwc_f16(const void* x, const void* w, const void* bias, const void* residual, void* out,
                          int B, int H, int W, int Cin, int Cout, int64_t ldx, int64_t ldr, int64_t ldo,
                          int resample, int out_nchw, int splits, int dtype, void* workspace, size_t workspace_bytes,
                          void* stream);
+
+/*
+ * The same Upsample2D pair - `F.interpolate(x, scale_factor=2.0, mode="nearest")` followed by the 3x3 / pad-1 `conv`
+ * (diffusers Upsample2D.forward, reached from reference u_net_condition_modify.py:1281-1300 with no `upsample_size`) - as FOUR
+ * 2x2 convolutions of the SOURCE image, one per output phase: a nearest-neighbour doubling hands the same source pixel to up to
+ * three taps per axis, so
+ *   out[b, 2i+py, 2j+px, n] = sum_{a,b in {0,1}} sum_c K[2py+px][n][2a+b][c] * x[b, i+py+a-1, j+px+b-1, c]  (+ bias[n]),  x = 0 outside
+ *   K[2py+px][n][2a+b][c]   = sum_{dy in R(py,a)} sum_{dx in R(px,b)} w[n][dy][dx][c],   R(0,0)={0} R(0,1)={1,2} R(1,0)={0,1} R(1,1)={2}
+ * - 4 taps per 64-channel slice instead of 9.  For the exact 2x target the zero padding of the doubled image and of the source
+ * coincide; the skip-sized targets 2s-1 of DSC_CONV_UPSAMPLE_CEIL do NOT (their last row / column has a tap on padding whose twin
+ * is inside) and stay with dsc_conv3x3_nhwc_f16.
+ * dsc_conv3x3_up2x_pack_f16: w [Cout,3,3,Cin] -> packed [4,Cout,4,Cin] fp16; the 1, 2 or 4 weights are added in fp32, dy ascending
+ * then dx ascending, and rounded ONCE - so results differ from dsc_conv3x3_nhwc_f16(DSC_CONV_UPSAMPLE2X) by that rounding of the
+ * weights.  Depends on the weight only: pack once per weight, not per call.  Cin % 64 == 0.
+ * dsc_conv3x3_up2x_nhwc_f16: x [B,h,w,Cin] with pixel stride ldx, out [B,2h,2w,Cout] with pixel stride ldo; Cin % 64 == 0,
+ * Cout % 64 == 0, strides % 8 == 0, 16-byte aligned pointers, any h, w >= 1 (dsc_conv3x3_up2x_supported).  splits / workspace
+ * as for dsc_conv3x3_nhwc_f16 (dsc_conv3x3_up2x_workspace_bytes; the partial sums are indexed by output pixel).  The tuning
+ * profile and dsc_debug_set_conv_ring's ring / loader settings select nothing here: one kernel per tile width, equal bytes.
+ */
+int dsc_conv3x3_up2x_pack_f16(const void* w, void* packed, int Cin, int Cout, void* stream);
+int dsc_conv3x3_up2x_supported(int B, int h, int w, int Cin, int Cout);
+size_t dsc_conv3x3_up2x_workspace_bytes(int B, int h, int w, int Cin, int Cout, int splits);
+int dsc_conv3x3_up2x_nhwc_f16(const void* x, const void* w_packed, const void* bias, void* out, int B, int h, int w,
+                              int Cin, int Cout, int splits, void* workspace, size_t workspace_bytes, int64_t ldx,
+                              int64_t ldo, int dtype, void* stream);
 
 /*
  * dsc_linear_f16 with a LayerNorm folded in on either side - removes the `nn.LayerNorm` launches of diffusers'
