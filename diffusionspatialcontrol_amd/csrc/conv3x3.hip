@@ -1,7 +1,7 @@
-// 3x3 / stride 1 / pad 1 convolution over channels-last fp16 activations (dsc_conv3x3_nhwc_f16) - the ResnetBlock2D
-// conv1/conv2 and the Upsample2D conv of the UNet that reference `source/modules/u_net_condition_modify.py` builds from
-// diffusers blocks (49 of the 52 3x3 convolutions of an SD1.5 step; the three stride-2
-// Downsample2D convolutions and the 4-channel conv_in / conv_out stay on MIOpen).
+// 3x3 / pad 1 convolution over channels-last fp16 activations (dsc_conv3x3_nhwc_f16) - every 3x3 convolution of the UNet that
+// reference `source/modules/u_net_condition_modify.py` builds from diffusers blocks (52 in an SD1.5 step)
+// but the 4-input-channel conv_in (conv_in.hip): the ResnetBlock2D conv1 / conv2, the Upsample2D conv, the three stride-2
+// Downsample2D convolutions (the even pixels of the stride-1 taps) and the 4-output-channel conv_out.  None stays on MIOpen.
 //
 // Why not MIOpen's NHWC implicit GEMM: at batch 1 (+CFG) the 49 convolutions are 33 % of the UNet step and every one of
 // them runs at 270-300 TFLOP/s (profiles/README.md).  A CU ingests only ~24-30 B/cycle from L2
@@ -582,27 +582,145 @@ int auto_splits(int tiles, int nc, long long npix, int cout, int taps, int per_c
     return best;
 }
 
+// the fp32 split-K partial sums of `pixels` pixels: bytes of workspace (0 without a split)
+size_t split_ws_bytes(const ConvParams& p, long long pixels) {
+    return p.splits > 1 ? (size_t)p.splits * pixels * p.Cout * sizeof(float) : 0;
+}
+
+// The whole geometry of a launch from the shape, the resample code (dsc_hip.h) and the pixel strides; returns the tile width, 0 for
+// a shape or code the kernels do not cover.
 // taps = 4 (phase form): H x W is the SOURCE image, the tiles are its tiles x 4 phases, the output has 4 B H W pixels
-int plan(int B, int H, int W, int Cin, int Cout, int splits, ConvParams* p, int taps = 9) {
+int plan(int B, int H, int W, int Cin, int Cout, int splits, int resample, long long ldx, long long ldr, long long ldo, int taps,
+         ConvParams* p) {
     const int tw = tile_width(H, W);
-    if (!tw || Cin % BK != 0 || Cout <= 0) return 0;
+    if (!tw || Cin % BK != 0 || Cout <= 0 || resample < 0 || resample > DSC_CONV_UPSAMPLE_CEIL) return 0;
     p->B = B; p->H = H; p->W = W; p->Cin = Cin; p->Cout = Cout;
+    p->ldx = ldx; p->ldr = ldr; p->ldo = ldo;
+    const bool ceil = resample == DSC_CONV_UPSAMPLE_CEIL;
+    p->up = resample == DSC_CONV_UPSAMPLE2X || ceil ? 1 : 0;
+    p->sh = ceil ? (H + 1) / 2 : H / 2; p->sw = ceil ? (W + 1) / 2 : W / 2;
+    p->sub2 = resample == DSC_CONV_STRIDE2 ? 1 : (resample == DSC_CONV_STRIDE2_PAD_BR ? 2 : 0);
+    p->oh = (H + 1) / 2; p->ow = (W + 1) / 2;          // pad 1 keeps pixel 0, 2, ..: ceil; the VAE's code has even sides
     p->nc = Cin / BK;
     p->bpr = (W + tw - 1) / tw; p->bpi = ((H + 7) / 8) * p->bpr; p->nblk = B * p->bpi;
     const int nsb = 16 / tw;
     p->mt = (p->nblk + nsb - 1) / nsb; p->nt = (Cout + BN - 1) / BN;    // a ragged last tile reads zero weight rows (buffer bounds)
+    if (taps == 4) p->mt *= 4;
     p->npix = (long long)B * H * W;
-    p->onpix = p->npix;
-    if (taps == 4) { p->mt *= 4; p->onpix = 4 * p->npix; }
+    const long long computed = taps == 4 ? 4 * p->npix : p->npix;        // what the cost model and the order rule count ...
+    p->onpix = p->sub2 ? (long long)B * p->oh * p->ow : computed;        // ... and what is stored
     if (Cout % BN != 0) splits = 1;                                      // the partial-sum layout assumes whole tiles
-    if (splits <= 0) splits = auto_splits(p->mt * p->nt, p->nc, p->onpix, Cout, taps, taps == 4 && tw == 8 ? 1 : 2);
+    if (splits <= 0) splits = auto_splits(p->mt * p->nt, p->nc, computed, Cout, taps, taps == 4 && tw == 8 ? 1 : 2);
     if (splits > p->nc) splits = p->nc;
     p->cps = (p->nc + splits - 1) / splits;
     p->splits = (p->nc + p->cps - 1) / p->cps;
     const long long total = (long long)p->mt * p->nt * p->splits;
     p->fd_mt = make_fastdiv(p->mt, total); p->fd_nt = make_fastdiv(p->nt, total);
     p->fd_bpi = make_fastdiv(p->bpi, (long long)p->mt * nsb + nsb); p->fd_bpr = make_fastdiv(p->bpr, p->bpi);
+    // activation-heavy shapes (the 64x64 level): a pixel tile's halo is fetched into one L2 for all of its channel blocks
+    // (640->320 @64x64 66.8 -> 61.5 us in the step); weight-heavy ones keep sharing the weight slab
+    p->order = g_conv_order >= 0 ? g_conv_order : (computed >= 2ll * Cout ? 1 : 0);
+    const long long in_pix = p->up ? (long long)B * p->sh * p->sw : p->npix;
+    p->x_bytes = (unsigned)(((in_pix - 1) * ldx + Cin) * 2);
+    p->w_bytes = (unsigned)((taps == 4 ? 16ll : 9ll) * Cin * Cout * 2);
     return tw;
+}
+
+// what both entries ask of their operands (H x W: the image the tiles cover - the source of the phase form, whose output has four
+// times the pixels and whose packed weights 16 Cin Cout elements): DSC_OK, or the code to return
+int check_operands(const void* x, const void* w, const void* bias, const void* residual, const void* out, int B, int H, int W, int Cin,
+                   int Cout, long long ldx, long long ldr, long long ldo, int out_nchw, int dtype, int taps) {
+    if (!x || !w || !out || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return DSC_ERR_BAD_ARG;
+    if (dtype != DSC_F16) return DSC_ERR_UNSUPPORTED;
+    if (ldx < Cin || (!out_nchw && ldo < Cout) || (residual && ldr < Cout)) return DSC_ERR_BAD_ARG;
+    if (ldx % 8 != 0 || (Cout % 8 == 0 && !out_nchw && ldo % 8 != 0) || (residual && Cout % 8 == 0 && ldr % 8 != 0)) return DSC_ERR_UNSUPPORTED;
+    if (!al16(x) || !al16(w) || !al16(out) || (bias && !al16(bias)) || (residual && !al16(residual))) return DSC_ERR_UNSUPPORTED;
+    // 32-bit byte offsets in the buffer-addressed DMAs (and kOob must lie beyond every extent)
+    if ((taps == 4 ? 4ll : 1ll) * B * H * W * (ldx > ldo ? ldx : ldo) >= (1ll << 30) ||
+        (taps == 4 ? 16ll : 9ll) * Cin * Cout >= (1ll << 30)) return DSC_ERR_UNSUPPORTED;
+    return DSC_OK;
+}
+
+// the pointers of a planned launch; DSC_ERR_WORKSPACE when its split needs more workspace than the caller brought
+int bind(ConvParams* p, const void* x, const void* w, const void* bias, const void* residual, void* out, void* workspace,
+         size_t workspace_bytes) {
+    p->x = static_cast<const half_t*>(x); p->w = static_cast<const half_t*>(w);
+    p->bias = static_cast<const half_t*>(bias); p->res = static_cast<const half_t*>(residual);
+    p->out = static_cast<half_t*>(out); p->ws = static_cast<float*>(workspace);
+    p->stamps = g_conv_stamps;
+    if (p->splits > 1 && (!workspace || workspace_bytes < split_ws_bytes(*p, p->onpix) || !al16(workspace))) return DSC_ERR_WORKSPACE;
+    return DSC_OK;
+}
+
+struct KernelForm { void (*fn)(ConvParams); int lds, block; };
+const KernelForm g_forms[] = {   // [2 * form + (8-wide tiles)]; forms: three-stage ring, nine-stage ring, nine stages + loader waves, phase form
+    {conv3x3_kernel<16, 3>, lds_bytes(3), T}, {conv3x3_kernel<8, 3>, lds_bytes(3), T},
+    {conv3x3_kernel<16, 9>, lds_bytes(9), T}, {conv3x3_kernel<8, 9>, lds_bytes(9), T},
+    {conv3x3_kernel<16, 9, 4>, lds_bytes(9), T + 256}, {conv3x3_kernel<8, 9, 4>, lds_bytes(9), T + 256},
+    {conv3x3_kernel_up2x<16>, lds_bytes_up2x(16), T}, {conv3x3_kernel_up2x<8>, lds_bytes_up2x(8), T}};
+
+// the convolution of a planned and bound ConvParams, and the reduce launch of its split
+int launch(const ConvParams& p, int tw, int taps, hipStream_t st) {
+    const int total = p.mt * p.nt * p.splits;
+    int form = 3;
+    // The phase form has one kernel per tile width under both tuning profiles and every dsc_debug_set_conv_ring setting: a four-stage
+    // ring, whose stage index is the tap.  A deeper ring (8) would have to issue the next slice's halo a slice earlier to keep its depth
+    // through the last tap's wait (the counted wait of tap 3 must cover the halo issued at tap 0: at most 6 DMAs may stay in
+    // flight there, whatever the ring holds), and the loader waves exist for that deep ring only: neither is built for it.
+    if (taps != 4) {
+        // Ring depth.  The 9-stage ring needs the whole LDS (one workgroup per CU), so every grid of more than 256 workgroups loses
+        // its second co-resident workgroup to it (320->320 @64x64 23.6 vs 31.4 us back to back, 29.7 vs 38.9 in the step).  A grid
+        // that has at most one workgroup per CU anyway gains: in the step its weight tiles come from HBM, and two tiles in flight
+        // (three stages) at ~550 cycles per step are less than that latency - 160 workgroups 32.9 -> 24.3 us, 200 (8-wide tiles)
+        // 15.4 -> 14.2, 64 22.6 -> 20.2 (tools/ab_step.sh, DSC_CONV_RING=3 / 9; the warm micro-benchmark shows no difference).
+        int ring = g_conv_ring;
+        // ... and only while this stream owns the chip: with a second generation in flight the whole-LDS workgroups keep the other
+        // stream's kernels off their CUs (dsc_set_tuning_profile)
+        if (ring != 3 && ring != 9) ring = (total <= 256 && g_dsc_tuning_profile == DSC_TUNE_LATENCY) ? 9 : 3;
+        // the nine-stage ring has the CU to itself anyway.  In the step: 16-wide tiles 29.2 -> 25.0 us (160 workgroups), 21.2 ->
+        // 19.5 (64); the 8-wide kernel (8x8 level, two halo parities, 12 spilled registers at the 256 cap) 15.0 -> 16.0: not used
+        const bool loaders = ring == 9 && (g_conv_loaders == 2 || (g_conv_loaders == 1 && tw == 16));
+        form = loaders ? 2 : (ring == 9 ? 1 : 0);
+    }
+    static bool attr_set = false;      // all eight at the first launch of the process, so that none falls into a later stream capture
+    if (!attr_set) {
+        for (const KernelForm& f : g_forms) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    const KernelForm& k = g_forms[2 * form + (tw == 16 ? 0 : 1)];
+    DSC_LAUNCH(k.fn, dim3(((total + 7) / 8) * 8), dim3(k.block), (size_t)k.lds, st, p);
+    if (hipGetLastError() != hipSuccess) return DSC_ERR_LAUNCH;
+    if (p.splits > 1) {
+        ConvParams r = p;
+        const long long n = p.onpix * (p.Cout / 8);
+        r.fd_cv = make_fastdiv(p.Cout / 8, n + 256);
+        DSC_LAUNCH(conv3x3_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r);
+        if (hipGetLastError() != hipSuccess) return DSC_ERR_LAUNCH;
+    }
+    return DSC_OK;
+}
+
+struct GnArgs { const void* add; int64_t add_ld; float* part; int groups; };
+
+int conv_impl(const void* x, const void* w, const void* bias, const void* residual, void* out,
+              int B, int H, int W, int Cin, int Cout, int64_t ldx, int64_t ldr, int64_t ldo,
+              int resample, int out_nchw, int splits, int dtype, void* workspace, size_t workspace_bytes, void* stream,
+              const GnArgs* gn) {
+    int rc = check_operands(x, w, bias, residual, out, B, H, W, Cin, Cout, ldx, ldr, ldo, out_nchw, dtype, 9);
+    if (rc != DSC_OK) return rc;
+    const bool stride2 = resample == DSC_CONV_STRIDE2 || resample == DSC_CONV_STRIDE2_PAD_BR;
+    if ((stride2 && out_nchw) || (resample == DSC_CONV_STRIDE2_PAD_BR && ((H | W) & 1))) return DSC_ERR_UNSUPPORTED;
+    if (out_nchw) splits = 1;     // conv3x3_reduce stores pixel-major: only the convolution's own epilogue writes [B, Cout, H, W]
+    ConvParams p{};
+    const int tw = plan(B, H, W, Cin, Cout, splits, resample, ldx, ldr, ldo, 9, &p);
+    if (!tw) return DSC_ERR_UNSUPPORTED;
+    p.nchw = out_nchw ? 1 : 0;
+    if (gn) {
+        p.add = static_cast<const half_t*>(gn->add); p.add_ld = gn->add_ld;
+        p.gn_part = gn->part; p.gn_G = gn->groups; p.gn_cpg = Cout / gn->groups;
+    }
+    rc = bind(&p, x, w, bias, residual, out, workspace, workspace_bytes);
+    return rc != DSC_OK ? rc : launch(p, tw, 9, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -621,21 +739,14 @@ extern "C" int dsc_conv3x3_supported(int B, int H, int W, int Cin, int Cout) {
     ConvParams p{};
     if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W * (long long)(Cin > Cout ? Cin : Cout) >= (1ll << 30) ||
         9ll * Cin * Cout >= (1ll << 30)) return 0;
-    return plan(B, H, W, Cin, Cout, 0, &p) ? 1 : 0;
+    return plan(B, H, W, Cin, Cout, 0, 0, Cin, 0, Cout, 9, &p) ? 1 : 0;
 }
 
+// (no resample argument: sized by the stride-1 pixels, which covers the fewer pixels a stride-2 launch stores)
 extern "C" size_t dsc_conv3x3_workspace_bytes(int B, int H, int W, int Cin, int Cout, int splits) {
     ConvParams p{};
-    if (B <= 0 || H <= 0 || W <= 0 || !plan(B, H, W, Cin, Cout, splits, &p)) return 0;
-    return p.splits > 1 ? (size_t)p.splits * p.npix * Cout * sizeof(float) : 0;
-}
-
-namespace {
-struct GnArgs { const void* add; int64_t add_ld; float* part; int groups; };
-int conv_impl(const void* x, const void* w, const void* bias, const void* residual, void* out,
-              int B, int H, int W, int Cin, int Cout, int64_t ldx, int64_t ldr, int64_t ldo,
-              int resample, int out_nchw, int splits, int dtype, void* workspace, size_t workspace_bytes, void* stream,
-              const GnArgs* gn);
+    if (B <= 0 || H <= 0 || W <= 0 || !plan(B, H, W, Cin, Cout, splits, 0, Cin, 0, Cout, 9, &p)) return 0;
+    return split_ws_bytes(p, p.npix);
 }
 
 extern "C" int dsc_conv3x3_nhwc_f16(const void* x, const void* w, const void* bias, const void* residual, void* out,
@@ -651,12 +762,10 @@ extern "C" int dsc_conv3x3_nhwc_f16(const void* x, const void* w, const void* bi
 // groups of at most 64 channels, at most 128 partial rows per image
 extern "C" int dsc_conv3x3_gn_rows(int B, int H, int W, int Cin, int Cout, int groups, int resample) {
     ConvParams p{};
-    const int Hc = H, Wc = W;
     // 2 <= channels per group <= 64: gn_tile_partials writes at most 32 group slots per 64-channel tile (gn_partials.h)
     if (B <= 0 || H <= 0 || W <= 0 || groups <= 0 || Cout % BN != 0 || Cout % groups != 0 || Cout / groups > 64 || Cout / groups < 2) return 0;
     if (resample == DSC_CONV_STRIDE2 || resample == DSC_CONV_STRIDE2_PAD_BR) return 0;   // (the kept pixels are a quarter of a tile's)
-    if (resample < 0 || resample > DSC_CONV_UPSAMPLE_CEIL) return 0;
-    if (plan(B, Hc, Wc, Cin, Cout, 0, &p) != 16 || p.splits != 1 || p.bpi > 128) return 0;
+    if (plan(B, H, W, Cin, Cout, 0, resample, Cin, 0, Cout, 9, &p) != 16 || p.splits != 1 || p.bpi > 128) return 0;
     return p.bpi;
 }
 
@@ -670,94 +779,6 @@ extern "C" int dsc_conv3x3_gn_nhwc_f16(const void* x, const void* w, const void*
     const GnArgs gn{add, add_ld, gn_part, groups};
     return conv_impl(x, w, bias, residual, out, B, H, W, Cin, Cout, ldx, ldr, ldo, resample, 0, 1, dtype, nullptr, 0, stream, &gn);
 }
-
-namespace {
-int conv_impl(const void* x, const void* w, const void* bias, const void* residual, void* out,
-              int B, int H, int W, int Cin, int Cout, int64_t ldx, int64_t ldr, int64_t ldo,
-              int resample, int out_nchw, int splits, int dtype, void* workspace, size_t workspace_bytes, void* stream,
-              const GnArgs* gn) {
-    if (!x || !w || !out || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16) return DSC_ERR_UNSUPPORTED;
-    if (ldx < Cin || (!out_nchw && ldo < Cout) || (residual && ldr < Cout)) return DSC_ERR_BAD_ARG;
-    if (ldx % 8 != 0 || (Cout % 8 == 0 && !out_nchw && ldo % 8 != 0) || (residual && Cout % 8 == 0 && ldr % 8 != 0)) return DSC_ERR_UNSUPPORTED;
-    if (!al16(x) || !al16(w) || !al16(out) || (bias && !al16(bias)) || (residual && !al16(residual))) return DSC_ERR_UNSUPPORTED;
-    // 32-bit byte offsets in the buffer-addressed DMAs (and kOob must lie beyond every extent)
-    if ((long long)B * H * W * (ldx > ldo ? ldx : ldo) >= (1ll << 30) || 9ll * Cin * Cout >= (1ll << 30)) return DSC_ERR_UNSUPPORTED;
-    ConvParams p{};
-    const int tw = plan(B, H, W, Cin, Cout, splits, &p);
-    if (!tw) return DSC_ERR_UNSUPPORTED;
-    p.x = static_cast<const half_t*>(x); p.w = static_cast<const half_t*>(w);
-    p.bias = static_cast<const half_t*>(bias); p.res = static_cast<const half_t*>(residual);
-    p.out = static_cast<half_t*>(out); p.ws = static_cast<float*>(workspace);
-    p.ldx = ldx; p.ldr = ldr; p.ldo = ldo;
-    p.stamps = g_conv_stamps;
-    if (gn) {
-        p.add = static_cast<const half_t*>(gn->add); p.add_ld = gn->add_ld;
-        p.gn_part = gn->part; p.gn_G = gn->groups; p.gn_cpg = Cout / gn->groups;
-    }
-    // activation-heavy shapes (the 64x64 level): a pixel tile's halo is fetched into one L2 for all of its channel blocks
-    // (640->320 @64x64 66.8 -> 61.5 us in the step); weight-heavy ones keep sharing the weight slab
-    p.order = g_conv_order >= 0 ? g_conv_order : (p.npix >= 2ll * Cout ? 1 : 0);
-    if (resample < 0 || resample > 4 || ((resample == DSC_CONV_STRIDE2 || resample == DSC_CONV_STRIDE2_PAD_BR) && out_nchw)) return DSC_ERR_UNSUPPORTED;
-    if (resample == DSC_CONV_STRIDE2_PAD_BR && ((H | W) & 1)) return DSC_ERR_UNSUPPORTED;
-    p.up = resample == DSC_CONV_UPSAMPLE2X || resample == DSC_CONV_UPSAMPLE_CEIL ? 1 : 0;
-    p.sh = resample == DSC_CONV_UPSAMPLE_CEIL ? (H + 1) / 2 : H / 2; p.sw = resample == DSC_CONV_UPSAMPLE_CEIL ? (W + 1) / 2 : W / 2;
-    p.sub2 = resample == DSC_CONV_STRIDE2 ? 1 : (resample == DSC_CONV_STRIDE2_PAD_BR ? 2 : 0);
-    p.oh = (H + 1) / 2; p.ow = (W + 1) / 2;          // pad 1 keeps pixel 0, 2, ..: ceil; the VAE's code has even sides
-    p.onpix = p.sub2 ? (long long)B * p.oh * p.ow : p.npix;
-    p.nchw = out_nchw ? 1 : 0;
-    {
-        const long long in_pix = p.up ? (long long)B * p.sh * p.sw : (long long)B * H * W;
-        p.x_bytes = (unsigned)(((in_pix - 1) * ldx + Cin) * 2);
-        p.w_bytes = (unsigned)(9ll * Cin * Cout * 2);
-    }
-    if (p.splits > 1) {
-        const size_t need = (size_t)p.splits * p.onpix * Cout * sizeof(float);
-        if (!workspace || workspace_bytes < need || !al16(workspace)) return DSC_ERR_WORKSPACE;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* fns[] = {reinterpret_cast<const void*>(&conv3x3_kernel<16, 3>), reinterpret_cast<const void*>(&conv3x3_kernel<8, 3>),
-                             reinterpret_cast<const void*>(&conv3x3_kernel<16, 9>), reinterpret_cast<const void*>(&conv3x3_kernel<8, 9>),
-                             reinterpret_cast<const void*>(&conv3x3_kernel<16, 9, 4>), reinterpret_cast<const void*>(&conv3x3_kernel<8, 9, 4>)};
-        for (const void* f : fns) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    const int total = p.mt * p.nt * p.splits;
-    const dim3 grid(((total + 7) / 8) * 8), block(T);
-    // Ring depth.  The 9-stage ring needs the whole LDS (one workgroup per CU), so every grid of more than 256 workgroups loses
-    // its second co-resident workgroup to it (320->320 @64x64 23.6 vs 31.4 us back to back, 29.7 vs 38.9 in the step).  A grid
-    // that has at most one workgroup per CU anyway gains: in the step its weight tiles come from HBM, and two tiles in flight
-    // (three stages) at ~550 cycles per step are less than that latency - 160 workgroups 32.9 -> 24.3 us, 200 (8-wide tiles)
-    // 15.4 -> 14.2, 64 22.6 -> 20.2 (tools/ab_step.sh, DSC_CONV_RING=3 / 9; the warm micro-benchmark shows no difference).
-    int ring = g_conv_ring;
-    // ... and only while this stream owns the chip: with a second generation in flight the whole-LDS workgroups keep the other
-    // stream's kernels off their CUs (dsc_set_tuning_profile)
-    if (ring != 3 && ring != 9) ring = (total <= 256 && g_dsc_tuning_profile == DSC_TUNE_LATENCY) ? 9 : 3;
-    // the nine-stage ring has the CU to itself anyway.  In the step: 16-wide tiles 29.2 -> 25.0 us (160 workgroups), 21.2 ->
-    // 19.5 (64); the 8-wide kernel (8x8 level, two halo parities, 12 spilled registers at the 256 cap) 15.0 -> 16.0: not used
-    const bool loaders = ring == 9 && (g_conv_loaders == 2 || (g_conv_loaders == 1 && tw == 16));
-    const dim3 block8(T + 256);
-    if (tw == 16) {
-        if (loaders) DSC_LAUNCH((conv3x3_kernel<16, 9, 4>), grid, block8, (size_t)lds_bytes(9), st, p);
-        else if (ring == 9) DSC_LAUNCH((conv3x3_kernel<16, 9>), grid, block, (size_t)lds_bytes(9), st, p);
-        else DSC_LAUNCH((conv3x3_kernel<16, 3>), grid, block, (size_t)lds_bytes(3), st, p);
-    } else {
-        if (loaders) DSC_LAUNCH((conv3x3_kernel<8, 9, 4>), grid, block8, (size_t)lds_bytes(9), st, p);
-        else if (ring == 9) DSC_LAUNCH((conv3x3_kernel<8, 9>), grid, block, (size_t)lds_bytes(9), st, p);
-        else DSC_LAUNCH((conv3x3_kernel<8, 3>), grid, block, (size_t)lds_bytes(3), st, p);
-    }
-    if (hipGetLastError() != hipSuccess) return DSC_ERR_LAUNCH;
-    if (p.splits > 1) {
-        const long long n = p.onpix * (Cout / 8);
-        p.fd_cv = make_fastdiv(Cout / 8, n + 256);
-        DSC_LAUNCH(conv3x3_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
-        if (hipGetLastError() != hipSuccess) return DSC_ERR_LAUNCH;
-    }
-    return DSC_OK;
-}
-}  // namespace
 
 // ---- the phase form of Upsample2D's convolution (see conv3x3_body, NT = 4) ------------------------------------------------
 
@@ -792,10 +813,12 @@ __global__ __launch_bounds__(256) void conv3x3_up2x_pack_kernel(const half_t* __
     *reinterpret_cast<h8_t*>(packed + idx * 8) = o;
 }
 
-bool up2x_shape_ok(int B, int h, int w, int Cin, int Cout) {
-    if (B <= 0 || h <= 0 || w <= 0 || Cin <= 0 || Cout <= 0 || Cin % BK != 0 || Cout % BN != 0) return false;
+// the phase form's shape rule; its plan (splits: 0 = by the cost model); tile width, 0 = not covered
+int plan_up2x(int B, int h, int w, int Cin, int Cout, int splits, long long ldx, long long ldo, ConvParams* p) {
+    if (B <= 0 || h <= 0 || w <= 0 || Cin <= 0 || Cout <= 0 || Cin % BK != 0 || Cout % BN != 0) return 0;
     // 32-bit byte offsets: the output has 4 B h w pixels, the packed weights 16 Cin Cout elements
-    return 4ll * B * h * w * (long long)(Cin > Cout ? Cin : Cout) < (1ll << 30) && 16ll * Cin * Cout < (1ll << 30);
+    if (4ll * B * h * w * (long long)(Cin > Cout ? Cin : Cout) >= (1ll << 30) || 16ll * Cin * Cout >= (1ll << 30)) return 0;
+    return plan(B, h, w, Cin, Cout, splits, 0, ldx, 0, ldo, 4, p);
 }
 
 }  // namespace
@@ -811,59 +834,22 @@ extern "C" int dsc_conv3x3_up2x_pack_f16(const void* w, void* packed, int Cin, i
 
 extern "C" int dsc_conv3x3_up2x_supported(int B, int h, int w, int Cin, int Cout) {
     ConvParams p{};
-    return up2x_shape_ok(B, h, w, Cin, Cout) && plan(B, h, w, Cin, Cout, 0, &p, 4) ? 1 : 0;
+    return plan_up2x(B, h, w, Cin, Cout, 0, Cin, Cout, &p) ? 1 : 0;
 }
 
 extern "C" size_t dsc_conv3x3_up2x_workspace_bytes(int B, int h, int w, int Cin, int Cout, int splits) {
     ConvParams p{};
-    if (!up2x_shape_ok(B, h, w, Cin, Cout) || !plan(B, h, w, Cin, Cout, splits, &p, 4)) return 0;
-    return p.splits > 1 ? (size_t)p.splits * p.onpix * Cout * sizeof(float) : 0;
+    return plan_up2x(B, h, w, Cin, Cout, splits, Cin, Cout, &p) ? split_ws_bytes(p, p.onpix) : 0;
 }
 
 extern "C" int dsc_conv3x3_up2x_nhwc_f16(const void* x, const void* w_packed, const void* bias, void* out, int B, int h, int w,
                                          int Cin, int Cout, int splits, void* workspace, size_t workspace_bytes, int64_t ldx,
                                          int64_t ldo, int dtype, void* stream) {
-    if (!x || !w_packed || !out || B <= 0 || h <= 0 || w <= 0 || Cin <= 0 || Cout <= 0) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16) return DSC_ERR_UNSUPPORTED;
-    if (ldx < Cin || ldo < Cout) return DSC_ERR_BAD_ARG;
-    if (ldx % 8 != 0 || ldo % 8 != 0) return DSC_ERR_UNSUPPORTED;
-    if (!al16(x) || !al16(w_packed) || !al16(out) || (bias && !al16(bias))) return DSC_ERR_UNSUPPORTED;
-    if (!up2x_shape_ok(B, h, w, Cin, Cout) || 4ll * B * h * w * (ldx > ldo ? ldx : ldo) >= (1ll << 30)) return DSC_ERR_UNSUPPORTED;
+    int rc = check_operands(x, w_packed, bias, nullptr, out, B, h, w, Cin, Cout, ldx, 0, ldo, 0, dtype, 4);
+    if (rc != DSC_OK) return rc;
     ConvParams p{};
-    const int tw = plan(B, h, w, Cin, Cout, splits, &p, 4);
+    const int tw = plan_up2x(B, h, w, Cin, Cout, splits, ldx, ldo, &p);
     if (!tw) return DSC_ERR_UNSUPPORTED;
-    p.x = static_cast<const half_t*>(x); p.w = static_cast<const half_t*>(w_packed);
-    p.bias = static_cast<const half_t*>(bias); p.out = static_cast<half_t*>(out); p.ws = static_cast<float*>(workspace);
-    p.ldx = ldx; p.ldo = ldo;
-    p.stamps = g_conv_stamps;
-    p.order = g_conv_order >= 0 ? g_conv_order : (p.onpix >= 2ll * Cout ? 1 : 0);     // the rule of the gather form it replaces
-    p.x_bytes = (unsigned)(((p.npix - 1) * ldx + Cin) * 2);
-    p.w_bytes = (unsigned)(16ll * Cin * Cout * 2);
-    if (p.splits > 1) {
-        const size_t need = (size_t)p.splits * p.onpix * Cout * sizeof(float);
-        if (!workspace || workspace_bytes < need || !al16(workspace)) return DSC_ERR_WORKSPACE;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel_up2x<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel_up2x<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    // One kernel per tile width under both tuning profiles and every dsc_debug_set_conv_ring setting: a four-stage ring, whose
-    // stage index is the tap.  A deeper ring (8) would have to issue the next slice's halo a slice earlier to keep its depth
-    // through the last tap's wait (the counted wait of tap 3 must cover the halo issued at tap 0: at most 6 DMAs may stay in
-    // flight there, whatever the ring holds), and the loader waves exist for that deep ring only: neither is built for this entry.
-    const int total = p.mt * p.nt * p.splits;
-    const dim3 grid(((total + 7) / 8) * 8), block(T);
-    if (tw == 16) DSC_LAUNCH((conv3x3_kernel_up2x<16>), grid, block, (size_t)lds_bytes_up2x(16), st, p);
-    else DSC_LAUNCH((conv3x3_kernel_up2x<8>), grid, block, (size_t)lds_bytes_up2x(8), st, p);
-    if (hipGetLastError() != hipSuccess) return DSC_ERR_LAUNCH;
-    if (p.splits > 1) {
-        const long long n = p.onpix * (Cout / 8);
-        p.fd_cv = make_fastdiv(Cout / 8, n + 256);
-        DSC_LAUNCH(conv3x3_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
-        if (hipGetLastError() != hipSuccess) return DSC_ERR_LAUNCH;
-    }
-    return DSC_OK;
+    rc = bind(&p, x, w_packed, bias, nullptr, out, workspace, workspace_bytes);
+    return rc != DSC_OK ? rc : launch(p, tw, 4, static_cast<hipStream_t>(stream));
 }

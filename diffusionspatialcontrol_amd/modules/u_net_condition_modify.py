@@ -12,9 +12,10 @@ What is kept from the reference surface:
   * `UNet2DConditionLoadersMixin_modify`, the symbol the reference imports but never defines (:23)
 
 Device work: activations are kept channels-last (NHWC) end to end - the same bytes as the transformer's token-major
-[B, h*w, C] view - so MIOpen's NHWC implicit-GEMM convolutions and the hipBLASLt projection GEMMs (plain library
-GEMMs, reached through torch) need no layout transposes; GroupNorm+SiLU(+time-embedding add), GEGLU,
-self-attention and region cross-attention run in libdsc_hip.so (see ..ops).
+[B, h*w, C] view - so the convolutions and the projection GEMMs need no layout transposes.  The 3x3 convolutions
+(stride 1 and 2, upsampled, conv_in / conv_out), the GEMMs, GroupNorm+SiLU(+time-embedding add), GEGLU, self-attention
+and region cross-attention run in libdsc_hip.so (see ..ops); the library convolution (MIOpen, through torch) is what
+is left for tensors the kernels do not cover: CPU, fp32, channel counts that are no multiples of 64.
 """
 import inspect
 import math
@@ -552,8 +553,9 @@ def _conv3x3(x, weight, bias=None, residual=None):
     """3x3 / pad 1 convolution (+ bias) (+ residual): dsc_conv3x3_nhwc_f16 where it covers the shape (channels-last fp16,
     input channel counts that are multiples of 64), otherwise the library convolution (MIOpen) with
     the separate fused add."""
-    if ops.conv3x3_supported(x, weight):
-        return ops.conv3x3(x, weight, bias, residual)
+    y = ops.conv3x3_try(x, weight, bias, residual)
+    if y is not None:
+        return y
     h = F.conv2d(x, weight, None, padding=1)
     if residual is not None:
         return ops.add_bias_residual(residual, h, bias)
@@ -610,10 +612,9 @@ class Downsample2D(nn.Module):
         self.conv = nn.Conv2d(c, c, 3, stride=2, padding=1)
 
     def forward(self, x):
-        if ops.conv3x3_supported(x, self.conv.weight):
-            # even pixels of the stride-1 taps; an odd side n keeps its last pixel: ceil(n / 2), as the stride-2 / pad-1 convolution does
-            return ops.conv3x3(x, self.conv.weight, self.conv.bias, stride2_ceil=True)
-        return self.conv(x)
+        # even pixels of the stride-1 taps; an odd side n keeps its last pixel: ceil(n / 2), as the stride-2 / pad-1 convolution does
+        y = ops.conv3x3_try(x, self.conv.weight, self.conv.bias, mode=ops.CONV_STRIDE2)
+        return self.conv(x) if y is None else y
 
 
 class Upsample2D(nn.Module):
@@ -630,18 +631,16 @@ class Upsample2D(nn.Module):
         the summed weight is wrong there - those targets keep the gather form."""
         if output_size is not None:
             output_size = tuple(int(v) for v in output_size)
-        if output_size is None or output_size == (2 * x.shape[2], 2 * x.shape[3]):
-            w = self.conv.weight
-            if ops.USE_UP2X_PHASES and ops.conv3x3_up2x_supported(x, w):
-                return ops.conv3x3_up2x(x, _derived(self, "up2x", (w,), lambda: ops.conv3x3_up2x_pack(w)), self.conv.bias)
+        w = self.conv.weight
+        if output_size in (None, (2 * x.shape[2], 2 * x.shape[3])) and ops.USE_UP2X_PHASES and ops.conv3x3_up2x_supported(x, w):
+            return ops.conv3x3_up2x(x, _derived(self, "up2x", (w,), lambda: ops.conv3x3_up2x_pack(w)), self.conv.bias)
         if output_size is None:
-            if ops.conv3x3_supported(x, self.conv.weight, upsample=True):      # the upsampling happens in the halo gather
-                return ops.conv3x3(x, self.conv.weight, self.conv.bias, upsample=True)
-            return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))
-        if all(t in (2 * s_, 2 * s_ - 1) for t, s_ in zip(output_size, x.shape[2:])) \
-                and ops.conv3x3_supported(x, self.conv.weight, upsample_size=output_size):
-            return ops.conv3x3(x, self.conv.weight, self.conv.bias, upsample_size=output_size)   # same gather, skip-sized extent
-        return self.conv(F.interpolate(x, size=output_size, mode="nearest"))
+            y = ops.conv3x3_try(x, w, self.conv.bias, mode=ops.CONV_UPSAMPLE2X)   # the upsampling happens in the halo gather
+            return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest")) if y is None else y
+        y = None
+        if all(t in (2 * s_, 2 * s_ - 1) for t, s_ in zip(output_size, x.shape[2:])):
+            y = ops.conv3x3_try(x, w, self.conv.bias, mode=ops.CONV_UPSAMPLE_SIZE, size=output_size)   # same gather, skip-sized extent
+        return self.conv(F.interpolate(x, size=output_size, mode="nearest")) if y is None else y
 
 
 class _Block(nn.Module):
@@ -953,8 +952,7 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
         h = self.conv_norm_out(x)                                            # reference :1304-1307
         co = self.conv_out
         wcl = _derived(self, "conv_out_cl", (co.weight,), lambda: co.weight.contiguous(memory_format=torch.channels_last))
-        if ops.conv3x3_supported(h, wcl):
-            x = ops.conv3x3(h, wcl, co.bias, out_nchw=True)                   # the sampler's layout, no conversion pass
-        else:
+        x = ops.conv3x3_try(h, wcl, co.bias, out_nchw=True)                   # the sampler's layout, no conversion pass
+        if x is None:
             x = co(h.contiguous()).contiguous()
         return UNet2DConditionOutput(sample=x) if return_dict else (x,)

@@ -41,8 +41,9 @@ class VaeConfig:
 def _conv(conv, x, residual=None, upsample=False):
     """3x3 / pad 1 convolution of a decoder block: dsc_conv3x3_nhwc_f16 (bias / residual / nearest-2x upsample fused) where
     it covers the shape, else the library convolution"""
-    if ops.conv3x3_supported(x, conv.weight, upsample=upsample):
-        return ops.conv3x3(x, conv.weight, conv.bias, residual=residual, upsample=upsample)
+    y = ops.conv3x3_try(x, conv.weight, conv.bias, residual, mode=ops.CONV_UPSAMPLE2X if upsample else ops.CONV_PLAIN)
+    if y is not None:
+        return y
     if upsample:
         x = F.interpolate(x, scale_factor=2.0, mode="nearest")
     h = conv(x)
@@ -186,9 +187,8 @@ class AutoencoderKLDecoder(nn.Module):
                 x = _conv(blk.upsamplers[0]["conv"], x, upsample=True)
         hn = d.conv_norm_out(x)
         wcl = d.conv_out.weight.contiguous(memory_format=torch.channels_last)
-        if ops.conv3x3_supported(hn, wcl):
-            x = ops.conv3x3(hn, wcl, d.conv_out.bias, out_nchw=True)          # 128 -> 3 channels, channel-major image
-        else:
+        x = ops.conv3x3_try(hn, wcl, d.conv_out.bias, out_nchw=True)          # 128 -> 3 channels, channel-major image
+        if x is None:
             x = d.conv_out(hn.contiguous()).contiguous()
         return type("DecoderOutput", (), {"sample": x})() if return_dict else (x,)
 
@@ -273,18 +273,15 @@ class AutoencoderKL(AutoencoderKLDecoder):
             if hasattr(blk, "downsamplers"):
                 conv = blk.downsamplers[0]["conv"]
                 wcl = _derived_w(conv, "cl", lambda w: w.contiguous(memory_format=cl))
-                if h.shape[-1] % 2 == 0 and h.shape[-2] % 2 == 0 and ops.conv3x3_supported(h, wcl):
-                    h = ops.conv3x3(h, wcl, conv.bias, stride2_pad_br=True)                # odd pixels of the stride-1 taps
-                else:
-                    h = F.conv2d(F.pad(h, (0, 1, 0, 1)), conv.weight, conv.bias, stride=2).contiguous(memory_format=cl)
+                y = ops.conv3x3_try(h, wcl, conv.bias, mode=ops.CONV_STRIDE2_PAD_BR)      # odd pixels of the stride-1 taps; even sides
+                h = F.conv2d(F.pad(h, (0, 1, 0, 1)), conv.weight, conv.bias, stride=2).contiguous(memory_format=cl) if y is None else y
         h = e.mid_block.resnets[0](h)
         h = e.mid_block.attentions[0](h)
         h = e.mid_block.resnets[1](h)
         hn = e.conv_norm_out(h)
         wcl = _derived_w(e.conv_out, "cl", lambda w: w.contiguous(memory_format=cl))
-        if ops.conv3x3_supported(hn, wcl):
-            m = ops.conv3x3(hn, wcl, e.conv_out.bias, out_nchw=True)                        # 512 -> 8 channels, channel-major
-        else:
+        m = ops.conv3x3_try(hn, wcl, e.conv_out.bias, out_nchw=True)                        # 512 -> 8 channels, channel-major
+        if m is None:
             m = e.conv_out(hn).contiguous()
         m = F.conv2d(m, self.quant_conv.weight, self.quant_conv.bias)                       # 8 x 8 1x1 on the moments
         dist = DiagonalGaussianDistribution(m)

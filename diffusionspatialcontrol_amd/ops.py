@@ -428,45 +428,25 @@ def groupnorm_apply_nhwc(x, part, groups, weight, bias, eps, act):
 def conv3x3_gn_rows(x, weight, groups, upsample=False, upsample_size=None):
     """pixel tiles per image when dsc_conv3x3_gn_nhwc_f16 covers this convolution (and GroupNorm grouping of its output), else 0;
     upsample_size as in conv3x3"""
-    size = _upsample_target(x, upsample, upsample_size)
-    if not (USE_GN_FUSE and conv3x3_supported(x, weight, upsample=upsample, upsample_size=upsample_size)):
+    geom = _conv3x3_geometry(x, upsample, upsample_size)
+    if not (USE_GN_FUSE and _conv3x3_covered(x, weight, geom)):
         return 0
-    B, C, H, W = x.shape
-    if size is not None:
-        return int(_lib.load_library().dsc_conv3x3_gn_rows(B, size[0], size[1], C, weight.shape[0], groups, 4))
-    f = 2 if upsample else 1
-    return int(_lib.load_library().dsc_conv3x3_gn_rows(B, H * f, W * f, C, weight.shape[0], groups, 1 if upsample else 0))
+    mode, (H, W), _ = geom
+    return int(_lib.load_library().dsc_conv3x3_gn_rows(x.shape[0], H, W, x.shape[1], weight.shape[0], groups, mode))
 
 
 def conv3x3_gn(x, weight, groups, bias=None, add=None, residual=None, upsample=False, upsample_size=None):
     """conv3x3 (+ bias) (+ per-image bias row add [B, Cout]) (+ residual), channels_last; the returned tensor carries the
     GroupNorm partial sums of what was stored (gn_partials_of) - call only when conv3x3_gn_rows() > 0"""
-    size = _upsample_target(x, upsample, upsample_size)
+    mode, (H, W), _ = _conv3x3_geometry(x, upsample, upsample_size)
     _require_gpu(x, weight)
     lib = _lib.load_library()
-    cl = torch.channels_last
-    if not x.is_contiguous(memory_format=cl):
-        x = x.contiguous(memory_format=cl)
-    if not weight.is_contiguous(memory_format=cl):
-        weight = weight.contiguous(memory_format=cl)
-    B, Cin, H, W = x.shape
-    if upsample:
-        H, W = 2 * H, 2 * W
-    if size is not None:
-        H, W = size
-    resample = 4 if size is not None else (1 if upsample else 0)
-    Cout = weight.shape[0]
-    rows = int(lib.dsc_conv3x3_gn_rows(B, H, W, Cin, Cout, groups, resample))
+    B, Cin, Cout = x.shape[0], x.shape[1], weight.shape[0]
+    rows = int(lib.dsc_conv3x3_gn_rows(B, H, W, Cin, Cout, groups, mode))
     if rows <= 0:
         raise ValueError("conv3x3_gn: shape not covered (ask conv3x3_gn_rows first)")
-    out = torch.empty((B, Cout, H, W), dtype=x.dtype, device=x.device, memory_format=cl)
-    ldr = 0
-    if residual is not None:
-        if residual.shape != out.shape:
-            raise ValueError("conv3x3_gn: residual must have the output's shape")
-        if not residual.is_contiguous(memory_format=cl):
-            residual = residual.contiguous(memory_format=cl)
-        ldr = Cout
+    x, weight, residual, ldr = _conv3x3_operands("conv3x3_gn", x, weight, residual, (B, Cout, H, W))
+    out = torch.empty((B, Cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     add_ld = 0
     if add is not None:
         if add.stride(-1) != 1 or add.stride(0) % 8 != 0 or add.data_ptr() % 16 != 0:
@@ -474,7 +454,7 @@ def conv3x3_gn(x, weight, groups, bias=None, add=None, residual=None, upsample=F
         add_ld = add.stride(0)
     part = torch.empty((B, rows, groups, 2, 2), dtype=torch.float32, device=x.device)
     rc = lib.dsc_conv3x3_gn_nhwc_f16(_p(x), _p(weight), _p(bias), _p(add), add_ld, _p(residual), _p(out), B, H, W, Cin, Cout, Cin,
-                                     ldr, Cout, resample, _p(part), groups, 0, _stream_ptr(x))
+                                     ldr, Cout, mode, _p(part), groups, 0, _stream_ptr(x))
     _lib.check(rc, "dsc_conv3x3_gn_nhwc_f16")
     return attach_gn_partials(out, GnPartials(part, rows, groups, Cout, B, H * W))
 
@@ -796,42 +776,77 @@ def linear(x, weight, bias=None, residual=None, geglu=False, prefer_kernel=False
 USE_DSC_CONV = True        # route qualifying 3x3 convolutions to dsc_conv3x3_nhwc_f16 (False: always MIOpen through torch)
 
 
-def _upsample_target(x, upsample, upsample_size, stride2=False, stride2_pad_br=False):
-    """the (H, W) a convolution with upsample_size runs at, or None without one; ValueError for a size the gather cannot serve"""
-    if upsample_size is None:
-        return None
-    if upsample or stride2 or stride2_pad_br:
-        raise ValueError("conv3x3: upsample_size, upsample, stride2 and stride2_pad_br exclude each other")
-    if x.dim() != 4 or len(upsample_size) != 2:
-        raise ValueError("conv3x3: upsample_size is the (H, W) of the upsampled [B, C, H, W] image")
-    size = (int(upsample_size[0]), int(upsample_size[1]))
-    for t, s in zip(size, x.shape[2:]):
-        # the only targets whose nearest-neighbour source index is dst >> 1 (and the only ones a UNet skip tensor demands)
-        if t not in (2 * s, 2 * s - 1) or t < 1:
-            raise ValueError(f"conv3x3: upsample_size {size} is not 2s or 2s-1 of the source sides {tuple(x.shape[2:])}")
-    return size
+# the `resample` codes of dsc_conv3x3_nhwc_f16 / dsc_conv3x3_gn_* (DSC_CONV_* of include/dsc_hip.h, which has no name for 0)
+CONV_PLAIN = 0
+CONV_UPSAMPLE2X = 1           # the convolution of the 2x nearest-neighbour upsampling of x
+CONV_STRIDE2 = 2              # stride 2 / pad 1: ceil(n / 2) pixels per side
+CONV_STRIDE2_PAD_BR = 3       # stride 2 / zero padding on the bottom and right only; even sides
+CONV_UPSAMPLE_SIZE = 4        # DSC_CONV_UPSAMPLE_CEIL: of x upsampled to a given size, each side 2s or 2s-1
+
+
+_CONV_MODE_KEYWORD = {CONV_PLAIN: None, CONV_UPSAMPLE2X: "upsample", CONV_STRIDE2: "stride2_ceil", CONV_STRIDE2_PAD_BR: "stride2_pad_br",
+                      CONV_UPSAMPLE_SIZE: "upsample_size"}      # conv3x3's keyword of each code
+
+
+def _conv3x3_geometry(x, upsample=False, upsample_size=None, stride2=False, stride2_ceil=False, stride2_pad_br=False):
+    """(mode, (H, W), (oh, ow)) of a conv3x3 call: the CONV_* code, the image the nine taps run over and the image that is stored.
+    Every ValueError of the conv3x3 family for its mode keywords is raised here, from the arguments alone."""
+    if sum(map(bool, (upsample, upsample_size is not None, stride2 or stride2_ceil, stride2_pad_br))) > 1:
+        raise ValueError("conv3x3: upsample, upsample_size, stride2 / stride2_ceil and stride2_pad_br exclude each other")
+    # (a tensor that is no [B, C, H, W] image: conv3x3_supported says False, conv3x3 fails on its shape)
+    H, W = (int(x.shape[2]), int(x.shape[3])) if x.dim() == 4 else (0, 0)
+    if upsample_size is not None:
+        if x.dim() != 4 or len(upsample_size) != 2:
+            raise ValueError("conv3x3: upsample_size is the (H, W) of the upsampled [B, C, H, W] image")
+        size = (int(upsample_size[0]), int(upsample_size[1]))
+        for t, s in zip(size, (H, W)):
+            # the only targets whose nearest-neighbour source index is dst >> 1 (and the only ones a UNet skip tensor demands)
+            if t not in (2 * s, 2 * s - 1) or t < 1:
+                raise ValueError(f"conv3x3: upsample_size {size} is not 2s or 2s-1 of the source sides {(H, W)}")
+        return CONV_UPSAMPLE_SIZE, size, size
+    if stride2 and (H % 2 or W % 2):
+        raise ValueError("conv3x3: stride2=True keeps its even-sides rule; stride2_ceil=True takes any side")
+    if upsample:
+        return CONV_UPSAMPLE2X, (2 * H, 2 * W), (2 * H, 2 * W)
+    if stride2 or stride2_ceil:
+        return CONV_STRIDE2, (H, W), ((H + 1) // 2, (W + 1) // 2)
+    if stride2_pad_br:
+        return CONV_STRIDE2_PAD_BR, (H, W), (H // 2, W // 2)
+    return CONV_PLAIN, (H, W), (H, W)
+
+
+def _conv3x3_covered(x, weight, geom):
+    """True when dsc_conv3x3_nhwc_f16 covers the convolution of this geometry: routing switch, device, dtypes, shapes, the kernel's plan"""
+    if not (USE_DSC_CONV and x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16 and x.dim() == 4
+            and tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] == x.shape[1]):
+        return False
+    _, (H, W), _ = geom
+    return bool(_lib.load_library().dsc_conv3x3_supported(x.shape[0], H, W, x.shape[1], weight.shape[0]))
+
+
+def _conv3x3_operands(what, x, weight, residual, out_shape):
+    """x, weight and residual in channels_last memory (weight / residual may be None) and the residual's pixel stride; ValueError
+    for a residual that has not the output's shape"""
+    if residual is not None and tuple(residual.shape) != tuple(out_shape):
+        raise ValueError(f"{what}: residual must have the output's shape")
+    cl = torch.channels_last
+    x, weight, residual = (t if t is None or t.is_contiguous(memory_format=cl) else t.contiguous(memory_format=cl)
+                           for t in (x, weight, residual))
+    return x, weight, residual, 0 if residual is None else out_shape[1]
 
 
 def conv3x3_supported(x, weight, upsample=False, upsample_size=None):
     """True when dsc_conv3x3_nhwc_f16 covers this [B, Cin, H, W] channels_last fp16 input / [Cout, Cin, 3, 3] weight
     (upsample: the convolution runs on the 2x nearest-upsampled image; upsample_size=(H', W'): on the image upsampled to that
     size, each side 2s or 2s-1 of the source side - ValueError otherwise)."""
-    size = _upsample_target(x, upsample, upsample_size)
-    if not (USE_DSC_CONV and x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16 and x.dim() == 4
-            and tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] == x.shape[1]):
-        return False
-    B, C, H, W = x.shape
-    f = 2 if upsample else 1
-    if size is not None:
-        return bool(_lib.load_library().dsc_conv3x3_supported(B, size[0], size[1], C, weight.shape[0]))
-    return bool(_lib.load_library().dsc_conv3x3_supported(B, H * f, W * f, C, weight.shape[0]))
+    return _conv3x3_covered(x, weight, _conv3x3_geometry(x, upsample, upsample_size))
 
 
 def conv3x3(x, weight, bias=None, residual=None, splits=0, upsample=False, out_nchw=False, stride2=False, stride2_pad_br=False,
             upsample_size=None, stride2_ceil=False):
     """3x3 / stride 1 / pad 1 convolution (+ bias) (+ residual) of a channels_last fp16 [B, Cin, H, W] tensor with a
     [Cout, Cin, 3, 3] weight held in channels_last memory format (dsc_conv3x3_nhwc_f16); returns channels_last
-    [B, Cout, H, W], or a plain contiguous (NCHW) tensor with out_nchw=True.  upsample=True convolves the 2x
+    [B, Cout, H, W], or a plain contiguous (NCHW) tensor with out_nchw=True (never split).  upsample=True convolves the 2x
     nearest-neighbour upsampling of x (output [B, Cout, 2H, 2W]) without materialising it; upsample_size=(H', W') convolves
     `F.interpolate(x, size=(H', W'), mode="nearest")`, each side 2s or 2s-1 of the source side (the UNet's upsampling to the
     size of a skip tensor; ValueError for any other size); stride2_ceil=True is the stride-2 / pad-1 convolution (output
@@ -839,45 +854,44 @@ def conv3x3(x, weight, bias=None, residual=None, splits=0, upsample=False, out_n
     rule (ValueError for an odd side: tests/test_unet_pipeline_gpu.py::test_conv3x3_unsupported pins that refusal, so the rule
     stays under this name until that assertion goes); stride2_pad_br=True the stride-2 convolution with zero padding on the bottom / right only
     (`F.pad(x, (0, 1, 0, 1))` + stride-2 / pad-0 conv: AutoencoderKL encoder; H and W even).  Raises on an unsupported shape - ask
-    conv3x3_supported() first."""
-    size = _upsample_target(x, upsample, upsample_size, stride2 or stride2_ceil, stride2_pad_br)
-    if stride2 and (x.shape[-1] % 2 or x.shape[-2] % 2):
-        raise ValueError("conv3x3: stride2=True keeps its even-sides rule; stride2_ceil=True takes any side")
-    stride2 = bool(stride2) or bool(stride2_ceil)
+    conv3x3_supported() first, or call conv3x3_try()."""
+    mode, (H, W), (oh, ow) = _conv3x3_geometry(x, upsample, upsample_size, stride2, stride2_ceil, stride2_pad_br)
     _require_gpu(x, weight)
     lib = _lib.load_library()
-    cl = torch.channels_last
-    if not x.is_contiguous(memory_format=cl):
-        x = x.contiguous(memory_format=cl)
-    if not weight.is_contiguous(memory_format=cl):
-        weight = weight.contiguous(memory_format=cl)
-    B, Cin, H, W = x.shape
-    if upsample:
-        H, W = 2 * H, 2 * W
-    if size is not None:
-        H, W = size
+    splits = 1 if out_nchw else splits    # as the library does: only the convolution's own epilogue stores channel-major
+    B, Cin, _, _ = x.shape
     Cout = weight.shape[0]
-    if int(bool(upsample)) + int(bool(stride2)) + int(bool(stride2_pad_br)) > 1:
-        raise ValueError("conv3x3: upsample, stride2 and stride2_pad_br exclude each other")
-    oh, ow = ((H + 1) // 2, (W + 1) // 2) if stride2 else ((H // 2, W // 2) if stride2_pad_br else (H, W))
-    if out_nchw:
-        out = torch.empty((B, Cout, oh, ow), dtype=x.dtype, device=x.device)
-    else:
-        out = torch.empty((B, Cout, oh, ow), dtype=x.dtype, device=x.device, memory_format=cl)
-    ldr = 0
-    if residual is not None:
-        if residual.shape != out.shape:
-            raise ValueError("conv3x3: residual must have the output's shape")
-        if not residual.is_contiguous(memory_format=cl):
-            residual = residual.contiguous(memory_format=cl)
-        ldr = Cout
+    x, weight, residual, ldr = _conv3x3_operands("conv3x3", x, weight, residual, (B, Cout, oh, ow))
+    out = torch.empty((B, Cout, oh, ow), dtype=x.dtype, device=x.device,
+                      memory_format=torch.contiguous_format if out_nchw else torch.channels_last)
     nbytes = lib.dsc_conv3x3_workspace_bytes(B, H, W, Cin, Cout, splits)
     ws = _workspace(x.device, nbytes) if nbytes else None
     rc = lib.dsc_conv3x3_nhwc_f16(_p(x), _p(weight), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, Cin, ldr, Cout,
-                                  3 if stride2_pad_br else (2 if stride2 else (1 if upsample else (4 if size is not None else 0))), 1 if out_nchw else 0, splits, 0, _p(ws),
-                                  ws.numel() * 8 if ws is not None else 0, _stream_ptr(x))
+                                  mode, 1 if out_nchw else 0, splits, 0, _p(ws), ws.numel() * 8 if ws is not None else 0,
+                                  _stream_ptr(x))
     _lib.check(rc, "dsc_conv3x3_nhwc_f16")
     return out
+
+
+def conv3x3_try(x, weight, bias=None, residual=None, *, mode=CONV_PLAIN, size=None, out_nchw=False, splits=0):
+    """conv3x3 in the given CONV_* mode (size: the upsample_size of CONV_UPSAMPLE_SIZE) where dsc_conv3x3_nhwc_f16 covers the call,
+    else None - a CPU tensor, another dtype, a shape outside the kernel's, USE_DSC_CONV off - and the caller takes its library
+    path.  ValueError for bad arguments, as conv3x3.
+    (dsc_conv3x3_workspace_bytes cannot double as the coverage answer: its 0 is "not covered" and "no split" alike, and it does not
+    apply the 2^30 bounds of dsc_conv3x3_supported - so coverage is asked once, through conv3x3_supported, and nothing is skipped.)"""
+    keyword = _CONV_MODE_KEYWORD.get(mode, "") if isinstance(mode, int) else ""
+    if keyword == "" or (size is None) == (mode == CONV_UPSAMPLE_SIZE):
+        raise ValueError("conv3x3_try: mode is one of ops.CONV_*; size goes with CONV_UPSAMPLE_SIZE, and only with it")
+    kw = {} if keyword is None else {keyword: True if size is None else size}
+    _, (H, W), _ = _conv3x3_geometry(x, **kw)
+    stride2 = mode in (CONV_STRIDE2, CONV_STRIDE2_PAD_BR)
+    # two refusals of conv_impl (conv3x3.hip) that dsc_conv3x3_supported, which is not told the mode, cannot give: a stride-2 code
+    # with a channel-major output, and odd sides with the bottom / right padding.  conv3x3 leaves both to the library's error.
+    if (stride2 and out_nchw) or (mode == CONV_STRIDE2_PAD_BR and (H % 2 or W % 2)):
+        return None
+    if not conv3x3_supported(x, weight, **({} if stride2 else kw)):
+        return None
+    return conv3x3(x, weight, bias, residual, splits=splits, out_nchw=out_nchw, **kw)
 
 
 # Upsample2D (exact 2x): four 2x2 phase convolutions of the source with pre-summed weights (dsc_conv3x3_up2x_nhwc_f16) instead of
@@ -932,10 +946,8 @@ def conv3x3_up2x(x, packed, bias=None, splits=0):
         raise ValueError("conv3x3_up2x: bias must be a contiguous fp16 [Cout] tensor")
     _require_gpu(x, packed)
     lib = _lib.load_library()
-    cl = torch.channels_last
-    if not x.is_contiguous(memory_format=cl):
-        x = x.contiguous(memory_format=cl)
-    out = torch.empty((B, Cout, 2 * h, 2 * w), dtype=x.dtype, device=x.device, memory_format=cl)
+    x, _, _, _ = _conv3x3_operands("conv3x3_up2x", x, None, None, None)
+    out = torch.empty((B, Cout, 2 * h, 2 * w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     nbytes = lib.dsc_conv3x3_up2x_workspace_bytes(B, h, w, Cin, Cout, splits)
     ws = _workspace(x.device, nbytes) if nbytes else None
     rc = lib.dsc_conv3x3_up2x_nhwc_f16(_p(x), _p(packed), _p(bias), _p(out), B, h, w, Cin, Cout, splits, _p(ws),

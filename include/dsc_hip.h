@@ -383,13 +383,14 @@ int dsc_linear_f16(const void* x, const void* w, const void* bias, const void* r
  * of diffusers Downsample2D (3 per UNet step), odd sides included (their last pixel is an even one).  The taps still run at H x W (4x the necessary MFMA work); it is nevertheless
  * faster than MIOpen's stride-2 kernels here (24-27 us vs 31-37 us) and, unlike their atomic split-K, bit-reproducible.
  * out_nchw != 0: out is [B,Cout,H,W] (channel-major; the UNet's 4-channel conv_out hands its result back in the sampler's
- * layout).  Cout need not be a multiple of 64: a ragged last channel tile reads zero weight rows through the buffer bounds.
+ * layout); such a launch is never split, whatever `splits` says (the split's reduce launch stores pixel-major).  Cout need not be a multiple of 64: a ragged last channel tile reads zero weight rows through the buffer bounds.
  * splits: number of input-channel ranges accumulated by separate workgroups (0 = chosen from the shape); splits > 1
  * needs `workspace` (dsc_conv3x3_workspace_bytes) and sums the partials in range order: bit-reproducible.
  * Supported (dsc_conv3x3_supported): Cin % 64 == 0, strides % 8 == 0 (when Cout % 8 == 0), 16-byte aligned pointers; any
  * H, W >= 1 (sides that are not multiples of the 8 x 16 / 8 x 8 pixel tile - 12 x 12, the lowest level of a 768 x 768 generation -
  * cost the overhang's MFMAs, nothing else); anything else returns DSC_ERR_UNSUPPORTED and the caller keeps the library convolution.
  */
+/* the resample codes (0: none of them); ops.py mirrors them as CONV_*, tests/test_conv_dispatch_host.py compares the two */
 #define DSC_CONV_UPSAMPLE2X 1
 #define DSC_CONV_STRIDE2 2
 #define DSC_CONV_STRIDE2_PAD_BR 3   /* stride 2 with zero padding on the bottom / right only (F.pad (0,1,0,1) + stride-2 conv of
