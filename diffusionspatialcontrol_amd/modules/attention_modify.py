@@ -302,7 +302,10 @@ class _RegionProcessor:
         residual = hidden_states
         img_sequence_length = hidden_states.shape[1]              # :427 - dim 1 also for 4-D input
         ip_hidden_states = None
-        if self.is_ip_adapter and encoder_hidden_states is not None:
+        # prepared rows (the continuous batcher's step, see prepared_ip_rows): the text arrives alone - no split, which in its
+        # deprecated single-tensor form would cut the last num_tokens[0] text rows off
+        ip_rows = prepared_ip_rows(region_prompt) if self.is_ip_adapter and encoder_hidden_states is not None else None
+        if self.is_ip_adapter and encoder_hidden_states is not None and ip_rows is None:
             encoder_hidden_states, ip_hidden_states = self._split_ip(encoder_hidden_states)
         if attn.spatial_norm is not None:
             hidden_states = attn.spatial_norm(hidden_states, temb)
@@ -410,7 +413,9 @@ class _RegionProcessor:
         else:
             out = ops.self_attention(q4, k4, v4, scale=sc)                  # [B, L, H, d]
         hidden_states = out.reshape(B, L, C)
-        if self.is_ip_adapter:
+        if ip_rows is not None:
+            hidden_states = self._ip_rows_branch(q4, hidden_states, ip_rows[self], ip_adapter_masks, sc)
+        elif self.is_ip_adapter:
             hidden_states = self._ip_branch(attn, q4, hidden_states, ip_hidden_states, ip_adapter_masks, sc)
         to_out = attn.to_out[0]
         if _ln_fold is not None:
@@ -431,6 +436,17 @@ class _RegionProcessor:
         if attn.rescale_output_factor != 1.0:
             hidden_states = hidden_states / attn.rescale_output_factor
         return hidden_states
+
+
+def prepared_ip_rows(region_prompt):
+    """The prepared IP-Adapter rows a call carries, or None: region_prompt["ip_rows"] = {processor: [(k_ip, v_ip, row_scale), ...
+    one per adapter]} with k_ip / v_ip [B, T, H * d] fp16 (to_k_ip / to_v_ip of the adapter's image tokens of every batch row,
+    computed once per request; a batch stride is allowed) and row_scale [B] fp32 on the device (0: the row has no image prompt).
+    The continuous batcher's captured step passes them (modules/serving.py): the buffers are static, their contents change
+    between replays.  Every other caller hands the image tokens over as the reference does, as (text, [tokens])."""
+    if not isinstance(region_prompt, dict):
+        return None
+    return region_prompt.get("ip_rows")
 
 
 class AttnProcessor2_0(_RegionProcessor):
@@ -539,6 +555,19 @@ class _IPAdapterProcessor(_RegionProcessor, nn.Module):
                 md = IPAdapterMaskProcessor.downsample(mask, B, o.shape[1], o.shape[2])
                 o = o * md.to(dtype=o.dtype, device=o.device)
             hidden_states = hidden_states + scale * o
+        return hidden_states
+
+    def _ip_rows_branch(self, q4, hidden_states, rows, ip_adapter_masks, sc):
+        """the static route of the continuous batcher: one launch per adapter adds row_scale[b] * softmax(q k_ip^T) v_ip to the text
+        branch's output in place (dsc_ip_xattn_add_f16) - instead of _ip_branch's two GEMMs, attention, multiply and add with
+        a scale baked in as a Python float"""
+        if ip_adapter_masks is not None:
+            raise ValueError("`ip_adapter_masks` are not supported with prepared IP-Adapter rows (the continuous batcher)")
+        if len(rows) != len(self.num_tokens):
+            raise ValueError(f"prepared IP-Adapter rows for {len(rows)} adapters, the processor holds {len(self.num_tokens)}")
+        B, L, H, d = q4.shape
+        for k_ip, v_ip, row_scale in rows:
+            ops.ip_xattn_add(q4, k_ip.unflatten(-1, (H, d)), v_ip.unflatten(-1, (H, d)), row_scale, hidden_states, scale=sc)
         return hidden_states
 
     def forward(self, *a, **k):

@@ -47,6 +47,16 @@ into a tensor of the second-pass record; an event is recorded, the record joins 
 stream waits on the event before it loads the row.  Only the first batcher ever takes the second's lock (no cycle); the caller's
 one Future resolves with the second pass's output.  No host synchronisation between the passes.
 
+Image prompts.  On a pipeline with IP-Adapters loaded (load_ip_adapter) the batcher's step carries, per cross-attention layer and
+adapter, to_k_ip / to_v_ip of every batch row's image tokens and one scale per row: a request with `ip_adapter_image_embeds` has
+its image tokens projected (unet.encoder_hid_proj) and pushed through every layer's to_k_ip / to_v_ip ONCE, at admission, into
+a flat row pair; `refresh` copies a member's pair into rows {i, n + i} of the bucket's static buffer (one per adapter; each
+layer's k_ip / v_ip are views into it) and writes its `ip_adapter_scale` into the bucket's row_scale vector.  In the captured
+step every IP-Adapter processor runs the stock text branch and then ONE launch per adapter of dsc_ip_xattn_add_f16, which reads
+row_scale on the device: idle slots and requests without an image prompt carry scale 0, their workgroups return at once and
+their rows are bit for bit those of a batcher without an adapter; joins, leaves and a changed scale need no capture.  The
+sampler launches do not know about any of it, so every request kind, sampler and guidance rescale combines with an image prompt.
+
 The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
 request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
 """
@@ -65,7 +75,14 @@ from .encode_region_map_function import encode_region_map
 from .external_k_diffusion import DiscreteVDDPMDenoiser
 
 MAX_TEXT_KEYS = 384                  # the chunked prepared-operand kernels (ops.region_xattn_packed)
-_UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter", "ip_adapter_image", "ip_adapter_image_embeds")
+_UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter")
+
+
+def _ip_layers(pipe):
+    """(attention module, its IP-Adapter processor) of every cross-attention layer in module order; [] without an adapter"""
+    from .attention_modify import _IPAdapterProcessor
+    from .u_net_condition_modify import Attention
+    return [(m, m.processor) for m in pipe.unet.modules() if isinstance(m, Attention) and isinstance(m.processor, _IPAdapterProcessor)]
 
 
 def _spatial_size(image):
@@ -83,7 +100,8 @@ def _spatial_size(image):
 class _Request:
     __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
                  "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known",
-                 "family", "snoise", "skipout", "noise", "rescale", "eta", "hires", "second", "ready", "hnoise", "t_handoff")
+                 "family", "snoise", "skipout", "noise", "rescale", "eta", "hires", "second", "ready", "hnoise", "t_handoff",
+                 "ip_embeds", "ip_scale", "ip_rows")
 
 
 class ServingBatcher:
@@ -114,6 +132,14 @@ class ServingBatcher:
         self._warm_captures = None
         self._thread = None
         self._stop = False
+        # the IP-Adapters this batcher's step is built for (load_ip_adapter): the processors, the image projection, tokens per adapter
+        self._ip = _ip_layers(pipe)
+        self._ip_proj = getattr(pipe.unet, "encoder_hid_proj", None) if self._ip else None
+        self._ip_tokens = [int(t) for t in self._ip[0][1].num_tokens] if self._ip else []
+        if any(t > ops.IP_MAX_TOKENS for t in self._ip_tokens):
+            raise ValueError(f"serve: a loaded IP-Adapter has {max(self._ip_tokens)} image tokens; the batcher's image-token attention "
+                             f"(dsc_ip_xattn_add_f16) takes at most {ops.IP_MAX_TOKENS} (ops.IP_MAX_TOKENS) - the 257-token Full "
+                             f"projection runs through txt2img(ip_adapter_image_embeds=...)")
         self.exec = executor if executor is not None else _GraphExecutor(self)
 
     # ------------------------------------------------------------------ public interface
@@ -149,7 +175,10 @@ class ServingBatcher:
         `output_type` ("latent", default, or what latent_to_image takes), `sampler_name` (sampling.LINEAR_FAMILY, default
         DPM++ 2M) with `eta` / `s_noise` / `solver_type`, `step_noise` ([steps, 1, 4, h, w]: the noise of every step;
         default: drawn as the sampler itself would, from `seed` / `generator`) and `guidance_rescale` (in [0, 1], default 0; not
-        with `mask_image`).  On a chained pair (chain_hires) `upscale=True` adds the hires pass: `upscale_x` (2.0), `upscale_method`
+        with `mask_image`).  On a pipeline with IP-Adapters loaded: `ip_adapter_image_embeds` (a list with one tensor per loaded
+        adapter, each [negative; positive] along dim 0 with ONE image per half - what txt2img takes, see encode_image; absent /
+        None: the request runs without an image prompt beside those that have one) and `ip_adapter_scale` (a float, or a list
+        with one entry per adapter; default: the processors' scale at submit time, so set_ip_adapter_scale needs no capture).  On a chained pair (chain_hires) `upscale=True` adds the hires pass: `upscale_x` (2.0), `upscale_method`
         ("bicubic"), `upscale_antialias`, `upscale_denoising_strength` (0.7), `sampler_name_hires`, `sampler_opt_hires` (default:
         the first pass's), `hires_latents` ([1, 4, H/8, W/8] unit noise of the second pass; default: drawn from `generator` after
         the first pass's draws) and `region_map_state_hires` (default: `region_map_state`; None: no region condition in the second
@@ -217,6 +246,7 @@ class ServingBatcher:
         if not isinstance(request, dict):
             raise TypeError("serve: a request is a dict (txt2img_coalesced's request + num_inference_steps / sampler_opt / "
                             "guidance_scale)")
+        self._check_ip_current()
         if request.get("upscale") and not second:
             return self._prepare_hires_pair(request)
         v_pred = bool(getattr(pipe, "v_prediction", False))
@@ -260,7 +290,11 @@ class ServingBatcher:
             raise ValueError("serve: a custom weight_func is not supported (use txt2img)")
         for k in _UNSUPPORTED_KEYS:
             if request.get(k) is not None:
-                raise ValueError(f"serve: `{k}` (ControlNet / T2I-Adapter / IP-Adapter) is not supported (use txt2img)")
+                raise ValueError(f"serve: `{k}` (ControlNet / T2I-Adapter) is not supported (use txt2img)")
+        if request.get("ip_adapter_image") is not None:
+            raise ValueError("serve: `ip_adapter_image` (a raw image) is not supported: encode it once with pipe.encode_image and "
+                             "pass `ip_adapter_image_embeds` ([negative; positive] per loaded adapter)")
+        ip_embeds, ip_scale = self._ip_request(request)
         pos, neg = request.get("prompt_embeds"), request.get("negative_prompt_embeds")
         if pos is None or neg is None:
             raise ValueError("serve: a request needs prompt_embeds and negative_prompt_embeds ([1, S, ctx] each)")
@@ -277,6 +311,7 @@ class ServingBatcher:
         if r.steps < 1:
             raise ValueError("serve: num_inference_steps must be >= 1")
         r.second, r.hires, r.ready, r.hnoise, r.t_handoff = second, None, None, None, None
+        r.ip_embeds, r.ip_scale, r.ip_rows = ip_embeds, ip_scale, None
         t_start = self._image_request(r)
         r.guidance = g
         r.output_type = request.get("output_type", "latent")
@@ -329,6 +364,53 @@ class ServingBatcher:
         if device:
             self._prepare_device(r)
         return r
+
+    def _check_ip_current(self):
+        """the captured steps were built for the IP-Adapter processors of construction time (their to_k_ip / to_v_ip, the static
+        buffers' layout): a batcher that has seen load_ip_adapter / unload_ip_adapter since is stale"""
+        now = _ip_layers(self.pipe)
+        proj = getattr(self.pipe.unet, "encoder_hid_proj", None) if now else None
+        if len(now) != len(self._ip) or any(a[1] is not b[1] for a, b in zip(now, self._ip)) or proj is not self._ip_proj:
+            raise RuntimeError("serve: the pipeline's IP-Adapter processors changed since this batcher was built (load_ip_adapter / "
+                               "unload_ip_adapter): its captured steps are stale - build a new one with pipe.serve(...)")
+
+    def _ip_request(self, request):
+        """submit-time checks of the image-prompt keys -> (embeds or None, one scale per loaded adapter; all 0 without embeds)"""
+        n = len(self._ip_tokens)
+        kw = request.get("cross_attention_kwargs")
+        if isinstance(kw, dict) and kw.get("ip_adapter_masks") is not None:
+            raise ValueError("serve: `ip_adapter_masks` (cross_attention_kwargs) are not supported (use txt2img)")
+        embeds, scale = request.get("ip_adapter_image_embeds"), request.get("ip_adapter_scale")
+        if scale is None:
+            scale = [float(v) for v in self._ip[0][1].scale] if n else []
+        elif isinstance(scale, (list, tuple)):
+            if len(scale) != n:
+                raise ValueError(f"serve: `ip_adapter_scale` lists {len(scale)} scales, the pipeline has {n} IP-Adapter(s) loaded")
+            scale = list(scale)
+        else:
+            scale = [scale] * n
+        for v in scale:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+                raise ValueError(f"serve: `ip_adapter_scale` must be a finite number or a list of them, got {v!r}")
+        scale = [float(v) for v in scale]
+        if embeds is None:
+            return None, [0.0] * n
+        if n == 0:
+            raise ValueError("serve: `ip_adapter_image_embeds` on a pipeline without an IP-Adapter (pipe.load_ip_adapter first, then "
+                             "build the batcher)")
+        if not isinstance(embeds, (list, tuple)) or len(embeds) != n:
+            got = len(embeds) if isinstance(embeds, (list, tuple)) else type(embeds).__name__
+            raise ValueError(f"serve: `ip_adapter_image_embeds` must be a list with one tensor per loaded IP-Adapter ({n}), got {got}")
+        for a, (e, t) in enumerate(zip(embeds, self._ip_tokens)):
+            if not torch.is_tensor(e) or e.dim() < 3 or e.shape[0] != 2:
+                raise ValueError(f"serve: `ip_adapter_image_embeds[{a}]` must be [negative; positive] along dim 0 ([2, 1, ...], what "
+                                 f"txt2img takes), got {list(e.shape) if torch.is_tensor(e) else type(e).__name__}")
+            if e.shape[1] != 1:
+                raise ValueError(f"serve: `ip_adapter_image_embeds[{a}]` holds {e.shape[1]} images = {e.shape[1] * t} image tokens, "
+                                 f"adapter {a} has {t} tokens per request in the batcher (one image; use txt2img for more)")
+        if all(v == 0.0 for v in scale):
+            return None, scale                                      # nothing to add: no projection work, the rows stay skipped
+        return list(embeds), scale
 
     def _prepare_device(self, r):
         """the device half of _prepare, in the order the pipeline's one generator is consumed: start latent, then step noise"""
@@ -655,6 +737,17 @@ class _GraphExecutor:
             self.old = torch.zeros_like(self.x)
         self.st = {}
         self._inflight = collections.deque()
+        # IP-Adapters: per adapter the layout of one flat row [sum over layers of (k_ip | v_ip), T * C_layer halfs each]
+        self.ip_layers = list(batcher._ip)
+        self.ip_tokens = list(batcher._ip_tokens)
+        self.ip_offsets, self.ip_width = [], []
+        for T in self.ip_tokens:
+            offs, w = [], 0
+            for _, proc in self.ip_layers:
+                offs.append(w)
+                w += 2 * T * proc.hidden_size
+            self.ip_offsets.append(offs)
+            self.ip_width.append(w)
 
     def bind_thread(self):
         _lib.check(_lib.load_library().dsc_set_workspace_slot(self.b.slot), "dsc_set_workspace_slot")
@@ -685,6 +778,27 @@ class _GraphExecutor:
         r.temb = self.pipe.unet.temb_add_table(torch.tensor(ts, dtype=torch.float32, device=dev))
         neg, pos = r.text
         r.text = (neg.to(device=dev, dtype=dt), pos.to(device=dev, dtype=dt))
+        if r.ip_embeds is not None:
+            self._ip_request_rows(r)
+
+    @torch.no_grad()
+    def _ip_request_rows(self, r):
+        """once per request: its image tokens (unet.encoder_hid_proj on its own [2, ...] embeds: txt2img's call shape) through
+        every layer's to_k_ip / to_v_ip, packed into one flat [2, width] row pair per adapter (uncond, cond)"""
+        dev, dt = self.device, self.dtype
+        tokens = self.pipe.unet.encoder_hid_proj([e.to(device=dev, dtype=dt) for e in r.ip_embeds])
+        r.ip_rows = []
+        for a, T in enumerate(self.ip_tokens):
+            tok = tokens[a]
+            if tuple(tok.shape) != (2, T, self.ctx):
+                raise ValueError(f"serve: `ip_adapter_image_embeds[{a}]` projects to {tuple(tok.shape)} image tokens, adapter {a} "
+                                 f"takes {(2, T, self.ctx)}")
+            row = torch.empty(2, self.ip_width[a], device=dev, dtype=dt)
+            for (_, proc), off in zip(self.ip_layers, self.ip_offsets[a]):
+                n = T * proc.hidden_size
+                row[:, off:off + n] = proc.to_k_ip[a](tok).reshape(2, n)
+                row[:, off + n:off + 2 * n] = proc.to_v_ip[a](tok).reshape(2, n)
+            r.ip_rows.append(row)
 
     def prepare_image(self, r):
         """img2img / inpainting: the start latent of the pipeline method, line for line, on the truncated schedule; for
@@ -832,8 +946,21 @@ class _GraphExecutor:
             st["dense"] = None
             pipe._refresh_text_kv(st["text"])
             self._pin_kv()
+            # one flat buffer and one row_scale vector per adapter; scale 0 (idle / no image prompt): the row's contents are never read
+            st["ip"] = [{"buf": torch.zeros(rows, w, device=dev, dtype=dt), "scale": torch.zeros(rows, device=dev, dtype=torch.float32)}
+                        for w in self.ip_width]
         kw = {"region_prompt": {"region_state": zero, "compressed": st["compressed"], "sigma": st["sigma"], "weight_func": None,
                                 "n_std_groups": n, "sigma_per_group": True}}
+        if self.ip_layers:
+            ip_rows = {}
+            for j, (_, proc) in enumerate(self.ip_layers):
+                per = []
+                for a, T in enumerate(self.ip_tokens):
+                    off, m, buf = self.ip_offsets[a][j], T * proc.hidden_size, st["ip"][a]["buf"]
+                    per.append((buf[:, off:off + m].unflatten(-1, (T, proc.hidden_size)),
+                                buf[:, off + m:off + 2 * m].unflatten(-1, (T, proc.hidden_size)), st["ip"][a]["scale"]))
+                ip_rows[proc] = per
+            kw["region_prompt"]["ip_rows"] = ip_rows
         unet = pipe.unet
 
         def step():
@@ -867,8 +994,19 @@ class _GraphExecutor:
             if isinstance(m, Attention) and m.is_cross_attention and getattr(m, "kv_cache", None) is not None:
                 m.kv_cache["pin"] = True
 
+    @staticmethod
+    def ip_row_scales(n, members, a):
+        """row_scale of adapter a for bucket n: a member's `ip_adapter_scale` at rows {i, n + i} (uncond, cond); 0 for idle slots
+        and members without an image prompt - those rows of the buffer are never read"""
+        scales = [0.0] * (2 * n)
+        for i, r in enumerate(members):
+            if r is not None and r.ip_embeds is not None:
+                scales[i] = scales[n + i] = float(r.ip_scale[a])
+        return scales
+
     def refresh(self, n, members):
-        """text rows, their packed K/V and the compressed tables of bucket n for these slot members (None = IDLE)"""
+        """text rows, their packed K/V, the compressed tables and (IP-Adapters) the image-token rows and scales of bucket n for
+        these slot members (None = IDLE)"""
         st = self.st[n]
         S = self.b.text_len
         with torch.cuda.stream(self.stream):
@@ -886,6 +1024,13 @@ class _GraphExecutor:
                 for L, w in r.tables.items():
                     dense[L][i] = w[0]
                     dense[L][n + i] = w[1]
+            for a, ip in enumerate(st["ip"]):
+                scales = self.ip_row_scales(n, members, a)
+                for i, r in enumerate(members):
+                    if scales[i] != 0.0:
+                        ip["buf"][i].copy_(r.ip_rows[a][0])
+                        ip["buf"][n + i].copy_(r.ip_rows[a][1])
+                ip["scale"].copy_(torch.tensor(scales, dtype=torch.float32).pin_memory(), non_blocking=True)
             self.pipe._refresh_text_kv(text)
             comp = self.pipe._compress_tables(dense)
             if comp is None:

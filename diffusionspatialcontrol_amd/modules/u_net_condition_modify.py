@@ -27,7 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .attention_modify import AttnProcessor, AttnProcessor2_0
+from .attention_modify import AttnProcessor, AttnProcessor2_0, _IPAdapterProcessor, prepared_ip_rows
 
 
 class ImageProjection(nn.Module):
@@ -475,9 +475,11 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = nn.LayerNorm(dim)
         self.ff = FeedForward(dim)
 
-    def _can_fold(self, x, stats):
+    def _can_fold(self, x, stats, ip_rows=False):
         """The three LayerNorms disappear into the neighbouring GEMMs when every one of those GEMMs runs on
-        dsc_linear_ln_f16 and both attentions carry this package's stock processors (the private `_ln_fold` protocol)."""
+        dsc_linear_ln_f16 and both attentions carry this package's stock processors (the private `_ln_fold` protocol).
+        ip_rows: the call carries prepared IP-Adapter rows (the continuous batcher's step) - the IP-Adapter processors then run
+        the stock text branch and count as stock; on every other route they keep the unfolded block they always had."""
         if stats is None or not x.is_cuda or x.dim() != 3:
             return False
         M, C = x.shape[0] * x.shape[1], x.shape[2]
@@ -485,7 +487,8 @@ class BasicTransformerBlock(nn.Module):
         if not (cover(M, 3 * C, C, x.dtype) and cover(M, C, C, x.dtype) and cover(M, 8 * C, C, x.dtype, True)):
             return False
         for a in (self.attn1, self.attn2):
-            if type(a.processor) not in (AttnProcessor2_0, AttnProcessor) or a.to_q.bias is not None \
+            stock = type(a.processor) in (AttnProcessor2_0, AttnProcessor) or (ip_rows and isinstance(a.processor, _IPAdapterProcessor))
+            if not stock or a.to_q.bias is not None \
                     or type(a.to_q) is not nn.Linear or type(a.to_out[0]) is not nn.Linear \
                     or a.spatial_norm is not None or a.group_norm is not None or a.residual_connection \
                     or a.rescale_output_factor != 1.0 or a.inner_dim != C:
@@ -494,7 +497,7 @@ class BasicTransformerBlock(nn.Module):
 
     def forward(self, x, encoder_hidden_states, cross_attention_kwargs, stats=None):
         kw = cross_attention_kwargs or {}
-        if ops.USE_LN_FOLD and self._can_fold(x, stats):
+        if ops.USE_LN_FOLD and self._can_fold(x, stats, prepared_ip_rows(kw.get("region_prompt")) is not None):
             x, st = self.attn1(x, None, _ln_fold=LNFold(self.norm1, stats, x), **kw)
             x, st = self.attn2(x, encoder_hidden_states, _ln_fold=LNFold(self.norm2, st, x), **kw)
             f = LNFold(self.norm3, st, None)
@@ -907,10 +910,13 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
         self._to_channels_last_once()
         if getattr(self, "encoder_hid_proj", None) is not None and self.config.get("encoder_hid_dim_type") == "ip_image_proj":
             # reference :1030-1037 - the IP-Adapter image tokens travel with the text as a tuple
-            if added_cond_kwargs is None or "image_embeds" not in added_cond_kwargs:
-                raise ValueError(f"{self.__class__} has the config param `encoder_hid_dim_type` set to 'ip_image_proj' which "
-                                 "requires the keyword argument `image_embeds` to be passed in  `added_conditions`")
-            encoder_hidden_states = (encoder_hidden_states, self.encoder_hid_proj(added_cond_kwargs.get("image_embeds")))
+            # (the continuous batcher's step carries every layer's projected image tokens as prepared rows instead - to_k_ip /
+            # to_v_ip applied once per request at admission, region_prompt["ip_rows"] - and the text travels alone)
+            if prepared_ip_rows((cross_attention_kwargs or {}).get("region_prompt")) is None:
+                if added_cond_kwargs is None or "image_embeds" not in added_cond_kwargs:
+                    raise ValueError(f"{self.__class__} has the config param `encoder_hid_dim_type` set to 'ip_image_proj' which "
+                                     "requires the keyword argument `image_embeds` to be passed in  `added_conditions`")
+                encoder_hidden_states = (encoder_hidden_states, self.encoder_hid_proj(added_cond_kwargs.get("image_embeds")))
         # cfg_shared_prefix (the caller's promise: rows [n:] of `sample` and of the time embedding equal rows [:n] - classifier-free
         # guidance's [x; x] input): everything before the first cross-attention is the same for both halves and runs on rows
         # [:n] only (conv_in, the first ResNet block, the first transformer block's GroupNorm / proj_in / self-attention / to_q);

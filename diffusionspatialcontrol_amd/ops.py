@@ -313,6 +313,50 @@ def self_attention(q, k, v, scale=None, out=None):
     return out
 
 
+IP_MAX_TOKENS = 16         # DSC_IP_MAX_TOKENS (include/dsc_hip.h): the image tokens of one adapter are one MFMA tile
+
+
+def ip_xattn_add(q4, k_ip, v_ip, row_scale, io, scale=None):
+    """io[b, l, h, :] += row_scale[b] * softmax(scale * q4[b, l, h, :] . k_ip[b, :, h, :]^T) . v_ip[b, :, h, :], in place
+    (dsc_ip_xattn_add_f16: the IP-Adapter term of a cross-attention layer with one scale per batch row, read on the device).
+    q4 [B, L, H, d] fp16 with its strides (a stride-0 batch dimension included), k_ip / v_ip [B, T, H, d] fp16 with contiguous
+    batch rows and one common batch stride (views into a buffer with one row per batch row),
+    row_scale [B] fp32 on the device, io [B, L, H * d] (or [B, L, H, d]) fp16 contiguous: the text branch's output.  Rows whose
+    scale is 0 are left untouched and their k_ip / v_ip rows are not read.  scale: default 1 / sqrt(d).  Returns io."""
+    _require_gpu(q4, k_ip, v_ip, row_scale, io)
+    if q4.dtype != torch.float16 or k_ip.dtype != torch.float16 or v_ip.dtype != torch.float16 or io.dtype != torch.float16:
+        raise TypeError("ip_xattn_add: q4 / k_ip / v_ip / io must be fp16")
+    if q4.dim() != 4 or k_ip.dim() != 4:
+        raise ValueError(f"ip_xattn_add: q4 is [B, L, H, d] and k_ip / v_ip [B, T, H, d], got {tuple(q4.shape)} / {tuple(k_ip.shape)}")
+    (sb, sl, sh), (B, H, L, d) = _blhd_strides(q4, "blc")
+    T = k_ip.shape[1]
+    if d % 8 != 0 or not 8 <= d <= 160:
+        raise ValueError(f"ip_xattn_add: head dim {d} is not a multiple of 8 in [8, 160]")
+    if not 1 <= T <= IP_MAX_TOKENS:
+        raise ValueError(f"ip_xattn_add: {T} image tokens; the kernel takes 1 .. {IP_MAX_TOKENS} (IP_MAX_TOKENS)")
+    skb = k_ip.stride(0) if B > 1 else T * H * d
+    want = (k_ip.stride(0), H * d, d, 1)
+    if tuple(k_ip.shape) != (B, T, H, d) or tuple(v_ip.shape) != (B, T, H, d) or k_ip.stride() != want or v_ip.stride() != want \
+            or skb < T * H * d:
+        raise ValueError(f"ip_xattn_add: k_ip / v_ip must be {(B, T, H, d)} tensors with contiguous batch rows and the same batch "
+                         f"stride, got {tuple(k_ip.shape)} {k_ip.stride()} / {tuple(v_ip.shape)} {v_ip.stride()}")
+    if row_scale.dtype != torch.float32 or tuple(row_scale.shape) != (B,) or not row_scale.is_contiguous():
+        raise ValueError(f"ip_xattn_add: row_scale must be a contiguous fp32 [{B}] tensor, got {row_scale.dtype} "
+                         f"{tuple(row_scale.shape)}")
+    if io.numel() != B * L * H * d or tuple(io.shape[:2]) != (B, L) or not io.is_contiguous():
+        raise ValueError(f"ip_xattn_add: io must be a contiguous {(B, L, H * d)} tensor, got {tuple(io.shape)}")
+    if any(t.device != q4.device for t in (k_ip, v_ip, row_scale, io)):
+        raise ValueError("ip_xattn_add: all operands must be on one device")
+    if sb % 8 or sl % 8 or sh % 8 or skb % 8 or any(t.data_ptr() % 16 for t in (q4, k_ip, v_ip, io)):
+        raise ValueError("ip_xattn_add: q4's strides must be multiples of 8 elements and every tensor 16-byte aligned")
+    _drop_gn_partials(io)
+    rc = _lib.load_library().dsc_ip_xattn_add_f16(_p(q4), sb, sl, sh, _p(k_ip), _p(v_ip), skb, _p(row_scale), _p(io), B, L,
+                                                  H, d, T,
+                                                  float(scale) if scale else float(d) ** -0.5, _stream_ptr(q4))
+    _lib.check(rc, "dsc_ip_xattn_add_f16")
+    return io
+
+
 def groupnorm_silu(x, groups, weight, bias, eps, act):
     """GroupNorm(groups, eps) [+ SiLU] over NCHW fp16 [B, C, h, w] (dsc_groupnorm_silu: two HIP launches)."""
     _require_gpu(x)

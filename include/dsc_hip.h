@@ -622,6 +622,33 @@ int dsc_latent_resample_noise(const void* src, const void* noise, void* dst, int
                               const int* idx_y, const float* w_y, const int* idx_x, const float* w_x,
                               float noise_scale_f16_value, void* stream);
 
+/*
+ * The IP-Adapter term of one cross-attention layer, accumulated in place with one scale per batch row, one launch per adapter.
+ * Replaces, per adapter, modules/attention_modify.py:370-374 + :385 (IPAdapterAttnProcessor) and :664-674 + :685
+ * (IPAdapterAttnProcessor2_0) of the reference: attention of the layer's queries over the adapter's image tokens and
+ * `hidden_states + scale * current_ip_hidden_states`, with the processor's Python float `scale` replaced by a device vector:
+ *     io[b, l, h, :] = fp16( float(io[b, l, h, :]) +
+ *                            row_scale[b] * sum_t softmax_t(softmax_scale * q[b, l, h, :] . k_ip[b, t, h, :]) * v_ip[b, t, h, :] )
+ * q [B, L, H, d] fp16 with its strides in elements (innermost 1; q_stride_b may be 0: the shared classifier-free-guidance
+ * prefix), k_ip / v_ip [B, T, H, d] fp16, each batch row contiguous and kv_stride_b >= T * H * d elements from the next (views
+ * into one buffer per batch row; to_k_ip / to_v_ip of the tokens, :368-369 / :662-663: computed once per generation by the
+ * caller), io [B, L, H * d] fp16 contiguous: the text branch's output on entry.  Products of fp16 values
+ * accumulate in fp32, the softmax subtracts the row maximum, its unnormalised weights (<= 1) round to fp16 for the second
+ * product, 1 / sum and row_scale are applied in fp32, one fp16 rounding at the store.
+ * row_scale [B] fp32 is read from DEVICE memory (never by value): a captured launch stays valid when a row's scale changes.
+ * row_scale[b] == 0: the workgroups of row b (b is a grid coordinate) return after that one uniform load - k_ip / v_ip / q of
+ * the row are not read (they may hold anything) and io is not touched.
+ * d % 8 == 0, 8 <= d <= 160; 1 <= T <= DSC_IP_MAX_TOKENS; any L >= 1.  16-byte loads and stores of q / k_ip / io: pointers
+ * 16-byte aligned, strides % 8 == 0.  No workspace, no allocation, no synchronisation, no atomics (every io element is read
+ * and written by the one lane that owns it), one fixed summation order: deterministic and safe under graph capture.
+ * DSC_ERR_BAD_ARG: null pointer, non-positive size or stride (q_stride_b < 0, kv_stride_b < T * H * d), io aliasing an input.  DSC_ERR_UNSUPPORTED:
+ * d, T or alignment outside the above, B or H > 65535.
+ */
+#define DSC_IP_MAX_TOKENS 16
+int dsc_ip_xattn_add_f16(const void* q, long long q_stride_b, long long q_stride_l, long long q_stride_h,
+                         const void* k_ip, const void* v_ip, long long kv_stride_b, const float* row_scale, void* io,
+                         int B, int L, int H, int d, int T, float softmax_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
