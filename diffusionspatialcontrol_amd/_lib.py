@@ -119,6 +119,8 @@ _SIGNATURES = {
     "dsc_latent_resample_noise": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 6 + [_vp] * 4 + [ctypes.c_float, _vp]),
     "dsc_ip_xattn_add_f16": (ctypes.c_int, [_vp] + [ctypes.c_longlong] * 3 + [_vp, _vp, ctypes.c_longlong, _vp, _vp] +
                              [ctypes.c_int] * 5 + [ctypes.c_float, _vp]),
+    "dsc_ip_xattn_add_masked_f16": (ctypes.c_int, [_vp] + [ctypes.c_longlong] * 3 + [_vp, _vp, ctypes.c_longlong, _vp, _vp] +
+                                    [_vp, ctypes.c_longlong] + [ctypes.c_int] * 5 + [ctypes.c_float, _vp]),
 }
 
 

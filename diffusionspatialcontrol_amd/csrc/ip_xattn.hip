@@ -21,6 +21,16 @@
 // same work costs 2 T d fp32 FMAs per 16-byte piece plus a cross-lane reduction over d / 8 lanes (5, 10, 20: no power of two)
 // or T LDS reads of k / v per query (10 x the global bytes at T = 16, the LDS : HBM ratio of the part); the MFMA form needs neither.
 //
+// The masked entry (dsc_ip_xattn_add_masked_f16) is the same body with MASKED = true: one fp16 weight per query, the IP-Adapter
+// region mask after the reference's down-sampling (modules/attention_modify.py:371-385 and :676-685: the adapter's output times
+// the mask, then `scale *` and the add), folded into the per-query fp32 coefficient as (row_scale[b] * w[b, l]) / sum - with
+// w == 1 that is row_scale[b] / sum bit for bit.  Lane (r, g) reads the half of its query, w[b, 16 tile + r]; a ballot over
+// w != 0 decides per wave whether the tile is worked on at all (a region mask is exactly zero over most of the image: no q
+// load, no io load, no store), and a query whose weight is zero in a mixed tile is not stored (its q may hold anything).  The
+// weight of a wave's first tile is requested before its K / V operands and the weight of tile i + 1 before the q / io loads of
+// tile i: from the second tile on the ballot waits for nothing; on the first the chain is row_scale -> weight -> q / io, one
+// load deeper than unmasked (the weights of a row with scale 0 are not read, and a skipped tile's q / io are not requested).
+//
 // row_scale[b] == 0: every workgroup of row b returns after that one (scalar, workgroup-uniform) load, before it reads k_ip / v_ip / q
 // or touches io.  b is grid coordinate z.  No allocation, no synchronisation, no atomics, one fixed summation order.
 #include "dsc_common.h"
@@ -28,16 +38,24 @@
 
 namespace {
 
-template <int NK>                                                    // NK = ceil(d / 32)
+template <int NK, bool MASKED>                                       // NK = ceil(d / 32); MASKED: one weight per query (qw)
 __global__ __launch_bounds__(256) void ip_xattn_add_kernel(const half_t* __restrict__ q, long long qs_b, long long qs_l, long long qs_h,
                                                            const half_t* __restrict__ k_ip, const half_t* __restrict__ v_ip,
                                                            long long kvs_b, const float* __restrict__ row_scale, half_t* __restrict__ io,
+                                                           const half_t* __restrict__ qw, long long ws_b,
                                                            int L, int H, int d, int T, float scale_log2e, int tiles_per_wave) {
     const int b = blockIdx.z, h = blockIdx.y;
     const float rs = row_scale[b];
     if (rs == 0.f) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
+    const int n_tiles = (L + 15) >> 4;
+    const int tile0 = (blockIdx.x * 4 + wave) * tiles_per_wave;
+    const half_t* wb = MASKED ? qw + b * ws_b : nullptr;
+    half_t w_next = (half_t)0;
+    if constexpr (MASKED) {
+        if (tile0 * 16 + r < L) w_next = wb[tile0 * 16 + r];          // ahead of the K / V loads: back by the time they are
+    }
     const long long tok = (long long)H * d;                           // elements between two tokens / two queries of io
     const half_t* kb = k_ip + b * kvs_b + h * d;
     const half_t* vb = v_ip + b * kvs_b + h * d;
@@ -58,13 +76,19 @@ __global__ __launch_bounds__(256) void ip_xattn_add_kernel(const half_t* __restr
             }
         }
     }
-    const int n_tiles = (L + 15) >> 4;
-    const int tile0 = (blockIdx.x * 4 + wave) * tiles_per_wave;
     for (int it = 0; it < tiles_per_wave; ++it) {
         const int tile = tile0 + it;
         if (tile >= n_tiles) break;                                   // wave-uniform
         const int l = tile * 16 + r;
         const bool ok = l < L;
+        float w = 1.f;
+        if constexpr (MASKED) {
+            w = (float)w_next;
+            w_next = (half_t)0;
+            const int ln = l + 16;                                    // the next tile's weight: in flight under this tile's work
+            if (it + 1 < tiles_per_wave && ln < L) w_next = wb[ln];
+            if (__ballot(w != 0.f) == 0ull) continue;                 // wave-uniform: nothing of this tile is read or written
+        }
         const half_t* qp = q + b * qs_b + l * qs_l + h * qs_h;
         half_t* op = io + ((long long)b * L + l) * tok + (long long)h * d;
         // every load of the tile is issued here: the io pieces do not wait for the scores (one memory latency per tile, not two)
@@ -100,14 +124,15 @@ __global__ __launch_bounds__(256) void ip_xattn_add_kernel(const half_t* __restr
         }
         sum += __shfl_xor(sum, 16, 64);
         sum += __shfl_xor(sum, 32, 64);
-        const float coef = rs / sum;
+        const float coef = MASKED ? (rs * w) / sum : rs / sum;
+        const bool st = ok && (!MASKED || w != 0.f);
 #pragma unroll
         for (int m = 0; m < NK; ++m) {
             const f4x_t z = {0.f, 0.f, 0.f, 0.f};
             const f4x_t o0 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf[m][0], pf, z, 0, 0, 0);
             const f4x_t o1 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf[m][1], pf, z, 0, 0, 0);
             const int dd = 32 * m + 8 * g;
-            if (ok && dd < d) {
+            if (st && dd < d) {
                 h8_t res;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -122,9 +147,10 @@ __global__ __launch_bounds__(256) void ip_xattn_add_kernel(const half_t* __restr
 
 }  // namespace
 
-extern "C" int dsc_ip_xattn_add_f16(const void* q, long long q_stride_b, long long q_stride_l, long long q_stride_h,
-                                    const void* k_ip, const void* v_ip, long long kv_stride_b, const float* row_scale, void* io,
-                                    int B, int L, int H, int d, int T, float softmax_scale, void* stream) {
+// both entries: q_weight == nullptr is the unmasked one (the masked entry has refused a null weight before it comes here)
+static int ip_xattn_add(const void* q, long long q_stride_b, long long q_stride_l, long long q_stride_h, const void* k_ip,
+                        const void* v_ip, long long kv_stride_b, const float* row_scale, void* io, const void* q_weight,
+                        long long w_stride_b, int B, int L, int H, int d, int T, float softmax_scale, void* stream) {
     if (!q || !k_ip || !v_ip || !row_scale || !io || io == q || io == k_ip || io == v_ip) return DSC_ERR_BAD_ARG;
     if (B < 1 || L < 1 || H < 1 || d < 1 || T < 1 || q_stride_b < 0 || q_stride_l < 1 || q_stride_h < 1) return DSC_ERR_BAD_ARG;
     if (kv_stride_b < (long long)T * H * d) return DSC_ERR_BAD_ARG;                      // rows of k_ip / v_ip must not overlap
@@ -144,9 +170,11 @@ extern "C" int dsc_ip_xattn_add_f16(const void* q, long long q_stride_b, long lo
     const half_t* kp = static_cast<const half_t*>(k_ip);
     const half_t* vp = static_cast<const half_t*>(v_ip);
     half_t* op = static_cast<half_t*>(io);
+    const half_t* wp = static_cast<const half_t*>(q_weight);
     const float sl = softmax_scale * 1.4426950408889634f;
-#define DSC_IP_LAUNCH(NK) DSC_LAUNCH(ip_xattn_add_kernel<NK>, grid, block, 0, st, qp, q_stride_b, q_stride_l, q_stride_h, kp, vp, \
-                                     kv_stride_b, row_scale, op, L, H, d, T, sl, tpw)
+#define DSC_IP_LAUNCH_M(NK, M) DSC_LAUNCH((ip_xattn_add_kernel<NK, M>), grid, block, 0, st, qp, q_stride_b, q_stride_l, q_stride_h, \
+                                          kp, vp, kv_stride_b, row_scale, op, wp, w_stride_b, L, H, d, T, sl, tpw)
+#define DSC_IP_LAUNCH(NK) do { if (wp) DSC_IP_LAUNCH_M(NK, true); else DSC_IP_LAUNCH_M(NK, false); } while (0)
     switch ((d + 31) / 32) {
         case 1: DSC_IP_LAUNCH(1); break;
         case 2: DSC_IP_LAUNCH(2); break;
@@ -155,5 +183,23 @@ extern "C" int dsc_ip_xattn_add_f16(const void* q, long long q_stride_b, long lo
         default: DSC_IP_LAUNCH(5); break;
     }
 #undef DSC_IP_LAUNCH
+#undef DSC_IP_LAUNCH_M
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+}
+
+extern "C" int dsc_ip_xattn_add_f16(const void* q, long long q_stride_b, long long q_stride_l, long long q_stride_h,
+                                    const void* k_ip, const void* v_ip, long long kv_stride_b, const float* row_scale, void* io,
+                                    int B, int L, int H, int d, int T, float softmax_scale, void* stream) {
+    return ip_xattn_add(q, q_stride_b, q_stride_l, q_stride_h, k_ip, v_ip, kv_stride_b, row_scale, io, nullptr, 0, B, L, H, d, T,
+                        softmax_scale, stream);
+}
+
+extern "C" int dsc_ip_xattn_add_masked_f16(const void* q, long long q_stride_b, long long q_stride_l, long long q_stride_h,
+                                           const void* k_ip, const void* v_ip, long long kv_stride_b, const float* row_scale,
+                                           void* io, const void* q_weight, long long w_stride_b, int B, int L, int H, int d, int T,
+                                           float softmax_scale, void* stream) {
+    if (!q_weight || q_weight == io || w_stride_b < L) return DSC_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(q_weight) & 1) return DSC_ERR_UNSUPPORTED;
+    return ip_xattn_add(q, q_stride_b, q_stride_l, q_stride_h, k_ip, v_ip, kv_stride_b, row_scale, io, q_weight, w_stride_b, B, L, H,
+                        d, T, softmax_scale, stream);
 }

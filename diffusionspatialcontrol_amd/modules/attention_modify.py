@@ -442,6 +442,8 @@ def prepared_ip_rows(region_prompt):
     """The prepared IP-Adapter rows a call carries, or None: region_prompt["ip_rows"] = {processor: [(k_ip, v_ip, row_scale), ...
     one per adapter]} with k_ip / v_ip [B, T, H * d] fp16 (to_k_ip / to_v_ip of the adapter's image tokens of every batch row,
     computed once per request; a batch stride is allowed) and row_scale [B] fp32 on the device (0: the row has no image prompt).
+    A fourth element is the adapter's region mask as one weight per query: a [B, L] fp16 buffer for the layer's query count, or
+    a {L: buffer} dict resolved by the layer's L (`ip_adapter_masks` down-sampled once per request; ones: no mask).
     The continuous batcher's captured step passes them (modules/serving.py): the buffers are static, their contents change
     between replays.  Every other caller hands the image tokens over as the reference does, as (text, [tokens])."""
     if not isinstance(region_prompt, dict):
@@ -560,14 +562,20 @@ class _IPAdapterProcessor(_RegionProcessor, nn.Module):
     def _ip_rows_branch(self, q4, hidden_states, rows, ip_adapter_masks, sc):
         """the static route of the continuous batcher: one launch per adapter adds row_scale[b] * softmax(q k_ip^T) v_ip to the text
         branch's output in place (dsc_ip_xattn_add_f16) - instead of _ip_branch's two GEMMs, attention, multiply and add with
-        a scale baked in as a Python float"""
+        a scale baked in as a Python float.  Rows with a fourth element carry the region mask as per-query weights
+        (dsc_ip_xattn_add_masked_f16) - instead of _ip_branch's interpolate, repeat and multiply per layer and step"""
         if ip_adapter_masks is not None:
-            raise ValueError("`ip_adapter_masks` are not supported with prepared IP-Adapter rows (the continuous batcher)")
+            raise ValueError("`ip_adapter_masks` are not supported with prepared IP-Adapter rows (the continuous batcher hands masks "
+                             "over inside the rows, as per-query weights)")
         if len(rows) != len(self.num_tokens):
             raise ValueError(f"prepared IP-Adapter rows for {len(rows)} adapters, the processor holds {len(self.num_tokens)}")
         B, L, H, d = q4.shape
-        for k_ip, v_ip, row_scale in rows:
-            ops.ip_xattn_add(q4, k_ip.unflatten(-1, (H, d)), v_ip.unflatten(-1, (H, d)), row_scale, hidden_states, scale=sc)
+        for k_ip, v_ip, row_scale, *rest in rows:
+            qw = rest[0] if rest else None
+            if isinstance(qw, dict):
+                qw = qw[L]
+            ops.ip_xattn_add(q4, k_ip.unflatten(-1, (H, d)), v_ip.unflatten(-1, (H, d)), row_scale, hidden_states, scale=sc,
+                             q_weight=qw)
         return hidden_states
 
     def forward(self, *a, **k):

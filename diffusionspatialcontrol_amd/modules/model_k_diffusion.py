@@ -25,6 +25,8 @@ Batches of B > 1 images use the reference's row layout [u_0..u_{B-1}, c_0..c_{B-
 per image (`n_std_groups = B`), which is what B separate reference calls compute (the reference itself cannot batch:
 external_k_diffusion.py:109-114 broadcasts c_in[B] against input[2B]).
 """
+import contextlib
+import gc
 import importlib
 import inspect
 import os
@@ -73,6 +75,24 @@ def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
 
 
 _CAPTURE_LOCK = threading.RLock()
+
+
+@contextlib.contextmanager
+def _capture_without_gc():
+    """Around a stream capture.  A cyclic collection that starts INSIDE a capture finalizes whatever dead cycles exist at that
+    moment - a dropped ServingBatcher and its executor refer to each other and hold CUDAGraphs, a stream, events and graph-pool
+    memory - and releasing those while a global-mode capture is open aborted the process (seen in a batcher's capture after
+    other batchers had been dropped; which collection lands inside a capture depends only on allocation counts).
+    torch.cuda.graph used to collect before every capture and no longer does (torch >= 2.9, force_cudagraph_gc): collect here,
+    outside the capture, and keep the collector off until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class StableDiffusionPipeline:
@@ -536,20 +556,24 @@ class StableDiffusionPipeline:
             return latents_process
         return [self.latent_to_image(latents, output_type)]
 
-    def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77):
+    def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77,
+              ip_masks: bool = False):
         """Continuous-batching server (modules/serving.py): requests join a running batch at any step boundary, each at its own
         point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
-        stats / warm)."""
+        stats / warm).  `ip_masks=True` (IP-Adapters loaded): requests may carry the reference's
+        `cross_attention_kwargs={"ip_adapter_masks": ...}`, the region mask of each image prompt."""
         from .serving import ServingBatcher
-        return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len)
+        return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len,
+                              ip_masks=ip_masks)
 
     def serve_hires(self, height: int = 512, width: int = 512, upscale_x: float = 1.25, max_batch: int = 8, buckets=(1, 2, 4, 8),
-                    text_len: int = 77, slots=(0, 1)):
+                    text_len: int = 77, slots=(0, 1), ip_masks: bool = False):
         """Continuous-batching server for requests with a hires pass (reference :1176-1228): a batcher at `height` x `width`
         chained to one at the target size of `upscale_x` (_hires_pass's expression), on two workspace slots.  A request with
         `upscale=True` runs its first pass on the one, is enlarged and re-noised on the device (dsc_latent_resample_noise) and
         finishes on the other; requests without it are served at the base size as by `serve`.  Returns a `HiresPair` with the
-        batcher's surface (submit / step / run_until_idle / start / stop / stats / warm)."""
+        batcher's surface (submit / step / run_until_idle / start / stop / stats / warm).  `ip_masks=True` builds both batchers for
+        `ip_adapter_masks` (see `serve`); the second pass down-samples a request's mask at its own levels."""
         from .latent_resample import hires_target_size
         from .serving import HiresPair, ServingBatcher
         th, tw = hires_target_size(height, width, upscale_x, self.vae_scale_factor)
@@ -569,7 +593,7 @@ class StableDiffusionPipeline:
                              f"forward the skip sizes to its upsamplers (the reference's `upsample_size`), so latents must be "
                              f"multiples of {m} (txt2img(upscale=True) has the same limit).  Choose an upscale_x whose target is a "
                              f"multiple of {8 * m} pixels, e.g. 1.25 or 1.5 at 512")
-        kw = dict(max_batch=max_batch, buckets=buckets, text_len=text_len)
+        kw = dict(max_batch=max_batch, buckets=buckets, text_len=text_len, ip_masks=ip_masks)
         return HiresPair(ServingBatcher(self, height, width, slot=slots[0], **kw), ServingBatcher(self, th, tw, slot=slots[1], **kw))
 
     def txt2img_coalesced(self, requests, height: int = 512, width: int = 512, num_inference_steps: int = 50,
@@ -1220,7 +1244,7 @@ class StableDiffusionPipeline:
             st["run"] = lambda: st.__setitem__("eps", step())
         else:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _capture_without_gc(), torch.cuda.graph(g):
                 st["eps"] = step()
             st["graph"] = g
             st["run"] = g.replay

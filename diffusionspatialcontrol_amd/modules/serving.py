@@ -57,6 +57,17 @@ row_scale on the device: idle slots and requests without an image prompt carry s
 their rows are bit for bit those of a batcher without an adapter; joins, leaves and a changed scale need no capture.  The
 sampler launches do not know about any of it, so every request kind, sampler and guidance rescale combines with an image prompt.
 
+Region masks of image prompts.  A batcher built with `ip_masks=True` takes the reference's
+`cross_attention_kwargs={"ip_adapter_masks": [n_adapters, 1, Hm, Wm]}` (app.py:1077-1091; both IP-Adapter processors multiply the
+adapter's output by the down-sampled mask, attention_modify.py:371-385 / :676-685).  After down-sampling a mask is one number per
+query, so at admission the request's mask is down-sampled ONCE per adapter and cross-attention level of this batcher
+(IPAdapterMaskProcessor.downsample, the restatement txt2img's eager route runs per layer and step) and rounded to fp16; the
+captured step hands every IP layer a static [rows, L] weight buffer per adapter (ones: no mask) and launches
+dsc_ip_xattn_add_masked_f16, which folds the weight into its per-query coefficient and skips 16-query tiles of zeros.  `refresh`
+writes a member's weights to rows {i, n + i} (the reference repeats the mask over the batch, unconditional rows included).  A
+batcher built without `ip_masks` launches the unmasked entry as before and refuses the key.  A hires request's second pass
+down-samples the same mask at the target size's levels.
+
 The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
 request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
 """
@@ -101,14 +112,14 @@ class _Request:
     __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
                  "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known",
                  "family", "snoise", "skipout", "noise", "rescale", "eta", "hires", "second", "ready", "hnoise", "t_handoff",
-                 "ip_embeds", "ip_scale", "ip_rows")
+                 "ip_embeds", "ip_scale", "ip_rows", "ip_weights")
 
 
 class ServingBatcher:
     """See the module docstring.  `executor` is the device side (default: the captured-graph executor on the pipeline's GPU);
     the scheduling here is host logic only."""
 
-    def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None):
+    def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False):
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
             raise ValueError(f"serve: buckets {buckets} must cover max_batch={max_batch}")
@@ -140,6 +151,11 @@ class ServingBatcher:
             raise ValueError(f"serve: a loaded IP-Adapter has {max(self._ip_tokens)} image tokens; the batcher's image-token attention "
                              f"(dsc_ip_xattn_add_f16) takes at most {ops.IP_MAX_TOKENS} (ops.IP_MAX_TOKENS) - the 257-token Full "
                              f"projection runs through txt2img(ip_adapter_image_embeds=...)")
+        # requests may carry `ip_adapter_masks`: the step hands per-query weights to the masked entry (see the module docstring)
+        self.ip_masks = bool(ip_masks)
+        if self.ip_masks and not self._ip:
+            raise ValueError("serve: `ip_masks=True` on a pipeline without an IP-Adapter (pipe.load_ip_adapter first, then build the "
+                             "batcher)")
         self.exec = executor if executor is not None else _GraphExecutor(self)
 
     # ------------------------------------------------------------------ public interface
@@ -178,7 +194,10 @@ class ServingBatcher:
         with `mask_image`).  On a pipeline with IP-Adapters loaded: `ip_adapter_image_embeds` (a list with one tensor per loaded
         adapter, each [negative; positive] along dim 0 with ONE image per half - what txt2img takes, see encode_image; absent /
         None: the request runs without an image prompt beside those that have one) and `ip_adapter_scale` (a float, or a list
-        with one entry per adapter; default: the processors' scale at submit time, so set_ip_adapter_scale needs no capture).  On a chained pair (chain_hires) `upscale=True` adds the hires pass: `upscale_x` (2.0), `upscale_method`
+        with one entry per adapter; default: the processors' scale at submit time, so set_ip_adapter_scale needs no capture); on a
+        batcher built with `ip_masks=True` also `cross_attention_kwargs={"ip_adapter_masks": t}`, t [n_adapters, 1, Hm, Wm]: each
+        adapter's term is multiplied by its mask, down-sampled per level as the reference does (ignored without an image prompt).
+        On a chained pair (chain_hires) `upscale=True` adds the hires pass: `upscale_x` (2.0), `upscale_method`
         ("bicubic"), `upscale_antialias`, `upscale_denoising_strength` (0.7), `sampler_name_hires`, `sampler_opt_hires` (default:
         the first pass's), `hires_latents` ([1, 4, H/8, W/8] unit noise of the second pass; default: drawn from `generator` after
         the first pass's draws) and `region_map_state_hires` (default: `region_map_state`; None: no region condition in the second
@@ -294,7 +313,10 @@ class ServingBatcher:
         if request.get("ip_adapter_image") is not None:
             raise ValueError("serve: `ip_adapter_image` (a raw image) is not supported: encode it once with pipe.encode_image and "
                              "pass `ip_adapter_image_embeds` ([negative; positive] per loaded adapter)")
+        ip_masks = self._ip_masks_of(request)
         ip_embeds, ip_scale = self._ip_request(request)
+        # masks without an image prompt (or with every scale 0) have nothing to weigh: accepted and ignored
+        ip_weights = self._ip_mask_weights(ip_masks) if ip_embeds is not None and ip_masks is not None else None
         pos, neg = request.get("prompt_embeds"), request.get("negative_prompt_embeds")
         if pos is None or neg is None:
             raise ValueError("serve: a request needs prompt_embeds and negative_prompt_embeds ([1, S, ctx] each)")
@@ -311,7 +333,7 @@ class ServingBatcher:
         if r.steps < 1:
             raise ValueError("serve: num_inference_steps must be >= 1")
         r.second, r.hires, r.ready, r.hnoise, r.t_handoff = second, None, None, None, None
-        r.ip_embeds, r.ip_scale, r.ip_rows = ip_embeds, ip_scale, None
+        r.ip_embeds, r.ip_scale, r.ip_rows, r.ip_weights = ip_embeds, ip_scale, None, ip_weights
         t_start = self._image_request(r)
         r.guidance = g
         r.output_type = request.get("output_type", "latent")
@@ -377,9 +399,6 @@ class ServingBatcher:
     def _ip_request(self, request):
         """submit-time checks of the image-prompt keys -> (embeds or None, one scale per loaded adapter; all 0 without embeds)"""
         n = len(self._ip_tokens)
-        kw = request.get("cross_attention_kwargs")
-        if isinstance(kw, dict) and kw.get("ip_adapter_masks") is not None:
-            raise ValueError("serve: `ip_adapter_masks` (cross_attention_kwargs) are not supported (use txt2img)")
         embeds, scale = request.get("ip_adapter_image_embeds"), request.get("ip_adapter_scale")
         if scale is None:
             scale = [float(v) for v in self._ip[0][1].scale] if n else []
@@ -411,6 +430,33 @@ class ServingBatcher:
         if all(v == 0.0 for v in scale):
             return None, scale                                      # nothing to add: no projection work, the rows stay skipped
         return list(embeds), scale
+
+    def _ip_masks_of(self, request):
+        """submit-time checks of `ip_adapter_masks` (cross_attention_kwargs) -> the [n_adapters, 1, Hm, Wm] tensor or None"""
+        kw = request.get("cross_attention_kwargs")
+        masks = kw.get("ip_adapter_masks") if isinstance(kw, dict) else None
+        if masks is None:
+            return None
+        if not self.ip_masks:
+            raise ValueError("serve: `ip_adapter_masks` (cross_attention_kwargs) are not supported by this batcher: build it with "
+                             "`ip_masks=True` (pipe.serve(..., ip_masks=True)), or use txt2img")
+        n = len(self._ip_tokens)
+        if not torch.is_tensor(masks) or masks.ndim != 4 or masks.shape[1] != 1:
+            raise ValueError(f"serve: `ip_adapter_masks` must be a tensor of shape [num_ip_adapter, 1, height, width], got "
+                             f"{list(masks.shape) if torch.is_tensor(masks) else type(masks).__name__}")
+        if masks.shape[0] != n:
+            raise ValueError(f"serve: `ip_adapter_masks` holds {masks.shape[0]} masks, the pipeline has {n} IP-Adapter(s) loaded")
+        if not torch.is_floating_point(masks) or masks.shape[2] < 1 or masks.shape[3] < 1 or not bool(torch.isfinite(masks).all()):
+            raise ValueError("serve: `ip_adapter_masks` must hold finite floating-point values")
+        return masks
+
+    def _ip_mask_weights(self, masks):
+        """once per request: per adapter {L: [L] fp16}, its mask down-sampled to every cross-attention level of THIS batcher as
+        the processors' eager route does per layer and step (IPAdapterMaskProcessor.downsample in the mask's own dtype, then the
+        query dtype: attention_modify.py:373-376 + :381 / :672-675 + :681)"""
+        from .attention_modify import IPAdapterMaskProcessor
+        return [{L: IPAdapterMaskProcessor.downsample(masks[a], 1, L, 1)[0, :, 0].to(torch.float16) for L in self.levels()}
+                for a in range(masks.shape[0])]
 
     def _prepare_device(self, r):
         """the device half of _prepare, in the order the pipeline's one generator is consumed: start latent, then step noise"""
@@ -449,6 +495,9 @@ class ServingBatcher:
         if sampling.linear_family(name2) is None:
             raise ValueError(f"serve: `sampler_name_hires` {getattr(name2, '__name__', name2)!r} has no per-row step (supported: "
                              f"{', '.join(sampling.LINEAR_FAMILY)}; use txt2img)")
+        if self.ip_masks and not hi.ip_masks and self._ip_masks_of(request) is not None:
+            raise ValueError("serve: `ip_adapter_masks` with `upscale`: the chained hires batcher was built without `ip_masks=True` "
+                             "(pipe.serve_hires(..., ip_masks=True) builds both with it)")
         noise = request.get("hires_latents")
         want = (1, 4, th // 8, tw // 8)
         if noise is not None and (not torch.is_tensor(noise) or tuple(noise.shape) != want):
@@ -780,6 +829,8 @@ class _GraphExecutor:
         r.text = (neg.to(device=dev, dtype=dt), pos.to(device=dev, dtype=dt))
         if r.ip_embeds is not None:
             self._ip_request_rows(r)
+            if r.ip_weights is not None:                 # on the device, in memory of this stream, until the request leaves
+                r.ip_weights = [{L: w.to(dev).clone() for L, w in per.items()} for per in r.ip_weights]
 
     @torch.no_grad()
     def _ip_request_rows(self, r):
@@ -949,6 +1000,9 @@ class _GraphExecutor:
             # one flat buffer and one row_scale vector per adapter; scale 0 (idle / no image prompt): the row's contents are never read
             st["ip"] = [{"buf": torch.zeros(rows, w, device=dev, dtype=dt), "scale": torch.zeros(rows, device=dev, dtype=torch.float32)}
                         for w in self.ip_width]
+            # (ip_masks) per adapter and level the weight of every query of every row: ones until a masked member is refreshed in
+            st["ipw"] = [{L: torch.ones(rows, L, device=dev, dtype=dt) for L in self.b.levels()} for _ in self.ip_width] \
+                if self.b.ip_masks else None
         kw = {"region_prompt": {"region_state": zero, "compressed": st["compressed"], "sigma": st["sigma"], "weight_func": None,
                                 "n_std_groups": n, "sigma_per_group": True}}
         if self.ip_layers:
@@ -957,8 +1011,9 @@ class _GraphExecutor:
                 per = []
                 for a, T in enumerate(self.ip_tokens):
                     off, m, buf = self.ip_offsets[a][j], T * proc.hidden_size, st["ip"][a]["buf"]
-                    per.append((buf[:, off:off + m].unflatten(-1, (T, proc.hidden_size)),
-                                buf[:, off + m:off + 2 * m].unflatten(-1, (T, proc.hidden_size)), st["ip"][a]["scale"]))
+                    row = (buf[:, off:off + m].unflatten(-1, (T, proc.hidden_size)),
+                           buf[:, off + m:off + 2 * m].unflatten(-1, (T, proc.hidden_size)), st["ip"][a]["scale"])
+                    per.append(row + (st["ipw"][a],) if st["ipw"] is not None else row)
                 ip_rows[proc] = per
             kw["region_prompt"]["ip_rows"] = ip_rows
         unet = pipe.unet
@@ -973,8 +1028,9 @@ class _GraphExecutor:
                 st["eps"] = step()
         if ops.GRAPHS_ENABLED:
             torch.cuda.current_stream(dev).wait_stream(side)
+            from .model_k_diffusion import _capture_without_gc
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _capture_without_gc(), torch.cuda.graph(g):
                 st["eps"] = step()
             side.wait_stream(torch.cuda.current_stream(dev))
             st["graph"] = g
@@ -1004,6 +1060,17 @@ class _GraphExecutor:
                 scales[i] = scales[n + i] = float(r.ip_scale[a])
         return scales
 
+    @staticmethod
+    def ip_row_weights(n, members, a, L, device=None):
+        """[2 n, L] fp16 query weights of adapter a at level L for bucket n: a masked member's down-sampled mask at rows
+        {i, n + i} (the reference repeats the mask over the batch, unconditional rows included); ones for idle slots, members
+        without a mask and members without an image prompt (whose rows are skipped by their scale 0 anyway)"""
+        out = torch.ones(2 * n, L, dtype=torch.float16, device=device)
+        for i, r in enumerate(members):
+            if r is not None and r.ip_embeds is not None and r.ip_weights is not None:
+                out[i] = out[n + i] = r.ip_weights[a][L]
+        return out
+
     def refresh(self, n, members):
         """text rows, their packed K/V, the compressed tables and (IP-Adapters) the image-token rows and scales of bucket n for
         these slot members (None = IDLE)"""
@@ -1031,6 +1098,9 @@ class _GraphExecutor:
                         ip["buf"][i].copy_(r.ip_rows[a][0])
                         ip["buf"][n + i].copy_(r.ip_rows[a][1])
                 ip["scale"].copy_(torch.tensor(scales, dtype=torch.float32).pin_memory(), non_blocking=True)
+                if st["ipw"] is not None:
+                    for L, buf in st["ipw"][a].items():
+                        buf.copy_(self.ip_row_weights(n, members, a, L, device=self.device))
             self.pipe._refresh_text_kv(text)
             comp = self.pipe._compress_tables(dense)
             if comp is None:

@@ -316,13 +316,16 @@ def self_attention(q, k, v, scale=None, out=None):
 IP_MAX_TOKENS = 16         # DSC_IP_MAX_TOKENS (include/dsc_hip.h): the image tokens of one adapter are one MFMA tile
 
 
-def ip_xattn_add(q4, k_ip, v_ip, row_scale, io, scale=None):
+def ip_xattn_add(q4, k_ip, v_ip, row_scale, io, scale=None, q_weight=None):
     """io[b, l, h, :] += row_scale[b] * softmax(scale * q4[b, l, h, :] . k_ip[b, :, h, :]^T) . v_ip[b, :, h, :], in place
     (dsc_ip_xattn_add_f16: the IP-Adapter term of a cross-attention layer with one scale per batch row, read on the device).
     q4 [B, L, H, d] fp16 with its strides (a stride-0 batch dimension included), k_ip / v_ip [B, T, H, d] fp16 with contiguous
     batch rows and one common batch stride (views into a buffer with one row per batch row),
     row_scale [B] fp32 on the device, io [B, L, H * d] (or [B, L, H, d]) fp16 contiguous: the text branch's output.  Rows whose
-    scale is 0 are left untouched and their k_ip / v_ip rows are not read.  scale: default 1 / sqrt(d).  Returns io."""
+    scale is 0 are left untouched and their k_ip / v_ip rows are not read.  scale: default 1 / sqrt(d).  q_weight: [B, L] fp16
+    with unit inner stride (a batch stride is allowed), one weight per query multiplied into the term - the down-sampled
+    IP-Adapter region mask (dsc_ip_xattn_add_masked_f16): queries with weight 0 are not written and 16-query tiles of zeros are
+    not read; a weight of 1 gives the bits of the call without weights.  Returns io."""
     _require_gpu(q4, k_ip, v_ip, row_scale, io)
     if q4.dtype != torch.float16 or k_ip.dtype != torch.float16 or v_ip.dtype != torch.float16 or io.dtype != torch.float16:
         raise TypeError("ip_xattn_add: q4 / k_ip / v_ip / io must be fp16")
@@ -349,10 +352,25 @@ def ip_xattn_add(q4, k_ip, v_ip, row_scale, io, scale=None):
         raise ValueError("ip_xattn_add: all operands must be on one device")
     if sb % 8 or sl % 8 or sh % 8 or skb % 8 or any(t.data_ptr() % 16 for t in (q4, k_ip, v_ip, io)):
         raise ValueError("ip_xattn_add: q4's strides must be multiples of 8 elements and every tensor 16-byte aligned")
+    sc = float(scale) if scale else float(d) ** -0.5
+    if q_weight is not None:
+        if not torch.is_tensor(q_weight) or q_weight.dtype != torch.float16 or tuple(q_weight.shape) != (B, L) \
+                or q_weight.stride(1) != 1:
+            got = f"{q_weight.dtype} {tuple(q_weight.shape)} {q_weight.stride()}" if torch.is_tensor(q_weight) else type(q_weight).__name__
+            raise ValueError(f"ip_xattn_add: q_weight must be an fp16 [{B}, {L}] tensor with unit inner stride, got {got}")
+        if q_weight.device != q4.device:
+            raise ValueError("ip_xattn_add: all operands must be on one device")
+        swb = q_weight.stride(0) if B > 1 else L
+        if swb < L:
+            raise ValueError(f"ip_xattn_add: q_weight's batch stride {swb} is below its row length {L} (rows would overlap)")
+        _drop_gn_partials(io)
+        rc = _lib.load_library().dsc_ip_xattn_add_masked_f16(_p(q4), sb, sl, sh, _p(k_ip), _p(v_ip), skb, _p(row_scale), _p(io),
+                                                             _p(q_weight), swb, B, L, H, d, T, sc, _stream_ptr(q4))
+        _lib.check(rc, "dsc_ip_xattn_add_masked_f16")
+        return io
     _drop_gn_partials(io)
     rc = _lib.load_library().dsc_ip_xattn_add_f16(_p(q4), sb, sl, sh, _p(k_ip), _p(v_ip), skb, _p(row_scale), _p(io), B, L,
-                                                  H, d, T,
-                                                  float(scale) if scale else float(d) ** -0.5, _stream_ptr(q4))
+                                                  H, d, T, sc, _stream_ptr(q4))
     _lib.check(rc, "dsc_ip_xattn_add_f16")
     return io
 

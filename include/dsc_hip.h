@@ -649,6 +649,28 @@ int dsc_ip_xattn_add_f16(const void* q, long long q_stride_b, long long q_stride
                          const void* k_ip, const void* v_ip, long long kv_stride_b, const float* row_scale, void* io,
                          int B, int L, int H, int d, int T, float softmax_scale, void* stream);
 
+/*
+ * dsc_ip_xattn_add_f16 with one weight per query: the IP-Adapter region mask (`ip_adapter_masks`) of the reference, which both
+ * IP-Adapter processors down-sample to one value per query, convert to the query dtype and multiply into the adapter's attention
+ * output before `scale *` and the add (modules/attention_modify.py:371-385 / :676-685):
+ *     io[b, l, h, :] = fp16( float(io[b, l, h, :]) + ((row_scale[b] * float(q_weight[b, l])) / sum) * (V^T P^T)[.., l] )
+ * q_weight [B, L] fp16, unit inner stride, w_stride_b >= L elements between batch rows, read from DEVICE memory like row_scale
+ * (a captured launch stays valid when a mask changes).  Weights are not clamped (bicubic down-sampling overshoots: they may be
+ * negative or above 1).  The coefficient is formed in that order: a weight of 1.0 gives the bits of dsc_ip_xattn_add_f16.  Same
+ * kernel body as the unmasked entry (a compile-time flag), same launch geometry, arguments and limits.
+ * A query whose weight is 0 is NOT stored: its io bits stay as they were, whatever q holds there.  A 16-query tile (queries
+ * 16 t .. 16 t + 15 of one (b, h)) whose weights are all 0 issues no q load, no io load and no store: the decision is one
+ * wave-uniform ballot over the 16 halfs w[b, 16 t ..], requested ahead of the tile's q / io loads (a tile ahead inside a wave
+ * that walks several), so tiles that are not skipped do not wait on it.  row_scale[b] == 0 still returns before anything else
+ * of row b is read, its weights included.
+ * DSC_ERR_BAD_ARG also for: null q_weight, q_weight == io, w_stride_b < L.  DSC_ERR_UNSUPPORTED also for: q_weight not 2-byte
+ * aligned.  No workspace, no LDS, no allocation, no atomics, one fixed summation order.
+ */
+int dsc_ip_xattn_add_masked_f16(const void* q, long long q_stride_b, long long q_stride_l, long long q_stride_h,
+                                const void* k_ip, const void* v_ip, long long kv_stride_b, const float* row_scale, void* io,
+                                const void* q_weight, long long w_stride_b, int B, int L, int H, int d, int T, float softmax_scale,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

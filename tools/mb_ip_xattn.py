@@ -8,6 +8,12 @@ call reads the same buffers, so what fits the caches (L2 4 MB per XCD, Infinity 
 step, where q and io were written by the two launches before; --sets N rotates over N buffer sets instead (N x the working set).
 `bound_fraction` = (6 B L C bytes / kernel time) / --peak-gbs: the q read, the io read and the io write against the HBM peak.
 
+The masked leg (one more line per level, 4 tokens): dsc_ip_xattn_add_masked_f16 with query weights of all ones, of ones on the top
+half of the image and zeros below, and of all zeros, beside the unmasked entry on the same inputs (all-ones / unmasked = what the
+weights cost a row without a mask; half / all-ones = what skipping all-zero tiles buys) and beside the eager route with a mask:
+the five ops above plus IPAdapterMaskProcessor.downsample (a bicubic interpolate, a repeat to [B, L, C]) and a multiply, as
+`_ip_branch` runs them in every layer and step.
+
     python tools/mb_ip_xattn.py [--calls 20] [--replays 50] [--sets 1] [--peak-gbs 8000]
 """
 import argparse
@@ -19,6 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffusionspatialcontrol_amd import ops  # noqa: E402
+from diffusionspatialcontrol_amd.modules.attention_modify import IPAdapterMaskProcessor  # noqa: E402
 
 LEVELS = [(4096, 40), (1024, 80), (256, 160), (64, 160)]        # (L, d) of SD1.5's cross-attention layers, 8 heads
 H, ROWS, CTX = 8, 16, 768
@@ -101,6 +108,42 @@ def main():
                               "bound_fraction": round(traffic / best / 1e3 / a.peak_gbs, 3),
                               "note": "us per call, device events around graph replays (no host work); fastest of three runs for "
                                       "achieved_gbs; eager = 2 library GEMMs + region_xattn (no table) + multiply + add"}), flush=True)
+            if T != 4:
+                continue
+            weights = {"ones": torch.ones(ROWS, L, dtype=torch.float16, device="cuda")}
+            weights["half"] = weights["ones"].clone()
+            weights["half"][:, L // 2:] = 0.0
+            weights["zero"] = torch.zeros_like(weights["ones"])
+            mask = torch.zeros(1, 512, 512, device="cuda")
+            mask[:, :256] = 1.0
+
+            def masked(name):
+                def fn(i):
+                    s = sets[i % len(sets)]
+                    ops.ip_xattn_add(s["q"], s["k"], s["v"], row_scale, s["io"], q_weight=weights[name])
+                return fn
+
+            def eager_masked(i):
+                s = sets[i % len(sets)]
+                k4 = torch.nn.functional.linear(s["tok"], wk).view(ROWS, T, H, d)
+                v4 = torch.nn.functional.linear(s["tok"], wv).view(ROWS, T, H, d)
+                o = ops.region_xattn(s["q"], k4, v4, None, layout="blhd", ref_fp16_rounding=False).reshape(ROWS, L, C)
+                o = o * IPAdapterMaskProcessor.downsample(mask, ROWS, L, C).to(dtype=o.dtype)
+                s["out"] = s["io"] + 1e-3 * o
+
+            legs = [kernel, masked("ones"), masked("half"), masked("zero"), eager_masked]
+            graphs = [graph_of(f, a.calls) for f in legs]
+            for gr in graphs:
+                timed(gr, 5, a.calls)
+            runs = [[timed(gr, a.replays, a.calls) for gr in graphs] for _ in range(3)]          # alternating
+            best = [min(r[j] for r in runs) for j in range(len(legs))]
+            print(json.dumps({"leg": "masked", "L": L, "d": d, "heads": H, "rows": ROWS, "tokens": T, "sets": a.sets,
+                              "unmasked_us": [round(r[0], 2) for r in runs], "masked_all_ones_us": [round(r[1], 2) for r in runs],
+                              "masked_top_half_us": [round(r[2], 2) for r in runs], "masked_all_zero_us": [round(r[3], 2) for r in runs],
+                              "eager_route_with_mask_us": [round(r[4], 2) for r in runs],
+                              "all_ones_over_unmasked": round(best[1] / best[0], 3), "top_half_over_all_ones": round(best[2] / best[1], 3),
+                              "note": "us per call as above, ratios of the fastest of three runs; eager = the five ops + bicubic "
+                                      "interpolate + repeat + multiply"}), flush=True)
 
 
 if __name__ == "__main__":

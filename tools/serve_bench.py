@@ -1,7 +1,7 @@
 """Continuous-batching serving measurements (modules/serving.py) on one GPU; one JSON line per leg.
 
     python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
-                                [--hires X] [--ip-adapter]
+                                [--hires X] [--ip-adapter [--ip-masks]]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -28,6 +28,9 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
               adapter with seeded random weights loaded - on an IP-capable batcher, first with no image prompt at all (what every
               step pays for 16 launches that return early), then with an image prompt on every other request; and one-at-a-time
               txt2img(fused=True) with the image prompt
+  ip_masks    (--ip-adapter --ip-masks: after the leg above) a batcher built with `ip_masks=True` on a third slot: the same mixed
+              requests without any mask (what the weight buffers of ones cost), then with a half-image `ip_adapter_masks` on
+              every other image-prompt request, alternating with the IP-capable batcher of the leg above
 """
 import argparse
 import json
@@ -125,7 +128,11 @@ def main():
                     help="only the hires leg: a chained pair, every other request with upscale_x = X (1.0 .. 2.0)")
     ap.add_argument("--ip-adapter", action="store_true",
                     help="only the IP-Adapter leg: every other request carries an image prompt (random adapter weights, 4 tokens)")
+    ap.add_argument("--ip-masks", action="store_true",
+                    help="with --ip-adapter: also a mask-capable batcher, every other image-prompt request with a half-image mask")
     a = ap.parse_args()
+    if a.ip_masks and not a.ip_adapter:
+        ap.error("--ip-masks goes with --ip-adapter")
     from diffusionspatialcontrol_amd.modules.model_k_diffusion import SD15Scheduler, StableDiffusionPipeline
     from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNet2DConditionModel, UNetConfig
     torch.manual_seed(0)
@@ -181,6 +188,22 @@ def main():
             pipe.txt2img(None, **one)
         torch.cuda.synchronize()
         emit(leg="ip_adapter_one_at_a_time", steps=25, txt2img_fused_with_image_prompt_img_s=round(4 / (time.perf_counter() - t0), 2))
+        if a.ip_masks:
+            bm = pipe.serve(512, 512, max_batch=8, slot=2, ip_masks=True).warm()
+            half = torch.zeros(1, 1, 512, 512, device="cuda")
+            half[:, :, :256] = 1.0                            # the adapter acts on the top half of the image
+            masked = [dict(r, cross_attention_kwargs={"ip_adapter_masks": half}) if i % 4 == 3 else dict(r) for i, r in enumerate(mixed)]
+            for group in (mixed[:8], masked[:8]):
+                run_full(bm, group, kw25)
+            runs = []
+            for _ in range(3):
+                runs.append((run_full(b, mixed, kw25), run_full(bm, mixed, kw25), run_full(bm, masked, kw25)))
+            emit(leg="ip_masks", requests=len(reqs), steps=25, tokens=4, layers=len(cross),
+                 ip_capable_every_other_with_image_prompt_img_s=[round(t[0][0], 2) for t in runs],
+                 mask_capable_same_requests_no_mask_img_s=[round(t[1][0], 2) for t in runs],
+                 mask_capable_every_other_image_prompt_masked_img_s=[round(t[2][0], 2) for t in runs],
+                 captures_after_warm=bm.stats()["captures_after_warm"],
+                 note="three alternating runs; the mask is ones on the top half of the image, down-sampled once per request")
         return
 
     if a.hires is not None:
