@@ -68,6 +68,19 @@ writes a member's weights to rows {i, n + i} (the reference repeats the mask ove
 batcher built without `ip_masks` launches the unmasked entry as before and refuses the key.  A hires request's second pass
 down-samples the same mask at the target size's levels.
 
+T2I-Adapter.  A batcher built with `t2i_adapter=True` on a pipeline with an adapter (setup_model_t2i_adapter) takes the pipeline's
+own `image_t2i_adapter` / `adapter_conditioning_scale` / `adapter_conditioning_factor`.  The adapter network runs ONCE per
+request, at admission (preprocessing_t2i_adapter's line for one image, without the CFG duplication: features times scale in
+fp16), and the request holds its four feature maps until it leaves.  Every bucket owns one static feature buffer
+[n, C_k, h_k, w_k] per down block and one fp32 gate vector [2 n]; the captured step hands both to the UNet as
+`down_intrablock_gated`, which adds `gate[r] * feats[k][r % n]` where the reference adds its residuals
+(u_net_condition_modify.py:1194-1230), one launch of dsc_add_rows_gated_f16 per down block.  `refresh` copies a member's
+features into its slot row on a membership change; the gate of rows {i, n + i} is 1 while the member's model call k (counted in
+its own schedule) satisfies k < int(steps_denoising * factor) - _adapter_hook's window - and 0 otherwise, for idle slots and
+for members without a control image: those rows keep their bits and their feature rows are never read.  The gate vector is
+uploaded only when it changes; a window that closes costs that one small copy and no refresh.  The sampler launches do not know
+about any of it.  A batcher built without the flag captures the step it captured before and refuses the key.
+
 The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
 request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
 """
@@ -87,6 +100,7 @@ from .external_k_diffusion import DiscreteVDDPMDenoiser
 
 MAX_TEXT_KEYS = 384                  # the chunked prepared-operand kernels (ops.region_xattn_packed)
 _UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter")
+_T2I_HINT = {"image_t2i_adapter": "; a batcher built with `t2i_adapter=True` (pipe.serve(..., t2i_adapter=True)) serves it"}
 
 
 def _ip_layers(pipe):
@@ -112,14 +126,15 @@ class _Request:
     __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
                  "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known",
                  "family", "snoise", "skipout", "noise", "rescale", "eta", "hires", "second", "ready", "hnoise", "t_handoff",
-                 "ip_embeds", "ip_scale", "ip_rows", "ip_weights")
+                 "ip_embeds", "ip_scale", "ip_rows", "ip_weights", "adapter", "adapter_limit", "adapter_feats")
 
 
 class ServingBatcher:
     """See the module docstring.  `executor` is the device side (default: the captured-graph executor on the pipeline's GPU);
     the scheduling here is host logic only."""
 
-    def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False):
+    def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
+                 t2i_adapter=False):
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
             raise ValueError(f"serve: buckets {buckets} must cover max_batch={max_batch}")
@@ -136,9 +151,10 @@ class ServingBatcher:
         self._done = []                        # (request, handle) whose final row copy is in flight
         self._n = None                         # bucket whose eps is pending (None: nothing ran yet / the batch drained)
         self._members = {}                     # bucket -> per-slot request ids its static buffers were last refreshed for
+        self._gates = {}                       # bucket -> the adapter gate vector last uploaded for it (absent: zeros, as captured)
         self._next_id = 0
         self._stats = collections.Counter(captures=0, joins=0, leaves=0, bucket_switches=0, steps=0, refreshes=0,
-                                          linear_transitions=0, handoffs=0)
+                                          linear_transitions=0, handoffs=0, adapter_gate_updates=0)
         self._hires = None                     # the chained batcher of the hires pass (chain_hires)
         self._warm_captures = None
         self._thread = None
@@ -156,12 +172,63 @@ class ServingBatcher:
         if self.ip_masks and not self._ip:
             raise ValueError("serve: `ip_masks=True` on a pipeline without an IP-Adapter (pipe.load_ip_adapter first, then build the "
                              "batcher)")
+        # requests may carry `image_t2i_adapter`: the step hands the UNet per-slot features and a per-row gate (module docstring)
+        self.t2i = bool(t2i_adapter)
+        self._adapter = getattr(pipe, "adapter", None) if self.t2i else None
+        self._adapter_shapes = self._adapter_setup() if self.t2i else None
         self.exec = executor if executor is not None else _GraphExecutor(self)
+
+    def _adapter_setup(self):
+        """the adapter against the UNet, at construction -> [(C_k, h_k, w_k)] of the feature each down block adds: as many maps
+        as down blocks, the UNet's channels, and the size of the tensor the add lands on.  Both sides are computed from their own
+        modules' parameters (the adapter's PixelUnshuffle and pooling, the UNet's stride-2 convolutions), not assumed equal."""
+        from .t2i_adapter import MultiAdapter
+        pipe, ad = self.pipe, self._adapter
+        if ad is None:
+            raise ValueError("serve: `t2i_adapter=True` on a pipeline without a T2I-Adapter "
+                             "(modules.t2i_adapter.setup_model_t2i_adapter(pipe, adapter) first, then build the batcher)")
+        unet = pipe.unet
+        # the UNet: block k adds after its last attention (before its downsampler) or, without attention, after the whole block
+        h, w = self.height // 8, self.width // 8
+        want = []
+        for c, blk in zip(unet.config.block_out_channels, unet.down_blocks):
+            size = (h, w)
+            if hasattr(blk, "downsamplers"):
+                conv = blk.downsamplers[0].conv
+                h, w = ((v + 2 * conv.padding[i] - conv.kernel_size[i]) // conv.stride[i] + 1 for i, v in enumerate((h, w)))
+                if not blk.has_attn:
+                    size = (h, w)
+            want.append((int(c), int(size[0]), int(size[1])))
+        for a, one in enumerate(ad.adapters if isinstance(ad, MultiAdapter) else [ad]):
+            full = getattr(one, "adapter", None)
+            if full is None or not hasattr(full, "body") or not hasattr(full, "unshuffle"):
+                raise ValueError(f"serve: `t2i_adapter=True`: adapter {a} is not a full_adapter T2IAdapter (the type the batcher serves)")
+            f = int(full.unshuffle.downscale_factor)
+            if self.height % f or self.width % f:
+                raise ValueError(f"serve: `t2i_adapter=True`: {self.height}x{self.width} is not a multiple of the adapter's "
+                                 f"downscale factor {f}")
+            ah, aw = self.height // f, self.width // f
+            got = []
+            for blk in full.body:
+                pool = blk.downsample
+                if pool is not None:
+                    k_, s_ = int(pool.kernel_size), int(pool.stride)
+                    ah, aw = ((-(-(v - k_) // s_) if pool.ceil_mode else (v - k_) // s_) + 1 for v in (ah, aw))
+                got.append((int(blk.resnets[-1].block2.out_channels), int(ah), int(aw)))
+            if len(got) != len(want):
+                raise ValueError(f"serve: `t2i_adapter=True`: adapter {a} gives {len(got)} feature maps, the UNet has {len(want)} "
+                                 f"down blocks")
+            if got != want:
+                raise ValueError(f"serve: `t2i_adapter=True`: adapter {a}'s feature maps (C, h, w) {got} do not match what the "
+                                 f"UNet's down blocks add to at {self.height}x{self.width}: {want}")
+        return want
 
     # ------------------------------------------------------------------ public interface
     def warm(self):
         """capture every bucket's step now (otherwise each is captured on first use)"""
         with self._lock:
+            if self.t2i:
+                self.exec.warm_adapter()             # the adapter's convolutions pay their first-call cost here, not at a join
             for n in self.buckets:
                 self._ensure(n)
             self._warm_captures = self._stats["captures"]
@@ -201,7 +268,11 @@ class ServingBatcher:
         ("bicubic"), `upscale_antialias`, `upscale_denoising_strength` (0.7), `sampler_name_hires`, `sampler_opt_hires` (default:
         the first pass's), `hires_latents` ([1, 4, H/8, W/8] unit noise of the second pass; default: drawn from `generator` after
         the first pass's draws) and `region_map_state_hires` (default: `region_map_state`; None: no region condition in the second
-        pass).  Returns a Future of the final output."""
+        pass).  On a batcher built with `t2i_adapter=True`: `image_t2i_adapter` (a [1, 3, H, W] tensor in [0, 1] of this
+        batcher's size or a PIL image; a list with one per adapter when pipe.adapter is a MultiAdapter), `adapter_conditioning_scale`
+        (default 1.0; a list for a MultiAdapter) and `adapter_conditioning_factor` (in [0, 1], default 1.0: the fraction of the
+        request's steps that carry the control) - the pipeline methods' own keys; not with `upscale`.  Returns a Future of the
+        final output."""
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -266,6 +337,7 @@ class ServingBatcher:
             raise TypeError("serve: a request is a dict (txt2img_coalesced's request + num_inference_steps / sampler_opt / "
                             "guidance_scale)")
         self._check_ip_current()
+        adapter = self._adapter_request(request)
         if request.get("upscale") and not second:
             return self._prepare_hires_pair(request)
         v_pred = bool(getattr(pipe, "v_prediction", False))
@@ -308,8 +380,8 @@ class ServingBatcher:
         if wf is not None and not weight_func_is_default(wf):
             raise ValueError("serve: a custom weight_func is not supported (use txt2img)")
         for k in _UNSUPPORTED_KEYS:
-            if request.get(k) is not None:
-                raise ValueError(f"serve: `{k}` (ControlNet / T2I-Adapter) is not supported (use txt2img)")
+            if request.get(k) is not None and not (self.t2i and k == "image_t2i_adapter"):
+                raise ValueError(f"serve: `{k}` (ControlNet / T2I-Adapter) is not supported (use txt2img)" + _T2I_HINT.get(k, ""))
         if request.get("ip_adapter_image") is not None:
             raise ValueError("serve: `ip_adapter_image` (a raw image) is not supported: encode it once with pipe.encode_image and "
                              "pass `ip_adapter_image_embeds` ([negative; positive] per loaded adapter)")
@@ -334,6 +406,7 @@ class ServingBatcher:
             raise ValueError("serve: num_inference_steps must be >= 1")
         r.second, r.hires, r.ready, r.hnoise, r.t_handoff = second, None, None, None, None
         r.ip_embeds, r.ip_scale, r.ip_rows, r.ip_weights = ip_embeds, ip_scale, None, ip_weights
+        r.adapter, r.adapter_limit, r.adapter_feats = adapter, 0, None
         t_start = self._image_request(r)
         r.guidance = g
         r.output_type = request.get("output_type", "latent")
@@ -343,6 +416,15 @@ class ServingBatcher:
         r.sig = sig if sig is not None else r.sig_dev.detach().float().cpu().tolist()
         if t_start:                                                  # img2img / inpaiting keep the schedule's tail (:637-647)
             r.sig, r.sig_dev = r.sig[t_start:], r.sig_dev[t_start:]
+        if r.adapter is not None:
+            # the window: what the pipeline method of this kind of request passes to _adapter_hook as `steps_denoising` is the
+            # length of the sigma schedule the sampler walks, final sigma included - len(sigmas) for txt2img
+            # (model_k_diffusion.py:530), len(sigma_sched) = len(sigmas[t_start:]) for img2img (:839), len(sigmas) after the
+            # `sigmas[t_start:]` of :940 for inpainting (:994) - and r.sig is that schedule for all three.  Every sampler served
+            # here makes one model call per step at a distinct sigma, so the hook's count of distinct sigmas seen is the step index
+            r.adapter_limit = int(len(r.sig) * r.adapter["factor"])
+            if r.adapter_limit < 1:
+                r.adapter = None                                     # no model call carries it: no adapter forward, no rows
         r.family = family
         r.rescale = phi
         eta = r.eta = float(request.get("eta", 1.0))
@@ -386,6 +468,73 @@ class ServingBatcher:
         if device:
             self._prepare_device(r)
         return r
+
+    def _adapter_request(self, request):
+        """submit-time checks of the T2I-Adapter keys -> {"image", "scale", "factor"} or None (no control image, or nothing to
+        add: every scale 0 / factor 0)"""
+        image = request.get("image_t2i_adapter")
+        if not self.t2i:
+            return None                                              # (the key itself is refused with the other unsupported keys)
+        from .t2i_adapter import MultiAdapter
+        if getattr(self.pipe, "adapter", None) is not self._adapter:
+            raise RuntimeError("serve: the pipeline's T2I-Adapter changed since this batcher was built (setup_model_t2i_adapter): "
+                               "build a new one with pipe.serve(..., t2i_adapter=True)")
+        multi = isinstance(self._adapter, MultiAdapter)
+        n = self._adapter.num_adapter if multi else 1
+        scale, factor = request.get("adapter_conditioning_scale", 1.0), request.get("adapter_conditioning_factor", 1.0)
+        scale = 1.0 if scale is None else scale
+        factor = 1.0 if factor is None else factor
+
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and v not in (float("inf"), float("-inf"))
+
+        if isinstance(scale, (list, tuple)):
+            if not multi:
+                raise ValueError("serve: `adapter_conditioning_scale` is a list, but pipe.adapter is one adapter (a list goes with a "
+                                 "MultiAdapter)")
+            if len(scale) != n:
+                raise ValueError(f"serve: `adapter_conditioning_scale` lists {len(scale)} scales, pipe.adapter holds {n} adapters")
+            if not all(number(v) for v in scale):
+                raise ValueError(f"serve: `adapter_conditioning_scale` must hold finite numbers, got {list(scale)!r}")
+            scale = [float(v) for v in scale]
+        elif not number(scale):
+            raise ValueError(f"serve: `adapter_conditioning_scale` must be a finite number (or a list of them for a MultiAdapter), "
+                             f"got {scale!r}")
+        else:
+            scale = float(scale)
+        if not number(factor) or not 0.0 <= factor <= 1.0:
+            raise ValueError(f"serve: `adapter_conditioning_factor` must be a number in [0, 1], got {factor!r}")
+        if image is None:
+            return None
+        if request.get("upscale"):
+            raise ValueError("serve: `image_t2i_adapter` with `upscale` (a control image in the hires pass) is not served yet; use "
+                             "txt2img")
+        images = list(image) if isinstance(image, (list, tuple)) else [image]
+        if isinstance(image, (list, tuple)) != multi or len(images) != n:
+            raise ValueError(f"serve: `image_t2i_adapter` must be " + (f"a list of {n} images (pipe.adapter is a MultiAdapter)" if multi
+                             else "one image (a list goes with a MultiAdapter)") +
+                             f", got {f'a list of {len(images)}' if isinstance(image, (list, tuple)) else type(image).__name__}")
+        for one in images:
+            if torch.is_tensor(one):
+                cin = (self._adapter.adapters[0] if multi else self._adapter).config.in_channels
+                if one.dim() != 4 or one.shape[0] != 1 or one.shape[1] != cin or not torch.is_floating_point(one) \
+                        or tuple(one.shape[-2:]) != (self.height, self.width):
+                    raise ValueError(f"serve: `image_t2i_adapter` as a tensor must be a floating-point [1, {cin}, {self.height}, "
+                                     f"{self.width}] image in [0, 1] (this batcher's size), got {one.dtype} {list(one.shape)}")
+            elif not (hasattr(one, "size") and hasattr(one, "resize") and not hasattr(one, "shape")):
+                raise ValueError(f"serve: `image_t2i_adapter` must be a [1, 3, H, W] tensor or a PIL image, got {type(one).__name__}")
+        if factor == 0.0 or all(v == 0.0 for v in (scale if isinstance(scale, list) else [scale])):
+            return None                                              # nothing to add: no adapter forward, the rows stay skipped
+        return {"image": images if multi else images[0], "scale": scale, "factor": float(factor)}
+
+    def _adapter_gates(self, n, members):
+        """the gate vector of bucket n for the model call about to run: 1.0 at rows {i, n + i} of a member whose call index
+        (r.i, counted in its own schedule) is inside its adapter window, 0.0 for every other row"""
+        gates = [0.0] * (2 * n)
+        for i, r in enumerate(members):
+            if r is not None and r.adapter is not None and r.i < r.adapter_limit:
+                gates[i] = gates[n + i] = 1.0
+        return gates
 
     def _check_ip_current(self):
         """the captured steps were built for the IP-Adapter processors of construction time (their to_k_ip / to_v_ip, the static
@@ -690,6 +839,7 @@ class ServingBatcher:
             r.hnoise = None                          # (a second-pass record: its start noise was read before it joined)
             r.known = None                           # its image / noise / mask rows go back to the allocator (stream-ordered)
             r.noise = None                           # ... and its noise table
+            r.adapter_feats = None                   # ... and its adapter features
             self._stats["leaves"] += 1
         for r in stepping:
             r.i += 1
@@ -702,6 +852,14 @@ class ServingBatcher:
                 self._stats["refreshes"] += 1
             if self._n is not None and n_dst != self._n:
                 self._stats["bucket_switches"] += 1
+            if self.t2i:
+                # (after r.i moved on: r.i is the index of the model call that runs now.)  Only a changed vector is uploaded, and
+                # a window that closes changes nothing else: no text, K/V or table work
+                gates = self._adapter_gates(n_dst, rows)
+                if self._gates.get(n_dst, [0.0] * (2 * n_dst)) != gates:
+                    self.exec.set_adapter_gates(n_dst, gates)
+                    self._gates[n_dst] = gates
+                    self._stats["adapter_gate_updates"] += 1
             self.exec.run(n_dst)
             self._stats["steps"] += 1
         self._n = n_dst
@@ -831,6 +989,38 @@ class _GraphExecutor:
             self._ip_request_rows(r)
             if r.ip_weights is not None:                 # on the device, in memory of this stream, until the request leaves
                 r.ip_weights = [{L: w.to(dev).clone() for L, w in per.items()} for per in r.ip_weights]
+        if r.adapter is not None:
+            self._adapter_rows(r)
+
+    @torch.no_grad()
+    def _adapter_rows(self, r):
+        """once per request: the adapter network on its control image(s), features times scale in the adapter's dtype
+        (t2i_adapter.adapter_features: preprocessing_t2i_adapter's lines before the CFG duplication), channels-last"""
+        from .t2i_adapter import adapter_features
+        feats = adapter_features(self.pipe, r.adapter["image"], self.b.width, self.b.height, r.adapter["scale"])
+        got = [tuple(int(v) for v in f.shape) for f in feats]
+        want = [(1,) + s for s in self.b._adapter_shapes]
+        if got != want:
+            raise ValueError(f"serve: `image_t2i_adapter` gives feature maps {got}, this batcher's step takes {want}")
+        r.adapter_feats = [f.to(device=self.device, dtype=self.dtype).contiguous(memory_format=torch.channels_last) for f in feats]
+
+    @torch.no_grad()
+    def warm_adapter(self):
+        """one adapter forward on a blank image (the convolution library's first-call cost, outside any request)"""
+        from .t2i_adapter import MultiAdapter, adapter_features
+        ad = self.b._adapter
+        multi = isinstance(ad, MultiAdapter)
+        cin = (ad.adapters[0] if multi else ad).config.in_channels
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            blank = torch.zeros(1, cin, self.b.height, self.b.width)
+            adapter_features(self.pipe, [blank] * ad.num_adapter if multi else blank, self.b.width, self.b.height,
+                             [1.0] * ad.num_adapter if multi else 1.0)
+
+    def set_adapter_gates(self, n, gates):
+        """the bucket's gate vector (read by the captured dsc_add_rows_gated_f16 launches) <- these 2 n values"""
+        with torch.cuda.stream(self.stream):
+            self.st[n]["adapter"]["gate"].copy_(torch.tensor(gates, dtype=torch.float32).pin_memory(), non_blocking=True)
 
     @torch.no_grad()
     def _ip_request_rows(self, r):
@@ -1003,6 +1193,11 @@ class _GraphExecutor:
             # (ip_masks) per adapter and level the weight of every query of every row: ones until a masked member is refreshed in
             st["ipw"] = [{L: torch.ones(rows, L, device=dev, dtype=dt) for L in self.b.levels()} for _ in self.ip_width] \
                 if self.b.ip_masks else None
+            # (t2i_adapter) one feature row per slot and down block, one gate per batch row: all gates 0 until a member's window
+            # opens, and a row whose gate is 0 is never read
+            st["adapter"] = {"feats": [torch.empty((n,) + shp, device=dev, dtype=dt).contiguous(memory_format=torch.channels_last).zero_()
+                                       for shp in self.b._adapter_shapes],
+                             "gate": torch.zeros(rows, device=dev, dtype=torch.float32)} if self.b.t2i else None
         kw = {"region_prompt": {"region_state": zero, "compressed": st["compressed"], "sigma": st["sigma"], "weight_func": None,
                                 "n_std_groups": n, "sigma_per_group": True}}
         if self.ip_layers:
@@ -1017,10 +1212,12 @@ class _GraphExecutor:
                 ip_rows[proc] = per
             kw["region_prompt"]["ip_rows"] = ip_rows
         unet = pipe.unet
+        # a batcher built without `t2i_adapter` calls the UNet exactly as it did before the keyword existed
+        gated = {"down_intrablock_gated": (st["adapter"]["feats"], st["adapter"]["gate"])} if st["adapter"] is not None else {}
 
         def step():
             return unet(st["x_in"], st["t"], encoder_hidden_states=st["text"], cross_attention_kwargs=kw,
-                        temb_adds=st["tadd"], cfg_shared_prefix=ops.USE_CFG_SHARED_PREFIX).sample
+                        temb_adds=st["tadd"], cfg_shared_prefix=ops.USE_CFG_SHARED_PREFIX, **gated).sample
 
         side = self.stream
         with torch.cuda.stream(side):
@@ -1072,8 +1269,8 @@ class _GraphExecutor:
         return out
 
     def refresh(self, n, members):
-        """text rows, their packed K/V, the compressed tables and (IP-Adapters) the image-token rows and scales of bucket n for
-        these slot members (None = IDLE)"""
+        """text rows, their packed K/V, the compressed tables, (IP-Adapters) the image-token rows and scales and (T2I-Adapter) the
+        feature rows of bucket n for these slot members (None = IDLE)"""
         st = self.st[n]
         S = self.b.text_len
         with torch.cuda.stream(self.stream):
@@ -1101,6 +1298,11 @@ class _GraphExecutor:
                 if st["ipw"] is not None:
                     for L, buf in st["ipw"][a].items():
                         buf.copy_(self.ip_row_weights(n, members, a, L, device=self.device))
+            if st["adapter"] is not None:                # members without a control image are skipped: their rows are never read
+                for i, r in enumerate(members):
+                    if r is not None and r.adapter_feats is not None:
+                        for buf, f in zip(st["adapter"]["feats"], r.adapter_feats):
+                            buf[i].copy_(f[0])
             self.pipe._refresh_text_kv(text)
             comp = self.pipe._compress_tables(dense)
             if comp is None:

@@ -140,15 +140,20 @@ def setup_model_t2i_adapter(class_name, adapter=None):
     class_name.adapter = adapter
 
 
-def preprocessing_t2i_adapter(class_name, image, width, height, adapter_conditioning_scale, num_images_per_prompt=1):
-    """reference :90-117: the adapter's features, scaled, repeated per image and duplicated for CFG"""
+def adapter_features(class_name, image, width, height, adapter_conditioning_scale):
+    """reference :90-108: the adapter's features times the conditioning scale, in the adapter's dtype (one entry per down block) -
+    preprocessing_t2i_adapter before the repeat per image and the CFG duplication (what the continuous batcher stores per slot)"""
     ad = class_name.adapter
     if isinstance(ad, MultiAdapter):
         inputs = [_preprocess_adapter_image(one, height, width).to(device=class_name.device, dtype=ad.dtype) for one in image]
-        state = ad(inputs, adapter_conditioning_scale)
-    else:
-        inp = _preprocess_adapter_image(image, height, width).to(device=class_name.device, dtype=ad.dtype)
-        state = [v * adapter_conditioning_scale for v in ad(inp)]
+        return ad(inputs, adapter_conditioning_scale)
+    inp = _preprocess_adapter_image(image, height, width).to(device=class_name.device, dtype=ad.dtype)
+    return [v * adapter_conditioning_scale for v in ad(inp)]
+
+
+def preprocessing_t2i_adapter(class_name, image, width, height, adapter_conditioning_scale, num_images_per_prompt=1):
+    """reference :90-117: the adapter's features, scaled, repeated per image and duplicated for CFG"""
+    state = adapter_features(class_name, image, width, height, adapter_conditioning_scale)
     if num_images_per_prompt > 1:
         state = [v.repeat(num_images_per_prompt, 1, 1, 1) for v in state]
     if class_name.do_classifier_free_guidance:

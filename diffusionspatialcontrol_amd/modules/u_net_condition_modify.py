@@ -737,13 +737,34 @@ class _EncoderHalf:
             return ops.conv3x3_fewcin(sample, wt, ci.bias, ci.out_channels)   # NCHW latents -> NHWC features, one launch
         return ci(sample.contiguous()).contiguous(memory_format=torch.channels_last)
 
-    def _run_down(self, x, temb_act, tadd, encoder_hidden_states, cross_attention_kwargs, intrablock=None, skip0=None):
+    @staticmethod
+    def _add_gated(x, feat, gate, in_place):
+        """x[r] + gate[r] * feat[r % F]: the static form of the intra-block add (one launch of dsc_add_rows_gated_f16 on the
+        GPU; rows with gate 0 keep their bits and never read `feat`).  Elsewhere the same values in torch ops."""
+        if x.is_cuda and x.dtype == torch.float16:
+            if not ops.add_rows_gated_supported(x, feat):
+                raise ValueError(f"down_intrablock_gated: a feature map {tuple(feat.shape)} {feat.stride()} {feat.dtype} does not fit "
+                                 f"the block's output {tuple(x.shape)} {x.stride()} (fp16, channels-last, the same C x h x w, "
+                                 f"batch rows a multiple of the feature rows)")
+            return ops.add_rows_gated(x, feat, gate, out=x if in_place else None)
+        g = gate.to(device=x.device).reshape(-1, 1, 1, 1)
+        f = feat.to(x.dtype).repeat(x.shape[0] // feat.shape[0], 1, 1, 1)
+        y = torch.where(g == 0, x, x + g.to(x.dtype) * f)
+        return x.copy_(y) if in_place else y
+
+    def _run_down(self, x, temb_act, tadd, encoder_hidden_states, cross_attention_kwargs, intrablock=None, skip0=None,
+                  gated=None):
         """intrablock: T2I-Adapter features, one per down block (reference :1194-1230): added after the LAST resnet /
-        attention pair of a cross-attention block (so the skip tensor carries it), after the whole block otherwise"""
+        attention pair of a cross-attention block (so the skip tensor carries it), after the whole block otherwise.
+        gated = (feats, gate): the same features at the same places as `x[r] + gate[r] * feats[k][r % F]` with the gate read on
+        the device (a captured step: which rows carry the term is data) - in place where the skip carries the term, into a new
+        tensor where the skip appended before it must keep the values without it."""
         intrablock = None if intrablock is None else list(intrablock)
+        g_feats, g_gate = (list(gated[0]), gated[1]) if gated is not None else (None, None)
         skips = [x if skip0 is None else skip0]                      # (skip0: conv_in's output for the WHOLE batch when x is its shared half)
-        for blk in self.down_blocks:
+        for k, blk in enumerate(self.down_blocks):
             extra = intrablock.pop(0) if intrablock else None
+            g_extra = g_feats[k] if g_feats is not None else None
             last = len(blk.resnets) - 1
             for j, res in enumerate(blk.resnets):
                 x = res(x, temb_act, tadd[res])
@@ -754,12 +775,16 @@ class _EncoderHalf:
                                  for s_ in skips]
                     if j == last and extra is not None:
                         x = x + extra.to(x.dtype)
+                    if j == last and g_extra is not None:
+                        x = self._add_gated(x, g_extra, g_gate, in_place=True)
                 skips.append(x)
             if hasattr(blk, "downsamplers"):
                 x = blk.downsamplers[0](x)
                 skips.append(x)
             if not blk.has_attn and extra is not None:
                 x = x + extra.to(x.dtype)
+            if not blk.has_attn and g_extra is not None:
+                x = self._add_gated(x, g_extra, g_gate, in_place=False)
         return skips, x
 
     def _run_mid(self, x, temb_act, tadd, encoder_hidden_states, cross_attention_kwargs):
@@ -901,9 +926,22 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
                 attention_mask=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
                 down_intrablock_additional_residuals=None, encoder_attention_mask=None, return_dict=True, temb_adds=None,
-                cfg_shared_prefix=False):
+                cfg_shared_prefix=False, down_intrablock_gated=None):
         if attention_mask is not None or encoder_attention_mask is not None:
             raise NotImplementedError("attention masks are not on the hot path (never passed by app.py)")
+        # down_intrablock_gated = (feats, gate): the static form of down_intrablock_additional_residuals for a captured step that
+        # serves a batch - feats one channels-last [F, C_k, h_k, w_k] tensor per down block (batch row r reads row r % F), gate
+        # fp32 [B] in device memory: row r gets `gate[r] * feats[k][r % F]` where the other keyword adds its tensor (_run_down)
+        if down_intrablock_gated is not None:
+            if down_intrablock_additional_residuals is not None or down_block_additional_residuals is not None \
+                    or mid_block_additional_residual is not None:
+                raise ValueError("down_intrablock_gated and down_intrablock_additional_residuals / down_block_additional_residuals "
+                                 "/ mid_block_additional_residual are mutually exclusive")
+            g_feats, g_gate = down_intrablock_gated
+            if len(g_feats) != len(self.down_blocks):
+                raise ValueError(f"down_intrablock_gated: {len(g_feats)} feature maps for {len(self.down_blocks)} down blocks")
+            if not torch.is_tensor(g_gate) or tuple(g_gate.shape) != (sample.shape[0],) or g_gate.dtype != torch.float32:
+                raise ValueError(f"down_intrablock_gated: gate must be an fp32 [{sample.shape[0]}] tensor (one per batch row)")
         # temb_adds: a [B, temb_width()] buffer holding this timestep's rows of temb_add_table() - the time-embedding path
         # is then not run (the captured step of the fused loop: its caller refreshes the buffer between replays)
         temb_act = None if temb_adds is not None else self._time_act(sample, timestep)
@@ -937,7 +975,7 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
             # legacy T2I-Adapter usage (reference :1200-1211): residuals without a mid residual are intra-block ones
             down_intrablock_additional_residuals, down_block_additional_residuals = down_block_additional_residuals, None
         skips, x = self._run_down(x, temb_act, tadd, encoder_hidden_states, cross_attention_kwargs,
-                                  intrablock=down_intrablock_additional_residuals, skip0=skip0)
+                                  intrablock=down_intrablock_additional_residuals, skip0=skip0, gated=down_intrablock_gated)
         if down_block_additional_residuals is not None:          # ControlNet hook (reference :1236-1245)
             skips = [s + r for s, r in zip(skips, down_block_additional_residuals)]
         x = self._run_mid(x, temb_act, tadd, encoder_hidden_states, cross_attention_kwargs)

@@ -1363,3 +1363,8 @@ def dpmpp2m_update(x, denoised, old, a, b, c):
 # The hires pass's resample + noise launch (dsc_latent_resample_noise).  Its wrapper lives beside the tap tables it is made of;
 # like every writer here it drops GroupNorm partial sums from its destination (tests/test_hires_gpu.py).
 from .modules.latent_resample import latent_resample_noise, noise_scale_f16  # noqa: E402,F401
+
+
+# the gated per-row residual add of the continuous batcher's T2I-Adapter step (dsc_add_rows_gated_f16): its wrapper lives beside
+# its kernel's name, like modules/latent_resample.py's, and is reached as ops.add_rows_gated / ops.add_rows_gated_supported
+from .gated_add import add_rows_gated, add_rows_gated_supported  # noqa: E402,F401

@@ -671,6 +671,28 @@ int dsc_ip_xattn_add_masked_f16(const void* q, long long q_stride_b, long long q
                                 const void* q_weight, long long w_stride_b, int B, int L, int H, int d, int T, float softmax_scale,
                                 void* stream);
 
+/*
+ * A residual added to a batch of feature rows with one gate per batch row: the T2I-Adapter hook of the continuous batcher's
+ * captured step.  Replaces modules/u_net_condition_modify.py:1194-1230 of the reference (`sample +=
+ * down_intrablock_additional_residuals.pop(0)` inside the down blocks), with "this row has a residual at this step" a device
+ * value, not Python control flow:
+ *     out[r][e] = fp16( float(x[r][e]) + gate[r] * float(feat[r % feat_rows][e]) )        r < rows, e < row_elems
+ * x, out: fp16, `rows` dense rows of row_elems halfs (a channels-last [B, C, h, w] tensor: row_elems = h * w * C).  feat: fp16,
+ * feat_rows rows of the same length, rows % feat_rows == 0 (one row per slot: batch rows i and n + i, the classifier-free-guidance
+ * pair, read row i).  gate [rows] fp32 is read from DEVICE memory (never by value): a captured launch sees the values of the
+ * moment it replays.  One fp32 fma and one fp16 rounding of its fp32 result per element: gate[r] == 1 gives the bits of torch's
+ * fp16 `x + feat`.  gate[r] == 0: the feature row is not read (it may hold anything); with out == x (in place, allowed) the
+ * workgroups of row r return after that one uniform load and the row is neither loaded nor stored; with out != x the row is
+ * copied bit for bit.  The batch row is a grid coordinate (rows <= 65535).
+ * row_elems % 8 == 0; x, feat, out 16-byte aligned, gate 4-byte aligned: 16-byte loads and stores.  No workspace, no LDS, no
+ * allocation, no synchronisation, no atomics, every element written by the one lane that owns it: deterministic and safe under
+ * graph capture.
+ * DSC_ERR_BAD_ARG: null pointer, rows / feat_rows / row_elems < 1, rows % feat_rows != 0, out overlapping x other than out == x,
+ * out overlapping feat or gate.  DSC_ERR_UNSUPPORTED: row_elems % 8 != 0, alignment, rows > 65535.
+ */
+int dsc_add_rows_gated_f16(const void* x, const void* feat, const void* gate, void* out, int rows, int feat_rows,
+                           long long row_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """Continuous-batching serving measurements (modules/serving.py) on one GPU; one JSON line per leg.
 
     python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
-                                [--hires X] [--ip-adapter [--ip-masks]]
+                                [--hires X] [--ip-adapter [--ip-masks]] [--t2i-adapter]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -31,6 +31,11 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
   ip_masks    (--ip-adapter --ip-masks: after the leg above) a batcher built with `ip_masks=True` on a third slot: the same mixed
               requests without any mask (what the weight buffers of ones cost), then with a half-image `ip_adapter_masks` on
               every other image-prompt request, alternating with the IP-capable batcher of the leg above
+  t2i_adapter (--t2i-adapter: this leg only) a T2I-Adapter with seeded random weights set up, then two batchers on two slots: one
+              built without `t2i_adapter` (the step of a pipeline without the feature) and one built with it.  8 slots kept full,
+              three alternating rounds: the plain requests on both (the price of the flag), then every other request with a
+              control image at factor 0.5 on the adapter-capable one; and what admission costs: the GPU time of one request's
+              adapter forward on the batch's stream (what the next step waits for) and the host time of submit with and without
 """
 import argparse
 import json
@@ -130,6 +135,8 @@ def main():
                     help="only the IP-Adapter leg: every other request carries an image prompt (random adapter weights, 4 tokens)")
     ap.add_argument("--ip-masks", action="store_true",
                     help="with --ip-adapter: also a mask-capable batcher, every other image-prompt request with a half-image mask")
+    ap.add_argument("--t2i-adapter", action="store_true",
+                    help="only the T2I-Adapter leg: every other request carries a control image with factor 0.5 (random weights)")
     a = ap.parse_args()
     if a.ip_masks and not a.ip_adapter:
         ap.error("--ip-masks goes with --ip-adapter")
@@ -142,6 +149,52 @@ def main():
     opt = {"scheduler": "karras"}
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    if a.t2i_adapter:
+        from diffusionspatialcontrol_amd.modules import t2i_adapter as t2i
+        torch.manual_seed(a.seed + 7)
+        with torch.device("cuda"):
+            ad = t2i.T2IAdapter(channels=unet.cfg.block_out_channels, num_res_blocks=2)
+        t2i.setup_model_t2i_adapter(pipe, ad.half().eval())
+        off = pipe.serve(512, 512, max_batch=8, slot=0).warm()
+        on = pipe.serve(512, 512, max_batch=8, slot=1, t2i_adapter=True).warm()
+        images = [torch.rand(1, 3, 512, 512, generator=torch.Generator().manual_seed(a.seed * 1000 + 4000 + i)) for i in range(len(reqs))]
+        mixed = [dict(r, image_t2i_adapter=images[i], adapter_conditioning_scale=0.8, adapter_conditioning_factor=0.5) if i % 2
+                 else dict(r) for i, r in enumerate(reqs)]
+        for b, group in ((off, reqs[:8]), (on, reqs[:8]), (on, mixed[:8])):     # one untimed pass each
+            run_full(b, group, kw25)
+        runs = []
+        for _ in range(3):                                # alternating, so that a drift of the box hits all alike
+            runs.append((run_full(off, reqs, kw25), run_full(on, reqs, kw25), run_full(on, mixed, kw25)))
+        emit(leg="t2i_adapter", requests=len(reqs), steps=25, mix="every other request with a control image, scale 0.8, factor 0.5",
+             flag_off_plain_img_s=[round(t[0][0], 2) for t in runs], flag_on_plain_img_s=[round(t[1][0], 2) for t in runs],
+             flag_on_every_other_with_control_img_s=[round(t[2][0], 2) for t in runs],
+             flag_off_plain_steps_s=[round(t[0][1], 1) for t in runs], flag_on_plain_steps_s=[round(t[1][1], 1) for t in runs],
+             adapter_gate_updates=on.stats()["adapter_gate_updates"], captures_after_warm=on.stats()["captures_after_warm"],
+             note="three alternating rounds in one process; the flag-off batcher captures the step of a pipeline without the feature")
+        # admission: the adapter forward runs on the batch's stream at submit; the next step of the batch waits for it
+        host = {"plain": [], "control": []}
+        gpu = []
+        for i in range(1, 7):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = on._prepare(dict(mixed[i], **kw25))
+            host["control" if i % 2 else "plain"].append(time.perf_counter() - t0)
+            if i % 2:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                with torch.cuda.stream(on.exec.stream):
+                    e0.record()
+                    on.exec._adapter_rows(r)
+                    e1.record()
+                torch.cuda.synchronize()
+                gpu.append(e0.elapsed_time(e1))
+        emit(leg="t2i_adapter_admission", adapter_forward_gpu_ms=[round(v, 3) for v in gpu],
+             submit_host_ms_plain=[round(1e3 * v, 3) for v in host["plain"]],
+             submit_host_ms_with_control=[round(1e3 * v, 3) for v in host["control"]],
+             note="gpu: device events around one request's adapter forward (library convolutions) + scale + layout on the batch's "
+                  "stream; host: the whole of submit's preparation on the caller's thread, launches included")
+        emit(leg="stats", flag_off=off.stats(), flag_on=on.stats())
+        return
 
     if a.ip_adapter:
         from diffusionspatialcontrol_amd.modules.u_net_condition_modify import Attention
