@@ -101,12 +101,18 @@ class ControlNetModel(_EncoderHalf, nn.Module):
 
     def forward(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale: float = 1.0,
                 class_labels=None, timestep_cond=None, attention_mask=None, added_cond_kwargs=None,
-                cross_attention_kwargs=None, guess_mode: bool = False, return_dict: bool = True, cond_embedding=None):
+                cross_attention_kwargs=None, guess_mode: bool = False, return_dict: bool = True, cond_embedding=None,
+                unscaled: bool = False):
         """cond_embedding: the conditioning embedding computed beforehand (`conditioning_embedding(image)`) - the pipeline's
         captured step graph keeps it in a static buffer instead of re-running the eight convolutions in every replay;
-        conditioning_scale may be a 0-dim device tensor there (the per-step value is written into it between replays)."""
+        conditioning_scale may be a 0-dim device tensor there (the per-step value is written into it between replays).
+        unscaled=True: the zero convolutions' outputs as they are - no `d * conditioning_scale` launches, conditioning_scale is
+        not read (the continuous batcher applies a per-row scale where it adds them, ops.scatter_add_rows); guess mode and
+        `global_pool_conditions` nets are refused with it."""
         if attention_mask is not None:
             raise NotImplementedError("attention masks are not on the hot path (never passed by app.py)")
+        if unscaled and (guess_mode or self.config.global_pool_conditions):
+            raise ValueError("ControlNetModel.forward(unscaled=True) does not serve guess mode (global_pool_conditions)")
         temb_act = self._time_act(sample, timestep)
         self._to_channels_last_once()
         x = self._conv_in(sample) + (self._cond_embedding(controlnet_cond) if cond_embedding is None else cond_embedding)
@@ -115,7 +121,9 @@ class ControlNetModel(_EncoderHalf, nn.Module):
         x = self._run_mid(x, temb_act, tadd, encoder_hidden_states, cross_attention_kwargs)
         down = [zc(s) for s, zc in zip(skips, self.controlnet_down_blocks)]
         mid = self.controlnet_mid_block(x)
-        if guess_mode and not self.config.global_pool_conditions:
+        if unscaled:                                            # (neither guess mode nor pooling: refused above)
+            pass
+        elif guess_mode and not self.config.global_pool_conditions:
             scales = torch.logspace(-1, 0, len(down) + 1, device=sample.device) * conditioning_scale   # 0.1 .. 1.0
             down = [d * sc for d, sc in zip(down, scales)]
             mid = mid * scales[-1]
@@ -143,9 +151,16 @@ class MultiControlNetModel(nn.Module):
 
     def forward(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale, class_labels=None,
                 timestep_cond=None, attention_mask=None, added_cond_kwargs=None, cross_attention_kwargs=None,
-                guess_mode: bool = False, return_dict: bool = True, cond_embedding=None):
-        down_sum, mid_sum = None, None
+                guess_mode: bool = False, return_dict: bool = True, cond_embedding=None, unscaled: bool = False):
+        """unscaled=True: ([down residuals of net 0, of net 1, ...], [mid residual of net 0, ...]) - every net's zero
+        convolutions' outputs as they are, neither scaled nor summed; conditioning_scale is not read"""
         embs = [None] * len(self.nets) if cond_embedding is None else cond_embedding
+        if unscaled:
+            outs = [net(sample, timestep, encoder_hidden_states, image, guess_mode=guess_mode, return_dict=False,
+                        cross_attention_kwargs=cross_attention_kwargs, cond_embedding=emb, unscaled=True)
+                    for image, net, emb in zip(controlnet_cond, self.nets, embs)]
+            return [o[0] for o in outs], [o[1] for o in outs]
+        down_sum, mid_sum = None, None
         for image, scale, net, emb in zip(controlnet_cond, conditioning_scale, self.nets, embs):
             down, mid = net(sample, timestep, encoder_hidden_states, image, scale, guess_mode=guess_mode, return_dict=False,
                             cross_attention_kwargs=cross_attention_kwargs, cond_embedding=emb)

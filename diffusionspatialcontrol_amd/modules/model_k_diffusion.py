@@ -557,16 +557,19 @@ class StableDiffusionPipeline:
         return [self.latent_to_image(latents, output_type)]
 
     def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77,
-              ip_masks: bool = False, t2i_adapter: bool = False):
+              ip_masks: bool = False, t2i_adapter: bool = False, controlnet: bool = False, control_slots=None):
         """Continuous-batching server (modules/serving.py): requests join a running batch at any step boundary, each at its own
         point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
         stats / warm).  `ip_masks=True` (IP-Adapters loaded): requests may carry the reference's
         `cross_attention_kwargs={"ip_adapter_masks": ...}`, the region mask of each image prompt.  `t2i_adapter=True` (an adapter
         set up with setup_model_t2i_adapter): requests may carry `image_t2i_adapter` / `adapter_conditioning_scale` /
-        `adapter_conditioning_factor`."""
+        `adapter_conditioning_factor`.  `controlnet=True` (a ControlNet set up with setup_controlnet; not together with
+        `t2i_adapter`): requests may carry `control_img` / `controlnet_conditioning_scale` / `control_guidance_start` /
+        `control_guidance_end`; the ControlNet runs on `control_slots` compact lanes (default: max_batch), so a request without a
+        control image does not pay for its neighbours'."""
         from .serving import ServingBatcher
         return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len,
-                              ip_masks=ip_masks, t2i_adapter=t2i_adapter)
+                              ip_masks=ip_masks, t2i_adapter=t2i_adapter, controlnet=controlnet, control_slots=control_slots)
 
     def serve_hires(self, height: int = 512, width: int = 512, upscale_x: float = 1.25, max_batch: int = 8, buckets=(1, 2, 4, 8),
                     text_len: int = 77, slots=(0, 1), ip_masks: bool = False):

@@ -81,6 +81,20 @@ for members without a control image: those rows keep their bits and their featur
 uploaded only when it changes; a window that closes costs that one small copy and no refresh.  The sampler launches do not know
 about any of it.  A batcher built without the flag captures the step it captured before and refuses the key.
 
+ControlNet.  A batcher built with `controlnet=True, control_slots=c` on a pipeline with a ControlNet (setup_controlnet) takes the
+pipeline's own `control_img` / `controlnet_conditioning_scale` / `control_guidance_start` / `control_guidance_end`.  The ControlNet
+does not run over the batch: a request with a control image takes the lowest free of c LANES at admission (lane j = rows j and
+c + j of the ControlNet's own batch) and keeps it until it leaves; with none free it waits at the head of the queue (FIFO).  One
+captured ControlNet graph per batcher reads static lane buffers (x, t, the text rows, one conditioning embedding per net - computed
+once per request at admission) and writes every zero convolution's UNSCALED output into static buffers.  Every bucket owns a dst
+vector [2 c] (the lane of the member in slot i -> batch rows i and n + i; idle: -1), a gather vector and an fp32 gate matrix
+[nets, 2 c]; its captured step hands them to the UNet as `down_block_scattered`, one launch of dsc_scatter_add_rows_f16 per skip
+tensor and one for the mid block's output, where the reference adds its residuals (u_net_condition_modify.py:1236-1245, 1269-1270).
+Per model call with an open gate: the lane rows of the bucket's input and timesteps are gathered, the ControlNet graph replays,
+then the bucket's graph; with no gate open the ControlNet is skipped.  The gate of a request's model call k is
+`scale * keep[min(k, len(keep) - 1)]` (preprocess_controlnet's keep for the step count the pipeline method passes); all gates 0 is a
+plain request (no lane).  A batcher built without the flag captures the step it captured before and refuses the key.
+
 The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
 request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
 """
@@ -98,9 +112,11 @@ from .attention_modify import weight_func_is_default
 from .encode_region_map_function import encode_region_map
 from .external_k_diffusion import DiscreteVDDPMDenoiser
 
+_EMBED_LOCK = threading.Lock()       # around the process-wide deterministic switch in _GraphExecutor._control_embedding
 MAX_TEXT_KEYS = 384                  # the chunked prepared-operand kernels (ops.region_xattn_packed)
 _UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter")
-_T2I_HINT = {"image_t2i_adapter": "; a batcher built with `t2i_adapter=True` (pipe.serve(..., t2i_adapter=True)) serves it"}
+_FLAG_HINT = {"image_t2i_adapter": "; a batcher built with `t2i_adapter=True` (pipe.serve(..., t2i_adapter=True)) serves it",
+             "control_img": "; a batcher built with `controlnet=True` (pipe.serve(..., controlnet=True)) serves it"}
 
 
 def _ip_layers(pipe):
@@ -126,7 +142,8 @@ class _Request:
     __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
                  "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known",
                  "family", "snoise", "skipout", "noise", "rescale", "eta", "hires", "second", "ready", "hnoise", "t_handoff",
-                 "ip_embeds", "ip_scale", "ip_rows", "ip_weights", "adapter", "adapter_limit", "adapter_feats")
+                 "ip_embeds", "ip_scale", "ip_rows", "ip_weights", "adapter", "adapter_limit", "adapter_feats",
+                 "control", "cgates", "lane", "cemb")
 
 
 class ServingBatcher:
@@ -134,7 +151,7 @@ class ServingBatcher:
     the scheduling here is host logic only."""
 
     def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
-                 t2i_adapter=False):
+                 t2i_adapter=False, controlnet=False, control_slots=None):
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
             raise ValueError(f"serve: buckets {buckets} must cover max_batch={max_batch}")
@@ -154,7 +171,8 @@ class ServingBatcher:
         self._gates = {}                       # bucket -> the adapter gate vector last uploaded for it (absent: zeros, as captured)
         self._next_id = 0
         self._stats = collections.Counter(captures=0, joins=0, leaves=0, bucket_switches=0, steps=0, refreshes=0,
-                                          linear_transitions=0, handoffs=0, adapter_gate_updates=0)
+                                          linear_transitions=0, handoffs=0, adapter_gate_updates=0, control_steps=0,
+                                          control_gate_updates=0)
         self._hires = None                     # the chained batcher of the hires pass (chain_hires)
         self._warm_captures = None
         self._thread = None
@@ -174,8 +192,18 @@ class ServingBatcher:
                              "batcher)")
         # requests may carry `image_t2i_adapter`: the step hands the UNet per-slot features and a per-row gate (module docstring)
         self.t2i = bool(t2i_adapter)
+        if controlnet and self.t2i:
+            raise ValueError("serve: `controlnet=True` and `t2i_adapter=True` are not served together yet (build one batcher for each)")
         self._adapter = getattr(pipe, "adapter", None) if self.t2i else None
         self._adapter_shapes = self._adapter_setup() if self.t2i else None
+        # requests may carry `control_img`: a compact ControlNet batch of `control_slots` lanes runs beside the step, and the
+        # step scatters its residuals into the rows of the requests that hold a lane (module docstring)
+        self.cn = bool(controlnet)
+        self._controlnet = getattr(pipe, "controlnet", None) if self.cn else None
+        self.control_slots = (self.max_batch if control_slots is None else int(control_slots)) if self.cn else 0
+        self._control_shapes = self._controlnet_setup() if self.cn else None
+        self._lanes = [None] * self.control_slots     # lane -> the request that holds it
+        self._cstate = {}                      # bucket -> (dst, gather, gates) last uploaded for it (absent: as captured)
         self.exec = executor if executor is not None else _GraphExecutor(self)
 
     def _adapter_setup(self):
@@ -223,12 +251,61 @@ class ServingBatcher:
                                  f"UNet's down blocks add to at {self.height}x{self.width}: {want}")
         return want
 
+    def _control_nets(self):
+        from .controlnet import MultiControlNetModel
+        cn = self._controlnet
+        return list(cn.nets) if isinstance(cn, MultiControlNetModel) else [cn]
+
+    @staticmethod
+    def _skip_shapes(model, h, w):
+        """[(C, h, w)] of the skip tensors an encoder half (the UNet's, a ControlNet's) collects at an h x w latent, the mid
+        block's output last - from the module's own convolutions (conv_in, every ResNet's conv2, the stride-2 downsamplers)"""
+        shapes = [(int(model.conv_in.out_channels), int(h), int(w))]
+        for blk in model.down_blocks:
+            for res in blk.resnets:
+                shapes.append((int(res.conv2.out_channels), int(h), int(w)))
+            if hasattr(blk, "downsamplers"):
+                conv = blk.downsamplers[0].conv
+                h, w = ((v + 2 * conv.padding[i] - conv.kernel_size[i]) // conv.stride[i] + 1 for i, v in enumerate((h, w)))
+                shapes.append((int(conv.out_channels), int(h), int(w)))
+        return shapes + [(int(model.mid_block.resnets[-1].conv2.out_channels), int(h), int(w))]
+
+    def _controlnet_setup(self):
+        """the ControlNet against the UNet, at construction -> [(C, h, w)] of every skip tensor and of the mid block's output,
+        the tensors its residuals are added to.  Both sides are computed from their own modules, not assumed equal."""
+        from .controlnet import ControlNetModel
+        if self._controlnet is None:
+            raise ValueError("serve: `controlnet=True` on a pipeline without a ControlNet (pipe.setup_controlnet(controlnet) first, "
+                             "then build the batcher)")
+        if not 1 <= self.control_slots <= self.max_batch:
+            raise ValueError(f"serve: `control_slots` must be in [1, max_batch = {self.max_batch}], got {self.control_slots}")
+        nets = self._control_nets()
+        from .. import scatter_add
+        if len(nets) > scatter_add.MAX_NETS:
+            raise ValueError(f"serve: `controlnet=True`: {len(nets)} ControlNets; the step's scatter-add takes at most "
+                             f"{scatter_add.MAX_NETS}")
+        want = self._skip_shapes(self.pipe.unet, self.height // 8, self.width // 8)
+        for a, net in enumerate(nets):
+            if not isinstance(net, ControlNetModel):
+                raise ValueError(f"serve: `controlnet=True`: net {a} is a {type(net).__name__}, not a ControlNetModel")
+            if net.config.global_pool_conditions:
+                raise ValueError(f"serve: `controlnet=True`: net {a} is a guess-mode ControlNet (global_pool_conditions), which the "
+                                 "batcher does not serve (use txt2img)")
+            got = self._skip_shapes(net, self.height // 8, self.width // 8)
+            if got != want:
+                raise ValueError(f"serve: `controlnet=True`: net {a}'s residuals (C, h, w) {got} do not match the UNet's skip tensors "
+                                 f"and mid output at {self.height}x{self.width}: {want}")
+        return want
+
     # ------------------------------------------------------------------ public interface
     def warm(self):
         """capture every bucket's step now (otherwise each is captured on first use)"""
         with self._lock:
             if self.t2i:
                 self.exec.warm_adapter()             # the adapter's convolutions pay their first-call cost here, not at a join
+            if self.cn:
+                self._ensure_control()               # the ControlNet graph first: every bucket's step reads its residual buffers
+                self.exec.warm_control()
             for n in self.buckets:
                 self._ensure(n)
             self._warm_captures = self._stats["captures"]
@@ -271,8 +348,11 @@ class ServingBatcher:
         pass).  On a batcher built with `t2i_adapter=True`: `image_t2i_adapter` (a [1, 3, H, W] tensor in [0, 1] of this
         batcher's size or a PIL image; a list with one per adapter when pipe.adapter is a MultiAdapter), `adapter_conditioning_scale`
         (default 1.0; a list for a MultiAdapter) and `adapter_conditioning_factor` (in [0, 1], default 1.0: the fraction of the
-        request's steps that carry the control) - the pipeline methods' own keys; not with `upscale`.  Returns a Future of the
-        final output."""
+        request's steps that carry the control) - the pipeline methods' own keys; not with `upscale`.  On a batcher built with
+        `controlnet=True`: `control_img` (a PIL image or a [1, 3, H, W] tensor in [0, 1]; a list with one per net when
+        pipe.controlnet is a MultiControlNetModel), `controlnet_conditioning_scale` (default 1.0), `control_guidance_start` (0.0)
+        and `control_guidance_end` (1.0) (numbers, or lists with one entry per net) - the pipeline methods' own keys; not with
+        `upscale` or `mask_image`.  Returns a Future of the final output."""
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -338,6 +418,7 @@ class ServingBatcher:
                             "guidance_scale)")
         self._check_ip_current()
         adapter = self._adapter_request(request)
+        control = self._control_request(request, second)
         if request.get("upscale") and not second:
             return self._prepare_hires_pair(request)
         v_pred = bool(getattr(pipe, "v_prediction", False))
@@ -380,8 +461,8 @@ class ServingBatcher:
         if wf is not None and not weight_func_is_default(wf):
             raise ValueError("serve: a custom weight_func is not supported (use txt2img)")
         for k in _UNSUPPORTED_KEYS:
-            if request.get(k) is not None and not (self.t2i and k == "image_t2i_adapter"):
-                raise ValueError(f"serve: `{k}` (ControlNet / T2I-Adapter) is not supported (use txt2img)" + _T2I_HINT.get(k, ""))
+            if request.get(k) is not None and not (self.t2i and k == "image_t2i_adapter") and not (self.cn and k == "control_img"):
+                raise ValueError(f"serve: `{k}` (ControlNet / T2I-Adapter) is not supported (use txt2img)" + _FLAG_HINT.get(k, ""))
         if request.get("ip_adapter_image") is not None:
             raise ValueError("serve: `ip_adapter_image` (a raw image) is not supported: encode it once with pipe.encode_image and "
                              "pass `ip_adapter_image_embeds` ([negative; positive] per loaded adapter)")
@@ -407,6 +488,7 @@ class ServingBatcher:
         r.second, r.hires, r.ready, r.hnoise, r.t_handoff = second, None, None, None, None
         r.ip_embeds, r.ip_scale, r.ip_rows, r.ip_weights = ip_embeds, ip_scale, None, ip_weights
         r.adapter, r.adapter_limit, r.adapter_feats = adapter, 0, None
+        r.control, r.cgates, r.lane, r.cemb = control, None, None, None
         t_start = self._image_request(r)
         r.guidance = g
         r.output_type = request.get("output_type", "latent")
@@ -425,6 +507,15 @@ class ServingBatcher:
             r.adapter_limit = int(len(r.sig) * r.adapter["factor"])
             if r.adapter_limit < 1:
                 r.adapter = None                                     # no model call carries it: no adapter forward, no rows
+        if r.control is not None:
+            # the step count the pipeline method of this kind of request hands preprocess_controlnet: num_inference_steps in
+            # txt2img (model_k_diffusion.py:527), len(sigma_sched) - the truncated schedule, final sigma included - in img2img
+            # (:838).  Every served sampler makes one model call per step at a distinct sigma, so _controlnet_hook's count of
+            # distinct sigmas seen is the call index
+            n_keep = r.steps if r.kind == "txt2img" else len(r.sig)
+            r.cgates = self.control_gates(n_keep, len(r.sig) - 1, r.control["scale"], r.control["start"], r.control["end"])
+            if all(g == 0.0 for call in r.cgates for g in call):
+                r.control, r.cgates = None, None                     # no model call carries it: no lane, no embedding
         r.family = family
         r.rescale = phi
         eta = r.eta = float(request.get("eta", 1.0))
@@ -535,6 +626,93 @@ class ServingBatcher:
             if r is not None and r.adapter is not None and r.i < r.adapter_limit:
                 gates[i] = gates[n + i] = 1.0
         return gates
+
+    def _control_request(self, request, second=False):
+        """submit-time checks of the ControlNet keys -> {"image": [one per net], "scale", "start", "end": one float per net} or
+        None (no control image).  Whether any model call carries it is decided once the schedule is known (_prepare)."""
+        image = request.get("control_img")
+        if not self.cn:
+            return None                                              # (the key itself is refused with the other unsupported keys)
+        from .controlnet import MultiControlNetModel
+        if getattr(self.pipe, "controlnet", None) is not self._controlnet:
+            raise RuntimeError("serve: the pipeline's ControlNet changed since this batcher was built (setup_controlnet): build a "
+                               "new one with pipe.serve(..., controlnet=True)")
+        multi = isinstance(self._controlnet, MultiControlNetModel)
+        n = len(self._control_nets())
+
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and v not in (float("inf"), float("-inf"))
+
+        per_net = {}
+        for key, default in (("controlnet_conditioning_scale", 1.0), ("control_guidance_start", 0.0), ("control_guidance_end", 1.0)):
+            v = request.get(key)
+            v = default if v is None else v
+            if isinstance(v, (list, tuple)):
+                if len(v) != n:
+                    raise ValueError(f"serve: `{key}` lists {len(v)} values, pipe.controlnet holds {n} net(s)")
+                if not all(number(e) for e in v):
+                    raise ValueError(f"serve: `{key}` must hold finite numbers, got {list(v)!r}")
+                per_net[key] = [float(e) for e in v]
+            elif not number(v):
+                raise ValueError(f"serve: `{key}` must be a finite number (or a list with one per net), got {v!r}")
+            else:
+                per_net[key] = [float(v)] * n
+        if image is None:
+            return None
+        if request.get("upscale") or second or self._hires is not None:
+            raise ValueError("serve: `control_img` with `upscale` / on a chained hires pair (a ControlNet in the hires pass) is not "
+                             "served yet; use txt2img")
+        if request.get("mask_image") is not None:
+            raise ValueError("serve: `control_img` with `mask_image` (a ControlNet with inpainting) is not served yet; use inpaiting")
+        images = list(image) if isinstance(image, (list, tuple)) else [image]
+        if isinstance(image, (list, tuple)) != multi or len(images) != n:
+            raise ValueError("serve: `control_img` must be " + (f"a list of {n} images (pipe.controlnet is a MultiControlNetModel)"
+                             if multi else "one image (a list goes with a MultiControlNetModel)") +
+                             f", got {f'a list of {len(images)}' if isinstance(image, (list, tuple)) else type(image).__name__}")
+        for one, net in zip(images, self._control_nets()):
+            if torch.is_tensor(one):
+                cin = int(net.controlnet_cond_embedding.conv_in.in_channels)
+                if one.dim() != 4 or one.shape[0] != 1 or one.shape[1] != cin or not torch.is_floating_point(one) \
+                        or one.shape[2] < 1 or one.shape[3] < 1:
+                    raise ValueError(f"serve: `control_img` as a tensor must be a floating-point [1, {cin}, H, W] image in [0, 1], got "
+                                     f"{one.dtype} {list(one.shape)}")
+            elif not (hasattr(one, "size") and hasattr(one, "resize") and not hasattr(one, "shape")):
+                raise ValueError(f"serve: `control_img` must be a [1, 3, H, W] tensor or a PIL image, got {type(one).__name__}")
+        return {"image": images, "scale": per_net["controlnet_conditioning_scale"], "start": per_net["control_guidance_start"],
+                "end": per_net["control_guidance_end"]}
+
+    @staticmethod
+    def control_keep(n_steps, starts, ends):
+        """preprocess_controlnet's keep schedule (reference :417-424) for one start / end per net: [n_steps][nets] of 1.0 / 0.0"""
+        return [[1.0 - float(i / n_steps < s or (i + 1) / n_steps > e) for s, e in zip(starts, ends)] for i in range(n_steps)]
+
+    @classmethod
+    def control_gates(cls, n_steps, n_calls, scales, starts, ends):
+        """the gates of a request's model calls, [n_calls][nets]: call k carries `scale * keep[min(k, len(keep) - 1)]` per net -
+        _controlnet_hook's `schedule`, python floats, unrounded (the reference multiplies the residuals by that float)"""
+        keep = cls.control_keep(n_steps, starts, ends)
+        return [[s * k for s, k in zip(scales, keep[min(call, len(keep) - 1)])] for call in range(n_calls)]
+
+    def _control_vectors(self, n, members):
+        """(dst, gather, gates) of bucket n for the model call about to run.  Lane j is ControlNet rows j (unconditional) and
+        c + j (conditional); held by the member in slot i it maps to batch rows i and n + i: dst [2 c] (idle: -1), gather [2 c]
+        (the rows of the bucket's input the lane rows are read from; idle: row 0, whose values are computed and never used),
+        gates [nets][2 c] (the member's gates of the call its own schedule is at: r.i; idle: 0)"""
+        c, nets = self.control_slots, len(self._control_nets())
+        dst, gather, gates = [-1] * (2 * c), [0] * (2 * c), [[0.0] * (2 * c) for _ in range(nets)]
+        for i, r in enumerate(members):
+            if r is None or r.control is None:
+                continue
+            j = r.lane
+            assert j is not None and self._lanes[j] is r, f"serve: slot {i}'s request holds no lane"
+            dst[j], dst[c + j] = gather[j], gather[c + j] = i, n + i
+            if r.i < len(r.cgates):
+                for a in range(nets):
+                    gates[a][j] = gates[a][c + j] = float(r.cgates[r.i][a])
+        active = [d for d in dst if d >= 0]
+        # the scatter-add's invariant (ops.scatter_add_rows): no two active lane rows name one batch row
+        assert len(set(active)) == len(active) and all(d < 2 * n for d in active), f"serve: lane rows share a batch row: {dst}"
+        return dst, gather, gates
 
     def _check_ip_current(self):
         """the captured steps were built for the IP-Adapter processors of construction time (their to_k_ip / to_v_ip, the static
@@ -773,6 +951,14 @@ class ServingBatcher:
                 break
             if not self._launch_compatible(head, [r for r in slots if r is not None]):
                 break
+            if head.control is not None:
+                # a ControlNet lane, the lowest free one, kept until the request leaves; with none free the request waits at the
+                # head of the queue although a slot is free (FIFO, the rule of _launch_compatible)
+                lane = next((j for j, holder in enumerate(self._lanes) if holder is None), None)
+                if lane is None:
+                    break
+                head.lane = lane
+                self._lanes[lane] = head
             self._queue.popleft()
             head.slot, head.i = free, 0
             slots[free] = head
@@ -820,6 +1006,8 @@ class ServingBatcher:
             self._ensure(n_dst)
         for r in joins:
             self.exec.load_latent(r)
+            if r.control is not None:
+                self.exec.load_lane(r)               # its text rows and conditioning embedding(s) into the lane's rows
         self._stats["joins"] += len(joins)
         if any(k is not None for k in known):
             if any(rec["mode"] == ops.ROW_STEP and rec["req"].skipout is not None for rec in recs):
@@ -840,6 +1028,9 @@ class ServingBatcher:
             r.known = None                           # its image / noise / mask rows go back to the allocator (stream-ordered)
             r.noise = None                           # ... and its noise table
             r.adapter_feats = None                   # ... and its adapter features
+            if r.lane is not None:                   # ... and its ControlNet lane goes to whoever waits for one
+                self._lanes[r.lane] = None
+                r.lane, r.cemb = None, None
             self._stats["leaves"] += 1
         for r in stepping:
             r.i += 1
@@ -860,6 +1051,20 @@ class ServingBatcher:
                     self.exec.set_adapter_gates(n_dst, gates)
                     self._gates[n_dst] = gates
                     self._stats["adapter_gate_updates"] += 1
+            if self.cn:
+                # (after r.i moved on, as above.)  Each of the three is uploaded only when it differs from what the bucket holds;
+                # the ControlNet itself runs only when some member's gate is open in the coming call
+                dst, gather, gates = self._control_vectors(n_dst, rows)
+                was = self._cstate.get(n_dst, ([-1] * len(dst), [0] * len(gather), [[0.0] * len(dst) for _ in gates]))
+                if (dst, gather, gates) != was:
+                    self.exec.set_control(n_dst, dst if dst != was[0] else None, gather if gather != was[1] else None,
+                                          gates if gates != was[2] else None)
+                    self._cstate[n_dst] = (dst, gather, gates)
+                    if gates != was[2]:
+                        self._stats["control_gate_updates"] += 1
+                if any(g != 0.0 for per in gates for g in per):
+                    self.exec.run_control(n_dst)
+                    self._stats["control_steps"] += 1
             self.exec.run(n_dst)
             self._stats["steps"] += 1
         self._n = n_dst
@@ -881,7 +1086,13 @@ class ServingBatcher:
             hi._wake.notify_all()
 
     def _ensure(self, n):
+        if self.cn:
+            self._ensure_control()
         if self.exec.ensure(n):
+            self._stats["captures"] += 1
+
+    def _ensure_control(self):
+        if self.exec.ensure_control():
             self._stats["captures"] += 1
 
     def _poll(self, wait=False):
@@ -955,6 +1166,9 @@ class _GraphExecutor:
                 w += 2 * T * proc.hidden_size
             self.ip_offsets.append(offs)
             self.ip_width.append(w)
+        # (controlnet) the lane buffers, the captured ControlNet graph and its residual buffers: one per batcher (ensure_control)
+        self.cn_nets = batcher._control_nets() if batcher.cn else []
+        self.cn = None
 
     def bind_thread(self):
         _lib.check(_lib.load_library().dsc_set_workspace_slot(self.b.slot), "dsc_set_workspace_slot")
@@ -991,6 +1205,149 @@ class _GraphExecutor:
                 r.ip_weights = [{L: w.to(dev).clone() for L, w in per.items()} for per in r.ip_weights]
         if r.adapter is not None:
             self._adapter_rows(r)
+
+    @torch.no_grad()
+    def _control_embedding(self, net, image):
+        """one net's conditioning embedding of one prepared [1, 3, H, W] image, channels-last [1, C0, h, w] - the eight
+        convolutions of ControlNetConditioningEmbedding.forward WITHOUT ControlNetModel's one-entry cache (`txt2img` on another
+        thread owns that).  The library's default algorithm for the LAST convolution (256 channels in, one image) adds partial
+        sums in an order that changes from call to call (8 distinct results in 8 calls), and a served request would differ from
+        its own repeat by 3e-3 of its range after a few steps through a ControlNet: that convolution runs on the package's own
+        3x3 kernel (dsc_conv3x3_nhwc_f16, a fixed summation order).  Where the kernel does not cover its shape, the library is
+        asked for a deterministic algorithm through torch's process-wide `torch.backends.cudnn.deterministic` for that one
+        call; _EMBED_LOCK keeps two batchers from restoring each other's value, and a library convolution another thread
+        launches inside that window is asked for a deterministic algorithm too (other last bits, never other validity)."""
+        ce = net.controlnet_cond_embedding
+        h = torch.nn.functional.silu(ce.conv_in(image.to(net.dtype).contiguous()))
+        for blk in ce.blocks:
+            h = torch.nn.functional.silu(blk(h))
+        h = h.contiguous(memory_format=torch.channels_last)
+        emb = ops.conv3x3_try(h, ce.conv_out.weight.contiguous(memory_format=torch.channels_last), ce.conv_out.bias)
+        if emb is None:
+            with _EMBED_LOCK:
+                was = torch.backends.cudnn.deterministic
+                torch.backends.cudnn.deterministic = True
+                try:
+                    emb = ce.conv_out(h)
+                finally:
+                    torch.backends.cudnn.deterministic = was
+        return emb.to(self.dtype).contiguous(memory_format=torch.channels_last)
+
+    @torch.no_grad()
+    def _control_rows(self, r):
+        """once per request, when it is admitted (load_lane): its control image(s) as the pipeline prepares them (prepare_image,
+        without the CFG duplication: both lane rows read the one embedding) and each net's conditioning embedding, held until the
+        request leaves; a request that waits for a lane holds nothing on the device for it"""
+        b, pipe = self.b, self.pipe
+        want = (1,) + b._control_shapes[0]
+        r.cemb = []
+        for net, image in zip(self.cn_nets, r.control["image"]):
+            img = pipe.prepare_image(image, b.width, b.height, 1, 1, self.device, net.dtype, do_classifier_free_guidance=False)
+            emb = self._control_embedding(net, img)
+            if tuple(emb.shape) != want:
+                raise ValueError(f"serve: `control_img` gives a conditioning embedding {tuple(emb.shape)}, this batcher's ControlNet "
+                                 f"step takes {want}")
+            r.cemb.append(emb)
+
+    @torch.no_grad()
+    def warm_control(self):
+        """one conditioning embedding of a blank image per net (the convolution library's first-call cost, outside any request)"""
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            for net in self.cn_nets:
+                cin = int(net.controlnet_cond_embedding.conv_in.in_channels)
+                self._control_embedding(net, torch.zeros(1, cin, self.b.height, self.b.width, device=self.device))
+
+    def ensure_control(self):
+        """lane buffers + the captured ControlNet graph of this batcher; True when this call captured it"""
+        if self.cn is not None:
+            return False
+        from .model_k_diffusion import _CAPTURE_LOCK
+        with _CAPTURE_LOCK:
+            self.bind_thread()
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+            self._capture_control()
+        return True
+
+    @torch.no_grad()
+    def _capture_control(self):
+        """The ControlNet(s) over the 2 c lane rows, captured once: reads the static lane buffers (x, t, text and one conditioning
+        embedding per net), writes every zero convolution's UNSCALED output into static buffers stacked over the nets - what the
+        buckets' steps scatter into their rows (ops.scatter_add_rows).  It does not depend on the bucket.  The nets get the text
+        rows and no region prompt, as in _controlnet_hook."""
+        dev, dt, b = self.device, self.dtype, self.b
+        c, nets = b.control_slots, self.cn_nets
+        rows, A = 2 * c, len(nets)
+        shapes = b._control_shapes
+
+        def stacked(shp):        # [A, 2 c, C, h, w], every net's rows channels-last, the nets dense behind one another
+            return torch.zeros((A, rows, shp[1], shp[2], shp[0]), device=dev, dtype=dt).permute(0, 1, 4, 2, 3)
+
+        with torch.cuda.stream(self.stream):
+            cn = {"x": torch.zeros((rows,) + self.lat_shape, device=dev, dtype=dt),
+                  "t": torch.zeros(rows, device=dev, dtype=torch.float32),
+                  "text": torch.zeros((rows, b.text_len, self.ctx), device=dev, dtype=dt),
+                  "emb": [torch.zeros((rows, shapes[0][1], shapes[0][2], shapes[0][0]), device=dev, dtype=dt).permute(0, 3, 1, 2)
+                          for _ in nets],
+                  "down": [stacked(shp) for shp in shapes[:-1]], "mid": stacked(shapes[-1])}
+            for net in nets:
+                net._to_channels_last_once()
+
+        def step():
+            for a, net in enumerate(nets):
+                down, mid = net(cn["x"], cn["t"], encoder_hidden_states=cn["text"], controlnet_cond=None, return_dict=False,
+                                cond_embedding=cn["emb"][a], unscaled=True)
+                for buf, d in zip(cn["down"] + [cn["mid"]], down + [mid]):
+                    buf[a].copy_(d)
+
+        side = self.stream
+        with torch.cuda.stream(side):
+            for _ in range(2):                       # warm-up: workspaces, kernel selection
+                step()
+        if ops.GRAPHS_ENABLED:
+            torch.cuda.current_stream(dev).wait_stream(side)
+            from .model_k_diffusion import _capture_without_gc
+            g = torch.cuda.CUDAGraph()
+            with _capture_without_gc(), torch.cuda.graph(g):
+                step()
+            side.wait_stream(torch.cuda.current_stream(dev))
+            cn["graph"] = g
+            cn["run"] = g.replay
+        else:
+            cn["run"] = step
+        self.cn = cn
+
+    def load_lane(self, r):
+        """a request took lane r.lane: its conditioning embedding(s) are computed (once per request, on this stream) and go,
+        with its text rows, into ControlNet rows {lane, c + lane}"""
+        c, j, cn = self.b.control_slots, r.lane, self.cn
+        with torch.cuda.stream(self.stream):
+            self._control_rows(r)
+            cn["text"][j].copy_(r.text[0][0])
+            cn["text"][c + j].copy_(r.text[1][0])
+            for buf, emb in zip(cn["emb"], r.cemb):
+                buf[j].copy_(emb[0])
+                buf[c + j].copy_(emb[0])
+
+    def set_control(self, n, dst, gather, gates):
+        """bucket n's dst / gather / gate vectors <- these values (None: unchanged); pinned, non-blocking"""
+        ct = self.st[n]["control"]
+        with torch.cuda.stream(self.stream):
+            if dst is not None:
+                ct["dst"].copy_(torch.tensor(dst, dtype=torch.int32).pin_memory(), non_blocking=True)
+            if gather is not None:
+                ct["gather"].copy_(torch.tensor(gather, dtype=torch.int64).pin_memory(), non_blocking=True)
+            if gates is not None:
+                ct["gate"].copy_(torch.tensor(gates, dtype=torch.float32).pin_memory(), non_blocking=True)
+
+    def run_control(self, n):
+        """the lane rows of bucket n's input and timesteps into the lane buffers (two static-shape launches), then the ControlNet
+        graph: its residual buffers are what bucket n's step, replayed next on this stream, scatters"""
+        st, cn = self.st[n], self.cn
+        with torch.cuda.stream(self.stream):
+            torch.index_select(st["x_in"], 0, st["control"]["gather"], out=cn["x"])
+            torch.index_select(st["t"], 0, st["control"]["gather"], out=cn["t"])
+            cn["run"]()
 
     @torch.no_grad()
     def _adapter_rows(self, r):
@@ -1198,6 +1555,12 @@ class _GraphExecutor:
             st["adapter"] = {"feats": [torch.empty((n,) + shp, device=dev, dtype=dt).contiguous(memory_format=torch.channels_last).zero_()
                                        for shp in self.b._adapter_shapes],
                              "gate": torch.zeros(rows, device=dev, dtype=torch.float32)} if self.b.t2i else None
+            # (controlnet) which batch row each ControlNet lane row lands on (-1: idle), which row of x_in / t it is read from, and
+            # one gate per net and lane row: all idle / closed until a member that holds a lane is inside its window
+            lanes = 2 * self.b.control_slots
+            st["control"] = {"dst": torch.full((lanes,), -1, device=dev, dtype=torch.int32),
+                             "gather": torch.zeros(lanes, device=dev, dtype=torch.int64),
+                             "gate": torch.zeros((len(self.cn_nets), lanes), device=dev, dtype=torch.float32)} if self.b.cn else None
         kw = {"region_prompt": {"region_state": zero, "compressed": st["compressed"], "sigma": st["sigma"], "weight_func": None,
                                 "n_std_groups": n, "sigma_per_group": True}}
         if self.ip_layers:
@@ -1214,6 +1577,8 @@ class _GraphExecutor:
         unet = pipe.unet
         # a batcher built without `t2i_adapter` calls the UNet exactly as it did before the keyword existed
         gated = {"down_intrablock_gated": (st["adapter"]["feats"], st["adapter"]["gate"])} if st["adapter"] is not None else {}
+        if st["control"] is not None:                # ... or the `controlnet` flag (the two are not built together)
+            gated = {"down_block_scattered": (self.cn["down"], self.cn["mid"], st["control"]["gate"], st["control"]["dst"])}
 
         def step():
             return unet(st["x_in"], st["t"], encoder_hidden_states=st["text"], cross_attention_kwargs=kw,

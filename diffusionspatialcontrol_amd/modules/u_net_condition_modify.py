@@ -752,6 +752,33 @@ class _EncoderHalf:
         y = torch.where(g == 0, x, x + g.to(x.dtype) * f)
         return x.copy_(y) if in_place else y
 
+    @staticmethod
+    def _scatter_add(x, feat, gate, dst):
+        """in place x[dst[j]] += sum over nets of gate[a][j] * feat[a][j] (one launch of dsc_scatter_add_rows_f16 on the GPU:
+        idle lanes and closed gates read and write nothing).  Elsewhere the same chain in torch ops."""
+        if x.is_cuda and x.dtype == torch.float16:
+            if not ops.scatter_add_rows_supported(x, feat):
+                raise ValueError(f"down_block_scattered: residuals {tuple(feat.shape)} {feat.stride()} {feat.dtype} do not fit the "
+                                 f"tensor {tuple(x.shape)} {x.stride()} they are added to (fp16, [nets, lane rows] + the same "
+                                 f"C x h x w, channels-last per net, the nets dense behind one another)")
+            return ops.scatter_add_rows(x, feat, gate, dst)
+        return ops.scatter_add_rows_torch(x, feat, gate, dst)
+
+    @classmethod
+    def _scatter_skips(cls, skips, read_later, feats, gate, dst):
+        """the ControlNet residuals added to the skip tensors in place (reference :1236-1245 adds them to the skips ONLY).  A skip
+        that shares storage with a tensor of `read_later` (the last skip IS the mid block's input) or with an earlier skip gets its
+        own storage first: an in-place add there would change what the other reader sees.  Returns the new list."""
+        def store(t):
+            return t.untyped_storage().data_ptr()
+        taken, own = {store(t) for t in read_later}, []
+        for s in skips:                                              # every copy is taken before the first add lands
+            if store(s) in taken:
+                s = s.clone(memory_format=torch.preserve_format)
+            taken.add(store(s))
+            own.append(s)
+        return [cls._scatter_add(s, f, gate, dst) for s, f in zip(own, feats)]
+
     def _run_down(self, x, temb_act, tadd, encoder_hidden_states, cross_attention_kwargs, intrablock=None, skip0=None,
                   gated=None):
         """intrablock: T2I-Adapter features, one per down block (reference :1194-1230): added after the LAST resnet /
@@ -926,9 +953,29 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
                 attention_mask=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
                 down_intrablock_additional_residuals=None, encoder_attention_mask=None, return_dict=True, temb_adds=None,
-                cfg_shared_prefix=False, down_intrablock_gated=None):
+                cfg_shared_prefix=False, down_intrablock_gated=None, down_block_scattered=None):
         if attention_mask is not None or encoder_attention_mask is not None:
             raise NotImplementedError("attention masks are not on the hot path (never passed by app.py)")
+        # down_block_scattered = (down_feats, mid_feat, gate, dst): the static form of down_block_additional_residuals /
+        # mid_block_additional_residual for a captured step that serves a batch of which only some rows have a ControlNet -
+        # down_feats one [nets, R, C_k, h_k, w_k] tensor per skip tensor (channels-last per net: a ControlNet's UNSCALED zero
+        # convolution outputs over R compact lane rows), mid_feat the same for the mid block's output, gate fp32 [nets, R] and
+        # dst int32 [R] in device memory: lane row j is added, scaled by its gates and summed over the nets, to batch row dst[j]
+        # where the other keywords add their tensors (ops.scatter_add_rows; active lane rows name distinct batch rows)
+        if down_block_scattered is not None:
+            if down_intrablock_additional_residuals is not None or down_block_additional_residuals is not None \
+                    or mid_block_additional_residual is not None or down_intrablock_gated is not None:
+                raise ValueError("down_block_scattered and down_block_additional_residuals / mid_block_additional_residual / "
+                                 "down_intrablock_additional_residuals / down_intrablock_gated are mutually exclusive")
+            s_down, s_mid, s_gate, s_dst = down_block_scattered
+            n_skips = 1 + sum(len(blk.resnets) + (1 if hasattr(blk, "downsamplers") else 0) for blk in self.down_blocks)
+            if len(s_down) != n_skips:
+                raise ValueError(f"down_block_scattered: {len(s_down)} residual tensors for {n_skips} skip tensors")
+            nets_rows = tuple(s_mid.shape[:2])
+            if not torch.is_tensor(s_gate) or tuple(s_gate.shape) != nets_rows or s_gate.dtype != torch.float32:
+                raise ValueError(f"down_block_scattered: gate must be an fp32 {list(nets_rows)} tensor (nets x lane rows)")
+            if not torch.is_tensor(s_dst) or tuple(s_dst.shape) != nets_rows[1:] or s_dst.dtype != torch.int32:
+                raise ValueError(f"down_block_scattered: dst must be an int32 [{nets_rows[1]}] tensor (one batch row per lane row)")
         # down_intrablock_gated = (feats, gate): the static form of down_intrablock_additional_residuals for a captured step that
         # serves a batch - feats one channels-last [F, C_k, h_k, w_k] tensor per down block (batch row r reads row r % F), gate
         # fp32 [B] in device memory: row r gets `gate[r] * feats[k][r % F]` where the other keyword adds its tensor (_run_down)
@@ -978,9 +1025,13 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
                                   intrablock=down_intrablock_additional_residuals, skip0=skip0, gated=down_intrablock_gated)
         if down_block_additional_residuals is not None:          # ControlNet hook (reference :1236-1245)
             skips = [s + r for s, r in zip(skips, down_block_additional_residuals)]
+        if down_block_scattered is not None:                     # the same hook, per lane row (x is read by the mid block next)
+            skips = self._scatter_skips(skips, [x], s_down, s_gate, s_dst)
         x = self._run_mid(x, temb_act, tadd, encoder_hidden_states, cross_attention_kwargs)
         if mid_block_additional_residual is not None:            # reference :1269-1270
             x = x + mid_block_additional_residual
+        if down_block_scattered is not None:
+            x = self._scatter_add(x, s_mid, s_gate, s_dst)
         # reference :1110-1123, 1281-1300: when a latent side is not a multiple of 2 ** (number of upsamplers) the down path's
         # ceil(n / 2) sizes are not what doubling gives back, and every upsampler is told the size of the skip tensor its result
         # is concatenated with.  Sides that divide: nothing is forwarded and the upsamplers double, as before.

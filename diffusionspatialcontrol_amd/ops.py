@@ -1368,3 +1368,8 @@ from .modules.latent_resample import latent_resample_noise, noise_scale_f16  # n
 # the gated per-row residual add of the continuous batcher's T2I-Adapter step (dsc_add_rows_gated_f16): its wrapper lives beside
 # its kernel's name, like modules/latent_resample.py's, and is reached as ops.add_rows_gated / ops.add_rows_gated_supported
 from .gated_add import add_rows_gated, add_rows_gated_supported  # noqa: E402,F401
+
+
+# the ControlNet residuals of the continuous batcher's compact lanes, added into their batch rows (dsc_scatter_add_rows_f16):
+# wrapper beside its kernel's name, like gated_add.py's, reached as ops.scatter_add_rows / ops.scatter_add_rows_supported
+from .scatter_add import scatter_add_rows, scatter_add_rows_supported, scatter_add_rows_torch  # noqa: E402,F401

@@ -693,6 +693,36 @@ int dsc_ip_xattn_add_masked_f16(const void* q, long long q_stride_b, long long q
 int dsc_add_rows_gated_f16(const void* x, const void* feat, const void* gate, void* out, int rows, int feat_rows,
                            long long row_elems, void* stream);
 
+/*
+ * Residuals of a compact ControlNet batch ("lanes") added into the batch rows they belong to: the ControlNet hook of the
+ * continuous batcher's captured step.  Replaces, in one launch per skip tensor, ControlNetModel.forward's
+ * `d * conditioning_scale`, MultiControlNetModel.forward's sum over the nets and modules/u_net_condition_modify.py:1236-1245 of
+ * the reference (`s + r`), with "lane row j serves batch row dst[j] at this scale" device values, not Python control flow.
+ * In place on x, for lane row j < lane_rows with dst[j] >= 0 and at least one gate[a][j] != 0, for e < row_elems:
+ *     t = fp16( gate[a0][j] * float(feat[a0][j][e]) )                          a0 the first net with gate[a0][j] != 0
+ *     t = fp16( float(t) + float(fp16( gate[a][j] * float(feat[a][j][e]) )) )  for each a > a0 with gate[a][j] != 0, in order
+ *     x[dst[j]][e] = fp16( float(x[dst[j]][e]) + float(t) )
+ * - every product and every sum an fp32 operation, rounded to fp32 and then to fp16 on its own (torch's fp16 `feat * g`,
+ * `a + b`, `s + r`); no step is contracted with its neighbour into a single-rounding mixed-precision fma.  With nets == 1 the
+ * bits of torch's fp16 `x[d] + feat[j] * g` for a python float g at tensors of 2048 elements and more (below that torch's own
+ * multiply launches a kernel variant that rounds the exact product once, and differs from its large-tensor self by an ulp in
+ * about 4 % of the elements; this entry rounds the same way at every size).
+ * x: fp16, x_rows dense rows of row_elems halfs (a channels-last [X, C, h, w] tensor: row_elems = h * w * C; a token-major
+ * [X, L, C] tensor: L * C).  feat: fp16 [nets][lane_rows][row_elems], dense.  gate: fp32 [nets][lane_rows], dst: int32
+ * [lane_rows], both read from DEVICE memory (never by value): a captured launch sees the values of the moment it replays.
+ * A lane row with dst[j] < 0 (or >= x_rows), or with every gate 0, reads and writes nothing: its feature rows may hold anything
+ * and its would-be destination keeps its bits.  A net whose gate is 0 is not read for that lane row.
+ * THE CALLER'S INVARIANT, which the kernel cannot check: the destination rows of active lane rows are distinct (two lanes on
+ * one row would race).  Rows of x that no active lane names are neither loaded nor stored.
+ * The lane row is a grid coordinate (lane_rows <= 65535); nets <= 8.  row_elems % 8 == 0; x, feat 16-byte aligned, gate, dst
+ * 4-byte aligned: 16-byte loads and stores.  No workspace, no LDS, no allocation, no synchronisation, no atomics, every element
+ * written by the one lane that owns it: deterministic and safe under graph capture.
+ * DSC_ERR_BAD_ARG: null pointer, x_rows / lane_rows / nets / row_elems < 1, nets > 8, x overlapping feat, gate or dst.
+ * DSC_ERR_UNSUPPORTED: row_elems % 8 != 0, alignment, lane_rows > 65535, x or feat of 2^60 bytes and more.
+ */
+int dsc_scatter_add_rows_f16(void* x, const void* feat, const void* gate, const void* dst, int x_rows, int lane_rows, int nets,
+                             long long row_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,488 @@
+"""ControlNet requests in the continuous batcher on the host (modules/serving.py against a fake executor): the gate of every
+model call against `preprocess_controlnet`'s keep schedule, lane allocation / release / FIFO waiting, the per-bucket dst / gather /
+gate vectors and their uploads, the submit-time and construction-time refusals, the C entry (declared, registered, validating its
+arguments without a GPU), the scatter-add's torch form against the written-out chain, and the aliasing rule of the UNet's
+`down_block_scattered` keyword on stand-in blocks."""
+import ctypes
+
+import pytest
+import torch
+
+from inputs import FakeTokenizer
+from test_serving_img_host import LAT, MASK, FakeImgExec, _req
+
+from diffusionspatialcontrol_amd import _lib
+from diffusionspatialcontrol_amd.modules.serving import ServingBatcher
+
+IMG = torch.rand(1, 3, 128, 128, generator=torch.Generator().manual_seed(1))
+CL = torch.channels_last
+
+
+class LaneExec(FakeImgExec):
+    """FakeImgExec plus the ControlNet side: the vectors in force at every run, uploads, lane loads and ControlNet runs in order"""
+
+    def __init__(self):
+        super().__init__()
+        self.log = []                # ("lane", lane, name) | ("set", n, dst, gather, gates) | ("control", n) | ("run", n, state, names)
+        self.state = {}
+        self.members = {}
+        self.captured = self.warmed = 0
+
+    def ensure_control(self):
+        self.captured += 1
+        return self.captured == 1
+
+    def warm_control(self):
+        self.warmed += 1
+
+    def prepare_noise(self, r, eta):
+        pass
+
+    def transition_linear(self, n_src, n_dst, recs):
+        self._record("linear", n_src, n_dst, recs, None)
+
+    def refresh(self, n, members):
+        self.members[n] = [None if r is None else r.req["name"] for r in members]
+
+    def load_lane(self, r):
+        self.log.append(("lane", r.lane, r.req["name"]))
+
+    def set_control(self, n, dst, gather, gates):
+        cur = self.state.setdefault(n, [None, None, None])
+        for k, v in enumerate((dst, gather, gates)):
+            if v is not None:
+                cur[k] = [list(p) for p in v] if k == 2 else list(v)
+        self.log.append(("set", n, dst, gather, gates))
+
+    def run_control(self, n):
+        self.log.append(("control", n))
+
+    def run(self, n):
+        self.log.append(("run", n, [None if v is None else list(v) for v in self.state.get(n, [None] * 3)],
+                         list(self.members.get(n, [None] * n))))
+
+
+def _controlnet(cfg, guess=False):
+    from diffusionspatialcontrol_amd.modules.controlnet import ControlNetModel
+    torch.manual_seed(3)
+    return ControlNetModel(cfg, global_pool_conditions=guess).half()
+
+
+def _pipe(nets=1):
+    from diffusionspatialcontrol_amd.modules.model_k_diffusion import SD15Scheduler, StableDiffusionPipeline
+    from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNet2DConditionModel, UNetConfig
+    torch.manual_seed(0)
+    unet = UNet2DConditionModel(UNetConfig.tiny()).half()
+    pipe = StableDiffusionPipeline(None, None, FakeTokenizer(), unet, SD15Scheduler())
+    if nets == 1:
+        pipe.setup_controlnet(_controlnet(unet.cfg))
+    elif nets > 1:
+        pipe.setup_controlnet([_controlnet(unet.cfg) for _ in range(nets)])
+    return pipe
+
+
+@pytest.fixture(scope="module")
+def pipe():
+    return _pipe()
+
+
+@pytest.fixture(scope="module")
+def pipe2():
+    return _pipe(2)
+
+
+def _batcher(pipe, **kw):
+    ex = LaneExec()
+    kw.setdefault("controlnet", True)
+    kw.setdefault("max_batch", 2)
+    kw.setdefault("buckets", (1, 2))
+    return ServingBatcher(pipe, 128, 128, executor=ex, **kw), ex
+
+
+def _runs(ex):
+    return [e for e in ex.log if e[0] == "run"]
+
+
+# ----------------------------------------------------------------------------- keep / gates per model call
+def _keep_steps(pipe, kind, steps, strength):
+    """the step count the pipeline methods hand preprocess_controlnet, restated: txt2img (model_k_diffusion.py:527)
+    num_inference_steps; img2img (:826, :838) len(sigmas[t_start:])"""
+    if kind == "txt2img":
+        return steps
+    sigmas = pipe._schedule(steps, {"scheduler": "karras"}, "cpu", torch.float16)
+    return len(sigmas[max(steps - min(int(steps * strength), steps), 0):])
+
+
+@pytest.mark.parametrize("start, end", [(0.0, 1.0), (0.0, 0.6), (0.3, 1.0), (0.25, 0.75), (0.5, 0.5), (0.9, 0.2)])
+@pytest.mark.parametrize("kind, strength", [("txt2img", None), ("img2img", 0.6), ("img2img", 1.0)])
+def test_gate_of_every_model_call_is_scale_times_preprocess_controlnets_keep(pipe, kind, strength, start, end):
+    """model call k carries `scale * keep[min(k, len(keep) - 1)]` with keep from preprocess_controlnet for the step count of the
+    pipeline method (_controlnet_hook's schedule: one control step per distinct sigma); lane rows j and c + j agree; windows that
+    open late, close early, are empty; the ControlNet runs exactly in the calls whose gate is open"""
+    steps, scale = 7, 0.9
+    b, ex = _batcher(pipe)
+    extra = {} if kind == "txt2img" else {"image": LAT, "strength": strength}
+    b.submit(_req("R", steps=steps, control_img=IMG, controlnet_conditioning_scale=scale, control_guidance_start=start,
+                  control_guidance_end=end, **extra))
+    b.run_until_idle()
+    _, keep, guess, _ = pipe.preprocess_controlnet(scale, start, end, IMG, 128, 128, _keep_steps(pipe, kind, steps, strength), 1, 1)
+    assert not guess
+    calls = steps if kind == "txt2img" else min(int(steps * strength), steps)
+    want = [scale * keep[min(k, len(keep) - 1)] for k in range(calls)]
+    runs = _runs(ex)
+    assert len(runs) == calls
+    got = []
+    for _, n, (dst, gather, gates), names in runs:
+        assert n == 1 and names == ["R"]
+        got.append(0.0 if gates is None else gates[0][0])
+        if gates is not None:
+            assert gates[0][0] == gates[0][2] and gates[0][1] == gates[0][3] == 0.0      # lane 0: rows 0 and c + 0; lane 1 idle
+    if all(w == 0.0 for w in want):
+        assert not any(e[0] in ("lane", "set", "control") for e in ex.log)               # a plain request: no lane, no upload
+        assert b.stats()["control_steps"] == 0 and b.stats()["control_gate_updates"] == 0
+        return
+    assert got == want, (got, want)
+    # the ControlNet ran right before exactly the runs whose gate is open
+    ran = [ex.log[i - 1][0] == "control" for i, e in enumerate(ex.log) if e[0] == "run"]
+    assert ran == [w != 0.0 for w in want] and b.stats()["control_steps"] == sum(w != 0.0 for w in want)
+    changes = sum(a != b_ for a, b_ in zip([0.0] + want[:-1], want))
+    assert b.stats()["control_gate_updates"] == changes                                  # uploaded only when the vector changes
+
+
+def test_two_nets_list_valued_scales_and_windows(pipe2):
+    steps, scales, starts, ends = 6, [0.5, 0.4], [0.0, 0.5], [0.5, 1.0]
+    b, ex = _batcher(pipe2)
+    b.submit(_req("R", steps=steps, control_img=[IMG, IMG], controlnet_conditioning_scale=scales, control_guidance_start=starts,
+                  control_guidance_end=ends))
+    b.run_until_idle()
+    _, keep, _, sc = pipe2.preprocess_controlnet(scales, starts, ends, [IMG, IMG], 128, 128, steps, 1, 1)
+    want = [[s * k for s, k in zip(sc, keep[i])] for i in range(steps)]
+    assert want[0] == [0.5, 0.0] and want[-1] == [0.0, 0.4]
+    got = [[e[2][2][a][0] for a in range(2)] for e in _runs(ex)]
+    assert got == want
+    # a scalar scale / window is every net's; all scales 0 is a request without control
+    b2, ex2 = _batcher(pipe2)
+    b2.submit(_req("S", steps=3, control_img=[IMG, IMG], controlnet_conditioning_scale=0.7, control_guidance_end=0.7))
+    b2.submit(_req("Z", steps=3, control_img=[IMG, IMG], controlnet_conditioning_scale=[0.0, 0.0]))
+    b2.run_until_idle()
+    assert [e[2][2][0][:2] for e in _runs(ex2)] == [[0.7, 0.0], [0.7, 0.0], [0.0, 0.0]]
+    assert [e[2] for e in ex2.log if e[0] == "lane"] == ["S"]
+
+
+def test_control_gates_static_helper_matches_the_hook_formula():
+    g = ServingBatcher.control_gates(4, 6, [0.9], [0.0], [0.5])                 # more calls than keep entries: the last repeats
+    assert g == [[0.9], [0.9], [0.0], [0.0], [0.0], [0.0]]
+    assert ServingBatcher.control_keep(5, [0.0], [0.6]) == [[1.0], [1.0], [1.0], [0.0], [0.0]]
+
+
+# ----------------------------------------------------------------------------- lanes and vectors
+def test_lane_allocation_release_and_fifo_waiting(pipe):
+    """one lane, two slots: A (control) alone in bucket 1; P (plain) joins -> bucket 2; B (control) waits at the head of the queue
+    although slot 1 is free, and Q (plain, behind it) waits too (FIFO); B takes the lane once A has left"""
+    b, ex = _batcher(pipe, control_slots=1)
+    b.submit(_req("A", steps=3, control_img=IMG))
+    b.step()
+    assert b._lanes[0].req["name"] == "A" and b._slots[0].lane == 0
+    assert _runs(ex)[-1][1] == 1 and _runs(ex)[-1][2][0] == [0, 1]                # bucket 1: lane rows -> batch rows 0, 1
+    b.submit(_req("B", steps=2, control_img=IMG))
+    b.submit(_req("Q", steps=2))
+    b.step()
+    assert b._slots[1] is None and b.stats()["queued"] == 2                      # a slot is free, the lane is not
+    b.step()
+    assert b._slots[1] is None and b.stats()["queued"] == 2
+    b.step()                                                                     # A's last step is applied: it leaves
+    assert b._slots[0] is None and b._lanes[0] is None
+    b.step()
+    assert b._slots[0].req["name"] == "B" and b._lanes[0] is b._slots[0] and b._slots[1].req["name"] == "Q"
+    assert _runs(ex)[-1][1] == 2 and _runs(ex)[-1][2][0] == [0, 2]                # bucket 2: rows 0 and n + 0
+    b.run_until_idle()
+    assert b._lanes == [None] and [e[1:] for e in ex.log if e[0] == "lane"] == [(0, "A"), (0, "B")]
+
+
+def test_dst_and_gather_follow_slot_and_bucket(pipe):
+    """P (plain) first, so that A (control) sits in slot 1 on lane 0: dst = [1, n + 1] = [1, 3] with two lanes [1, -1, 3, -1];
+    P leaves, A stays in slot 1 (bucket 2); idle lanes are -1 in dst and read row 0"""
+    b, ex = _batcher(pipe, control_slots=2)
+    b.submit(_req("P", steps=1))
+    b.submit(_req("A", steps=3, control_img=IMG, controlnet_conditioning_scale=0.5))
+    b.run_until_idle()
+    for e in _runs(ex):
+        dst, gather, gates = e[2]
+        assert e[1] == 2 and dst == [1, -1, 3, -1] and gather == [1, 0, 3, 0] and gates == [[0.5, 0.0, 0.5, 0.0]]
+    assert b.stats()["control_gate_updates"] == 1 and b.stats()["control_steps"] == 3
+    assert len([e for e in ex.log if e[0] == "set"]) == 1
+    # two control requests on two lanes
+    b.submit(_req("C", steps=2, control_img=IMG))
+    b.submit(_req("D", steps=2, control_img=IMG, controlnet_conditioning_scale=0.25))
+    b.run_until_idle()
+    dst, gather, gates = _runs(ex)[-1][2]
+    assert dst == [0, 1, 2, 3] and gather == [0, 1, 2, 3] and gates == [[1.0, 0.25, 1.0, 0.25]]
+
+
+def test_vectors_assert_distinct_destination_rows(pipe):
+    b, ex = _batcher(pipe, control_slots=2)
+    b.submit(_req("A", steps=2, control_img=IMG))
+    b.submit(_req("B", steps=2, control_img=IMG))
+    b.step()
+    r, r2 = b._slots
+    dst, gather, gates = b._control_vectors(2, [r, None])
+    assert dst == [0, -1, 2, -1]
+    assert b._control_vectors(2, [r, r2])[0] == [0, 1, 2, 3]
+    with pytest.raises(AssertionError, match="share a batch row"):
+        b._control_vectors(1, [r, r2])                                           # n too small: rows 0, 1 and 1, 2
+    r.lane = 1
+    with pytest.raises(AssertionError, match="holds no lane"):
+        b._control_vectors(2, [r, None])
+    r.lane = 0
+    b.run_until_idle()
+
+
+def test_warm_captures_the_controlnet_graph_first(pipe):
+    b, ex = _batcher(pipe)
+    b.warm()
+    assert ex.captured >= 1 and ex.warmed == 1 and b.stats()["captures"] == 1 and b.stats()["captures_after_warm"] == 0
+    b2, ex2 = _batcher(pipe, controlnet=False)
+    b2.warm()
+    assert ex2.captured == 0 and ex2.warmed == 0
+
+
+# ----------------------------------------------------------------------------- refusals
+@pytest.mark.parametrize("extra, needle", [
+    ({"control_img": object()}, "control_img"),
+    ({"control_img": [IMG]}, "control_img"),                                            # a list goes with a MultiControlNetModel
+    ({"control_img": IMG[0]}, "control_img"),                                           # [3, H, W]
+    ({"control_img": torch.rand(1, 1, 128, 128)}, "control_img"),                       # not the net's channels
+    ({"control_img": (IMG * 255).to(torch.uint8)}, "control_img"),
+    ({"control_img": IMG, "controlnet_conditioning_scale": "1"}, "controlnet_conditioning_scale"),
+    ({"control_img": IMG, "controlnet_conditioning_scale": [1.0, 1.0]}, "controlnet_conditioning_scale"),
+    ({"control_img": IMG, "controlnet_conditioning_scale": float("nan")}, "controlnet_conditioning_scale"),
+    ({"control_img": IMG, "controlnet_conditioning_scale": float("inf")}, "controlnet_conditioning_scale"),
+    ({"control_img": IMG, "controlnet_conditioning_scale": True}, "controlnet_conditioning_scale"),
+    ({"control_img": IMG, "control_guidance_start": "0"}, "control_guidance_start"),
+    ({"control_img": IMG, "control_guidance_end": [0.5, 0.6]}, "control_guidance_end"),
+    ({"control_img": IMG, "control_guidance_end": float("nan")}, "control_guidance_end"),
+    ({"controlnet_conditioning_scale": "x"}, "controlnet_conditioning_scale"),          # checked without an image too
+    ({"control_img": IMG, "upscale": True}, "not served yet; use txt2img"),
+    ({"control_img": IMG, "image": LAT, "mask_image": MASK}, "with `mask_image`"),
+    ({"image_t2i_adapter": IMG}, "image_t2i_adapter"),
+])
+def test_submit_refusals_name_the_key(pipe, extra, needle):
+    b, _ = _batcher(pipe)
+    with pytest.raises(ValueError, match=needle):
+        b.submit(_req("R", **extra))
+
+
+def test_two_nets_list_lengths(pipe2):
+    b, _ = _batcher(pipe2)
+    for extra, needle in [({"control_img": IMG}, "control_img"), ({"control_img": [IMG]}, "control_img"),
+                          ({"control_img": [IMG, IMG, IMG]}, "control_img"),
+                          ({"control_img": [IMG, IMG], "controlnet_conditioning_scale": [0.5]}, "controlnet_conditioning_scale"),
+                          ({"control_img": [IMG, IMG], "control_guidance_start": [0.1, 0.2, 0.3]}, "control_guidance_start"),
+                          ({"control_img": [IMG, IMG], "controlnet_conditioning_scale": [0.5, "x"]}, "controlnet_conditioning_scale")]:
+        with pytest.raises(ValueError, match=needle):
+            b.submit(_req("R", **extra))
+
+
+def test_control_img_on_a_chained_hires_pair_is_refused(pipe):
+    b, _ = _batcher(pipe)
+    hi = ServingBatcher(pipe, 192, 192, executor=LaneExec(), slot=1)
+    b.chain_hires(hi)
+    with pytest.raises(ValueError, match="hires pair"):
+        b.submit(_req("R", control_img=IMG))
+
+
+def test_construction_refusals_and_the_flag_off_batcher():
+    import dataclasses
+    from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNetConfig
+    bare = _pipe(0)
+    with pytest.raises(ValueError, match="setup_controlnet"):
+        ServingBatcher(bare, 128, 128, executor=LaneExec(), controlnet=True)
+    with pytest.raises(ValueError, match="setup_controlnet"):
+        bare.serve(128, 128, controlnet=True)
+    p = _pipe(1)
+    with pytest.raises(ValueError, match="not served together yet"):
+        ServingBatcher(p, 128, 128, executor=LaneExec(), controlnet=True, t2i_adapter=True)
+    for c in (0, 3):
+        with pytest.raises(ValueError, match="control_slots"):
+            ServingBatcher(p, 128, 128, executor=LaneExec(), max_batch=2, buckets=(2,), controlnet=True, control_slots=c)
+    p.setup_controlnet(_controlnet(p.unet.cfg, guess=True))
+    with pytest.raises(ValueError, match="guess-mode"):
+        ServingBatcher(p, 128, 128, executor=LaneExec(), controlnet=True)
+    p.setup_controlnet(_controlnet(dataclasses.replace(UNetConfig.tiny(), block_out_channels=(32, 64, 64, 128))))
+    with pytest.raises(ValueError, match="do not match the UNet's skip tensors"):
+        ServingBatcher(p, 128, 128, executor=LaneExec(), controlnet=True)
+    # a flag-off batcher on a pipeline with (or without) a ControlNet keeps refusing the key, with a hint at the flag
+    for q in (bare, _pipe(1)):
+        b, ex = _batcher(q, controlnet=False)
+        with pytest.raises(ValueError, match="control_img") as e:
+            b.submit(_req("R", control_img=IMG))
+        assert "is not supported (use txt2img)" in str(e.value) and "controlnet=True" in str(e.value)
+        b.submit(_req("R", steps=2))
+        b.run_until_idle()
+        assert not [x for x in ex.log if x[0] in ("set", "lane", "control")] and b.stats()["control_steps"] == 0
+
+
+def test_a_replaced_controlnet_makes_the_batcher_stale():
+    p = _pipe(1)
+    b, _ = _batcher(p)
+    p.setup_controlnet(_controlnet(p.unet.cfg))
+    with pytest.raises(RuntimeError, match="setup_controlnet"):
+        b.submit(_req("R", control_img=IMG))
+
+
+def test_skip_shapes_at_an_odd_latent_size(pipe):
+    """72 x 88 pixels = a 9 x 11 latent: 12 skips and the mid output, halved by ceil at every downsampler"""
+    b = ServingBatcher(pipe, 72, 88, executor=LaneExec(), controlnet=True)
+    assert b._control_shapes == [(32, 9, 11)] * 3 + [(32, 5, 6)] + [(64, 5, 6)] * 2 + [(64, 3, 3)] * 3 + [(64, 2, 2)] * 3 + \
+        [(64, 2, 2)]
+
+
+def test_unscaled_keyword_refuses_guess_mode_and_the_unet_keyword_is_exclusive(pipe):
+    from diffusionspatialcontrol_amd.modules.controlnet import MultiControlNetModel
+    guess = _controlnet(pipe.unet.cfg, guess=True)
+    x, t, text = torch.zeros(2, 4, 16, 16).half(), torch.zeros(2), torch.zeros(2, 77, 64).half()
+    with pytest.raises(ValueError, match="guess mode"):
+        guess(x, t, text, IMG, unscaled=True)
+    with pytest.raises(ValueError, match="guess mode"):
+        _controlnet(pipe.unet.cfg)(x, t, text, IMG, guess_mode=True, unscaled=True)
+    with pytest.raises(ValueError, match="guess mode"):
+        MultiControlNetModel([guess])(x, t, text, [IMG], None, unscaled=True)
+    feats = [torch.zeros(1, 2, c, h, w) for c, h, w in ServingBatcher._skip_shapes(pipe.unet, 16, 16)]
+    sc = (feats[:-1], feats[-1], torch.zeros(1, 2), torch.full((2,), -1, dtype=torch.int32))
+    for other in ({"down_block_additional_residuals": []}, {"mid_block_additional_residual": x},
+                  {"down_intrablock_additional_residuals": []}, {"down_intrablock_gated": ([], torch.zeros(2))}):
+        with pytest.raises(ValueError, match="mutually exclusive"):
+            pipe.unet(x, t, text, down_block_scattered=sc, **other)
+    with pytest.raises(ValueError, match="11 residual tensors for 12"):
+        pipe.unet(x, t, text, down_block_scattered=(feats[:-2], feats[-1], sc[2], sc[3]))
+    with pytest.raises(ValueError, match="gate must be"):
+        pipe.unet(x, t, text, down_block_scattered=(feats[:-1], feats[-1], torch.zeros(2), sc[3]))
+    with pytest.raises(ValueError, match="dst must be"):
+        pipe.unet(x, t, text, down_block_scattered=(feats[:-1], feats[-1], sc[2], torch.zeros(2, dtype=torch.int64)))
+
+
+# ----------------------------------------------------------------------------- the C entry
+NAME = "dsc_scatter_add_rows_f16"
+
+
+def test_entry_is_declared_and_registered_with_matching_arity():
+    assert NAME in _lib.declared_symbols() and NAME in _lib._SIGNATURES and hasattr(_lib.load_library(), NAME)
+    txt = open(_lib.header_path()).read()
+    at = txt.index("int " + NAME + "(")
+    decl = txt[at:txt.index(";", at)]
+    assert decl.count(",") + 1 == len(_lib._SIGNATURES[NAME][1]) == 9
+    doc = txt[txt.rindex("/*", 0, at):at]
+    assert "u_net_condition_modify.py:1236-1245" in doc and "distinct" in doc
+
+
+def test_entry_validates_its_arguments_without_a_gpu():
+    """every refusal comes back before anything touches the GPU (this test runs on a machine without one)"""
+    lib = _lib.load_library()
+    P = ctypes.c_void_p
+
+    def call(x=0x100000, feat=0x200000, gate=0x300000, dst=0x400000, X=4, R=2, A=1, n=1024):
+        return getattr(lib, NAME)(P(x) if x else None, P(feat) if feat else None, P(gate) if gate else None,
+                                  P(dst) if dst else None, X, R, A, n, None)
+
+    BAD, UNSUPPORTED = -1, -2
+    assert call(x=0) == BAD and call(feat=0) == BAD and call(gate=0) == BAD and call(dst=0) == BAD
+    assert call(X=0) == BAD and call(R=0) == BAD and call(A=0) == BAD and call(n=0) == BAD and call(R=-2) == BAD
+    assert call(A=9) == BAD                                                   # nets out of range
+    assert call(feat=0x100000) == BAD and call(feat=0x100000 + 4 * 1024 * 2 - 16) == BAD       # x over feat
+    assert call(feat=0x100000 - 2 * 1024 * 2 + 16) == BAD
+    assert call(feat=0x100000 - 2 * 2 * 1024 * 2 + 16, A=2) == BAD            # the second net's rows reach into x
+    assert call(gate=0x100000 + 64) == BAD and call(gate=0x100000 - 4) == BAD
+    assert call(dst=0x100000 + 4 * 1024 * 2 - 4) == BAD and call(dst=0x100000 - 8 + 4) == BAD
+    assert call(n=1020) == UNSUPPORTED and call(n=4) == UNSUPPORTED          # row_elems % 8
+    assert call(x=0x100008) == UNSUPPORTED and call(feat=0x200008) == UNSUPPORTED
+    assert call(gate=0x300002) == UNSUPPORTED and call(dst=0x400002) == UNSUPPORTED
+    assert call(R=65536, n=8, feat=0x10000000) == UNSUPPORTED                 # the lane row is gridDim.y
+    assert call(X=2 ** 31 - 1, n=1 << 39) == UNSUPPORTED                     # byte counts that would wrap the overlap tests
+
+
+# ----------------------------------------------------------------------------- the torch form and the aliasing rule
+def _chain(x, feat, gate, dst):
+    """the contract, written out: per active lane row t = g0 * f0; t = t + g_a * f_a (open nets only); x[d] = x[d] + t, every
+    operation a torch op in x's dtype"""
+    out = x.clone()
+    for j, d in enumerate(dst.tolist()):
+        open_nets = [a for a in range(feat.shape[0]) if gate[a, j] != 0]
+        if d < 0 or not open_nets:
+            continue
+        t = feat[open_nets[0], j] * float(gate[open_nets[0], j])
+        for a in open_nets[1:]:
+            t = t + feat[a, j] * float(gate[a, j])
+        out[d] = x[d] + t
+    return out
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+def test_torch_form_of_the_scatter_add_is_the_written_out_chain(dtype):
+    from diffusionspatialcontrol_amd import ops
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(6, 8, 3, 3, generator=g).to(dtype).contiguous(memory_format=CL)
+    feat = torch.randn(2, 4, 8, 3, 3, generator=g).to(dtype)
+    feat[1, 2] = float("nan")                                                 # net 1 is closed for lane row 2
+    feat[:, 3] = float("nan")                                                 # lane row 3 is idle
+    gate = torch.tensor([[0.9, 0.0, 0.3, 1.0], [0.5, -0.5, 0.0, 1.0]])
+    dst = torch.tensor([5, 0, 2, -1], dtype=torch.int32)
+    want = _chain(x, feat, gate, dst)
+    got = ops.scatter_add_rows_torch(x.clone(memory_format=torch.preserve_format), feat, gate, dst)
+    assert torch.equal(got, want) and torch.isfinite(got).all()
+    for r in (1, 3, 4):
+        assert torch.equal(got[r], x[r])
+    assert not torch.equal(got[5], x[5]) and not torch.equal(got[0], x[0])
+    # closed gates everywhere: untouched, whatever the features hold
+    same = ops.scatter_add_rows_torch(x.clone(), feat * float("nan"), torch.zeros(2, 4), dst)
+    assert torch.equal(same, x)
+    with pytest.raises(AssertionError, match="share a destination row"):
+        ops.scatter_add_rows_torch(x.clone(), feat, gate, torch.tensor([5, 5, 2, -1], dtype=torch.int32))
+
+
+class _Scale:
+    """a stand-in for a ResNet / transformer / downsampler: an affine map (every UNet module of this package needs the GPU, so
+    the CPU checks the keyword's aliasing rule on stand-in blocks; the real UNet runs in tests/test_controlnet_serving_gpu.py)"""
+
+    def __init__(self, a, b, stride=1):
+        self.a, self.b, self.stride = a, b, stride
+
+    def __call__(self, x, *_):
+        return (x * self.a + self.b)[..., ::self.stride, ::self.stride].contiguous(memory_format=CL)
+
+
+def test_scattered_skips_never_change_a_tensor_that_is_read_later():
+    """_run_down on stand-in blocks: its last skip IS the tensor the mid block reads.  _scatter_skips adds the residuals to every
+    skip (the values of the eager `s + r`), and the mid block's input keeps its bits: that skip got its own storage first; so
+    does a skip that shares storage with an earlier one."""
+    from types import SimpleNamespace
+    from diffusionspatialcontrol_amd.modules.u_net_condition_modify import _EncoderHalf
+    blocks = []
+    for k in range(2):
+        blk = SimpleNamespace(resnets=[_Scale(1.5, 0.1 * k), _Scale(0.75, -0.2)], has_attn=False, attentions=[])
+        if k == 0:
+            blk.downsamplers = [_Scale(2.0, 0.0, stride=2)]
+        blocks.append(blk)
+    half = SimpleNamespace(down_blocks=blocks)
+    tadd = {r: None for blk in blocks for r in blk.resnets}
+    g = torch.Generator().manual_seed(7)
+    x0 = torch.randn(4, 8, 4, 4, generator=g).contiguous(memory_format=CL)
+    skips, x = _EncoderHalf._run_down(half, x0, None, tadd, None, None)
+    assert len(skips) == 6 and skips[-1] is x                                 # the trap: the last skip is the mid block's input
+    before = [s.clone() for s in skips]
+    feats = [torch.randn((1, 2) + tuple(s.shape[1:]), generator=g) for s in skips]
+    gate, dst = torch.tensor([[0.9, 0.5]]), torch.tensor([3, 1], dtype=torch.int32)
+    x_before = x.clone()
+    out = _EncoderHalf._scatter_skips(skips, [x], feats, gate, dst)
+    assert torch.equal(x, x_before) and out[-1] is not x                      # the mid block's input is what it was
+    for o, s, f in zip(out, before, feats):
+        assert torch.equal(o[3], s[3] + f[0, 0] * 0.9) and torch.equal(o[1], s[1] + f[0, 1] * 0.5)
+        assert torch.equal(o[0], s[0]) and torch.equal(o[2], s[2])
+        assert o.is_contiguous(memory_format=CL)
+    # the other skips were added to in place (no copies where nothing reads the tensor again)
+    assert all(o is s for o, s in zip(out[:-1], skips[:-1]))
+    # two skips on one storage: the second gets its own, the first is not added to twice
+    base = torch.randn(4, 8, 2, 2, generator=g).contiguous(memory_format=CL)
+    f2 = [torch.randn(1, 2, 8, 2, 2, generator=g) for _ in range(2)]
+    keep = base.clone()
+    o2 = _EncoderHalf._scatter_skips([base, base[:]], [], f2, gate, dst)
+    assert torch.equal(o2[0][3], keep[3] + f2[0][0, 0] * 0.9) and torch.equal(o2[1][3], keep[3] + f2[1][0, 0] * 0.9)

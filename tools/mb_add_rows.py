@@ -11,7 +11,12 @@ where x was written by the launch before.
 `achieved_gbs` = traffic / the fastest in-place time, traffic = read x + read feat + write out of the rows whose gate is on (an
 in-place row with gate 0 moves nothing); `hbm_fraction` is that against --peak-gbs (6300: the achievable HBM rate of one MI355X).
 
-    python tools/mb_add_rows.py [--calls 20] [--replays 50] [--peak-gbs 6300]
+The scatter leg (`--legs scatter`): ops.scatter_add_rows (dsc_scatter_add_rows_f16, the ControlNet residuals of the batcher's
+compact lanes) beside the eager route it replaces - per skip tensor a multiply by the per-row scales, a sum over the nets and an
+indexed add into the batch rows - at the six distinct SD1.5 skip shapes, 16 batch rows, 8 and 16 lane rows (control_slots 4 and
+8), one and two nets, every lane active and every other lane idle.  Same method, one JSON line per case ("leg": "scatter").
+
+    python tools/mb_add_rows.py [--legs gated,scatter] [--calls 20] [--replays 50] [--peak-gbs 6300]
 """
 import argparse
 import json
@@ -51,12 +56,65 @@ def timed(g, replays, calls):
     return 1e3 * e0.elapsed_time(e1) / (replays * calls)        # us per call
 
 
+SKIPS = [(320, 64, 64), (320, 32, 32), (640, 32, 32), (640, 16, 16), (1280, 16, 16), (1280, 8, 8)]
+
+
+def scatter_leg(a):
+    X = 16
+    for C, h, w in SKIPS:
+        for R in (8, 16):
+            for A in (1, 2):
+                g = torch.Generator().manual_seed(C + h + R + A)
+                x = torch.randn(X, C, h, w, generator=g).half().contiguous(memory_format=torch.channels_last).cuda()
+                feat = (torch.randn(A, R, h, w, C, generator=g) * 1e-2).half().cuda().permute(0, 1, 4, 2, 3)
+                lanes = R // 2                                             # lane j: rows j and X / 2 + j, as the batcher maps them
+                dst = torch.tensor([j for j in range(lanes)] + [X // 2 + j for j in range(lanes)], dtype=torch.int32).cuda()
+                half_dst = dst.clone()
+                half_dst[1::2] = -1
+                gate = torch.full((A, R), 0.9, device="cuda")
+                idx = dst.long()
+                gcol = gate.half().view(A, R, 1, 1, 1)
+                xs = [x.clone(memory_format=torch.preserve_format) for _ in range(4)]
+
+                def kernel(buf, d):
+                    return lambda: ops.scatter_add_rows(buf, feat, gate, d)
+
+                def eager():
+                    scaled = feat * gcol
+                    xs[3].index_add_(0, idx, scaled.sum(0) if A > 1 else scaled[0])
+
+                legs = {"kernel_us": kernel(xs[0], dst), "kernel_twin_us": kernel(xs[1], dst),
+                        "kernel_every_other_lane_idle_us": kernel(xs[2], half_dst), "eager_route_us": eager}
+                graphs = {k: graph_of(f, a.calls) for k, f in legs.items()}
+                for gr in graphs.values():
+                    timed(gr, 5, a.calls)
+                runs = [{k: timed(gr, a.replays, a.calls) for k, gr in graphs.items()} for _ in range(3)]
+                best = {k: min(r[k] for r in runs) for k in legs}
+                row_bytes = 2 * C * h * w
+                traffic = (2 + A) * R * row_bytes                          # read x rows, read A feature rows, write x rows
+                line = {"leg": "scatter", "C": C, "h": h, "w": w, "batch_rows": X, "lane_rows": R, "nets": A}
+                line.update({k: [round(r[k], 2) for r in runs] for k in legs})
+                line.update({"twin_spread_us": round(max(abs(r["kernel_us"] - r["kernel_twin_us"]) for r in runs), 2),
+                             "kernel_over_eager": round(min(best["kernel_us"], best["kernel_twin_us"]) / best["eager_route_us"], 3),
+                             "traffic_bytes": traffic, "achieved_gbs": round(traffic / best["kernel_us"] / 1e3, 1),
+                             "hbm_fraction": round(traffic / best["kernel_us"] / 1e3 / a.peak_gbs, 3),
+                             "note": "us per call, device events around graph replays, three alternating rounds; eager = `feat * "
+                                     "scale` (+ `.sum(0)` over two nets) then `x.index_add_`"})
+                print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--replays", type=int, default=50)
     ap.add_argument("--peak-gbs", type=float, default=6300.0, help="achievable HBM rate the traffic is taken against")
+    ap.add_argument("--legs", default="gated,scatter", help="comma-separated: gated (add_rows_gated), scatter (scatter_add_rows)")
     a = ap.parse_args()
+    legs_wanted = set(a.legs.split(","))
+    if "scatter" in legs_wanted:
+        scatter_leg(a)
+    if "gated" not in legs_wanted:
+        return
     cl = torch.channels_last
     for C, h, w in LEVELS:
         for rows in ROWS:

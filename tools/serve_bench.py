@@ -1,7 +1,7 @@
 """Continuous-batching serving measurements (modules/serving.py) on one GPU; one JSON line per leg.
 
     python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
-                                [--hires X] [--ip-adapter [--ip-masks]] [--t2i-adapter]
+                                [--hires X] [--ip-adapter [--ip-masks]] [--t2i-adapter] [--controlnet [--control-slots C]]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -36,6 +36,13 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
               three alternating rounds: the plain requests on both (the price of the flag), then every other request with a
               control image at factor 0.5 on the adapter-capable one; and what admission costs: the GPU time of one request's
               adapter forward on the batch's stream (what the next step waits for) and the host time of submit with and without
+  controlnet  (--controlnet [--control-slots C, default 4]: this leg only) an SD1.5-size ControlNet with seeded random weights
+              set up, then two batchers on two slots: one built without `controlnet` and one built with it on C lanes.  8 slots
+              kept full, three alternating rounds: the plain requests on both (the price of the flag: thirteen launches that
+              return at once and one copy of the last skip tensor), then every other request with a control image (scale 0.9,
+              window [0, 0.6]) on the ControlNet-capable one; and what admission costs: the GPU time of one request's
+              conditioning embedding on the batch's stream (it runs when the request is admitted), whether it repeats bit for bit, and
+              the host time of submit with and without
 """
 import argparse
 import json
@@ -137,6 +144,9 @@ def main():
                     help="with --ip-adapter: also a mask-capable batcher, every other image-prompt request with a half-image mask")
     ap.add_argument("--t2i-adapter", action="store_true",
                     help="only the T2I-Adapter leg: every other request carries a control image with factor 0.5 (random weights)")
+    ap.add_argument("--controlnet", action="store_true",
+                    help="only the ControlNet leg: every other request carries a control image (random weights, SD1.5 size)")
+    ap.add_argument("--control-slots", type=int, default=4, help="with --controlnet: the ControlNet lanes of the batcher")
     a = ap.parse_args()
     if a.ip_masks and not a.ip_adapter:
         ap.error("--ip-masks goes with --ip-adapter")
@@ -149,6 +159,81 @@ def main():
     opt = {"scheduler": "karras"}
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    if a.controlnet:
+        from diffusionspatialcontrol_amd.modules.controlnet import ControlNetModel
+        torch.manual_seed(a.seed + 9)
+        with torch.device("cuda"):
+            cn = ControlNetModel(UNetConfig.sd15())
+        for conv in list(cn.controlnet_down_blocks) + [cn.controlnet_mid_block, cn.controlnet_cond_embedding.conv_out]:
+            torch.nn.init.normal_(conv.weight, 0.0, 0.02)                  # (zero convolutions would make every residual zero)
+        pipe.setup_controlnet(cn.half().eval())
+        off = pipe.serve(512, 512, max_batch=8, slot=0).warm()
+        on = pipe.serve(512, 512, max_batch=8, slot=1, controlnet=True, control_slots=a.control_slots).warm()
+        images = [torch.rand(1, 3, 512, 512, generator=torch.Generator().manual_seed(a.seed * 1000 + 5000 + i)) for i in range(len(reqs))]
+        mixed = [dict(r, control_img=images[i], controlnet_conditioning_scale=0.9, control_guidance_start=0.0,
+                      control_guidance_end=0.6) if i % 2 else dict(r) for i, r in enumerate(reqs)]
+        for b, group in ((off, reqs[:8]), (on, reqs[:8]), (on, mixed[:8])):     # one untimed pass each
+            run_full(b, group, kw25)
+        runs = []
+        s_before = on.stats()
+        for _ in range(3):                                # alternating, so that a drift of the box hits all alike
+            runs.append((run_full(off, reqs, kw25), run_full(on, reqs, kw25), run_full(on, mixed, kw25)))
+        s_after = on.stats()
+        emit(leg="controlnet", requests=len(reqs), steps=25, control_slots=a.control_slots,
+             mix="every other request with a control image, scale 0.9, window [0, 0.6] (15 of 25 model calls)",
+             flag_off_plain_img_s=[round(t[0][0], 2) for t in runs], flag_on_plain_img_s=[round(t[1][0], 2) for t in runs],
+             flag_on_every_other_with_control_img_s=[round(t[2][0], 2) for t in runs],
+             flag_off_plain_steps_s=[round(t[0][1], 1) for t in runs], flag_on_plain_steps_s=[round(t[1][1], 1) for t in runs],
+             flag_on_every_other_with_control_steps_s=[round(t[2][1], 1) for t in runs],
+             control_steps=s_after["control_steps"] - s_before["control_steps"], steps_in_those_rounds=s_after["steps"] - s_before["steps"],
+             control_gate_updates=s_after["control_gate_updates"] - s_before["control_gate_updates"],
+             captures_after_warm=on.stats()["captures_after_warm"],
+             note="three alternating rounds in one process; the flag-off batcher captures the step of a pipeline without the feature; "
+                  "with fewer lanes than control requests the later ones wait in the queue (FIFO)")
+        # one ControlNet replay (all 2 c lane rows) and one bucket-8 step, device time
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        with torch.cuda.stream(on.exec.stream):
+            e0.record()
+            for _ in range(10):
+                on.exec.run_control(8)
+            e1.record()
+            for _ in range(10):
+                on.exec.run(8)
+            e2.record()
+        torch.cuda.synchronize()
+        emit(leg="controlnet_replay", control_slots=a.control_slots, lane_rows=2 * a.control_slots,
+             controlnet_replay_gpu_ms=round(e0.elapsed_time(e1) / 10, 3), bucket8_step_gpu_ms=round(e1.elapsed_time(e2) / 10, 3),
+             note="ten back-to-back replays each on the batch's stream (gather launches included), every lane idle in the step")
+        # admission: the conditioning embedding runs on the batch's stream when the request takes its lane; that step waits for it
+        host = {"plain": [], "control": []}
+        gpu, repeats = [], []
+        for i in range(1, 7):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = on._prepare(dict(mixed[i], **kw25))
+            host["control" if i % 2 else "plain"].append(time.perf_counter() - t0)
+            if i % 2:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                with torch.cuda.stream(on.exec.stream):
+                    e0.record()
+                    on.exec._control_rows(r)
+                    e1.record()
+                torch.cuda.synchronize()
+                gpu.append(e0.elapsed_time(e1))
+                first = [e.clone() for e in r.cemb]
+                with torch.cuda.stream(on.exec.stream):
+                    on.exec._control_rows(r)
+                torch.cuda.synchronize()
+                repeats.append(all(torch.equal(a_, b_) for a_, b_ in zip(first, r.cemb)))
+        emit(leg="controlnet_admission", conditioning_embedding_gpu_ms=[round(v, 3) for v in gpu],
+             embedding_repeats_bit_for_bit=repeats,
+             submit_host_ms_plain=[round(1e3 * v, 3) for v in host["plain"]],
+             submit_host_ms_with_control=[round(1e3 * v, 3) for v in host["control"]],
+             note="gpu: device events around one request's image preparation + conditioning embedding (seven library convolutions and the last one on the package's 3x3 kernel) "
+                  "+ layout on the batch's stream; host: the whole of submit's preparation on the caller's thread, launches included")
+        emit(leg="stats", flag_off=off.stats(), flag_on=on.stats())
+        return
 
     if a.t2i_adapter:
         from diffusionspatialcontrol_amd.modules import t2i_adapter as t2i
