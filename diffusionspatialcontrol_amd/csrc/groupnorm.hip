@@ -3,7 +3,7 @@
 // In NCHW the (C/groups) channels of a group are adjacent, so group g of row b is ONE contiguous span of
 // n = (C/groups)*hw halves.  The op is HBM-bound (read x, write y) and the UNet has only B*32 groups per
 // tensor (64 at batch 1), far fewer than the 256 CUs, so every span is cut into `nsplit` chunks:
-//   launch 1  gn_stats : one workgroup per (group, chunk): 16-B loads, fp32 lane sums -> fp64 (sum, sumsq)
+//   launch 1  gn_stats : one workgroup per (group, chunk): 16-B loads, fp32 lane sums about a pivot -> fp64 (sum, sumsq)
 //   launch 2  gn_apply : same grid; each workgroup re-adds its group's nsplit partials (fixed order ->
 //                        bit-reproducible), then normalises its chunk with the per-channel affine and SiLU.
 // The second read of x comes from L2 / Infinity Cache (the tensors are 0.3 - 10 MB).
@@ -28,16 +28,26 @@ __global__ __launch_bounds__(kT) void gn_stats(GnParams p) {
     const half_t* base = p.x + (long long)bg * p.n8 * 8;
     const long long v0 = (long long)sp * p.chunk8;
     const long long v1 = min(v0 + p.chunk8, p.n8);
+    // The fp32 sums are taken about a pivot (the thread's first value; all of a workgroup's values belong to one group) and
+    // moved back to sums about zero in fp64: a group that sits hundreds of standard deviations from zero otherwise loses its
+    // variance to the rounding of an fp32 sum of squares of order mean^2, 128 values of it or not.
     double d1 = 0.0, d2 = 0.0;
-    float s1 = 0.f, s2 = 0.f;
+    float s1 = 0.f, s2 = 0.f, pv = 0.f;
     int cnt = 0;
-    for (long long v = v0 + threadIdx.x; v < v1; v += kT) {
+    long long nv = 0;                                          // vectors this thread read
+    for (long long v = v0 + threadIdx.x; v < v1; v += kT, ++nv) {
         const h8_t val = *reinterpret_cast<const h8_t*>(base + v * 8);
+        if (nv == 0) pv = (float)val[0];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const float f = (float)val[j]; s1 += f; s2 += f * f; }
+        for (int j = 0; j < 8; ++j) { const float f = (float)val[j] - pv; s1 += f; s2 += f * f; }
         if (++cnt == 16) { d1 += s1; d2 += s2; s1 = s2 = 0.f; cnt = 0; }    // fp32 only over 128 values
     }
     d1 += s1; d2 += s2;
+    {   // sum x = sum (x - p) + n p,  sum x^2 = sum (x - p)^2 + 2 p sum (x - p) + n p^2
+        const double n = 8.0 * (double)nv, pp = (double)pv;
+        d2 += pp * (2.0 * d1 + n * pp);
+        d1 += n * pp;
+    }
     d1 = wave_sum_f64(d1); d2 = wave_sum_f64(d2);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { red[2 * wave] = d1; red[2 * wave + 1] = d2; }

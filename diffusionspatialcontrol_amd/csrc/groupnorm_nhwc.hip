@@ -7,6 +7,10 @@
 //   launch 1 gn_nhwc_stats    : workgroup = (image, row chunk, channel slab of whole groups): per-thread channel sums -> LDS
 //                               [slices][slab] -> per-channel -> per-group (sum, sumsq) in fp64 -> partials[b][chunk][g].
 //                               At most 32 row chunks per image; the slabs supply the rest of the parallelism.
+//                               The fp32 per-thread sums are taken about a PIVOT (the thread's first row, per channel):
+//                               sum (x - p), sum (x - p)^2, moved back to sums about zero in fp64.  A channel that sits
+//                               hundreds of standard deviations from zero (residual-stream DC offsets) otherwise loses its
+//                               variance to the rounding of an fp32 sum of squares of order mean^2 before fp64 ever sees it.
 //   (gn_nhwc_finalize         : one wave per (image, group) adds the chunk partials -> (mean, rstd)[b][g] - only in the
 //                               diagnostic three-launch form (mode 4) now: before the slabs a large tensor needed ~256 row
 //                               chunks per image to fill the chip, too many for every apply workgroup to re-add)
@@ -61,15 +65,16 @@ __global__ __launch_bounds__(kMaxT) void gn_nhwc_stats(GnN p) {
     const int v0 = slab * p.scv;                              // first vector of the slab
     const int sw = min(p.scv, p.cv - v0);                     // this slab's width in vectors (the last one may be narrower)
     const int SC = p.scv * 8;                                 // LDS row pitch in channels
-    float* ssum = reinterpret_cast<float*>(smem);            // [sk][SC]
-    float* ssq = ssum + p.sk * SC;                           // [sk][SC]
+    double* ssum = reinterpret_cast<double*>(smem);          // [sk][SC]
+    double* ssq = ssum + p.sk * SC;                          // [sk][SC]
     const int slice = fdiv(threadIdx.x, p.fd_scv), lv = threadIdx.x - slice * p.scv;
     const bool live = lv < sw;
     const int c8 = v0 + lv;
     const int r0 = chunk * p.rows, r1 = min(r0 + p.rows, p.HW);
-    float s[8], q[8], ad[8];
+    float s[8], q[8], ad[8], pv[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; ad[j] = 0.f; }
+    for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; ad[j] = 0.f; pv[j] = 0.f; }
+    int nrow = 0;                                             // rows this thread summed
     if (live) {
         if (p.add) {
             const h8_t a = *reinterpret_cast<const h8_t*>(p.add + (long long)b * p.add_stride + c8 * 8);
@@ -87,6 +92,7 @@ __global__ __launch_bounds__(kMaxT) void gn_nhwc_stats(GnN p) {
             cdst = p.cat + (long long)b * p.HW * p.C + c8 * 8;
         }
         // four rows in flight per thread (the loads of a runtime-bounded loop are otherwise issued one latency apart)
+        bool first = true;
         for (int row = r0 + slice; row < r1; row += 4 * p.sk) {
             h8_t v[4];
 #pragma unroll
@@ -94,28 +100,43 @@ __global__ __launch_bounds__(kMaxT) void gn_nhwc_stats(GnN p) {
                 v[u] = h8_t{0, 0, 0, 0, 0, 0, 0, 0};
                 if (row + u * p.sk < r1) v[u] = *reinterpret_cast<const h8_t*>(base + (long long)(row + u * p.sk) * rs);
             }
+            if (first) {                                      // pivot = this thread's first row (v[0] is in range: row < r1)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pv[j] = (float)v[0][j] + ad[j];
+                first = false;
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (row + u * p.sk < r1) {
+                    ++nrow;
                     if (cdst) *reinterpret_cast<h8_t*>(cdst + (long long)(row + u * p.sk) * p.C) = v[u];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) { const float f = (float)v[u][j] + ad[j]; s[j] += f; q[j] += f * f; }
+                    for (int j = 0; j < 8; ++j) { const float f = ((float)v[u][j] + ad[j]) - pv[j]; s[j] += f; q[j] += f * f; }
                 }
             }
         }
     }
+    // every thread moves its own sums from its pivots back to zero, in fp64 (in parallel, ahead of the serial additions below):
+    // sum x = sum (x - p) + n p,  sum x^2 = sum (x - p)^2 + 2 p sum (x - p) + n p^2
+    {
+        const double n = (double)nrow;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { ssum[slice * SC + lv * 8 + j] = s[j]; ssq[slice * SC + lv * 8 + j] = q[j]; }
+        for (int j = 0; j < 8; ++j) {
+            const double d1 = (double)s[j], pp = (double)pv[j];
+            ssum[slice * SC + lv * 8 + j] = d1 + n * pp;
+            ssq[slice * SC + lv * 8 + j] = (double)q[j] + pp * (2.0 * d1 + n * pp);
+        }
+    }
     __syncthreads();
     // per-channel totals over the sk slices (threads stride the channels, fixed order, fp64) into tot[SC][2] behind the
     // slice sums, then per-group totals over the cpg channels: two short dependent chains (sk, cpg) instead of one of
     // sk * cpg fp64 adds
-    double* tot = reinterpret_cast<double*>(ssq + p.sk * SC);
+    double* tot = ssq + p.sk * SC;
     const int nch = sw * 8;                                   // channels of this slab
     if (p.sk > 1) {                                           // one slice: the group sum reads the slice values directly
         for (int c = threadIdx.x; c < nch; c += blockDim.x) {
             double c1 = 0.0, c2 = 0.0;
-            for (int sl = 0; sl < p.sk; ++sl) { c1 += (double)ssum[sl * SC + c]; c2 += (double)ssq[sl * SC + c]; }
+            for (int sl = 0; sl < p.sk; ++sl) { c1 += ssum[sl * SC + c]; c2 += ssq[sl * SC + c]; }
             tot[2 * c] = c1; tot[2 * c + 1] = c2;
         }
         __syncthreads();
@@ -125,7 +146,7 @@ __global__ __launch_bounds__(kMaxT) void gn_nhwc_stats(GnN p) {
         const int gl = threadIdx.x;
         double a1 = 0.0, a2 = 0.0;
         if (p.sk > 1) for (int c = gl * p.cpg; c < (gl + 1) * p.cpg; ++c) { a1 += tot[2 * c]; a2 += tot[2 * c + 1]; }
-        else for (int c = gl * p.cpg; c < (gl + 1) * p.cpg; ++c) { a1 += (double)ssum[c]; a2 += (double)ssq[c]; }
+        else for (int c = gl * p.cpg; c < (gl + 1) * p.cpg; ++c) { a1 += ssum[c]; a2 += ssq[c]; }
         const int g = v0 * 8 / p.cpg + gl;
         double* dst = p.partials + (((long long)b * p.nchunk + chunk) * p.G + g) * 2;
         dst[0] = a1; dst[1] = a2;
@@ -618,7 +639,7 @@ int run_groupnorm(const void* x, const void* x2, int C1, void* cat, void* y, con
         p.rows = p.arows; p.nchunk = p.anchunk; p.inline_stats = 0;
         p.scv = p.cv; p.nslab = 1; p.sk = p.k;
     }
-    const size_t stats_lds = (size_t)2 * p.sk * p.scv * 8 * sizeof(float) + (size_t)2 * p.scv * 8 * sizeof(double);
+    const size_t stats_lds = (size_t)2 * p.sk * p.scv * 8 * sizeof(double) + (size_t)2 * p.scv * 8 * sizeof(double);
     if (stats_lds > 64 * 1024) {
         static bool attr_set = false;
         if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_nhwc_stats), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }

@@ -1902,6 +1902,16 @@ def test_groupnorm_epilogue_statistics_with_a_large_channel_offset(ops, offset):
     e1, e2 = (one.float() - gref).abs(), (two.float() - gref).abs()
     assert e1.max().item() <= 2.0 * e2.max().item() + 4e-3 and e1.mean().item() <= 2.0 * e2.mean().item() + 2e-4, \
         (e1.max().item(), e2.max().item(), e1.mean().item(), e2.mean().item())
+    # the relative bound alone passes when both forms are wrong together: each against an fp64 GroupNorm of the same tensor, with
+    # the bound of test_groupnorm_silu_nhwc
+    grp = out.double().reshape(B, groups, -1)
+    mean = grp.mean(dim=2, keepdim=True)
+    norm = ((grp - mean) / torch.sqrt(((grp - mean) ** 2).mean(dim=2, keepdim=True) + 1e-5)).reshape(B, cout, hw, hw)
+    ref64 = norm * gamma.double().view(1, -1, 1, 1) + beta.double().view(1, -1, 1, 1)
+    for name, y in (("one", one), ("two", two)):
+        err = (y.double() - ref64).abs()
+        assert err.max().item() < 4e-3 * max(1.0, ref64.abs().max().item()) and err.mean().item() < 4e-4, \
+            (name, err.max().item(), err.mean().item())
 
 
 @pytest.mark.parametrize("B,L,K,N,groups", [(2, 4096, 320, 320, 32), (2, 1024, 640, 640, 32), (2, 4096, 960, 320, 32), (2, 1024, 1920, 640, 32),
