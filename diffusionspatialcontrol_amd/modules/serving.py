@@ -95,6 +95,20 @@ then the bucket's graph; with no gate open the ControlNet is skipped.  The gate 
 `scale * keep[min(k, len(keep) - 1)]` (preprocess_controlnet's keep for the step count the pipeline method passes); all gates 0 is a
 plain request (no lane).  A batcher built without the flag captures the step it captured before and refuses the key.
 
+Finished images.  A batcher built with `decode=True, decode_batch=d` on a pipeline with a VAE decoder hands out images without
+stopping the step for them.  A request whose `output_type` is "pil", "np" or "uint8" leaves as before (its final row is cloned on
+the batcher's stream); at the end of that transition the cloned rows go, up to d at a time, to the DECODE LANE: a second stream
+with, per decode bucket (1, d and the powers of two between), a static input, static uint8 and float32 [m, H, W, 3] outputs and ONE
+captured graph - `1 / scaling_factor * z`, `vae.decode`, and dsc_image_finish once per output kind (decode_latents' clamp, NHWC
+permute and float conversion, numpy_to_pil's rounding to bytes, on the device).  The lane's stream waits on the clones' events,
+copies the rows into the static input (rows of a padded bucket that hold no request are zeros), replays the graph, copies each
+request's row of the kind it asked for into a slot of a small ring of pinned host buffers (non-blocking) and records an event.
+The lane has no thread: the thread that steps the batcher queues its work, and the poll that resolves latent rows resolves
+images too - `ready` queries the lane's event, `result` copies the row out of the pinned slot (which frees it) and, for "pil",
+wraps it.  No GPU work, allocation or stream synchronisation happens under the lock after `warm()`; only a full ring makes the
+dispatcher wait, for the oldest decode.  "latent" requests never touch the lane, and a batcher built without the flag has no lane,
+no second stream and the inline `latent_to_image` path it had ("uint8", which that path does not know, is refused at submit).
+
 The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
 request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
 """
@@ -115,6 +129,8 @@ from .external_k_diffusion import DiscreteVDDPMDenoiser
 _EMBED_LOCK = threading.Lock()       # around the process-wide deterministic switch in _GraphExecutor._control_embedding
 MAX_TEXT_KEYS = 384                  # the chunked prepared-operand kernels (ops.region_xattn_packed)
 _UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter")
+_IMAGE_TYPES = ("pil", "np", "numpy", "uint8")      # what a batcher built with `decode=True` hands out besides "latent"
+_DECODE_RING = 4                     # pinned host slots of the decode lane: decodes whose rows have not been collected yet
 _FLAG_HINT = {"image_t2i_adapter": "; a batcher built with `t2i_adapter=True` (pipe.serve(..., t2i_adapter=True)) serves it",
              "control_img": "; a batcher built with `controlnet=True` (pipe.serve(..., controlnet=True)) serves it"}
 
@@ -124,6 +140,15 @@ def _ip_layers(pipe):
     from .attention_modify import _IPAdapterProcessor
     from .u_net_condition_modify import Attention
     return [(m, m.processor) for m in pipe.unet.modules() if isinstance(m, Attention) and isinstance(m.processor, _IPAdapterProcessor)]
+
+
+def decode_buckets(decode_batch):
+    """the batch sizes the decode lane captures: 1, decode_batch and the powers of two between"""
+    out, m = {1, int(decode_batch)}, 2
+    while m < decode_batch:
+        out.add(m)
+        m *= 2
+    return tuple(sorted(out))
 
 
 def _spatial_size(image):
@@ -151,7 +176,7 @@ class ServingBatcher:
     the scheduling here is host logic only."""
 
     def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
-                 t2i_adapter=False, controlnet=False, control_slots=None):
+                 t2i_adapter=False, controlnet=False, control_slots=None, decode=False, decode_batch=2):
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
             raise ValueError(f"serve: buckets {buckets} must cover max_batch={max_batch}")
@@ -174,6 +199,17 @@ class ServingBatcher:
                                           linear_transitions=0, handoffs=0, adapter_gate_updates=0, control_steps=0,
                                           control_gate_updates=0)
         self._hires = None                     # the chained batcher of the hires pass (chain_hires)
+        # requests may ask for images ("pil" / "np" / "uint8"): a decode lane beside the step finishes them (module docstring)
+        self.decode = bool(decode)
+        self.decode_batch = 0
+        if self.decode:
+            if getattr(pipe, "vae", None) is None:
+                raise ValueError("serve: `decode=True` on a pipeline without a VAE (construct it with a "
+                                 "modules.vae_decoder.AutoencoderKLDecoder, or serve latents)")
+            if isinstance(decode_batch, bool) or not isinstance(decode_batch, int) or not 1 <= decode_batch <= self.max_batch:
+                raise ValueError(f"serve: `decode_batch` must be an integer in [1, max_batch = {self.max_batch}], got {decode_batch!r}")
+            self.decode_batch = decode_batch
+            self._stats["decodes"] = self._stats["decode_rows"] = 0
         self._warm_captures = None
         self._thread = None
         self._stop = False
@@ -308,6 +344,8 @@ class ServingBatcher:
                 self.exec.warm_control()
             for n in self.buckets:
                 self._ensure(n)
+            if self.decode:
+                self._ensure_decode()                # the lane's stream, static buffers, graphs and pinned ring
             self._warm_captures = self._stats["captures"]
         return self
 
@@ -332,8 +370,9 @@ class ServingBatcher:
     def submit(self, request):
         """request: txt2img_coalesced's request dict plus its own `num_inference_steps` (default 25), `sampler_opt` (the
         schedule: karras / exponential / ...), `guidance_scale` (> 1, default 7.5) and `latents` / `generator`; optional
-        `output_type` ("latent", default, or what latent_to_image takes), `sampler_name` (sampling.LINEAR_FAMILY, default
-        DPM++ 2M) with `eta` / `s_noise` / `solver_type`, `step_noise` ([steps, 1, 4, h, w]: the noise of every step;
+        `output_type` ("latent", default, or what latent_to_image takes; on a batcher built with `decode=True`: "latent", "pil",
+        "np" / "numpy" - float32 [H, W, 3] - or "uint8" - np.uint8 [H, W, 3], the bytes of the PIL image), `sampler_name`
+        (sampling.LINEAR_FAMILY, default DPM++ 2M) with `eta` / `s_noise` / `solver_type`, `step_noise` ([steps, 1, 4, h, w]: the noise of every step;
         default: drawn as the sampler itself would, from `seed` / `generator`) and `guidance_rescale` (in [0, 1], default 0; not
         with `mask_image`).  On a pipeline with IP-Adapters loaded: `ip_adapter_image_embeds` (a list with one tensor per loaded
         adapter, each [negative; positive] along dim 0 with ONE image per half - what txt2img takes, see encode_image; absent /
@@ -421,6 +460,19 @@ class ServingBatcher:
         control = self._control_request(request, second)
         if request.get("upscale") and not second:
             return self._prepare_hires_pair(request)
+        out_type = request.get("output_type", "latent")
+        if self.decode:
+            if out_type not in ("latent",) + _IMAGE_TYPES:
+                raise ValueError(f"serve: `output_type` {out_type!r} is not served by a batcher built with `decode=True` (one of: "
+                                 f"latent, {', '.join(_IMAGE_TYPES)})")
+            if out_type == "pil":
+                try:
+                    import PIL.Image  # noqa: F401
+                except ImportError as e:
+                    raise ValueError("serve: `output_type` 'pil' needs Pillow; ask for 'uint8' (the same bytes as an array)") from e
+        elif out_type == "uint8":
+            raise ValueError("serve: `output_type` 'uint8' is made by the decode lane: build the batcher with `decode=True` "
+                             "(pipe.serve(..., decode=True))")
         v_pred = bool(getattr(pipe, "v_prediction", False))
         # the v scalars (step_skip, c_out) come from the denoiser object, the choice of launch from the flag: setup_unet sets
         # both from the scheduler; a flag flipped by hand on an eps-prediction pipeline (tests/test_serving_host.py does that to
@@ -491,7 +543,7 @@ class ServingBatcher:
         r.control, r.cgates, r.lane, r.cemb = control, None, None, None
         t_start = self._image_request(r)
         r.guidance = g
-        r.output_type = request.get("output_type", "latent")
+        r.output_type = out_type
         dev, dt = self.exec.device, self.exec.dtype
         r.sig_dev = pipe._schedule(r.steps, request.get("sampler_opt") or {}, dev, dt)      # txt2img's schedule, fp16-rounded
         sig = getattr(r.sig_dev, "_dsc_host", None)
@@ -1022,6 +1074,8 @@ class ServingBatcher:
             slots[r.slot] = None
             if r.hires is not None:
                 self._hand_off(r)
+            elif self.decode and r.output_type != "latent":
+                self._done.append((r, self.exec.finish_image(r)))       # the row is cloned now and goes to the lane below
             else:
                 self._done.append((r, self.exec.finish(r)))
             r.hnoise = None                          # (a second-pass record: its start noise was read before it joined)
@@ -1068,6 +1122,12 @@ class ServingBatcher:
             self.exec.run(n_dst)
             self._stats["steps"] += 1
         self._n = n_dst
+        if self.decode and any(r.output_type != "latent" for r in leaving):
+            # after the next step is queued: the lane's stream waits on the clones' events only, so the decode runs beside it
+            self._ensure_decode()
+            decodes, rows = self.exec.flush_decodes()
+            self._stats["decodes"] += decodes
+            self._stats["decode_rows"] += rows
         return True
 
     def _hand_off(self, r):
@@ -1094,6 +1154,9 @@ class ServingBatcher:
     def _ensure_control(self):
         if self.exec.ensure_control():
             self._stats["captures"] += 1
+
+    def _ensure_decode(self):
+        self._stats["captures"] += self.exec.ensure_decode()
 
     def _poll(self, wait=False):
         """resolve the futures of requests whose final row copy has completed (in completion order)"""
@@ -1169,6 +1232,8 @@ class _GraphExecutor:
         # (controlnet) the lane buffers, the captured ControlNet graph and its residual buffers: one per batcher (ensure_control)
         self.cn_nets = batcher._control_nets() if batcher.cn else []
         self.cn = None
+        # (decode) the lane that finishes images beside the step; its stream and buffers are built by ensure_decode
+        self.lane = _DecodeLane(self, batcher.decode_batch) if getattr(batcher, "decode", False) else None
 
     def bind_thread(self):
         _lib.check(_lib.load_library().dsc_set_workspace_slot(self.b.slot), "dsc_set_workspace_slot")
@@ -1505,10 +1570,30 @@ class _GraphExecutor:
             ev.record(self.stream)
         return out, ev
 
+    def finish_image(self, r):
+        """finish() for a request that leaves a decode batcher with an image `output_type`: the same clone and event, wrapped in
+        the handle the lane resolves; the row waits in the lane's pending list until flush_decodes"""
+        out, ev = self.finish(r)
+        h = _LaneHandle(out, ev, r.output_type)
+        self.lane.pending.append(h)
+        return h
+
+    def ensure_decode(self):
+        """the decode lane's stream, per-bucket static buffers and graphs, pinned ring -> how many graphs this call captured"""
+        return self.lane.ensure()
+
+    def flush_decodes(self):
+        """the pending rows to the lane, up to decode_batch at a time -> (decodes queued, rows in them)"""
+        return self.lane.dispatch()
+
     def ready(self, h):
+        if isinstance(h, _LaneHandle):
+            return self.lane.ready(h)
         return h[1].query()
 
     def result(self, r, h):
+        if isinstance(h, _LaneHandle):
+            return self.lane.result(h)
         out, ev = h
         ev.synchronize()
         if r.output_type == "latent":
@@ -1710,6 +1795,159 @@ class _GraphExecutor:
     def run(self, n):
         with torch.cuda.stream(self.stream):
             self.st[n]["run"]()
+
+
+class _LaneHandle:
+    """one image request between leaving the batch and its resolved future: the cloned latent row and its event, then (once
+    queued) the lane entry and row index its image lands in, then the value"""
+    __slots__ = ("row", "cloned", "output_type", "kind", "entry", "index", "value")
+
+    def __init__(self, row, cloned, output_type):
+        self.row, self.cloned, self.output_type = row, cloned, output_type
+        self.kind = "uint8" if output_type in ("pil", "uint8") else "float32"
+        self.entry, self.index, self.value = None, None, None
+
+
+class _DecodeLane:
+    """The decode lane of a batcher built with `decode=True` (module docstring): device side only, driven by the thread that
+    steps the batcher, under the batcher's lock."""
+
+    def __init__(self, ex, decode_batch):
+        self.ex, self.device = ex, ex.device
+        self.vae = ex.pipe.vae
+        p = next(self.vae.parameters())
+        if p.dtype != torch.float16 or p.device != self.device:
+            raise NotImplementedError(f"serve: `decode=True` needs the VAE in fp16 on the pipeline's GPU ({self.device}), got "
+                                      f"{p.dtype} on {p.device}")
+        self.decode_batch = int(decode_batch)
+        self.buckets = decode_buckets(self.decode_batch)
+        self.stream = None
+        self.st = {}                           # decode bucket -> static input, outputs and the captured graph
+        self.ring, self.free = None, []        # pinned host slots {"uint8", "float32"}: [decode_batch, H, W, 3] each
+        self.inflight = collections.deque()    # queued decodes whose rows have not all been collected, oldest first
+        self.pending = []                      # handles of rows cloned in this transition, not queued yet
+
+    def ensure(self):
+        if self.st:
+            return 0
+        from .model_k_diffusion import _CAPTURE_LOCK
+        with _CAPTURE_LOCK:
+            self.ex.bind_thread()
+            self.stream = torch.cuda.Stream(device=self.device)
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+            for m in self.buckets:
+                self._capture(m)
+            H, W = self.st[self.buckets[0]]["uint8"].shape[1:3]
+            self.ring = [{"uint8": torch.empty((self.decode_batch, H, W, 3), dtype=torch.uint8).pin_memory(),
+                          "float32": torch.empty((self.decode_batch, H, W, 3), dtype=torch.float32).pin_memory()}
+                         for _ in range(_DECODE_RING)]
+            self.free = list(range(_DECODE_RING))
+        return len(self.buckets)
+
+    @torch.no_grad()
+    def _capture(self, m):
+        """bucket m's static buffers and ONE graph: decode_latents' `1 / scaling_factor * latents` and `vae.decode(...).sample`,
+        then dsc_image_finish once per output kind.  Same order as _GraphExecutor._capture: two eager runs on the lane's stream,
+        the capture, replays on the lane's stream."""
+        dev, vae = self.device, self.vae
+        inv = 1 / vae.config.scaling_factor
+        with torch.cuda.stream(self.stream):
+            st = {"z": torch.zeros((m,) + self.ex.lat_shape, device=dev, dtype=torch.float16)}
+
+        def decode():
+            img = vae.decode(inv * st["z"]).sample
+            return img if img.is_contiguous() else img.contiguous()
+
+        with torch.cuda.stream(self.stream):
+            shape = tuple(decode().shape)
+            if len(shape) != 4 or shape[:2] != (m, 3) or shape[2] % 8 or shape[3] % 8:
+                raise NotImplementedError(f"serve: `decode=True`: the VAE decodes {(m,) + self.ex.lat_shape} to {shape}; the lane "
+                                          f"finishes [m, 3, H, W] images with sides that are multiples of 8 (dsc_image_finish)")
+            st["uint8"] = torch.zeros((m, shape[2], shape[3], 3), device=dev, dtype=torch.uint8)
+            st["float32"] = torch.zeros((m, shape[2], shape[3], 3), device=dev, dtype=torch.float32)
+
+        def run():
+            img = decode()
+            ops.image_finish(img, "uint8", out=st["uint8"])
+            ops.image_finish(img, "float32", out=st["float32"])
+
+        side = self.stream
+        with torch.cuda.stream(side):
+            for _ in range(2):                       # warm-up: workspaces, kernel selection, the decoder's derived weights
+                run()
+        if ops.GRAPHS_ENABLED:
+            torch.cuda.current_stream(dev).wait_stream(side)
+            from .model_k_diffusion import _capture_without_gc
+            g = torch.cuda.CUDAGraph()
+            with _capture_without_gc(), torch.cuda.graph(g):
+                run()
+            side.wait_stream(torch.cuda.current_stream(dev))
+            st["graph"] = g
+            st["run"] = g.replay
+        else:
+            st["run"] = run
+        self.st[m] = st
+
+    def dispatch(self):
+        decodes = rows = 0
+        while self.pending:
+            chunk, self.pending = self.pending[:self.decode_batch], self.pending[self.decode_batch:]
+            self._queue(chunk)
+            decodes, rows = decodes + 1, rows + len(chunk)
+        return decodes, rows
+
+    @torch.no_grad()
+    def _queue(self, chunk):
+        """one decode of these rows: wait for their clones, fill the static input, replay, copy each request's row of its kind
+        into a pinned slot, record the event the poll queries"""
+        m = next(b for b in self.buckets if b >= len(chunk))
+        st = self.st[m]
+        if not self.free:                            # every pinned slot holds rows nobody has collected: wait for the oldest
+            for h in list(self.inflight[0]["handles"]):
+                if h.value is None:
+                    h.value = self._take(h)
+        slot = self.free.pop()
+        with torch.cuda.stream(self.stream):
+            for i, h in enumerate(chunk):
+                self.stream.wait_event(h.cloned)
+                st["z"][i].copy_(h.row[0])
+            if len(chunk) < m:
+                st["z"][len(chunk):].zero_()
+            st["run"]()
+            for i, h in enumerate(chunk):
+                self.ring[slot][h.kind][i].copy_(st[h.kind][i], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        entry = {"ev": ev, "slot": slot, "handles": list(chunk), "left": len(chunk)}
+        for i, h in enumerate(chunk):
+            h.entry, h.index = entry, i
+        self.inflight.append(entry)
+
+    def ready(self, h):
+        return h.value is not None or (h.entry is not None and h.entry["ev"].query())
+
+    def _take(self, h):
+        """the value of a queued handle, copied out of its pinned slot (waits for the decode when it has not completed); the last
+        row taken frees the slot, and the cloned latent row is dropped - its decode has completed"""
+        entry = h.entry
+        entry["ev"].synchronize()
+        arr = self.ring[entry["slot"]][h.kind][h.index].numpy().copy()
+        h.row = None
+        entry["left"] -= 1
+        if entry["left"] == 0:
+            self.inflight.remove(entry)
+            self.free.append(entry["slot"])
+        if h.output_type == "pil":
+            from PIL import Image
+            return Image.fromarray(arr)
+        return arr
+
+    def result(self, h):
+        if h.value is None:
+            if h.entry is None:                      # (asked for before the transition that cloned it has flushed)
+                self.dispatch()
+            h.value = self._take(h)
+        return h.value
 
 
 class HiresPair:

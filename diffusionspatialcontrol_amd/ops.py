@@ -1373,3 +1373,8 @@ from .gated_add import add_rows_gated, add_rows_gated_supported  # noqa: E402,F4
 # the ControlNet residuals of the continuous batcher's compact lanes, added into their batch rows (dsc_scatter_add_rows_f16):
 # wrapper beside its kernel's name, like gated_add.py's, reached as ops.scatter_add_rows / ops.scatter_add_rows_supported
 from .scatter_add import scatter_add_rows, scatter_add_rows_supported, scatter_add_rows_torch  # noqa: E402,F401
+
+
+# the finished image of a served request (dsc_image_finish: the decoder's fp16 NCHW output -> uint8 / float32 NHWC): wrapper beside
+# its kernel's name, like gated_add.py's, reached as ops.image_finish; image_finish_torch restates its arithmetic in torch
+from .image_finish import IMAGE_KINDS, image_finish, image_finish_torch  # noqa: E402,F401

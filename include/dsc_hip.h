@@ -723,6 +723,29 @@ int dsc_add_rows_gated_f16(const void* x, const void* feat, const void* gate, vo
 int dsc_scatter_add_rows_f16(void* x, const void* feat, const void* gate, const void* dst, int x_rows, int lane_rows, int nets,
                              long long row_elems, void* stream);
 
+/*
+ * The decoder's output turned into the image a caller receives, in one launch: the decode lane of the continuous batcher.
+ * Replaces the tail of modules/model_k_diffusion.py:291-299 of the reference (`decode_latents`: `(image / 2 + 0.5).clamp(0, 1)` on
+ * the fp16 tensor, `.cpu().permute(0, 2, 3, 1).float().numpy()`) and, for DSC_IMAGE_U8, `numpy_to_pil`'s
+ * `(images * 255).round().astype("uint8")`, reached from :533-539 (`latent_to_image`).
+ * img: fp16 [n, 3, H, W], dense and channel-major (what AutoencoderKLDecoder.decode returns).  out: [n, H, W, 3], dense, uint8
+ * (DSC_IMAGE_U8) or float32 (DSC_IMAGE_F32).  Per element, every rounding of the reference chain on its own:
+ *     h = fp16( float(fp16( float(x) * 0.5f )) + 0.5f ), clamped to [0, 1]
+ *     DSC_IMAGE_F32: float(h)          DSC_IMAGE_U8: (uint8) rintf( float(h) * 255.0f )
+ * (the product is exact in fp32 - h has at most 11 significant bits - and its only tie, h = 0.5, goes to 128): bit for bit the
+ * torch / numpy chain for every fp16 input that is not a NaN.  +-inf clamp like any other value.  NaN inputs are OUTSIDE the
+ * contract: 0 is written for them (the reference would propagate the NaN / cast it with an undefined result).
+ * H % 8 == 0 and W % 8 == 0 (every image of this project; one lane owns 8 consecutive pixels of a row: three 16-byte loads, 24
+ * contiguous output bytes as 8-byte stores or 96 as 16-byte stores).  img 16-byte aligned; out 8-byte (U8) / 16-byte (F32) aligned.
+ * No workspace, no LDS, no allocation, no synchronisation, no atomics, every element written by the one lane that owns it and
+ * nothing behind the last one: deterministic and safe under graph capture.
+ * DSC_ERR_BAD_ARG (before any GPU call): null pointer, out == img, n / H / W < 1, an unknown out_kind.  DSC_ERR_UNSUPPORTED: a side
+ * that is no multiple of 8, alignment, 2^31 pieces of 8 pixels and more per image.
+ */
+#define DSC_IMAGE_U8  0
+#define DSC_IMAGE_F32 1
+int dsc_image_finish(const void* img, void* out, int n, int H, int W, int out_kind, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

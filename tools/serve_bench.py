@@ -2,6 +2,7 @@
 
     python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
                                 [--hires X] [--ip-adapter [--ip-masks]] [--t2i-adapter] [--controlnet [--control-slots C]]
+                                [--images uint8|pil|np [--decode-batch D]]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -43,6 +44,14 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
               window [0, 0.6]) on the ControlNet-capable one; and what admission costs: the GPU time of one request's
               conditioning embedding on the batch's stream (it runs when the request is admitted), whether it repeats bit for bit, and
               the host time of submit with and without
+  images      (--images uint8|pil|np [--decode-batch D, default 2]: this leg only) an SD1.x-size VAE decoder with seeded random
+              weights in the pipeline, then two batchers on two slots: one built without `decode` (image output types run
+              latent_to_image inline, in the poll, on the batch's stream) and one built with `decode=True, decode_batch=D` (the
+              decode lane).  8 slots kept full, three alternating rounds of four runs: (a) latent output on the flagless batcher,
+              (b) that image type on the flagless batcher, (c) that image type on the decode-lane batcher, (d) latent output on
+              the decode-lane batcher; images/s and p50 / p95 of `dsc_latency_s` (submit -> resolved) for each; the same four
+              legs with each batcher driven by its own thread and mixed step counts (20 / 25 / 30); and the device time of
+              one captured decode per lane bucket
 """
 import argparse
 import json
@@ -122,6 +131,35 @@ def run_full(b, reqs, kw):
     return len(reqs) / dt, (b.stats()["steps"] - s0) / dt
 
 
+def run_full_latency(b, reqs, kw):
+    """run_full, also giving the requests' submit -> resolved latencies: (images/s, p50 s, p95 s)"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    futs = [b.submit(dict(r, **kw)) for r in reqs]
+    b.run_until_idle()
+    for f in futs:
+        f.result()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    lat = [f.dsc_latency_s for f in futs]
+    return len(reqs) / dt, pct(lat, 50), pct(lat, 95)
+
+
+def run_started_latency(b, reqs, kw):
+    """run_full_latency with the batcher driven by its own thread (start / stop): (images/s, p50 s, p95 s)"""
+    torch.cuda.synchronize()
+    b.start()
+    t0 = time.perf_counter()
+    futs = [b.submit(dict(r, **kw)) for r in reqs]
+    for f in futs:
+        f.result()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    b.stop()
+    lat = [f.dsc_latency_s for f in futs]
+    return len(reqs) / dt, pct(lat, 50), pct(lat, 95)
+
+
 def pct(v, p):
     return float(np.percentile(np.array(v), p)) if v else None
 
@@ -147,6 +185,9 @@ def main():
     ap.add_argument("--controlnet", action="store_true",
                     help="only the ControlNet leg: every other request carries a control image (random weights, SD1.5 size)")
     ap.add_argument("--control-slots", type=int, default=4, help="with --controlnet: the ControlNet lanes of the batcher")
+    ap.add_argument("--images", choices=("uint8", "pil", "np"), default=None,
+                    help="only the finished-images leg: latent output, this image type inline, this image type on the decode lane")
+    ap.add_argument("--decode-batch", type=int, default=2, help="with --images: rows per captured decode of the lane")
     a = ap.parse_args()
     if a.ip_masks and not a.ip_adapter:
         ap.error("--ip-masks goes with --ip-adapter")
@@ -159,6 +200,66 @@ def main():
     opt = {"scheduler": "karras"}
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    if a.images:
+        from diffusionspatialcontrol_amd.modules.vae_decoder import AutoencoderKLDecoder
+        torch.manual_seed(a.seed + 11)
+        with torch.device("cuda"):
+            vae = AutoencoderKLDecoder()
+        pipe.vae = vae.half().eval()
+        plain = pipe.serve(512, 512, max_batch=8, slot=0).warm()
+        lane = pipe.serve(512, 512, max_batch=8, slot=1, decode=True, decode_batch=a.decode_batch).warm()
+        # the flagless batcher has never heard of "uint8": its nearest inline equivalent is the PIL image (the same bytes)
+        inline_type = "pil" if a.images == "uint8" else a.images
+        legs = (("a_latent_flagless", plain, "latent"), ("b_image_inline", plain, inline_type),
+                ("c_image_decode_lane", lane, a.images), ("d_latent_decode_lane", lane, "latent"))
+        for _, b, out_type in legs:                       # one untimed pass each (allocator, kernel selection, the inline decoder)
+            run_full_latency(b, reqs[:8], dict(kw25, output_type=out_type))
+        before = lane.stats()
+        runs = []
+        for _ in range(3):                                # alternating, so that a drift of the box hits all alike
+            runs.append({name: run_full_latency(b, reqs, dict(kw25, output_type=out_type)) for name, b, out_type in legs})
+        after = lane.stats()
+        emit(leg="images", requests=len(reqs), steps=25, image_type=a.images, inline_type=inline_type, decode_batch=a.decode_batch,
+             **{f"{name}_img_s": [round(r[name][0], 2) for r in runs] for name, _, _ in legs},
+             **{f"{name}_p50_s": [round(r[name][1], 3) for r in runs] for name, _, _ in legs},
+             **{f"{name}_p95_s": [round(r[name][2], 3) for r in runs] for name, _, _ in legs},
+             decodes=after["decodes"] - before["decodes"], decode_rows=after["decode_rows"] - before["decode_rows"],
+             captures_after_warm=after["captures_after_warm"],
+             note="three alternating rounds in one process, each batcher stepped by the caller's thread (run_until_idle); latency = "
+                  "submit -> future resolved (dsc_latency_s), the queueing of requests 9..16 behind the first eight included")
+        # the same four legs with each batcher driven by its own thread (start / stop), mixed step counts so that rows leave one
+        # or two at a time instead of a wave of eight
+        rng = random.Random(a.seed)
+        mixed = [dict(r, num_inference_steps=rng.choice((20, 25, 30))) for r in reqs]
+        kwm = dict(guidance_scale=7.5, sampler_opt=opt)
+        for _, b, out_type in legs:
+            run_started_latency(b, mixed[:8], dict(kwm, output_type=out_type))
+        runs = []
+        for _ in range(3):
+            runs.append({name: run_started_latency(b, mixed, dict(kwm, output_type=out_type)) for name, b, out_type in legs})
+        emit(leg="images_driver_thread", requests=len(reqs), steps="20 / 25 / 30 mixed", image_type=a.images, inline_type=inline_type,
+             decode_batch=a.decode_batch,
+             **{f"{name}_img_s": [round(r[name][0], 2) for r in runs] for name, _, _ in legs},
+             **{f"{name}_p50_s": [round(r[name][1], 3) for r in runs] for name, _, _ in legs},
+             **{f"{name}_p95_s": [round(r[name][2], 3) for r in runs] for name, _, _ in legs},
+             captures_after_warm=lane.stats()["captures_after_warm"],
+             note="as the `images` leg, but each batcher is driven by its own thread and the requests have mixed step counts")
+        per = {}
+        for m, st in lane.exec.lane.st.items():          # one captured decode (scale, decoder, both finishes), device time
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(lane.exec.lane.stream):
+                st["run"]()
+                e0.record()
+                for _ in range(10):
+                    st["run"]()
+                e1.record()
+            torch.cuda.synchronize()
+            per[m] = round(e0.elapsed_time(e1) / 10, 3)
+        emit(leg="images_decode_replay", decode_graph_gpu_ms_per_bucket=per,
+             note="ten back-to-back replays on the lane's stream with nothing else running")
+        emit(leg="stats", flagless=plain.stats(), decode_lane=lane.stats())
+        return
 
     if a.controlnet:
         from diffusionspatialcontrol_amd.modules.controlnet import ControlNetModel
