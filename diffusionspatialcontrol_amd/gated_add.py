@@ -1,6 +1,6 @@
 """ops.add_rows_gated / ops.add_rows_gated_supported: the wrapper of dsc_add_rows_gated_f16 (csrc/gated_add.hip), the residual
 added with one gate per batch row that the continuous batcher's captured step uses for T2I-Adapter features
-(modules/serving.py, UNet2DConditionModel.forward(down_intrablock_gated=...))."""
+(modules/serving/, UNet2DConditionModel.forward(down_intrablock_gated=...))."""
 import torch
 
 from . import _lib

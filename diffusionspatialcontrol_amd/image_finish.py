@@ -1,6 +1,6 @@
 """ops.image_finish: the wrapper of dsc_image_finish (csrc/image_finish.hip), the launch that turns the VAE decoder's fp16
 channel-major output into the uint8 / float32 [n, H, W, 3] image a served request receives (the decode lane of
-modules/serving.py), and `image_finish_torch`, the same arithmetic restated in torch for tests and tools."""
+modules/serving/), and `image_finish_torch`, the same arithmetic restated in torch for tests and tools."""
 import torch
 
 from . import _lib

@@ -193,7 +193,7 @@ def _region_attention(q, k, v, w, sigma, weight_func, layout, n_std_groups, scal
     """comp: the caller's (ids, rows) of `w`, None = compress `w` here (cached per tensor version), False = `w` is a static
     buffer whose CONTENTS change between replays of a captured step: read it densely, derive nothing from its values.
     per_group_sigma: `sigma` is an [n_std_groups] fp32 device tensor, one sigma per std group (continuous batching,
-    modules/serving.py) - only the fused default-weight_func kernels take it; every other route raises NotImplementedError."""
+    modules/serving/) - only the fused default-weight_func kernels take it; every other route raises NotImplementedError."""
     S = k.shape[2 if layout == "bhld" else 1]
     if per_group_sigma:
         if mask is not None:
@@ -444,7 +444,7 @@ def prepared_ip_rows(region_prompt):
     computed once per request; a batch stride is allowed) and row_scale [B] fp32 on the device (0: the row has no image prompt).
     A fourth element is the adapter's region mask as one weight per query: a [B, L] fp16 buffer for the layer's query count, or
     a {L: buffer} dict resolved by the layer's L (`ip_adapter_masks` down-sampled once per request; ones: no mask).
-    The continuous batcher's captured step passes them (modules/serving.py): the buffers are static, their contents change
+    The continuous batcher's captured step passes them (modules/serving/): the buffers are static, their contents change
     between replays.  Every other caller hands the image tokens over as the reference does, as (text, [tokens])."""
     if not isinstance(region_prompt, dict):
         return None

@@ -559,7 +559,7 @@ class StableDiffusionPipeline:
     def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77,
               ip_masks: bool = False, t2i_adapter: bool = False, controlnet: bool = False, control_slots=None,
               decode: bool = False, decode_batch: int = 2):
-        """Continuous-batching server (modules/serving.py): requests join a running batch at any step boundary, each at its own
+        """Continuous-batching server (modules/serving/): requests join a running batch at any step boundary, each at its own
         point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
         stats / warm).  `ip_masks=True` (IP-Adapters loaded): requests may carry the reference's
         `cross_attention_kwargs={"ip_adapter_masks": ...}`, the region mask of each image prompt.  `t2i_adapter=True` (an adapter
@@ -1354,7 +1354,7 @@ class StableDiffusionPipeline:
                 B, S, C = k.shape
                 d = C // m.heads
                 # one entry per static text buffer (= per generation slot); the newest few are kept, and every entry a serving
-                # batcher pinned (its bucket graphs read those buffers for as long as the batcher lives, modules/serving.py)
+                # batcher pinned (its bucket graphs read those buffers for as long as the batcher lives, modules/serving/)
                 slots = m.__dict__.setdefault("kv_caches", [])
                 c = next((e for e in slots if e["src"] is text and e["k"].shape == k.shape), None)
                 if c is not None:

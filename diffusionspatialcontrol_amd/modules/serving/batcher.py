@@ -1,0 +1,795 @@
+"""The host side of the continuous batcher: `ServingBatcher` (construction, the public interface, the scheduling of every step
+against a replaceable device executor) and `HiresPair`.  The package docstring has slots, buckets and the step.
+
+Samplers and parameterisation.  A request names its sampler (`sampler_name`: one of sampling.LINEAR_FAMILY - Euler, Euler a,
+DPM++ 2M (default), DPM++ 2M SDE, LCM - by name or as the callable) with `eta` / `s_noise` / `solver_type`; the noise of all its
+steps is one table on the device from submit until it leaves (`step_noise`, or sampling.step_noise_table from `seed` /
+`generator`), and its record for step j points at row j.  A transition in which every stepping slot is DPM++ 2M on an
+eps-prediction model launches dsc_cfg_dpmpp2m_step_rows as before; any other launches dsc_cfg_linear_step_rows for all slots
+(DPM++ 2M slots ride in it with the same bits).  On a v-prediction pipeline every slot carries CompVisVDenoiser's scalars (and,
+with `pass_kwargs = False`, zero region tables: the reference's v-prediction path never sees the region prompt).  The
+known-region launch of inpainting carries DPM++ 2M records only, so an inpainting request and a request of another sampler never
+share a batch: the later one waits in the queue until the others have left.
+
+Guidance rescale.  A request may carry `guidance_rescale` (phi in [0, 1], arXiv 2305.08891 sec. 3.4; the usual companion of
+v-prediction models).  Its STEP records carry `rescale` and, DPM++ 2M on an eps-prediction model included, (c_skip, c_out); a
+transition in which such a slot steps launches dsc_cfg_linear_step_rows_rescale for all slots (ops.cfg_linear_step_rows picks it
+from the records), every other transition the launch it had.  Inpainting with rescale is refused at submit.
+
+Hires requests.  A batcher is built for one image size, so the reference's "Hires fix" (generate at the base size, enlarge the
+final latents, img2img at the target size; model_k_diffusion.py:1176-1228) runs on a chained PAIR of batchers on two workspace
+slots (`pipe.serve_hires`, or `base.chain_hires(hi)`).  A request with `upscale=True` is validated and prepared for BOTH passes at
+submit (the second pass with its own sampler, schedule tail, coefficients, time-embedding table, region tables at the target
+size and noise).  When it leaves the first batcher, ONE launch of dsc_latent_resample_noise on that batcher's stream reads its
+final row of x and writes the second pass's start latent (the enlarged row + noise * fp16 sqrt(sigma_0^2 + 1), img2img's line)
+into a tensor of the second-pass record; an event is recorded, the record joins the second batcher's queue, and that batcher's
+stream waits on the event before it loads the row.  Only the first batcher ever takes the second's lock (no cycle); the caller's
+one Future resolves with the second pass's output.  No host synchronisation between the passes.
+
+The region tables of a batch are compressed to at most 32 distinct rows per level (the prepared-operand kernels' LDS table): a
+request whose admission would push the union of the active requests' rows past that waits in the queue (FIFO) until a slot frees.
+"""
+import collections
+import concurrent.futures
+import threading
+import time
+
+import torch
+
+from ... import ops
+from .. import sampling
+from ..encode_region_map_function import encode_region_map
+from . import requests
+from .executor import _GraphExecutor, step_launch
+from .requests import MAX_TEXT_KEYS, _Request, _ip_layers
+
+
+def _conv_out_hw(conv, h, w):
+    """(h, w) of `conv`'s output on an h x w input, from the module's own kernel size, padding and stride"""
+    return tuple((v + 2 * conv.padding[i] - conv.kernel_size[i]) // conv.stride[i] + 1 for i, v in enumerate((h, w)))
+
+
+class ServingBatcher:
+    """See the package docstring.  `executor` is the device side (default: the captured-graph executor on the pipeline's GPU);
+    the scheduling here is host logic only."""
+
+    def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
+                 t2i_adapter=False, controlnet=False, control_slots=None, decode=False, decode_batch=2):
+        buckets = tuple(sorted(set(int(b) for b in buckets)))
+        if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
+            raise ValueError(f"serve: buckets {buckets} must cover max_batch={max_batch}")
+        if max_batch > ops.ROW_STEP_MAX_SLOTS:
+            raise ValueError(f"serve: at most {ops.ROW_STEP_MAX_SLOTS} slots (dsc_cfg_dpmpp2m_step_rows)")
+        if text_len > MAX_TEXT_KEYS:
+            raise ValueError(f"serve: at most {MAX_TEXT_KEYS} text keys")
+        self.pipe, self.height, self.width = pipe, int(height), int(width)
+        self.max_batch, self.slot, self.buckets, self.text_len = int(max_batch), int(slot), buckets, int(text_len)
+        self._lock = threading.RLock()
+        self._wake = threading.Condition(self._lock)
+        self._queue = collections.deque()
+        self._slots = [None] * self.max_batch
+        self._done = []                        # (request, handle) whose final row copy is in flight
+        self._n = None                         # bucket whose eps is pending (None: nothing ran yet / the batch drained)
+        self._members = {}                     # bucket -> per-slot request ids its static buffers were last refreshed for
+        self._gates = {}                       # bucket -> the adapter gate vector last uploaded for it (absent: zeros, as captured)
+        self._next_id = 0
+        self._stats = collections.Counter(captures=0, joins=0, leaves=0, bucket_switches=0, steps=0, refreshes=0,
+                                          linear_transitions=0, handoffs=0, adapter_gate_updates=0, control_steps=0,
+                                          control_gate_updates=0)
+        self._hires = None                     # the chained batcher of the hires pass (chain_hires)
+        # requests may ask for images ("pil" / "np" / "uint8"): a decode lane beside the step finishes them (decode_lane.py)
+        self.decode = bool(decode)
+        self.decode_batch = 0
+        if self.decode:
+            if getattr(pipe, "vae", None) is None:
+                raise ValueError("serve: `decode=True` on a pipeline without a VAE (construct it with a "
+                                 "modules.vae_decoder.AutoencoderKLDecoder, or serve latents)")
+            if isinstance(decode_batch, bool) or not isinstance(decode_batch, int) or not 1 <= decode_batch <= self.max_batch:
+                raise ValueError(f"serve: `decode_batch` must be an integer in [1, max_batch = {self.max_batch}], got {decode_batch!r}")
+            self.decode_batch = decode_batch
+            self._stats["decodes"] = self._stats["decode_rows"] = 0
+        self._warm_captures = None
+        self._thread = None
+        self._stop = False
+        # the IP-Adapters this batcher's step is built for (load_ip_adapter): the processors, the image projection, tokens per adapter
+        self._ip = _ip_layers(pipe)
+        self._ip_proj = getattr(pipe.unet, "encoder_hid_proj", None) if self._ip else None
+        self._ip_tokens = [int(t) for t in self._ip[0][1].num_tokens] if self._ip else []
+        if any(t > ops.IP_MAX_TOKENS for t in self._ip_tokens):
+            raise ValueError(f"serve: a loaded IP-Adapter has {max(self._ip_tokens)} image tokens; the batcher's image-token attention "
+                             f"(dsc_ip_xattn_add_f16) takes at most {ops.IP_MAX_TOKENS} (ops.IP_MAX_TOKENS) - the 257-token Full "
+                             f"projection runs through txt2img(ip_adapter_image_embeds=...)")
+        # requests may carry `ip_adapter_masks`: the step hands per-query weights to the masked entry (requests.py)
+        self.ip_masks = bool(ip_masks)
+        if self.ip_masks and not self._ip:
+            raise ValueError("serve: `ip_masks=True` on a pipeline without an IP-Adapter (pipe.load_ip_adapter first, then build the "
+                             "batcher)")
+        # requests may carry `image_t2i_adapter`: the step hands the UNet per-slot features and a per-row gate (executor.py)
+        self.t2i = bool(t2i_adapter)
+        if controlnet and self.t2i:
+            raise ValueError("serve: `controlnet=True` and `t2i_adapter=True` are not served together yet (build one batcher for each)")
+        self._adapter = getattr(pipe, "adapter", None) if self.t2i else None
+        self._adapter_shapes = self._adapter_setup() if self.t2i else None
+        # requests may carry `control_img`: a compact ControlNet batch of `control_slots` lanes runs beside the step, and the
+        # step scatters its residuals into the rows of the requests that hold a lane (executor.py)
+        self.cn = bool(controlnet)
+        self._controlnet = getattr(pipe, "controlnet", None) if self.cn else None
+        self.control_slots = (self.max_batch if control_slots is None else int(control_slots)) if self.cn else 0
+        self._control_shapes = self._controlnet_setup() if self.cn else None
+        self._lanes = [None] * self.control_slots     # lane -> the request that holds it
+        self._cstate = {}                      # bucket -> (dst, gather, gates) last uploaded for it (absent: as captured)
+        self.exec = executor if executor is not None else _GraphExecutor(self)
+
+    def _adapter_setup(self):
+        """the adapter against the UNet, at construction -> [(C_k, h_k, w_k)] of the feature each down block adds: as many maps
+        as down blocks, the UNet's channels, and the size of the tensor the add lands on.  Both sides are computed from their own
+        modules' parameters (the adapter's PixelUnshuffle and pooling, the UNet's stride-2 convolutions), not assumed equal."""
+        from ..t2i_adapter import MultiAdapter
+        pipe, ad = self.pipe, self._adapter
+        if ad is None:
+            raise ValueError("serve: `t2i_adapter=True` on a pipeline without a T2I-Adapter "
+                             "(modules.t2i_adapter.setup_model_t2i_adapter(pipe, adapter) first, then build the batcher)")
+        unet = pipe.unet
+        # the UNet: block k adds after its last attention (before its downsampler) or, without attention, after the whole block
+        h, w = self.height // 8, self.width // 8
+        want = []
+        for c, blk in zip(unet.config.block_out_channels, unet.down_blocks):
+            size = (h, w)
+            if hasattr(blk, "downsamplers"):
+                h, w = _conv_out_hw(blk.downsamplers[0].conv, h, w)
+                if not blk.has_attn:
+                    size = (h, w)
+            want.append((int(c), int(size[0]), int(size[1])))
+        for a, one in enumerate(ad.adapters if isinstance(ad, MultiAdapter) else [ad]):
+            full = getattr(one, "adapter", None)
+            if full is None or not hasattr(full, "body") or not hasattr(full, "unshuffle"):
+                raise ValueError(f"serve: `t2i_adapter=True`: adapter {a} is not a full_adapter T2IAdapter (the type the batcher serves)")
+            f = int(full.unshuffle.downscale_factor)
+            if self.height % f or self.width % f:
+                raise ValueError(f"serve: `t2i_adapter=True`: {self.height}x{self.width} is not a multiple of the adapter's "
+                                 f"downscale factor {f}")
+            ah, aw = self.height // f, self.width // f
+            got = []
+            for blk in full.body:
+                pool = blk.downsample
+                if pool is not None:
+                    k_, s_ = int(pool.kernel_size), int(pool.stride)
+                    ah, aw = ((-(-(v - k_) // s_) if pool.ceil_mode else (v - k_) // s_) + 1 for v in (ah, aw))
+                got.append((int(blk.resnets[-1].block2.out_channels), int(ah), int(aw)))
+            if len(got) != len(want):
+                raise ValueError(f"serve: `t2i_adapter=True`: adapter {a} gives {len(got)} feature maps, the UNet has {len(want)} "
+                                 f"down blocks")
+            if got != want:
+                raise ValueError(f"serve: `t2i_adapter=True`: adapter {a}'s feature maps (C, h, w) {got} do not match what the "
+                                 f"UNet's down blocks add to at {self.height}x{self.width}: {want}")
+        return want
+
+    def _control_nets(self):
+        from ..controlnet import MultiControlNetModel
+        cn = self._controlnet
+        return list(cn.nets) if isinstance(cn, MultiControlNetModel) else [cn]
+
+    @staticmethod
+    def _skip_shapes(model, h, w):
+        """[(C, h, w)] of the skip tensors an encoder half (the UNet's, a ControlNet's) collects at an h x w latent, the mid
+        block's output last - from the module's own convolutions (conv_in, every ResNet's conv2, the stride-2 downsamplers)"""
+        shapes = [(int(model.conv_in.out_channels), int(h), int(w))]
+        for blk in model.down_blocks:
+            for res in blk.resnets:
+                shapes.append((int(res.conv2.out_channels), int(h), int(w)))
+            if hasattr(blk, "downsamplers"):
+                conv = blk.downsamplers[0].conv
+                h, w = _conv_out_hw(conv, h, w)
+                shapes.append((int(conv.out_channels), int(h), int(w)))
+        return shapes + [(int(model.mid_block.resnets[-1].conv2.out_channels), int(h), int(w))]
+
+    def _controlnet_setup(self):
+        """the ControlNet against the UNet, at construction -> [(C, h, w)] of every skip tensor and of the mid block's output,
+        the tensors its residuals are added to.  Both sides are computed from their own modules, not assumed equal."""
+        from ..controlnet import ControlNetModel
+        if self._controlnet is None:
+            raise ValueError("serve: `controlnet=True` on a pipeline without a ControlNet (pipe.setup_controlnet(controlnet) first, "
+                             "then build the batcher)")
+        if not 1 <= self.control_slots <= self.max_batch:
+            raise ValueError(f"serve: `control_slots` must be in [1, max_batch = {self.max_batch}], got {self.control_slots}")
+        nets = self._control_nets()
+        from ... import scatter_add
+        if len(nets) > scatter_add.MAX_NETS:
+            raise ValueError(f"serve: `controlnet=True`: {len(nets)} ControlNets; the step's scatter-add takes at most "
+                             f"{scatter_add.MAX_NETS}")
+        want = self._skip_shapes(self.pipe.unet, self.height // 8, self.width // 8)
+        for a, net in enumerate(nets):
+            if not isinstance(net, ControlNetModel):
+                raise ValueError(f"serve: `controlnet=True`: net {a} is a {type(net).__name__}, not a ControlNetModel")
+            if net.config.global_pool_conditions:
+                raise ValueError(f"serve: `controlnet=True`: net {a} is a guess-mode ControlNet (global_pool_conditions), which the "
+                                 "batcher does not serve (use txt2img)")
+            got = self._skip_shapes(net, self.height // 8, self.width // 8)
+            if got != want:
+                raise ValueError(f"serve: `controlnet=True`: net {a}'s residuals (C, h, w) {got} do not match the UNet's skip tensors "
+                                 f"and mid output at {self.height}x{self.width}: {want}")
+        return want
+
+    # ------------------------------------------------------------------ public interface
+    def warm(self):
+        """capture every bucket's step now (otherwise each is captured on first use)"""
+        with self._lock:
+            if self.t2i:
+                self.exec.warm_adapter()             # the adapter's convolutions pay their first-call cost here, not at a join
+            if self.cn:
+                self._ensure_control()               # the ControlNet graph first: every bucket's step reads its residual buffers
+                self.exec.warm_control()
+            for n in self.buckets:
+                self._ensure(n)
+            if self.decode:
+                self._ensure_decode()                # the lane's stream, static buffers, graphs and pinned ring
+            self._warm_captures = self._stats["captures"]
+        return self
+
+    def chain_hires(self, hi):
+        """requests with `upscale=True` run their second pass on `hi`, a batcher of the target size on another workspace slot
+        (executor.py); `hi` keeps serving ordinary requests of its size.  Returns self."""
+        if not isinstance(hi, ServingBatcher):
+            raise TypeError("serve: chain_hires takes the ServingBatcher of the hires pass")
+        if hi is self:
+            raise ValueError("serve: a batcher cannot be chained to itself (the hires pass runs at another image size)")
+        if hi.slot == self.slot:
+            raise ValueError(f"serve: both batchers of a hires pair sit on workspace slot {self.slot}; give the second its own")
+        if hi.pipe is not self.pipe:
+            raise ValueError("serve: both batchers of a hires pair serve the same pipeline")
+        if hi.height < self.height or hi.width < self.width:
+            raise ValueError(f"serve: the hires batcher runs {hi.height}x{hi.width}, smaller than this one's "
+                             f"{self.height}x{self.width} (only enlarging is served)")
+        with self._lock:
+            self._hires = hi
+        return self
+
+    def submit(self, request):
+        """request: txt2img_coalesced's request dict plus its own `num_inference_steps` (default 25), `sampler_opt` (the
+        schedule: karras / exponential / ...), `guidance_scale` (> 1, default 7.5) and `latents` / `generator`; optional
+        `output_type` ("latent", default, or what latent_to_image takes; on a batcher built with `decode=True`: "latent", "pil",
+        "np" / "numpy" - float32 [H, W, 3] - or "uint8" - np.uint8 [H, W, 3], the bytes of the PIL image), `sampler_name`
+        (sampling.LINEAR_FAMILY, default DPM++ 2M) with `eta` / `s_noise` / `solver_type`, `step_noise` ([steps, 1, 4, h, w]: the noise of every step;
+        default: drawn as the sampler itself would, from `seed` / `generator`) and `guidance_rescale` (in [0, 1], default 0; not
+        with `mask_image`).  On a pipeline with IP-Adapters loaded: `ip_adapter_image_embeds` (a list with one tensor per loaded
+        adapter, each [negative; positive] along dim 0 with ONE image per half - what txt2img takes, see encode_image; absent /
+        None: the request runs without an image prompt beside those that have one) and `ip_adapter_scale` (a float, or a list
+        with one entry per adapter; default: the processors' scale at submit time, so set_ip_adapter_scale needs no capture); on a
+        batcher built with `ip_masks=True` also `cross_attention_kwargs={"ip_adapter_masks": t}`, t [n_adapters, 1, Hm, Wm]: each
+        adapter's term is multiplied by its mask, down-sampled per level as the reference does (ignored without an image prompt).
+        On a chained pair (chain_hires) `upscale=True` adds the hires pass: `upscale_x` (2.0), `upscale_method`
+        ("bicubic"), `upscale_antialias`, `upscale_denoising_strength` (0.7), `sampler_name_hires`, `sampler_opt_hires` (default:
+        the first pass's), `hires_latents` ([1, 4, H/8, W/8] unit noise of the second pass; default: drawn from `generator` after
+        the first pass's draws) and `region_map_state_hires` (default: `region_map_state`; None: no region condition in the second
+        pass).  On a batcher built with `t2i_adapter=True`: `image_t2i_adapter` (a [1, 3, H, W] tensor in [0, 1] of this
+        batcher's size or a PIL image; a list with one per adapter when pipe.adapter is a MultiAdapter), `adapter_conditioning_scale`
+        (default 1.0; a list for a MultiAdapter) and `adapter_conditioning_factor` (in [0, 1], default 1.0: the fraction of the
+        request's steps that carry the control) - the pipeline methods' own keys; not with `upscale`.  On a batcher built with
+        `controlnet=True`: `control_img` (a PIL image or a [1, 3, H, W] tensor in [0, 1]; a list with one per net when
+        pipe.controlnet is a MultiControlNetModel), `controlnet_conditioning_scale` (default 1.0), `control_guidance_start` (0.0)
+        and `control_guidance_end` (1.0) (numbers, or lists with one entry per net) - the pipeline methods' own keys; not with
+        `upscale` or `mask_image`.  Returns a Future of the final output."""
+        r = self._prepare(request)
+        with self._lock:
+            r.rid = self._next_id
+            self._next_id += 1
+            self._queue.append(r)
+            self._wake.notify_all()
+        return r.future
+
+    def step(self):
+        """advance every active request by one sigma (admitting queued requests into free slots first); False when idle"""
+        with self._lock:
+            self.exec.bind_thread()
+            self._poll()
+            ran = self._step_locked()
+            self._poll()
+            return ran
+
+    def run_until_idle(self):
+        """step until the queue is empty and every request has finished, then wait for the last rows and resolve their futures"""
+        while self.step():
+            pass
+        with self._lock:
+            self._poll(wait=True)
+
+    def start(self):
+        """drive the batcher from a background thread (one per batcher; two batchers on two slots = two batches in flight)"""
+        with self._lock:
+            if self._thread is not None:
+                return self
+            self._stop = False
+            self._thread = threading.Thread(target=self._drive, name=f"dsc-serve-{self.slot}", daemon=True)
+            self._thread.start()
+        return self
+
+    def stop(self):
+        """stop the driver thread after the step it is in (queued and active requests stay where they are)"""
+        with self._lock:
+            self._stop = True
+            self._wake.notify_all()
+            t = self._thread
+        if t is not None:
+            t.join()
+        with self._lock:
+            self._thread = None
+            self._poll(wait=True)
+
+    def stats(self):
+        with self._lock:
+            s = dict(self._stats)
+            s["captures_after_warm"] = None if self._warm_captures is None else s["captures"] - self._warm_captures
+            s["queued"] = len(self._queue)
+            s["active"] = sum(r is not None for r in self._slots)
+            s["bucket"] = self._n
+            return s
+
+    # ------------------------------------------------------------------ request preparation (caller's thread)
+    def _prepare(self, request, second=False, device=True):
+        """validate a request (requests.py) and build its record; `second`: the record of a hires request's second pass on
+        this batcher (its start latent comes from the hand-off); `device=False` leaves the device half (_prepare_device) to the
+        caller"""
+        pipe = self.pipe
+        if not isinstance(request, dict):
+            raise TypeError("serve: a request is a dict (txt2img_coalesced's request + num_inference_steps / sampler_opt / "
+                            "guidance_scale)")
+        requests.check_ip_current(self)
+        adapter = requests.adapter_request(self, request)
+        control = requests.control_request(self, request, second)
+        if request.get("upscale") and not second:
+            return self._prepare_hires_pair(request)
+        out_type, v_pred, family, phi, g = requests.common_request(self, request)
+        ip_masks = requests.ip_masks_of(self, request)
+        ip_embeds, ip_scale = requests.ip_request(self, request)
+        # masks without an image prompt (or with every scale 0) have nothing to weigh: accepted and ignored
+        ip_weights = requests.ip_mask_weights(self, ip_masks) if ip_embeds is not None and ip_masks is not None else None
+        text = requests.text_request(self, request)
+        steps = int(request.get("num_inference_steps", 25))
+        if steps < 1:
+            raise ValueError("serve: num_inference_steps must be >= 1")
+        r = _Request(req=request, future=concurrent.futures.Future(), steps=steps, second=second, ip_embeds=ip_embeds,
+                     ip_scale=ip_scale, ip_weights=ip_weights, adapter=adapter, control=control, guidance=g, output_type=out_type,
+                     family=family, rescale=phi, eta=float(request.get("eta", 1.0)), text=text)
+        t_start = requests.image_request(self, r)
+        dev, dt = self.exec.device, self.exec.dtype
+        r.sig_dev = pipe._schedule(r.steps, request.get("sampler_opt") or {}, dev, dt)      # txt2img's schedule, fp16-rounded
+        sig = getattr(r.sig_dev, "_dsc_host", None)
+        r.sig = sig if sig is not None else r.sig_dev.detach().float().cpu().tolist()
+        if t_start:                                                  # img2img / inpaiting keep the schedule's tail (:637-647)
+            r.sig, r.sig_dev = r.sig[t_start:], r.sig_dev[t_start:]
+        if r.adapter is not None:
+            # the window: what the pipeline method of this kind of request passes to _adapter_hook as `steps_denoising` is the
+            # length of the sigma schedule the sampler walks, final sigma included - len(sigmas) for txt2img
+            # (model_k_diffusion.py:530), len(sigma_sched) = len(sigmas[t_start:]) for img2img (:839), len(sigmas) after the
+            # `sigmas[t_start:]` of :940 for inpainting (:994) - and r.sig is that schedule for all three.  Every sampler served
+            # here makes one model call per step at a distinct sigma, so the hook's count of distinct sigmas seen is the step index
+            r.adapter_limit = int(len(r.sig) * r.adapter["factor"])
+            if r.adapter_limit < 1:
+                r.adapter = None                                     # no model call carries it: no adapter forward, no rows
+        if r.control is not None:
+            # the step count the pipeline method of this kind of request hands preprocess_controlnet: num_inference_steps in
+            # txt2img (model_k_diffusion.py:527), len(sigma_sched) - the truncated schedule, final sigma included - in img2img
+            # (:838).  Every served sampler makes one model call per step at a distinct sigma, so _controlnet_hook's count of
+            # distinct sigmas seen is the call index
+            n_keep = r.steps if r.kind == "txt2img" else len(r.sig)
+            r.cgates = self.control_gates(n_keep, len(r.sig) - 1, r.control["scale"], r.control["start"], r.control["end"])
+            if all(g == 0.0 for call in r.cgates for g in call):
+                r.control, r.cgates = None, None                     # no model call carries it: no lane, no embedding
+        args = {}
+        if family in ("euler_ancestral", "dpmpp_2m_sde"):
+            args.update(eta=r.eta, s_noise=float(request.get("s_noise", 1.0)))
+        if family == "dpmpp_2m_sde":
+            args["solver_type"] = request.get("solver_type") or "midpoint"
+            if args["solver_type"] not in ("midpoint", "heun"):
+                raise ValueError(f"serve: `solver_type` must be 'midpoint' or 'heun', got {args['solver_type']!r}")
+        abcs = sampling.linear_step_coefficients(family, r.sig, **args)
+        r.coeffs = [c4[:3] for c4 in abcs]
+        r.snoise = [c4[3] for c4 in abcs]
+        kdm = pipe.k_diffusion_model
+        r.scal = []
+        # None: DPM++ 2M's own launch serves the request (c_skip = 1, c_out = -sigma); with a rescale it needs the linear family's
+        # launch, so its (1, -sigma) are spelled out like any other member's
+        r.skipout = [] if family != "dpmpp_2m" or v_pred or phi > 0.0 else None
+        for s_ in r.sig[:len(r.coeffs)]:
+            c_in, c_out, t = kdm.step_scalars(s_)
+            r.scal.append((c_in, float(t)))
+            if r.skipout is not None:
+                r.skipout.append((kdm.step_skip(s_), c_out))
+        table = request.get("step_noise")
+        if table is not None:
+            want = (len(r.coeffs), 1, 4, self.height // 8, self.width // 8)
+            if not torch.is_tensor(table) or tuple(table.shape) != want:
+                raise ValueError(f"serve: `step_noise` must be a {list(want)} tensor (one unit-noise row per step), got "
+                                 f"{list(table.shape) if torch.is_tensor(table) else type(table).__name__}")
+        ids = request.get("text_input_ids") or [None, None]
+        tabs = encode_region_map(pipe, request.get("region_map_state"), width=self.width, height=self.height,
+                                 num_images_per_prompt=1, text_ids=ids)
+        r.tables = self._request_tables(tabs)
+        if not self._tables_fit([r]):
+            raise ValueError(f"serve: the request's region tables (with the zero row of an idle slot) hold more than "
+                             f"{ops.MAX_REGION_ROWS} distinct rows at some level; run it through txt2img")
+        r.t_submit = time.perf_counter()
+        if device:
+            self._prepare_device(r)
+        return r
+
+    def _adapter_gates(self, n, members):
+        """the gate vector of bucket n for the model call about to run: 1.0 at rows {i, n + i} of a member whose call index
+        (r.i, counted in its own schedule) is inside its adapter window, 0.0 for every other row"""
+        gates = [0.0] * (2 * n)
+        for i, r in enumerate(members):
+            if r is not None and r.adapter is not None and r.i < r.adapter_limit:
+                gates[i] = gates[n + i] = 1.0
+        return gates
+
+    @staticmethod
+    def control_keep(n_steps, starts, ends):
+        """preprocess_controlnet's keep schedule (reference :417-424) for one start / end per net: [n_steps][nets] of 1.0 / 0.0"""
+        return [[1.0 - float(i / n_steps < s or (i + 1) / n_steps > e) for s, e in zip(starts, ends)] for i in range(n_steps)]
+
+    @classmethod
+    def control_gates(cls, n_steps, n_calls, scales, starts, ends):
+        """the gates of a request's model calls, [n_calls][nets]: call k carries `scale * keep[min(k, len(keep) - 1)]` per net -
+        _controlnet_hook's `schedule`, python floats, unrounded (the reference multiplies the residuals by that float)"""
+        keep = cls.control_keep(n_steps, starts, ends)
+        return [[s * k for s, k in zip(scales, keep[min(call, len(keep) - 1)])] for call in range(n_calls)]
+
+    def _control_vectors(self, n, members):
+        """(dst, gather, gates) of bucket n for the model call about to run.  Lane j is ControlNet rows j (unconditional) and
+        c + j (conditional); held by the member in slot i it maps to batch rows i and n + i: dst [2 c] (idle: -1), gather [2 c]
+        (the rows of the bucket's input the lane rows are read from; idle: row 0, whose values are computed and never used),
+        gates [nets][2 c] (the member's gates of the call its own schedule is at: r.i; idle: 0)"""
+        c, nets = self.control_slots, len(self._control_nets())
+        dst, gather, gates = [-1] * (2 * c), [0] * (2 * c), [[0.0] * (2 * c) for _ in range(nets)]
+        for i, r in enumerate(members):
+            if r is None or r.control is None:
+                continue
+            j = r.lane
+            assert j is not None and self._lanes[j] is r, f"serve: slot {i}'s request holds no lane"
+            dst[j], dst[c + j] = gather[j], gather[c + j] = i, n + i
+            if r.i < len(r.cgates):
+                for a in range(nets):
+                    gates[a][j] = gates[a][c + j] = float(r.cgates[r.i][a])
+        active = [d for d in dst if d >= 0]
+        # the scatter-add's invariant (ops.scatter_add_rows): no two active lane rows name one batch row
+        assert len(set(active)) == len(active) and all(d < 2 * n for d in active), f"serve: lane rows share a batch row: {dst}"
+        return dst, gather, gates
+
+    def _prepare_device(self, r):
+        """the device half of _prepare, in the order the pipeline's one generator is consumed: start latent, then step noise"""
+        if r.second:
+            self.exec.prepare_hires(r)
+        elif r.kind == "txt2img":
+            self.exec.prepare(r)
+        else:
+            self.exec.prepare_image(r)
+        if any(v != 0.0 for v in r.snoise):
+            self.exec.prepare_noise(r, r.eta)
+
+    def _prepare_hires_pair(self, request):
+        """a request with `upscale=True`: both passes validated first, then prepared (first pass, then second: the order in which
+        txt2img / img2img and _hires_pass draw from the request's generator) -> the first-pass record, its `.hires` the second's"""
+        first, second = requests.hires_request(self, request)
+        hi = self._hires
+        r = self._prepare(first, device=False)
+        r2 = hi._prepare(second, second=True, device=False)
+        r2.future, r2.t_submit = r.future, r.t_submit
+        r.hires = r2
+        self._prepare_device(r)
+        hi._prepare_device(r2)
+        return r
+
+
+    def levels(self):
+        """{L: S} of the region tables at this image size (one level per down block, encode_region_map_function.py)"""
+        out = {}
+        sr = 8
+        for _ in self.pipe.unet.down_blocks:
+            w_r, h_r = -(-self.width // sr), -(-self.height // sr)
+            out[w_r * h_r] = self.text_len
+            sr *= 2
+        return out
+
+    def _request_tables(self, tabs):
+        lv = self.levels()
+        if getattr(self.pipe, "v_prediction", False) and not self.pipe.k_diffusion_model.pass_kwargs:
+            tabs = None                                             # CompVisVDenoiser.get_v drops the region prompt
+        if not isinstance(tabs, dict) or not tabs:                  # no masks: the region path with zero tables (quirk q2)
+            return {L: torch.zeros(2, L, S) for L, S in lv.items()}
+        if sorted(tabs) != sorted(lv) or any(tuple(w.shape) != (2, L, lv[L]) for L, w in tabs.items()):
+            raise ValueError("serve: the request's region tables do not match this batcher's image size / text length")
+        return {L: w.float().cpu() for L, w in tabs.items()}
+
+    # ------------------------------------------------------------------ scheduling (host)
+    def _bucket_for(self, top):
+        return next(b for b in self.buckets if b > top)
+
+    def _tables_fit(self, members):
+        """the union of these requests' table rows compresses at every level (<= 32 distinct rows, zero rows of IDLE slots in)"""
+        for L in self.levels():
+            rows = [r.tables[L].reshape(-1, r.tables[L].shape[-1]) for r in members]
+            rows.append(torch.zeros(1, self.text_len))
+            if ops.compress_region_table(torch.cat(rows)[None]) is None:
+                return False
+        return True
+
+    @staticmethod
+    def _launch_compatible(head, members):
+        """One launch serves every stepping slot of a transition, and the known-region launch (inpainting) carries DPM++ 2M /
+        eps-prediction records only: it has no c_skip / c_out / noise fields.  So an inpainting request and a request of another
+        sampler never share a batch - whichever comes second waits at the head of the queue (FIFO) until the others have left."""
+        if head.kind == "inpaint":
+            return all(r.skipout is None for r in members)
+        if head.skipout is not None:
+            return all(r.kind != "inpaint" for r in members)
+        return True
+
+    def _step_locked(self):
+        """one step, as phases in the order the device sees them: admit, build the records, ensure the next bucket and load the
+        joins, ONE transition launch, let the finished leave, advance, refresh / upload / run the next bucket, flush decodes"""
+        slots = self._slots
+        stepping = [r for r in slots if r is not None and r.i < len(r.coeffs) and self._n is not None]
+        joins = self._admit()
+        if not stepping and not joins:
+            return False
+        # who leaves after this transition: a request whose last step is the one being applied now
+        leaving = [r for r in stepping if r.i + 1 == len(r.coeffs)]
+        staying = [r for r in slots if r is not None and r not in leaving]
+        n_src = self._n or 0
+        n_dst = self._bucket_for(max(r.slot for r in staying)) if staying else None
+        nd = n_dst if n_dst is not None else self.buckets[0]
+        recs, known = self._records(max(n_src, nd), stepping, joins, leaving)
+        self._load_joins(n_dst, joins)
+        self._transition(n_src, nd, recs, known)
+        self._leave(leaving)
+        for r in stepping:
+            r.i += 1
+        if n_dst is not None:
+            self._run_bucket(n_dst)
+        self._n = n_dst
+        if self.decode and any(r.output_type != "latent" for r in leaving):
+            # after the next step is queued: the lane's stream waits on the clones' events only, so the decode runs beside it
+            self._ensure_decode()
+            decodes, rows = self.exec.flush_decodes()
+            self._stats["decodes"] += decodes
+            self._stats["decode_rows"] += rows
+        return True
+
+    def _admit(self):
+        """admissions: FIFO, lowest free slot, while the union of the tables still compresses -> the requests that join"""
+        slots, joins = self._slots, []
+        while self._queue:
+            free = next((i for i, r in enumerate(slots) if r is None), None)
+            if free is None:
+                break
+            head = self._queue[0]
+            if not self._tables_fit([r for r in slots if r is not None] + [head]):
+                break
+            if not self._launch_compatible(head, [r for r in slots if r is not None]):
+                break
+            if head.control is not None:
+                # a ControlNet lane, the lowest free one, kept until the request leaves; with none free the request waits at the
+                # head of the queue although a slot is free (FIFO, the rule of _launch_compatible)
+                lane = next((j for j, holder in enumerate(self._lanes) if holder is None), None)
+                if lane is None:
+                    break
+                head.lane = lane
+                self._lanes[lane] = head
+            self._queue.popleft()
+            head.slot, head.i = free, 0
+            slots[free] = head
+            joins.append(head)
+        return joins
+
+    def _records(self, n_slots, stepping, joins, leaving):
+        """the per-slot records of this transition's launch and, per slot, the known-region record of an inpainting slot that
+        steps (None for every other slot)"""
+        slots, recs = self._slots, []
+        for i in range(n_slots):
+            r = slots[i] if i < len(slots) else None
+            if r is not None and r in stepping:
+                a, b, c = r.coeffs[r.i]
+                rec = {"mode": ops.ROW_STEP, "sigma": r.sig[r.i], "guidance": r.guidance, "a": a, "b": b, "c": c}
+                if r.skipout is not None:
+                    rec.update(c_skip=r.skipout[r.i][0], c_out=r.skipout[r.i][1], s=r.snoise[r.i],
+                               noise=self.exec.noise_row(r, r.i) if r.snoise[r.i] != 0.0 else None)
+                    if r.rescale > 0.0:
+                        rec["rescale"] = r.rescale
+                if r in leaving:
+                    rec.update(c_in_next=0.0, t_next=0.0, sigma_next=1.0, temb_row=None, req=r, step=r.i, next_step=None)
+                else:
+                    j = r.i + 1
+                    rec.update(c_in_next=r.scal[j][0], t_next=r.scal[j][1], sigma_next=max(r.sig[j], 1e-10),
+                               temb_row=self.exec.temb_row(r, j), req=r, step=r.i, next_step=j)
+            elif r is not None and r in joins:
+                rec = {"mode": ops.ROW_JOIN, "c_in_next": r.scal[0][0], "t_next": r.scal[0][1], "sigma_next": r.sig[0],
+                       "temb_row": self.exec.temb_row(r, 0), "req": r, "step": None, "next_step": 0}
+            else:
+                rec = {"mode": ops.ROW_IDLE, "t_next": 0.0, "sigma_next": 1.0, "temb_row": None, "req": None}
+            recs.append(rec)
+        # known region of inpainting slots that step now: the model call of request step k >= 1 saw a blended input, and the
+        # coming call is blended unless the request leaves (a JOIN is a request's first call: never blended)
+        known = [None] * n_slots
+        for i, rec in enumerate(recs):
+            r = rec["req"]
+            if rec["mode"] == ops.ROW_STEP and r.known is not None:
+                known[i] = dict(r.known, blend_now=r.i >= 1, blend_next=r not in leaving)
+        return recs, known
+
+    def _load_joins(self, n_dst, joins):
+        if n_dst is not None:
+            self._ensure(n_dst)
+        for r in joins:
+            self.exec.load_latent(r)
+            if r.control is not None:
+                self.exec.load_lane(r)               # its text rows and conditioning embedding(s) into the lane's rows
+        self._stats["joins"] += len(joins)
+
+    def _transition(self, n_src, n_dst, recs, known):
+        """the ONE launch of this step; executor.step_launch names it from the records"""
+        kind = step_launch(recs, known)
+        if kind == "known" and step_launch(recs) == "linear":
+            raise RuntimeError("serve: an inpainting slot and a slot of another sampler step together (admission check bypassed)")
+        if kind == "known":
+            self.exec.transition(n_src, n_dst, recs, known)
+        else:                                        # (no inpainting slot steps: an executor without known regions serves it)
+            self.exec.transition(n_src, n_dst, recs)
+        if kind == "linear":                         # a slot steps another sampler / a v-prediction model / with a rescale
+            self._stats["linear_transitions"] += 1
+
+    def _leave(self, leaving):
+        """hand-off / finish of the requests whose last step was just applied, and the release of what they held"""
+        for r in leaving:
+            self._slots[r.slot] = None
+            if r.hires is not None:
+                self._hand_off(r)
+            elif self.decode and r.output_type != "latent":
+                self._done.append((r, self.exec.finish_image(r)))       # the row is cloned now and goes to the lane below
+            else:
+                self._done.append((r, self.exec.finish(r)))
+            r.hnoise = None                          # (a second-pass record: its start noise was read before it joined)
+            r.known = None                           # its image / noise / mask rows go back to the allocator (stream-ordered)
+            r.noise = None                           # ... and its noise table
+            r.adapter_feats = None                   # ... and its adapter features
+            if r.lane is not None:                   # ... and its ControlNet lane goes to whoever waits for one
+                self._lanes[r.lane] = None
+                r.lane, r.cemb = None, None
+            self._stats["leaves"] += 1
+
+    def _run_bucket(self, n_dst):
+        """bucket n_dst's static buffers brought up to date for the model call about to run (each only when it changed), then
+        the ControlNet graph when some gate is open, then the bucket's step"""
+        slots = self._slots
+        rows = [slots[i] if i < len(slots) else None for i in range(n_dst)]      # (a bucket may exceed max_batch)
+        members = tuple(None if r is None else r.rid for r in rows)
+        if self._members.get(n_dst) != members:
+            self.exec.refresh(n_dst, rows)
+            self._members[n_dst] = members
+            self._stats["refreshes"] += 1
+        if self._n is not None and n_dst != self._n:
+            self._stats["bucket_switches"] += 1
+        if self.t2i:
+            # (after r.i moved on: r.i is the index of the model call that runs now.)  Only a changed vector is uploaded, and
+            # a window that closes changes nothing else: no text, K/V or table work
+            gates = self._adapter_gates(n_dst, rows)
+            if self._gates.get(n_dst, [0.0] * (2 * n_dst)) != gates:
+                self.exec.set_adapter_gates(n_dst, gates)
+                self._gates[n_dst] = gates
+                self._stats["adapter_gate_updates"] += 1
+        if self.cn:
+            # (after r.i moved on, as above.)  Each of the three is uploaded only when it differs from what the bucket holds;
+            # the ControlNet itself runs only when some member's gate is open in the coming call
+            dst, gather, gates = self._control_vectors(n_dst, rows)
+            was = self._cstate.get(n_dst, ([-1] * len(dst), [0] * len(gather), [[0.0] * len(dst) for _ in gates]))
+            if (dst, gather, gates) != was:
+                self.exec.set_control(n_dst, dst if dst != was[0] else None, gather if gather != was[1] else None,
+                                      gates if gates != was[2] else None)
+                self._cstate[n_dst] = (dst, gather, gates)
+                if gates != was[2]:
+                    self._stats["control_gate_updates"] += 1
+            if any(g != 0.0 for per in gates for g in per):
+                self.exec.run_control(n_dst)
+                self._stats["control_steps"] += 1
+        self.exec.run(n_dst)
+        self._stats["steps"] += 1
+
+    def _hand_off(self, r):
+        """r leaves this batcher for its hires pass: the resample + noise launch on this batcher's stream, then the second-pass
+        record joins the chained batcher's queue (the only place one batcher takes another's lock)"""
+        hi, r2 = self._hires, r.hires
+        r2.ready = self.exec.hand_off(r, r2)
+        r2.t_handoff = time.perf_counter()
+        r.future.dsc_first_pass_s = r2.t_handoff - r.t_submit    # submit -> handed off (host clock), for measurement tools
+        r.hires = None
+        self._stats["handoffs"] += 1
+        with hi._lock:
+            r2.rid = hi._next_id
+            hi._next_id += 1
+            hi._queue.append(r2)
+            hi._wake.notify_all()
+
+    def _ensure(self, n):
+        if self.cn:
+            self._ensure_control()
+        if self.exec.ensure(n):
+            self._stats["captures"] += 1
+
+    def _ensure_control(self):
+        if self.exec.ensure_control():
+            self._stats["captures"] += 1
+
+    def _ensure_decode(self):
+        self._stats["captures"] += self.exec.ensure_decode()
+
+    def _poll(self, wait=False):
+        """resolve the futures of requests whose final row copy has completed (in completion order)"""
+        keep = []
+        for r, h in self._done:
+            if wait or self.exec.ready(h):
+                out = self.exec.result(r, h)
+                r.t_done = time.perf_counter()
+                r.future.dsc_latency_s = r.t_done - r.t_submit        # submit -> resolved, for measurement tools
+                if not r.future.done():
+                    r.future.set_result(out)
+            else:
+                keep.append((r, h))
+        self._done = keep
+
+    def _drive(self):
+        self.exec.bind_thread()
+        while True:
+            with self._lock:
+                if self._stop:
+                    return
+                self._poll()
+                if self._step_locked():
+                    # bound how far the host runs ahead of the GPU (a join lands within a few steps, not after every
+                    # step already queued): wait for the step before last, never for the one just queued
+                    self.exec.throttle()
+                elif self._done:
+                    self._wake.wait(0.0005)              # rows in flight: look again soon
+                else:
+                    self._wake.wait()
+
+class HiresPair:
+    """Two chained batchers (pipe.serve_hires): `base` at the request's size, `hires` at the target size, with the batcher's own
+    public surface.  Requests go to `base`; those with `upscale=True` continue on `hires` (which also takes ordinary requests of
+    its size through `pair.hires.submit`)."""
+
+    def __init__(self, base, hires):
+        self.base, self.hires = base.chain_hires(hires), hires
+
+    def warm(self):
+        self.base.warm()
+        self.hires.warm()
+        if hasattr(self.base.exec, "warm_hand_off"):
+            self.base.exec.warm_hand_off(self.hires.exec)
+        return self
+
+    def submit(self, request):
+        return self.base.submit(request)
+
+    def step(self):
+        """advance both batchers by one step each; False when both are idle"""
+        a = self.base.step()
+        b = self.hires.step()
+        return a or b
+
+    def run_until_idle(self):
+        while self.step():
+            pass
+        self.base.run_until_idle()
+        self.hires.run_until_idle()
+
+    def start(self):
+        self.base.start()
+        self.hires.start()
+        return self
+
+    def stop(self):
+        self.base.stop()
+        self.hires.stop()
+
+    def stats(self):
+        b = self.base.stats()
+        return {"base": b, "hires": self.hires.stats(), "handoffs": b["handoffs"]}

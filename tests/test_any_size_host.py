@@ -152,12 +152,8 @@ def _serve_request(h, w, **kw):
 
 
 def _fake_exec():
-    from test_serving_host import FakeExec
-
-    class Exec(FakeExec):
-        def prepare_noise(self, r, eta):                                 # (the ancestral / SDE members draw their step noise)
-            pass
-    return Exec()
+    from serving_fakes import RecordingExec
+    return RecordingExec()
 
 
 LINEAR_STEP_REQUESTS = [{"sampler_name": "sample_euler"}, {"sampler_name": "sample_euler_ancestral"},

@@ -1,4 +1,4 @@
-"""ControlNet requests in the continuous batcher on the host (modules/serving.py against a fake executor): the gate of every
+"""ControlNet requests in the continuous batcher on the host (modules/serving/ against a fake executor): the gate of every
 model call against `preprocess_controlnet`'s keep schedule, lane allocation / release / FIFO waiting, the per-bucket dst / gather /
 gate vectors and their uploads, the submit-time and construction-time refusals, the C entry (declared, registered, validating its
 arguments without a GPU), the scatter-add's torch form against the written-out chain, and the aliasing rule of the UNet's
@@ -26,20 +26,14 @@ class LaneExec(FakeImgExec):
         self.log = []                # ("lane", lane, name) | ("set", n, dst, gather, gates) | ("control", n) | ("run", n, state, names)
         self.state = {}
         self.members = {}
-        self.captured = self.warmed = 0
+        self.captured = 0                    # calls of ensure_control; only the first captures
+
+    def ensure(self, n):
+        return False                         # (the ControlNet graph is the one capture these tests count)
 
     def ensure_control(self):
         self.captured += 1
         return self.captured == 1
-
-    def warm_control(self):
-        self.warmed += 1
-
-    def prepare_noise(self, r, eta):
-        pass
-
-    def transition_linear(self, n_src, n_dst, recs):
-        self._record("linear", n_src, n_dst, recs, None)
 
     def refresh(self, n, members):
         self.members[n] = [None if r is None else r.req["name"] for r in members]

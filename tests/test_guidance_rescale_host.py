@@ -76,8 +76,7 @@ def _strip(transitions):
 
 
 def test_phi_zero_is_todays_record_lists_on_the_old_executor_protocol(pipe):
-    """an executor with no linear / noise methods at all (tests/test_serving_host.py's) serves phi = 0 requests, and an
-    explicit 0 leaves every record of every transition as it is without the key"""
+    """phi = 0 requests never reach the linear launch (every transition is step_launch's "rows"), and an explicit 0 leaves every record of every transition as it is without the key"""
     runs = []
     for kw in ({}, {"guidance_rescale": 0.0}, {"guidance_rescale": None}):
         ex = FakeExec()
@@ -87,7 +86,7 @@ def test_phi_zero_is_todays_record_lists_on_the_old_executor_protocol(pipe):
         b.submit(_req("B", steps=3, g=5.0, **kw))
         b.submit(_req("C", steps=2, **kw))
         b.run_until_idle()
-        assert b.stats()["linear_transitions"] == 0 and b.stats()["leaves"] == 3
+        assert b.stats()["linear_transitions"] == 0 and not ex.linear and b.stats()["leaves"] == 3
         runs.append(_strip(ex.transitions))
     assert runs[0] == runs[1] == runs[2] and len(runs[0]) == 5          # A joins; A steps + B, C join; three more steps
     assert all("rescale" not in r and "c_skip" not in r for t in runs[0] for r in t[2])

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from inputs import FakeTokenizer
+from serving_fakes import RecordingExec
 
 import diffusionspatialcontrol_amd as dsc
 from diffusionspatialcontrol_amd import _lib, build as dsc_build
@@ -98,16 +99,7 @@ def test_restatement_equals_the_reference_chain_over_all_fp16():
 
 
 # ----------------------------------------------------------------------------- the batcher's refusals
-class _NoDeviceExec:
-    """the executor's face at construction and submit; nothing here reaches a device"""
-    device = torch.device("cpu")
-    dtype = torch.float16
-
-    def prepare(self, r):
-        pass
-
-    def prepare_noise(self, r, eta):
-        pass
+_NoDeviceExec = RecordingExec         # nothing in these tests reaches a device
 
 
 def _pipe(with_vae):

@@ -1,4 +1,4 @@
-"""IP-Adapter region masks in the continuous batcher on the host (modules/serving.py against a fake executor): the opt-in at
+"""IP-Adapter region masks in the continuous batcher on the host (modules/serving/ against a fake executor): the opt-in at
 construction, the submit-time refusals of `ip_adapter_masks`, the per-level weights recorded at submit (square and ragged
 levels, a hires pair), the rows `refresh` is handed, and the masked C entry (declared, exported, validating without a GPU)."""
 import ctypes
@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from inputs import FakeTokenizer
+from serving_fakes import RecordingExec
 
 import diffusionspatialcontrol_amd as dsc
 from diffusionspatialcontrol_amd import _lib, build as dsc_build, ops
@@ -17,59 +18,7 @@ from diffusionspatialcontrol_amd.modules.serving import HiresPair, ServingBatche
 S, EMB = 77, 48
 
 
-class FakeExec:
-    """records what the batcher hands the device side (tests/test_ip_serving_host.py's)"""
-    device = torch.device("cpu")
-    dtype = torch.float16
-
-    def __init__(self):
-        self.refreshes = []
-
-    def bind_thread(self):
-        pass
-
-    def throttle(self):
-        pass
-
-    def prepare(self, r):
-        pass
-
-    prepare_image = prepare_hires = prepare
-
-    def prepare_noise(self, r, eta):
-        pass
-
-    def hand_off(self, r, r2):
-        return "event"
-
-    def temb_row(self, r, j):
-        return j
-
-    def load_latent(self, r):
-        pass
-
-    def ensure(self, n):
-        return False
-
-    def transition(self, n_src, n_dst, recs):
-        pass
-
-    transition_linear = transition
-
-    def refresh(self, n, members):
-        self.refreshes.append((n, list(members)))
-
-    def run(self, n):
-        pass
-
-    def finish(self, r):
-        return r
-
-    def ready(self, h):
-        return True
-
-    def result(self, r, h):
-        return r.req["name"]
+FakeExec = RecordingExec
 
 
 def _adapter(unet):
@@ -132,7 +81,7 @@ def _still_usable(b):
     assert b.stats()["queued"] == 0
     fut = b.submit(_req("plain"))
     b.run_until_idle()
-    assert fut.result() == "plain"
+    assert fut.result()[0] == "plain"
 
 
 def test_a_mask_capable_batcher_accepts_what_the_default_one_refuses(pipe1):
@@ -142,7 +91,7 @@ def test_a_mask_capable_batcher_accepts_what_the_default_one_refuses(pipe1):
     fut = b.submit(_req("masked", **request))
     assert b._queue[0].ip_weights is not None
     b.run_until_idle()
-    assert fut.result() == "masked"
+    assert fut.result()[0] == "masked"
     default, _ = _batcher(pipe1, ip_masks=False)
     with pytest.raises(ValueError, match="ip_adapter_masks") as e:
         default.submit(_req("X", **request))
@@ -176,7 +125,7 @@ def test_a_hires_request_with_masks_needs_a_mask_capable_second_batcher(pipe1):
     assert base.stats()["queued"] == 0 and hi.stats()["queued"] == 0
     fut = pair.submit(_req("plain", upscale=True, upscale_x=1.5, ip_adapter_image_embeds=_embeds(1)))
     pair.run_until_idle()
-    assert fut.result() == "plain"
+    assert fut.result()[0] == "plain"
 
 
 def _expected(mask_a, L):
@@ -220,7 +169,7 @@ def test_a_hires_second_pass_records_weights_at_its_own_levels(pipe1):
     for L in hi.levels():
         assert torch.equal(first.hires.ip_weights[0][L], _expected(masks[0], L))
     pair.run_until_idle()
-    assert fut.result() == "H"
+    assert fut.result()[0] == "H"
 
 
 def test_masks_without_an_image_prompt_are_ignored(pipe1):

@@ -1,4 +1,4 @@
-"""IP-Adapter requests in the continuous batcher on the host (modules/serving.py against a fake executor): the submit-time
+"""IP-Adapter requests in the continuous batcher on the host (modules/serving/ against a fake executor): the submit-time
 refusals of the image-prompt keys, the default scale, the row scales `refresh` writes, the hires pair, stale batchers, and the
 C entry (declared, exported, validating its arguments without a GPU)."""
 import ctypes
@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from inputs import FakeTokenizer
+from serving_fakes import RecordingExec
 
 import diffusionspatialcontrol_amd as dsc
 from diffusionspatialcontrol_amd import _lib, build as dsc_build, ops
@@ -16,59 +17,7 @@ from diffusionspatialcontrol_amd.modules.serving import HiresPair, ServingBatche
 S, EMB = 77, 48
 
 
-class FakeExec:
-    """records what the batcher hands the device side"""
-    device = torch.device("cpu")
-    dtype = torch.float16
-
-    def __init__(self):
-        self.refreshes = []
-
-    def bind_thread(self):
-        pass
-
-    def throttle(self):
-        pass
-
-    def prepare(self, r):
-        pass
-
-    prepare_image = prepare_hires = prepare
-
-    def prepare_noise(self, r, eta):
-        pass
-
-    def hand_off(self, r, r2):
-        return "event"
-
-    def temb_row(self, r, j):
-        return j
-
-    def load_latent(self, r):
-        pass
-
-    def ensure(self, n):
-        return False
-
-    def transition(self, n_src, n_dst, recs):
-        pass
-
-    transition_linear = transition
-
-    def refresh(self, n, members):
-        self.refreshes.append((n, list(members)))
-
-    def run(self, n):
-        pass
-
-    def finish(self, r):
-        return r
-
-    def ready(self, h):
-        return True
-
-    def result(self, r, h):
-        return r.req["name"]
+FakeExec = RecordingExec
 
 
 def _pipe(adapters=()):
@@ -144,7 +93,7 @@ def test_submit_refusals_leave_the_batcher_usable(pipe1, bad, match):
     assert b.stats()["queued"] == 0
     fut = b.submit(_req("plain"))
     b.run_until_idle()
-    assert fut.result() == "plain"
+    assert fut.result()[0] == "plain"
 
 
 def test_embeds_without_an_adapter_are_refused():
@@ -153,7 +102,7 @@ def test_embeds_without_an_adapter_are_refused():
         b.submit(_req("X", ip_adapter_image_embeds=_embeds(1)))
     fut = b.submit(_req("plain"))
     b.run_until_idle()
-    assert fut.result() == "plain"
+    assert fut.result()[0] == "plain"
 
 
 def test_submit_accepts_embeds_and_takes_the_default_scale_at_submit_time(pipe1):
@@ -194,7 +143,7 @@ def test_hires_pair_hands_the_keys_to_the_second_pass(pipe1):
     assert first.ip_scale == [0.4] and first.ip_embeds[0] is e[0]
     assert first.hires.ip_scale == [0.4] and first.hires.ip_embeds[0] is e[0]
     pair.run_until_idle()
-    assert fut.result() == "H" and base.stats()["handoffs"] == 1
+    assert fut.result()[0] == "H" and base.stats()["handoffs"] == 1
     with pytest.raises(ValueError, match="one tensor per loaded IP-Adapter"):
         pair.submit(_req("bad", upscale=True, upscale_x=1.5, ip_adapter_image_embeds=_embeds(2)))
 

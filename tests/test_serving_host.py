@@ -1,4 +1,4 @@
-"""Continuous-batching scheduler (modules/serving.py) on the host, against a fake step executor: admission order and slot
+"""Continuous-batching scheduler (modules/serving/) on the host, against a fake step executor: admission order and slot
 placement, bucket choice, the 32-row table admission wait, submit-time rejections, per-request DPM++ 2M coefficient and
 time-embedding index sequences (those of txt2img's fused loop for the same schedule), futures in completion order."""
 import numpy as np
@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from inputs import FakeTokenizer
+from serving_fakes import RecordingExec
 
 from diffusionspatialcontrol_amd import ops
 from diffusionspatialcontrol_amd.modules import sampling
@@ -14,63 +15,7 @@ from diffusionspatialcontrol_amd.modules.serving import ServingBatcher
 S = 77
 
 
-class FakeExec:
-    """records what the batcher asks of the device; a request's 'latent' is the list of steps applied to it"""
-    device = torch.device("cpu")
-    dtype = torch.float16
-
-    def __init__(self):
-        self.captured, self.runs, self.transitions, self.refreshes, self.finished = [], [], [], [], []
-        self.applied = {}
-
-    def bind_thread(self):
-        pass
-
-    def throttle(self):
-        pass
-
-    def prepare(self, r):
-        self.applied[id(r)] = []
-
-    def temb_row(self, r, j):
-        return ("temb", r.req["name"], j)
-
-    def load_latent(self, r):
-        pass
-
-    def ensure(self, n):
-        if n in self.captured:
-            return False
-        self.captured.append(n)
-        return True
-
-    def transition(self, n_src, n_dst, recs):
-        self.transitions.append((n_src, n_dst, [dict(r) for r in recs]))
-        for i, rec in enumerate(recs):
-            r = rec.get("req")
-            if rec["mode"] == ops.ROW_STEP:
-                assert i < n_src
-                self.applied[id(r)].append(("step", rec["step"], rec["sigma"], rec["guidance"], rec["a"], rec["b"], rec["c"],
-                                            rec["c_in_next"], rec["t_next"], rec["temb_row"]))
-            elif rec["mode"] == ops.ROW_JOIN:
-                assert i < n_dst
-                self.applied[id(r)].append(("join", rec["c_in_next"], rec["t_next"], rec["sigma_next"], rec["temb_row"]))
-
-    def refresh(self, n, members):
-        self.refreshes.append((n, [None if m is None else m.req["name"] for m in members]))
-
-    def run(self, n):
-        self.runs.append(n)
-
-    def finish(self, r):
-        self.finished.append(r.req["name"])
-        return r
-
-    def ready(self, h):
-        return True
-
-    def result(self, r, h):
-        return (r.req["name"], self.applied[id(r)])
+FakeExec = RecordingExec
 
 
 @pytest.fixture(scope="module")

@@ -1,10 +1,11 @@
-"""img2img / inpainting requests in the continuous-batching scheduler (modules/serving.py) on the host, against a fake
+"""img2img / inpainting requests in the continuous-batching scheduler (modules/serving/) on the host, against a fake
 executor: schedule truncation by `strength`, the known-region records handed to the per-row step, which launch a transition
 takes, and the submit-time rejections of the image keys."""
 import pytest
 import torch
 
 from inputs import FakeTokenizer
+from serving_fakes import RecordingExec
 
 from diffusionspatialcontrol_amd import ops
 from diffusionspatialcontrol_amd.modules import sampling
@@ -13,69 +14,10 @@ from diffusionspatialcontrol_amd.modules.serving import ServingBatcher
 S = 77
 
 
-class FakeImgExec:
-    """test_serving_host.FakeExec's interface plus the two methods only image requests reach"""
-    device = torch.device("cpu")
-    dtype = torch.float16
-
-    def __init__(self):
-        self.calls = []                     # ("plain" | "known", n_src, n_dst, recs, known)
-        self.prepared, self.applied = [], {}
-
-    def bind_thread(self):
-        pass
-
-    def throttle(self):
-        pass
-
-    def prepare(self, r):
-        self.prepared.append(("txt2img", r.req["name"]))
-        self.applied[id(r)] = []
-
-    def prepare_image(self, r):
-        self.prepared.append((r.kind, r.req["name"]))
-        self.applied[id(r)] = []
-        if r.kind == "inpaint":
-            r.known = {"image": ("image", r.req["name"]), "noise": ("noise", r.req["name"]), "mask": ("mask", r.req["name"])}
-
-    def temb_row(self, r, j):
-        return ("temb", r.req["name"], j)
-
-    def load_latent(self, r):
-        pass
-
-    def ensure(self, n):
-        return False
-
-    def _record(self, kind, n_src, n_dst, recs, known):
-        self.calls.append((kind, n_src, n_dst, [dict(r) for r in recs], known))
-        for i, rec in enumerate(recs):
-            r = rec.get("req")
-            if rec["mode"] == ops.ROW_STEP:
-                self.applied[id(r)].append(("step", rec["step"], rec["sigma"], rec["a"], rec["b"], rec["c"], rec["c_in_next"],
-                                            rec["t_next"], rec["temb_row"], None if known is None else known[i]))
-            elif rec["mode"] == ops.ROW_JOIN:
-                self.applied[id(r)].append(("join", rec["c_in_next"], rec["t_next"], rec["sigma_next"], rec["temb_row"],
-                                            None if known is None else known[i]))
-
-    def transition(self, n_src, n_dst, recs):
-        self._record("plain", n_src, n_dst, recs, None)
-
-    def transition_known(self, n_src, n_dst, recs, known):
-        assert len(known) == len(recs)
-        self._record("known", n_src, n_dst, recs, known)
-
-    def refresh(self, n, members):
-        pass
-
-    def run(self, n):
-        pass
-
-    def finish(self, r):
-        return r
-
-    def ready(self, h):
-        return True
+class FakeImgExec(RecordingExec):
+    """a request's result is what was applied to it: no guidance, and the known-region record each entry was launched with"""
+    step_keys = tuple(k for k in RecordingExec.step_keys if k != "guidance")
+    applied_known = True
 
     def result(self, r, h):
         return self.applied[id(r)]
@@ -147,7 +89,7 @@ def test_inpainting_records_and_launch_choice(pipe):
     fm = b.submit(_req("M", steps=5, image=LAT, strength=0.6))
     b.run_until_idle()
     kinds = [c[0] for c in ex.calls]
-    assert kinds[0] == "plain" and kinds[1] == "plain"                 # T joins; then I and M join while T steps
+    assert kinds[0] == "rows" and kinds[1] == "rows"                 # T joins; then I and M join while T steps
     assert ex.calls[1][3][1]["mode"] == ops.ROW_JOIN and ex.calls[1][3][1]["req"].req["name"] == "I"
     steps_i = [a for a in fi.result() if a[0] == "step"]
     assert len(steps_i) == 3 and fi.result()[0][0] == "join" and fi.result()[0][-1] is None
@@ -155,7 +97,7 @@ def test_inpainting_records_and_launch_choice(pipe):
         kn = a[-1]
         assert kn["blend_now"] == (k >= 1) and kn["blend_next"] == (k < 2), (k, kn)
         assert (kn["image"], kn["noise"], kn["mask"]) == (("image", "I"), ("noise", "I"), ("mask", "I"))
-    assert kinds[2:5] == ["known"] * 3 and set(kinds[5:]) == {"plain"}  # once I has left, the plain launch again
+    assert kinds[2:5] == ["known"] * 3 and set(kinds[5:]) == {"rows"}  # once I has left, the plain launch again
     for call in ex.calls[2:5]:
         for rec, kn in zip(call[3], call[4]):
             name = None if rec["req"] is None else rec["req"].req["name"]
@@ -171,7 +113,7 @@ def test_batch_without_inpainting_never_takes_the_known_launch(pipe):
     futs = [b.submit(_req("A", steps=3, latents=LAT)), b.submit(_req("B", steps=4, image=LAT, strength=0.5)),
             b.submit(_req("C", steps=2, latents=LAT))]
     b.run_until_idle()
-    assert all(f.done() for f in futs) and {c[0] for c in ex.calls} == {"plain"}
+    assert all(f.done() for f in futs) and {c[0] for c in ex.calls} == {"rows"}
     assert ex.prepared == [("txt2img", "A"), ("img2img", "B"), ("txt2img", "C")]
 
 

@@ -1,4 +1,4 @@
-"""T2I-Adapter requests in the continuous batcher on the host (modules/serving.py against a fake executor): the per-row gate
+"""T2I-Adapter requests in the continuous batcher on the host (modules/serving/ against a fake executor): the per-row gate
 vector of every step against the pipeline methods' window, uploads only on change and no refresh when a window closes, the
 submit-time and construction-time refusals, the adapter-vs-UNet size check at odd sizes, the C entry (declared, registered,
 validating its arguments without a GPU) and the UNet's `down_intrablock_gated` keyword on the CPU."""
@@ -26,16 +26,6 @@ class GateExec(FakeImgExec):
         self.log = []                        # ("refresh", n, names) | ("gates", n, gates) | ("run", n, gates in force, names)
         self.gates = {}
         self.members = {}
-        self.warmed = 0
-
-    def warm_adapter(self):
-        self.warmed += 1
-
-    def prepare_noise(self, r, eta):
-        pass
-
-    def transition_linear(self, n_src, n_dst, recs):
-        self._record("linear", n_src, n_dst, recs, None)
 
     def refresh(self, n, members):
         self.members[n] = [None if r is None else r.req["name"] for r in members]

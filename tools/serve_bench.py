@@ -1,4 +1,4 @@
-"""Continuous-batching serving measurements (modules/serving.py) on one GPU; one JSON line per leg.
+"""Continuous-batching serving measurements (modules/serving/) on one GPU; one JSON line per leg.
 
     python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
                                 [--hires X] [--ip-adapter [--ip-masks]] [--t2i-adapter] [--controlnet [--control-slots C]]
