@@ -558,7 +558,8 @@ class StableDiffusionPipeline:
 
     def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77,
               ip_masks: bool = False, t2i_adapter: bool = False, controlnet: bool = False, control_slots=None,
-              decode: bool = False, decode_batch: int = 2):
+              decode: bool = False, decode_batch: int = 2, previews: bool = False, preview_scale: int = 8, preview_coef=None,
+              preview_ring: int = 8):
         """Continuous-batching server (modules/serving/): requests join a running batch at any step boundary, each at its own
         point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
         stats / warm).  `ip_masks=True` (IP-Adapters loaded): requests may carry the reference's
@@ -570,21 +571,31 @@ class StableDiffusionPipeline:
         control image does not pay for its neighbours'.  `decode=True` (a pipeline with a VAE decoder): requests may ask for
         finished images - `output_type` "pil", "np" (float32 [H, W, 3]) or "uint8" (np.uint8 [H, W, 3]) - which a decode lane
         on a second stream produces beside the step, up to `decode_batch` (in [1, max_batch]) rows per captured decode; without
-        it image output types run `latent_to_image` inline, as before, and "uint8" is refused."""
+        it image output types run `latent_to_image` inline, as before, and "uint8" is refused.  `previews=True`: requests may
+        carry `preview_every=k` and `on_preview=f`; after every k-th of a request's steps but the last, `f(step, steps, image)`
+        receives an approximate np.uint8 [h * preview_scale, w * preview_scale, 3] thumbnail of its denoised estimate (h, w: the
+        latent's sides; `preview_scale` in {1, 2, 4, 8} with a thumbnail width that is a multiple of 8; `preview_coef`: C * 3 + 3
+        numbers, the latent-to-RGB matrix k[c][rgb] then a bias, default ops.LATENT_RGB_SD15) made by one launch beside the step
+        and copied out on a second stream through a ring of `preview_ring` pinned buffers; a preview that finds the ring full
+        is dropped, never waited for."""
         from .serving import ServingBatcher
+        kw = dict(previews=True, preview_scale=preview_scale, preview_coef=preview_coef, preview_ring=preview_ring) if previews else {}
         return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len,
                               ip_masks=ip_masks, t2i_adapter=t2i_adapter, controlnet=controlnet, control_slots=control_slots,
-                              decode=decode, decode_batch=decode_batch)
+                              decode=decode, decode_batch=decode_batch, **kw)
 
     def serve_hires(self, height: int = 512, width: int = 512, upscale_x: float = 1.25, max_batch: int = 8, buckets=(1, 2, 4, 8),
-                    text_len: int = 77, slots=(0, 1), ip_masks: bool = False, decode: bool = False, decode_batch: int = 2):
+                    text_len: int = 77, slots=(0, 1), ip_masks: bool = False, decode: bool = False, decode_batch: int = 2,
+                    previews: bool = False, preview_scale: int = 8, preview_coef=None, preview_ring: int = 8):
         """Continuous-batching server for requests with a hires pass (reference :1176-1228): a batcher at `height` x `width`
         chained to one at the target size of `upscale_x` (_hires_pass's expression), on two workspace slots.  A request with
         `upscale=True` runs its first pass on the one, is enlarged and re-noised on the device (dsc_latent_resample_noise) and
         finishes on the other; requests without it are served at the base size as by `serve`.  Returns a `HiresPair` with the
         batcher's surface (submit / step / run_until_idle / start / stop / stats / warm).  `ip_masks=True` builds both batchers for
         `ip_adapter_masks` (see `serve`); the second pass down-samples a request's mask at its own levels.  `decode=True` gives
-        each batcher a decode lane at its own image size (see `serve`): a request without `upscale` finishes on the base batcher."""
+        each batcher a decode lane at its own image size (see `serve`): a request without `upscale` finishes on the base batcher.
+        `previews=True` gives both batchers the preview path (see `serve`): each pass of a request with `upscale` counts its own
+        steps, and the second pass previews at its own size."""
         from .latent_resample import hires_target_size
         from .serving import HiresPair, ServingBatcher
         th, tw = hires_target_size(height, width, upscale_x, self.vae_scale_factor)
@@ -607,6 +618,8 @@ class StableDiffusionPipeline:
         kw = dict(max_batch=max_batch, buckets=buckets, text_len=text_len, ip_masks=ip_masks)
         if decode:                               # (a pair built without the flag is constructed exactly as before)
             kw.update(decode=True, decode_batch=decode_batch)
+        if previews:
+            kw.update(previews=True, preview_scale=preview_scale, preview_coef=preview_coef, preview_ring=preview_ring)
         return HiresPair(ServingBatcher(self, height, width, slot=slots[0], **kw), ServingBatcher(self, th, tw, slot=slots[1], **kw))
 
     def txt2img_coalesced(self, requests, height: int = 512, width: int = 512, num_inference_steps: int = 50,

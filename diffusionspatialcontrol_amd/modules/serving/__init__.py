@@ -24,6 +24,7 @@ The seam is host scheduling against a replaceable device executor:
   executor.py     _GraphExecutor, the capture sequence, step_launch (which launch serves a transition); image prompts,
                   T2I-Adapter, ControlNet
   decode_lane.py  the decode lane that finishes images beside the step
+  preview_lane.py the preview path: thumbnails of running requests' denoised estimates, beside the step
 """
 # every name that is imported from `modules.serving`
 from .batcher import HiresPair, ServingBatcher

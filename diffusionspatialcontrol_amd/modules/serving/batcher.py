@@ -54,7 +54,8 @@ class ServingBatcher:
     the scheduling here is host logic only."""
 
     def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
-                 t2i_adapter=False, controlnet=False, control_slots=None, decode=False, decode_batch=2):
+                 t2i_adapter=False, controlnet=False, control_slots=None, decode=False, decode_batch=2, previews=False,
+                 preview_scale=8, preview_coef=None, preview_ring=8):
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
             raise ValueError(f"serve: buckets {buckets} must cover max_batch={max_batch}")
@@ -88,6 +89,14 @@ class ServingBatcher:
                 raise ValueError(f"serve: `decode_batch` must be an integer in [1, max_batch = {self.max_batch}], got {decode_batch!r}")
             self.decode_batch = decode_batch
             self._stats["decodes"] = self._stats["decode_rows"] = 0
+        # requests may carry `preview_every` / `on_preview`: thumbnails of the denoised estimate leave beside the step
+        # (preview_lane.py)
+        self.previews = bool(previews)
+        self.preview_scale, self.preview_coef, self.preview_ring = 0, None, 0
+        self._preview_queue = collections.deque()   # (handle, [(state, step, steps)] in row order) of queued previews, oldest first
+        self._preview_of = {}                  # request -> its _PreviewState (only requests that asked), until it resolves / hands off
+        if self.previews:
+            self._preview_setup(preview_scale, preview_coef, preview_ring)
         self._warm_captures = None
         self._thread = None
         self._stop = False
@@ -119,6 +128,25 @@ class ServingBatcher:
         self._lanes = [None] * self.control_slots     # lane -> the request that holds it
         self._cstate = {}                      # bucket -> (dst, gather, gates) last uploaded for it (absent: as captured)
         self.exec = executor if executor is not None else _GraphExecutor(self)
+
+    def _preview_setup(self, scale, coef, ring):
+        """the preview arguments against this batcher's latent, at construction"""
+        from ...latent_preview import preview_coef
+        from .preview_lane import preview_scales_for
+        C, w = int(self.pipe.unet.config.in_channels), self.width // 8
+        if self.max_batch > ops.PREVIEW_MAX_ROWS or C > ops.PREVIEW_MAX_CHANNELS:
+            raise ValueError(f"serve: `previews=True` takes at most {ops.PREVIEW_MAX_ROWS} slots and {ops.PREVIEW_MAX_CHANNELS} latent "
+                             f"channels (dsc_latent_preview), got max_batch = {self.max_batch}, {C} channels")
+        works = preview_scales_for(w)
+        if isinstance(scale, bool) or not isinstance(scale, int) or scale not in works:
+            raise ValueError(f"serve: `preview_scale` {scale!r} does not work at a latent width of {w}: the thumbnail's width "
+                             f"(latent width * scale) must be a multiple of 8; at this size use one of {', '.join(map(str, works))}")
+        if isinstance(ring, bool) or not isinstance(ring, int) or ring < 1:
+            raise ValueError(f"serve: `preview_ring` must be an integer >= 1, got {ring!r}")
+        self.preview_scale, self.preview_ring = scale, ring
+        self.preview_coef = preview_coef(coef, C)                # (None: LATENT_RGB_SD15; a wrong count is refused here)
+        for key in ("previews", "preview_rows", "previews_dropped", "preview_callback_errors"):
+            self._stats[key] = 0
 
     def _adapter_setup(self):
         """the adapter against the UNet, at construction -> [(C_k, h_k, w_k)] of the feature each down block adds: as many maps
@@ -223,6 +251,8 @@ class ServingBatcher:
                 self._ensure(n)
             if self.decode:
                 self._ensure_decode()                # the lane's stream, static buffers, graphs and pinned ring
+            if self.previews:
+                self.exec.ensure_preview()           # the preview stream and its ring of device / pinned buffers
             self._warm_captures = self._stats["captures"]
         return self
 
@@ -268,7 +298,10 @@ class ServingBatcher:
         `controlnet=True`: `control_img` (a PIL image or a [1, 3, H, W] tensor in [0, 1]; a list with one per net when
         pipe.controlnet is a MultiControlNetModel), `controlnet_conditioning_scale` (default 1.0), `control_guidance_start` (0.0)
         and `control_guidance_end` (1.0) (numbers, or lists with one entry per net) - the pipeline methods' own keys; not with
-        `upscale` or `mask_image`.  Returns a Future of the final output."""
+        `upscale` or `mask_image`.  On a batcher built with `previews=True`: `preview_every` (an int k >= 1; absent, None or 0: no
+        previews) and `on_preview` (a callable f(step, steps, image)): after every k-th of the request's steps but the last, f
+        receives the count of steps applied, the steps of this pass and an np.uint8 [h * scale, w * scale, 3] thumbnail of the
+        denoised estimate (preview_lane.py); f runs on the thread that steps the batcher.  Returns a Future of the final output."""
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -344,6 +377,7 @@ class ServingBatcher:
         # masks without an image prompt (or with every scale 0) have nothing to weigh: accepted and ignored
         ip_weights = requests.ip_mask_weights(self, ip_masks) if ip_embeds is not None and ip_masks is not None else None
         text = requests.text_request(self, request)
+        every, on_preview = requests.preview_request(self, request)
         steps = int(request.get("num_inference_steps", 25))
         if steps < 1:
             raise ValueError("serve: num_inference_steps must be >= 1")
@@ -411,6 +445,9 @@ class ServingBatcher:
         r.t_submit = time.perf_counter()
         if device:
             self._prepare_device(r)
+        if every:                                    # (last: a request refused above leaves nothing behind)
+            from .preview_lane import _PreviewState
+            self._preview_of[r] = _PreviewState(every, on_preview)
         return r
 
     def _adapter_gates(self, n, members):
@@ -472,11 +509,19 @@ class ServingBatcher:
         first, second = requests.hires_request(self, request)
         hi = self._hires
         r = self._prepare(first, device=False)
-        r2 = hi._prepare(second, second=True, device=False)
-        r2.future, r2.t_submit = r.future, r.t_submit
-        r.hires = r2
-        self._prepare_device(r)
-        hi._prepare_device(r2)
+        r2 = None
+        try:
+            r2 = hi._prepare(second, second=True, device=False)
+            r2.future, r2.t_submit = r.future, r.t_submit
+            r.hires = r2
+            self._prepare_device(r)
+            hi._prepare_device(r2)
+        except BaseException:                        # (a refused request leaves no preview state behind)
+            self._preview_of.pop(r, None)
+            hi._preview_of.pop(r2, None)
+            raise
+        if r in self._preview_of:                    # (its future also waits for the first pass's queued previews, _poll)
+            hi._preview_of[r2].first = self._preview_of[r]
         return r
 
 
@@ -526,7 +571,8 @@ class ServingBatcher:
 
     def _step_locked(self):
         """one step, as phases in the order the device sees them: admit, build the records, ensure the next bucket and load the
-        joins, ONE transition launch, let the finished leave, advance, refresh / upload / run the next bucket, flush decodes"""
+        joins, ONE transition launch, (previews) the launch for the slots that are due, let the finished leave, advance, refresh /
+        upload / run the next bucket, flush decodes"""
         slots = self._slots
         stepping = [r for r in slots if r is not None and r.i < len(r.coeffs) and self._n is not None]
         joins = self._admit()
@@ -541,6 +587,8 @@ class ServingBatcher:
         recs, known = self._records(max(n_src, nd), stepping, joins, leaving)
         self._load_joins(n_dst, joins)
         self._transition(n_src, nd, recs, known)
+        if self.previews:
+            self._preview(stepping, leaving)         # reads `old` of the step just applied, before the next transition
         self._leave(leaving)
         for r in stepping:
             r.i += 1
@@ -637,6 +685,37 @@ class ServingBatcher:
         if kind == "linear":                         # a slot steps another sampler / a v-prediction model / with a rescale
             self._stats["linear_transitions"] += 1
 
+    def _preview(self, stepping, leaving):
+        """the slots whose request is due a preview after the step just applied (every preview_every-th of its steps, never its
+        last) go to ONE launch; with no free ring entry it is skipped and counted - the step does not wait"""
+        asked = self._preview_of
+        due = [r for r in stepping if r in asked and (r.i + 1) % asked[r].every == 0 and r not in leaving]
+        if not due:
+            return
+        self.exec.ensure_preview()
+        h = self.exec.preview([r.slot for r in due])
+        if h is None:
+            self._stats["previews_dropped"] += 1
+            return
+        for r in due:
+            asked[r].out += 1
+        self._preview_queue.append((h, [(asked[r], r.i + 1, len(r.coeffs)) for r in due]))
+        self._stats["previews"] += 1
+        self._stats["preview_rows"] += len(due)
+
+    def _deliver_previews(self, wait=False):
+        """completed previews to their callbacks, oldest first (one request's previews arrive in step order): the row is copied
+        out of the pinned buffer, then `on_preview(step, steps, image)` runs here; what it raises is counted, never passed on"""
+        while self._preview_queue and (wait or self.exec.preview_ready(self._preview_queue[0][0])):
+            h, rows = self._preview_queue.popleft()
+            for j, (state, step, steps) in enumerate(rows):
+                image = self.exec.preview_image(h, j)
+                state.out -= 1
+                try:
+                    state.call(step, steps, image)
+                except Exception:                    # noqa: BLE001 - a client's callback must not disturb the batch
+                    self._stats["preview_callback_errors"] += 1
+
     def _leave(self, leaving):
         """hand-off / finish of the requests whose last step was just applied, and the release of what they held"""
         for r in leaving:
@@ -697,6 +776,7 @@ class ServingBatcher:
         """r leaves this batcher for its hires pass: the resample + noise launch on this batcher's stream, then the second-pass
         record joins the chained batcher's queue (the only place one batcher takes another's lock)"""
         hi, r2 = self._hires, r.hires
+        self._preview_of.pop(r, None)                # (its queued previews keep their state; the second pass's future waits for them)
         r2.ready = self.exec.hand_off(r, r2)
         r2.t_handoff = time.perf_counter()
         r.future.dsc_first_pass_s = r2.t_handoff - r.t_submit    # submit -> handed off (host clock), for measurement tools
@@ -722,10 +802,18 @@ class ServingBatcher:
         self._stats["captures"] += self.exec.ensure_decode()
 
     def _poll(self, wait=False):
-        """resolve the futures of requests whose final row copy has completed (in completion order)"""
+        """resolve the futures of requests whose final row copy has completed (in completion order); on a previews batcher the
+        completed previews are delivered first, and a future is held back while previews of its request are still queued (of a
+        hires request's second pass: of its first pass too, which the other batcher's poll delivers)"""
+        if self.previews:
+            self._deliver_previews(wait)
         keep = []
         for r, h in self._done:
-            if wait or self.exec.ready(h):
+            state = self._preview_of.get(r) if self.previews else None
+            held = state is not None and (state.out > 0 or (state.first is not None and state.first.out > 0 and not wait))
+            if not held and (wait or self.exec.ready(h)):
+                if state is not None:
+                    del self._preview_of[r]
                 out = self.exec.result(r, h)
                 r.t_done = time.perf_counter()
                 r.future.dsc_latency_s = r.t_done - r.t_submit        # submit -> resolved, for measurement tools
@@ -746,7 +834,7 @@ class ServingBatcher:
                     # bound how far the host runs ahead of the GPU (a join lands within a few steps, not after every
                     # step already queued): wait for the step before last, never for the one just queued
                     self.exec.throttle()
-                elif self._done:
+                elif self._done or self._preview_queue:
                     self._wake.wait(0.0005)              # rows in flight: look again soon
                 else:
                     self._wake.wait()

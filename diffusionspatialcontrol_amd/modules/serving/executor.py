@@ -48,6 +48,7 @@ from ... import _lib, ops
 from .. import sampling
 from ..latent_resample import MODES as _RESAMPLE_MODES, device_taps
 from .decode_lane import _DecodeLane, _LaneHandle
+from .preview_lane import _PreviewLane
 
 _EMBED_LOCK = threading.Lock()       # around the process-wide deterministic switch in _GraphExecutor._control_embedding
 _STEP_ROWS = {"rows": "cfg_dpmpp2m_step_rows", "linear": "cfg_linear_step_rows", "known": "cfg_dpmpp2m_step_rows_known"}     # in ops
@@ -148,6 +149,9 @@ class _GraphExecutor:
         self.cn = None
         # (decode) the lane that finishes images beside the step; its stream and buffers are built by ensure_decode
         self.lane = _DecodeLane(self, batcher.decode_batch) if getattr(batcher, "decode", False) else None
+        # (previews) the path that turns rows of `old` into thumbnails beside the step; its stream and ring are built by ensure_preview
+        self.previews = _PreviewLane(self, batcher.preview_scale, batcher.preview_coef, batcher.preview_ring) \
+            if getattr(batcher, "previews", False) else None
 
     def bind_thread(self):
         _lib.check(_lib.load_library().dsc_set_workspace_slot(self.b.slot), "dsc_set_workspace_slot")
@@ -479,6 +483,22 @@ class _GraphExecutor:
     def flush_decodes(self):
         """the pending rows to the lane, up to decode_batch at a time -> (decodes queued, rows in them)"""
         return self.lane.dispatch()
+
+    def ensure_preview(self):
+        """the preview path's stream and its ring of device / pinned buffers (preview_lane.py)"""
+        self.previews.ensure()
+
+    def preview(self, slots):
+        """one launch of dsc_latent_preview on these slots' rows of `old`, now - after the transition that wrote them, before the
+        next - and their copy to pinned memory on the preview stream -> a handle, or None when every ring entry is in use"""
+        return self.previews.launch(slots)
+
+    def preview_ready(self, h):
+        return self.previews.ready(h)
+
+    def preview_image(self, h, j):
+        """thumbnail j (the order of `slots`) of a queued preview: np.uint8 [h * scale, w * scale, 3], the caller's own"""
+        return self.previews.image(h, j)
 
     def ready(self, h):
         if isinstance(h, _LaneHandle):

@@ -181,6 +181,23 @@ def common_request(b, request):
     return out_type, v_pred, family, phi, g
 
 
+def preview_request(b, request):
+    """submit-time checks of the preview keys -> (preview_every, on_preview); (0, None): no previews"""
+    every, call = request.get("preview_every"), request.get("on_preview")
+    if every is not None and (isinstance(every, bool) or not isinstance(every, int) or every < 0):
+        raise ValueError(f"serve: `preview_every` must be an integer >= 1 (absent, None or 0: no previews), got {every!r}")
+    if call is not None and not callable(call):
+        raise ValueError(f"serve: `on_preview` must be a callable f(step, steps, image), got {type(call).__name__}")
+    if not every:
+        return 0, None                                           # (a callback alone is accepted and never called)
+    if not b.previews:
+        raise ValueError("serve: `preview_every` (live previews) is not supported by this batcher: build it with `previews=True` "
+                         "(pipe.serve(..., previews=True))")
+    if call is None:
+        raise ValueError("serve: `preview_every` needs `on_preview`, a callable f(step, steps, image)")
+    return every, call
+
+
 def text_request(b, request):
     """the prompt embeddings -> (negative, positive), [1, S, ctx] each at this batcher's text length"""
     pos, neg = request.get("prompt_embeds"), request.get("negative_prompt_embeds")

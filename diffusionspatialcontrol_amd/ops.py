@@ -1378,3 +1378,7 @@ from .scatter_add import scatter_add_rows, scatter_add_rows_supported, scatter_a
 # the finished image of a served request (dsc_image_finish: the decoder's fp16 NCHW output -> uint8 / float32 NHWC): wrapper beside
 # its kernel's name, like gated_add.py's, reached as ops.image_finish; image_finish_torch restates its arithmetic in torch
 from .image_finish import IMAGE_KINDS, image_finish, image_finish_torch  # noqa: E402,F401
+
+# live previews of running requests (dsc_latent_preview: up to 16 fp16 latent rows -> uint8 RGB thumbnails): wrapper beside its
+# kernel's name, reached as ops.latent_preview; latent_preview_numpy restates its arithmetic in numpy float32, op by op
+from .latent_preview import LATENT_RGB_SD15, PREVIEW_MAX_CHANNELS, PREVIEW_MAX_ROWS, PREVIEW_SCALES, latent_preview, latent_preview_numpy  # noqa: E402,F401

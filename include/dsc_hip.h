@@ -746,6 +746,36 @@ int dsc_scatter_add_rows_f16(void* x, const void* feat, const void* gate, const 
 #define DSC_IMAGE_F32 1
 int dsc_image_finish(const void* img, void* out, int n, int H, int W, int out_kind, void* stream);
 
+/*
+ * Live previews of running requests: up to 16 latent rows become approximate RGB thumbnails in one launch - the preview path of
+ * the continuous batcher (modules/serving/preview_lane.py), which reads the denoised estimate every per-row step entry above
+ * leaves in `old`.  Replaces, per preview, the eager chain index / matmul with a [C, 3] matrix / `/ 2 + 0.5` / clamp / `* 255` /
+ * round / cast / permute / nearest upsample and its blocking copy.
+ * lat: fp16; row rows[j] starts at lat + rows[j] * row_stride halfs and is dense [C, h, w].  rows (n ints) and coef (C * 3 + 3
+ * floats: k[c][rgb] row-major, then bias[rgb]) are HOST arrays, read at the call and passed to the kernel by value, as the step
+ * records are: the caller may reuse both at once.  out: uint8 [n, h * up, w * up, 3], dense; up in {1, 2, 4, 8}, nearest
+ * neighbour (every latent pixel becomes an up x up block).  Per latent pixel and colour, all fp32, every product and every sum
+ * rounded to fp32 on its own (no contraction into an fma):
+ *     v = bias;  for c in 0..C-1:  v = v + k[c] * float(z[c])                  (channel order, left to right)
+ *     y = v * 0.5f + 0.5f;   y = y > 0 ? y : 0;   y = y < 1 ? y : 1            (a NaN compares false: 0)
+ *     byte = (uint8) rintf(y * 255.0f)
+ * - bit for bit what a numpy float32 restatement gives (ops.latent_preview_numpy).  Non-finite inputs are OUTSIDE the contract:
+ * a byte is written for them and nothing else happens.  A row index is not checked against the buffer (its size is not known
+ * here): rows[j] must name a row of lat.
+ * One lane owns 8 consecutive pixels of one output row (24 contiguous bytes, three 8-byte stores) and loads, per channel, the
+ * 8 / up latent pixels under them in one piece of 16, 8, 4 or 2 bytes; the up output rows of a latent row are written by up lanes
+ * that each recompute it.  n <= DSC_PREVIEW_MAX_ROWS (the thumbnail is a grid coordinate), C <= DSC_PREVIEW_MAX_CHANNELS.
+ * No workspace, no LDS, no allocation, no synchronisation, no atomics, every byte written by the one lane that owns it and nothing
+ * behind the last one: deterministic and safe beside captured graphs.
+ * DSC_ERR_BAD_ARG (before any GPU call): null pointer; n / C / h / w < 1; n > 16; C > 8; up not in {1, 2, 4, 8}; a negative row
+ * index.  DSC_ERR_UNSUPPORTED: (w * up) % 8 != 0 (any w runs with up = 8); lat not aligned to, or row_stride no multiple of, the
+ * piece of 8 / up halfs; out not 8-byte aligned; 2^31 pieces of 8 pixels and more per thumbnail.
+ */
+#define DSC_PREVIEW_MAX_ROWS     16
+#define DSC_PREVIEW_MAX_CHANNELS 8
+int dsc_latent_preview(const void* lat, long long row_stride, const int* rows, int n, int C, int h, int w, const float* coef,
+                       int up, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 
     python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
                                 [--hires X] [--ip-adapter [--ip-masks]] [--t2i-adapter] [--controlnet [--control-slots C]]
-                                [--images uint8|pil|np [--decode-batch D]]
+                                [--images uint8|pil|np [--decode-batch D]] [--previews K [--preview-scale S]]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -52,6 +52,12 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
               the decode-lane batcher; images/s and p50 / p95 of `dsc_latency_s` (submit -> resolved) for each; the same four
               legs with each batcher driven by its own thread and mixed step counts (20 / 25 / 30); and the device time of
               one captured decode per lane bucket
+  previews    (--previews K [--preview-scale S, default 8]: this leg only) two batchers on two slots: one built without
+              `previews` (the step of a batcher without the feature) and one built with `previews=True, preview_scale=S`.  8 slots
+              kept full, three alternating rounds of three runs: (a) the plain requests on the flagless batcher, (b) the plain
+              requests on the previews batcher (no slot is ever due: the price of the flag), (c) every request with
+              `preview_every=K` and a no-op callback; images/s and p50 / p95 latency for each, with the previews launched,
+              their rows, the callbacks made and the previews dropped; then (c) with the batcher driven by its own thread
 """
 import argparse
 import json
@@ -188,6 +194,9 @@ def main():
     ap.add_argument("--images", choices=("uint8", "pil", "np"), default=None,
                     help="only the finished-images leg: latent output, this image type inline, this image type on the decode lane")
     ap.add_argument("--decode-batch", type=int, default=2, help="with --images: rows per captured decode of the lane")
+    ap.add_argument("--previews", type=int, default=None, metavar="K",
+                    help="only the previews leg: every request with preview_every = K and a no-op callback")
+    ap.add_argument("--preview-scale", type=int, default=8, help="with --previews: the thumbnails' enlargement (1, 2, 4, 8)")
     a = ap.parse_args()
     if a.ip_masks and not a.ip_adapter:
         ap.error("--ip-masks goes with --ip-adapter")
@@ -200,6 +209,43 @@ def main():
     opt = {"scheduler": "karras"}
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    if a.previews:
+        plain = pipe.serve(512, 512, max_batch=8, slot=0).warm()
+        live = pipe.serve(512, 512, max_batch=8, slot=1, previews=True, preview_scale=a.preview_scale).warm()
+        made = [0]
+
+        def on_preview(step, steps, image):
+            made[0] += 1
+
+        asking = dict(kw25, preview_every=a.previews, on_preview=on_preview)
+        legs = (("a_flagless", plain, kw25), ("b_previews_none_asked", live, kw25), ("c_previews_every_k", live, asking))
+        for _, b, kw in legs:                             # one untimed pass each (allocator, kernel selection, the ring)
+            run_full_latency(b, reqs[:8], kw)
+        before, made[0] = live.stats(), 0
+        runs = []
+        for _ in range(3):                                # alternating, so that a drift of the box hits all alike
+            runs.append({name: run_full_latency(b, reqs, kw) for name, b, kw in legs})
+        after = live.stats()
+        counters = ("previews", "preview_rows", "previews_dropped", "preview_callback_errors")
+        emit(leg="previews", requests=len(reqs), steps=25, preview_every=a.previews, preview_scale=a.preview_scale,
+             **{f"{name}_img_s": [round(r[name][0], 3) for r in runs] for name, _, _ in legs},
+             **{f"{name}_p50_s": [round(r[name][1], 3) for r in runs] for name, _, _ in legs},
+             **{f"{name}_p95_s": [round(r[name][2], 3) for r in runs] for name, _, _ in legs},
+             **{k: after[k] - before[k] for k in counters}, callbacks=made[0], captures_after_warm=after["captures_after_warm"],
+             note="three alternating rounds in one process, each batcher stepped by the caller's thread (run_until_idle); the counters "
+                  "are those of the three timed (c) runs together")
+        run_started_latency(live, reqs[:8], asking)
+        before, made[0] = live.stats(), 0
+        runs = [run_started_latency(live, reqs, asking) for _ in range(3)]
+        after = live.stats()
+        emit(leg="previews_driver_thread", requests=len(reqs), steps=25, preview_every=a.previews, preview_scale=a.preview_scale,
+             c_previews_every_k_img_s=[round(r[0], 3) for r in runs], c_previews_every_k_p50_s=[round(r[1], 3) for r in runs],
+             c_previews_every_k_p95_s=[round(r[2], 3) for r in runs], **{k: after[k] - before[k] for k in counters},
+             callbacks=made[0], captures_after_warm=after["captures_after_warm"],
+             note="the (c) run with the batcher driven by its own thread (start / stop), three runs")
+        emit(leg="stats", flagless=plain.stats(), previews=live.stats())
+        return
 
     if a.images:
         from diffusionspatialcontrol_amd.modules.vae_decoder import AutoencoderKLDecoder
