@@ -167,6 +167,25 @@ __device__ __forceinline__ void rows_write_scalars(float* t_buf, float* sigma_gr
     }
 }
 
+// dsc_cfg_linear_step_rows_cat: the channels a 9-channel inpainting UNet reads beside the latent (reference
+// model_k_diffusion.py:1617-1619), scaled like the latent by the coming step's c_in; zeros for an IDLE slot or one without a row
+template <int T = 256>
+__device__ __forceinline__ void rows_cat_extra(const void* extra, bool idle, float c_in, half_t* xe_u, half_t* xe_c, int e8) {
+    const half_t* ex = idle ? nullptr : static_cast<const half_t*>(extra);      // per slot: uniform per workgroup
+    for (int k = blockIdx.x * T + threadIdx.x; k < e8; k += gridDim.x * T) {
+        h8_t o{};
+        if (ex) {
+            float f[8];
+            unpack8(*reinterpret_cast<const h8_t*>(ex + k * 8), f);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = as_f32(f[j] * c_in);
+            o = pack8(f);
+        }
+        *reinterpret_cast<h8_t*>(xe_u + k * 8) = o;
+        *reinterpret_cast<h8_t*>(xe_c + k * 8) = o;
+    }
+}
+
 // dsc_cfg_dpmpp2m_step_rows: the records ride in the kernel arguments (kernarg segment, read through scalar loads: the slot is
 // blockIdx.y, uniform per workgroup)
 struct RowSteps { dsc_row_step r[DSC_ROW_STEP_MAX_SLOTS]; };
@@ -297,17 +316,22 @@ __global__ __launch_bounds__(256) void step_rows_known_kernel(half_t* x, const h
 // samplers_extra_k_diffusion.py) with their scalars computed on the host (sampling.linear_step_coefficients).  A slot with
 // c_skip = 1, c_out = -sigma and no noise row runs step_rows_kernel's arithmetic (same bits); JOIN / IDLE slots are its lines.
 struct RowLinears { dsc_row_linear r[DSC_ROW_STEP_MAX_SLOTS]; };
+// CAT (dsc_cfg_linear_step_rows_cat): an x_in row is chw + extra_halfs halfs long and ends with the slot's extra channels
+struct RowExtras { dsc_row_extra r[DSC_ROW_STEP_MAX_SLOTS]; };
 
-__global__ __launch_bounds__(256) void linear_rows_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
-                                                          float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
-                                                          int n_dst, int chw, const RowLinears rs) {
+template <bool CAT>
+__device__ __forceinline__ void linear_rows_body(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
+                                                 float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
+                                                 int n_dst, int chw, const RowLinears& rs, int extra_halfs, const RowExtras* es) {
     const int i = blockIdx.y;
     const dsc_row_linear& r = rs.r[i];
     const bool dst = i < n_dst;
     const long long v8 = chw / 8;
     if (dst) rows_copy_temb(r.temb_row, tadd, tadd_halfs, n_dst, i);
-    half_t* xi_u = x_in + (long long)i * chw;
-    half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
+    const long long xs = CAT ? (long long)chw + extra_halfs : chw;         // halfs per x_in row
+    half_t* xi_u = x_in + (long long)i * xs;
+    half_t* xi_c = x_in + (long long)(n_dst + i) * xs;
+    if (CAT && dst) rows_cat_extra(es->r[i].extra, r.mode == DSC_ROW_IDLE, r.c_in_next, xi_u + chw, xi_c + chw, extra_halfs / 8);
     if (r.mode == DSC_ROW_STEP) {
         const float g = r.guidance, a = r.a, b = r.b, c = r.c, c_in_next = r.c_in_next;
         const float c_skip = r.c_skip, c_out = r.c_out, s = r.s;
@@ -349,6 +373,18 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(half_t* x, const half_
     if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
 }
 
+__global__ __launch_bounds__(256) void linear_rows_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
+                                                          float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
+                                                          int n_dst, int chw, const RowLinears rs) {
+    linear_rows_body<false>(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, chw, rs, 0, nullptr);
+}
+__global__ __launch_bounds__(256) void linear_rows_cat_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
+                                                              float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
+                                                              int n_dst, int chw, const RowLinears rs, int extra_halfs,
+                                                              const RowExtras es) {
+    linear_rows_body<true>(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, chw, rs, extra_halfs, &es);
+}
+
 // dsc_cfg_linear_step_rows_rescale: linear_rows_kernel with the guidance rescale of arXiv 2305.08891 sec. 3.4 per slot, applied
 // - as the reference does - to the denoised estimate: D' = K D, K = phi sqrt(SSD(D_c) / SSD(D)) + (1 - phi), the two sums of
 // squared deviations taken over the slot's whole row.  x is updated in place, so a slot with phi > 0 belongs to ONE workgroup
@@ -363,10 +399,11 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(half_t* x, const half_
 #endif
 struct RowRescales { float phi[DSC_ROW_STEP_MAX_SLOTS]; };
 
-template <int T>
-__global__ __launch_bounds__(T) void linear_rows_rescale_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
-                                                                float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
-                                                                int n_dst, int chw, const RowLinears rs, const RowRescales ps) {
+template <int T, bool CAT>
+__device__ __forceinline__ void linear_rows_rescale_body(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
+                                                         float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
+                                                         int n_dst, int chw, const RowLinears& rs, const RowRescales& ps,
+                                                         int extra_halfs, const RowExtras* es) {
     static_assert(T % 64 == 0 && T <= 1024, "whole waves");
     __shared__ double red[T / 64][4];
     const int i = blockIdx.y;
@@ -374,8 +411,11 @@ __global__ __launch_bounds__(T) void linear_rows_rescale_kernel(half_t* x, const
     const bool dst = i < n_dst;
     const long long v8 = chw / 8;
     if (dst) rows_copy_temb<T>(r.temb_row, tadd, tadd_halfs, n_dst, i);
-    half_t* xi_u = x_in + (long long)i * chw;
-    half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
+    const long long xs = CAT ? (long long)chw + extra_halfs : chw;         // halfs per x_in row
+    half_t* xi_u = x_in + (long long)i * xs;
+    half_t* xi_c = x_in + (long long)(n_dst + i) * xs;
+    // (before an owned slot's other workgroups leave: the extra channels stride over the whole grid)
+    if (CAT && dst) rows_cat_extra<T>(es->r[i].extra, r.mode == DSC_ROW_IDLE, r.c_in_next, xi_u + chw, xi_c + chw, extra_halfs / 8);
     if (r.mode == DSC_ROW_STEP) {
         const float phi = ps.phi[i];
         const bool owned = phi > 0.0f;                                      // per slot: uniform per workgroup
@@ -465,6 +505,21 @@ __global__ __launch_bounds__(T) void linear_rows_rescale_kernel(half_t* x, const
         rows_join_or_idle<T>(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
     }
     if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
+}
+
+template <int T>
+__global__ __launch_bounds__(T) void linear_rows_rescale_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
+                                                                float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
+                                                                int n_dst, int chw, const RowLinears rs, const RowRescales ps) {
+    linear_rows_rescale_body<T, false>(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, chw, rs, ps, 0, nullptr);
+}
+template <int T>
+__global__ __launch_bounds__(T) void linear_rows_rescale_cat_kernel(half_t* x, const half_t* eps, half_t* old, int n_src,
+                                                                    half_t* x_in, float* t_buf, float* sigma_groups, half_t* tadd,
+                                                                    int tadd_halfs, int n_dst, int chw, const RowLinears rs,
+                                                                    const RowRescales ps, int extra_halfs, const RowExtras es) {
+    linear_rows_rescale_body<T, true>(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, chw, rs, ps,
+                                      extra_halfs, &es);
 }
 
 int grid_for(long long n8) {
@@ -674,5 +729,58 @@ extern "C" int dsc_cfg_linear_step_rows_rescale(void* x, const void* eps, void* 
     DSC_LAUNCH(linear_rows_rescale_kernel<T>, dim3((unsigned)gx, (unsigned)n_slots), dim3(T), 0, static_cast<hipStream_t>(stream),
                static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
                static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs, ps);
+    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+}
+
+extern "C" int dsc_cfg_linear_step_rows_cat(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
+                                            float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
+                                            const dsc_row_linear* rows, const float* rescale, const dsc_row_extra* extras,
+                                            int extra_halfs, int n_slots, int chw, int dtype, void* stream) {
+    if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || !extras || n_src < 0 || n_dst <= 0 || chw <= 0)
+        return DSC_ERR_BAD_ARG;
+    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
+    if (extra_halfs <= 0 || extra_halfs % 8 != 0 || chw % 8 != 0) return DSC_ERR_BAD_ARG;     // 16-byte rows of chw + extra_halfs
+    if (dtype != DSC_F16 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
+    RowLinears rs{};
+    RowRescales ps{};
+    RowExtras es{};
+    bool any_row = false, any_phi = false;
+    for (int i = 0; i < n_slots; ++i) {
+        const dsc_row_linear& r = rows[i];
+        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
+        if (r.mode == DSC_ROW_STEP) {
+            if (r.noise && !al16(r.noise)) return DSC_ERR_UNSUPPORTED;
+            if (rescale) {
+                if (!(rescale[i] >= 0.0f && rescale[i] <= 1.0f)) return DSC_ERR_BAD_ARG;      // (NaN lands here too)
+                ps.phi[i] = rescale[i];
+                any_phi |= rescale[i] > 0.0f;
+            }
+        }
+        if (extras[i].extra && !al16(extras[i].extra)) return DSC_ERR_BAD_ARG;
+        rs.r[i] = r;
+        es.r[i] = extras[i];
+    }
+    if (any_row) {
+        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
+        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
+    }
+    // the grids of the two entries this one shares its arithmetic with (the extra channels stride over the same grid)
+    const long long v8 = chw / 8;
+    if (!any_phi) {
+        long long gx = (v8 + 255) / 256;
+        gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
+        DSC_LAUNCH(linear_rows_cat_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
+                   static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
+                   static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs,
+                   extra_halfs, es);
+    } else {
+        constexpr int T = DSC_RESCALE_THREADS;
+        long long gx = (v8 + T - 1) / T;
+        gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
+        DSC_LAUNCH(linear_rows_rescale_cat_kernel<T>, dim3((unsigned)gx, (unsigned)n_slots), dim3(T), 0,
+                   static_cast<hipStream_t>(stream), static_cast<half_t*>(x), static_cast<const half_t*>(eps),
+                   static_cast<half_t*>(old), n_src, static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd),
+                   tadd_halfs, n_dst, chw, rs, ps, extra_halfs, es);
+    }
     return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }

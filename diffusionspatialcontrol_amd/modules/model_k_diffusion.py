@@ -559,7 +559,7 @@ class StableDiffusionPipeline:
     def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77,
               ip_masks: bool = False, t2i_adapter: bool = False, controlnet: bool = False, control_slots=None,
               decode: bool = False, decode_batch: int = 2, previews: bool = False, preview_scale: int = 8, preview_coef=None,
-              preview_ring: int = 8):
+              preview_ring: int = 8, inpaint_unet: bool = False):
         """Continuous-batching server (modules/serving/): requests join a running batch at any step boundary, each at its own
         point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
         stats / warm).  `ip_masks=True` (IP-Adapters loaded): requests may carry the reference's
@@ -577,16 +577,22 @@ class StableDiffusionPipeline:
         latent's sides; `preview_scale` in {1, 2, 4, 8} with a thumbnail width that is a multiple of 8; `preview_coef`: C * 3 + 3
         numbers, the latent-to-RGB matrix k[c][rgb] then a bias, default ops.LATENT_RGB_SD15) made by one launch beside the step
         and copied out on a second stream through a ring of `preview_ring` pinned buffers; a preview that finds the ring full
-        is dropped, never waited for."""
+        is dropped, never waited for.  `inpaint_unet=True` (a 9-channel inpainting UNet; not together with `controlnet` /
+        `t2i_adapter`): every request is an inpainting request (`image`, `mask_image`, optional `masked_image_latents` /
+        `strength`) with any served sampler, v-prediction and `guidance_rescale`; every step writes the request's mask and
+        masked-image latents behind its latent row (dsc_cfg_linear_step_rows_cat)."""
         from .serving import ServingBatcher
         kw = dict(previews=True, preview_scale=preview_scale, preview_coef=preview_coef, preview_ring=preview_ring) if previews else {}
+        if inpaint_unet:                         # (a batcher built without the flag is constructed exactly as before)
+            kw["inpaint_unet"] = True
         return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len,
                               ip_masks=ip_masks, t2i_adapter=t2i_adapter, controlnet=controlnet, control_slots=control_slots,
                               decode=decode, decode_batch=decode_batch, **kw)
 
     def serve_hires(self, height: int = 512, width: int = 512, upscale_x: float = 1.25, max_batch: int = 8, buckets=(1, 2, 4, 8),
                     text_len: int = 77, slots=(0, 1), ip_masks: bool = False, decode: bool = False, decode_batch: int = 2,
-                    previews: bool = False, preview_scale: int = 8, preview_coef=None, preview_ring: int = 8):
+                    previews: bool = False, preview_scale: int = 8, preview_coef=None, preview_ring: int = 8,
+                    inpaint_unet: bool = False):
         """Continuous-batching server for requests with a hires pass (reference :1176-1228): a batcher at `height` x `width`
         chained to one at the target size of `upscale_x` (_hires_pass's expression), on two workspace slots.  A request with
         `upscale=True` runs its first pass on the one, is enlarged and re-noised on the device (dsc_latent_resample_noise) and
@@ -598,6 +604,9 @@ class StableDiffusionPipeline:
         steps, and the second pass previews at its own size."""
         from .latent_resample import hires_target_size
         from .serving import HiresPair, ServingBatcher
+        if inpaint_unet:
+            raise ValueError("serve_hires: `inpaint_unet=True` is not served (inpaiting refuses the hires pass too); build the "
+                             "batcher with pipe.serve(..., inpaint_unet=True)")
         th, tw = hires_target_size(height, width, upscale_x, self.vae_scale_factor)
         if th < height or tw < width:
             raise ValueError(f"serve_hires: upscale_x {upscale_x} shrinks {height}x{width} to {th}x{tw}; only enlarging is served "
@@ -942,10 +951,12 @@ class StableDiffusionPipeline:
                   cross_attention_kwargs=None, clip_skip=None, long_encode=0, num_images_per_prompt=1,
                   ip_adapter_image_embeds=None,
                   prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
-                  text_input_ids=None, **unsupported):
+                  text_input_ids=None, fused: Optional[bool] = None, step_noise: Optional[torch.Tensor] = None, **unsupported):
         """reference :1365-1760 (method name as spelled there).  4-channel UNet: the known region `image_latents + sigma * noise` is
         re-imposed on the model input before every model call after the first (:1599-1612).  9-channel UNet (the inpainting
-        checkpoints): mask and masked-image latents are concatenated to the duplicated latent (:1617-1619) - eager protocol mode."""
+        checkpoints): mask and masked-image latents are concatenated to the duplicated latent (:1617-1619) - eager protocol mode,
+        or with fused=True the captured 9-channel step and one dsc_cfg_linear_step_rows_cat launch per step (_denoise_fused with
+        `extra`: every sampler of sampling.LINEAR_FAMILY, v-prediction, guidance_rescale; step_noise as in img2img)."""
         if upscale or padding_mask_crop is not None:
             raise NotImplementedError("hires upscale after inpainting and mask cropping are outside the denoising hot path "
                                       "built here")
@@ -1019,10 +1030,26 @@ class StableDiffusionPipeline:
         control_hook = self._merge_hooks(control_hook, self._adapter_hook(
             image_t2i_adapter, adapter_conditioning_scale, adapter_conditioning_factor, width, height, len(sigmas),
             num_images_per_prompt))                                                                         # :1588-1591
-        latents = self._denoise_protocol(sampler, latents, sigmas, text, region_state, weight_func, guidance_scale,
-                                         guidance_rescale, n_img, cross_attention_kwargs, eta, num_inference_steps,
-                                         sampler_opt, seed, start_time, timeout, input_hook=keep_known_region,
-                                         control_hook=control_hook, extra_input=extra_input, preview=preview)
+        if fused:
+            if num_channels_unet != 9:
+                raise NotImplementedError("inpaiting(fused=True) runs the 9-channel inpainting UNets; the known-region blend of a "
+                                          "4-channel UNet has no fused loop: run it with fused=False")
+            if control_hook is not None or preview is not None:
+                raise NotImplementedError("ControlNet / T2I-Adapter / latent previews run in protocol mode (fused=False)")
+            if latents.shape[-2] * latents.shape[-1] % 8 != 0:
+                raise NotImplementedError(f"inpaiting(fused=True): the 9-channel input row must stay 16-byte aligned, which needs a "
+                                          f"latent of h * w % 8 == 0, got {list(latents.shape[-2:])}; run it with fused=False")
+            latents = self._denoise_fused(latents, sigmas, text, region_state, weight_func, guidance_scale, n_img,
+                                          cross_attention_kwargs, start_time, timeout, sampler=sampler,
+                                          sampler_args=self._fused_sampler_args(sampler, sigmas, eta, num_inference_steps,
+                                                                                sampler_opt, latents, seed, step_noise),
+                                          step_noise=step_noise, guidance_rescale=guidance_rescale,
+                                          extra=torch.cat([mask, mil], dim=1))
+        else:
+            latents = self._denoise_protocol(sampler, latents, sigmas, text, region_state, weight_func, guidance_scale,
+                                             guidance_rescale, n_img, cross_attention_kwargs, eta, num_inference_steps,
+                                             sampler_opt, seed, start_time, timeout, input_hook=keep_known_region,
+                                             control_hook=control_hook, extra_input=extra_input, preview=preview)
         if latent_processing == 1:                               # :1759-1760
             return latents_process
         return [self.latent_to_image(latents, output_type)]
@@ -1412,9 +1439,11 @@ class StableDiffusionPipeline:
                              f"got {tuple(noise.shape) if torch.is_tensor(noise) else type(noise).__name__}")
         return noise.to(device=x.device, dtype=x.dtype).contiguous()
 
-    def _linear_fused_loop(self, st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout, rescale=0.0):
+    def _linear_fused_loop(self, st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout, rescale=0.0,
+                           extras=None):
         """the fused loop's steps through the per-row kernel: one record per image, all on the same step of the same schedule;
-        rescale > 0: every record carries it (ops.cfg_linear_step_rows then issues the rescale launch)"""
+        rescale > 0: every record carries it (ops.cfg_linear_step_rows then issues the rescale launch); extras: the images' extra
+        input channels of a 9-channel UNet (ops.cfg_linear_step_rows_cat writes them behind each latent row)"""
         kdm = self.k_diffusion_model
         for i, (a, b, c, s) in enumerate(coeffs):
             if start_time > 0 and timeout > 0:
@@ -1429,17 +1458,25 @@ class StableDiffusionPipeline:
                 rec["rescale"] = rescale
             recs = [dict(rec, noise=None if noise is None or s == 0.0 else noise[i, j if noise.shape[1] > 1 else 0])
                     for j in range(n_img)]
-            ops.cfg_linear_step_rows(x, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, tadd=st["tadd"])
+            if extras is not None:
+                ops.cfg_linear_step_rows_cat(x, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, extras,
+                                             tadd=st["tadd"])
+            else:
+                ops.cfg_linear_step_rows(x, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, tadd=st["tadd"])
 
     def _denoise_fused(self, latents, sigmas, text, region_state, weight_func, guidance_scale, n_img,
                        cross_attention_kwargs, start_time, timeout, slot=0, sampler=None, sampler_args=None, step_noise=None,
-                       guidance_rescale=0.0):
+                       guidance_rescale=0.0, extra=None):
         """sampler: None (DPM++ 2M) or one of sampling.LINEAR_FAMILY's functions.  DPM++ 2M on an eps-prediction model is one
         dsc_cfg_dpmpp2m_step per step; every other member, and every v-prediction model, one dsc_cfg_linear_step_rows with a
         record per image.  step_noise: the noise table [steps, 1 or n_img, c, h, w] (default: sampling.step_noise_table).
         guidance_rescale (phi, arXiv 2305.08891 sec. 3.4) > 0: every family member, DPM++ 2M on an eps model included, takes the
         per-row path and its records carry phi - the statistics of rescale_noise_cfg are taken inside the sampler launch
-        (dsc_cfg_linear_step_rows_rescale), on the denoised estimate as protocol mode's model_fn does."""
+        (dsc_cfg_linear_step_rows_rescale), on the denoised estimate as protocol mode's model_fn does.
+        extra: fp16 [n_img, c, h, w], the step-invariant channels a UNet with in_channels = 4 + c reads beside the latent (the
+        9-channel inpainting checkpoints, reference :1617-1619).  The static step's x_in then has 4 + c channels, every sampler
+        takes the per-row path (DPM++ 2M on an eps model too: its records are that sampler's bits) and every launch, the first
+        input's JOIN records included, is dsc_cfg_linear_step_rows_cat, which scales the extra channels by the coming c_in."""
         guidance_rescale = float(guidance_rescale)
         if not 0.0 <= guidance_rescale <= 1.0:
             raise ValueError(f"fused=True: guidance_rescale must be in [0, 1], got {guidance_rescale}")
@@ -1447,7 +1484,7 @@ class StableDiffusionPipeline:
         if family is None:
             raise NotImplementedError(f"fused=True: sampler {getattr(sampler, '__name__', sampler)!r} has no fused step "
                                       f"(supported: {', '.join(sampling.LINEAR_FAMILY)}); run it with fused=False")
-        rows_path = family != "dpmpp_2m" or self.v_prediction or guidance_rescale > 0.0
+        rows_path = family != "dpmpp_2m" or self.v_prediction or guidance_rescale > 0.0 or extra is not None
         if rows_path and n_img > ops.ROW_STEP_MAX_SLOTS:
             raise NotImplementedError(f"fused=True: the per-row sampler step takes at most {ops.ROW_STEP_MAX_SLOTS} images per "
                                       f"batch, got {n_img}; run it with fused=False")
@@ -1489,13 +1526,22 @@ class StableDiffusionPipeline:
         # a callable that behaves as the default `w * sigma * qk.std()` (app.py:1004 builds a fresh lambda per request) runs
         # the fused kernels whatever object it is; any other callable is baked into the captured step, so the key is the
         # OBJECT (two closures of one code object may capture different values) and the step keeps it alive
-        key = (("slot", slot), n_img, tuple(latents.shape), levels, tuple(text.shape), text.dtype,
+        in_shape = tuple(latents.shape)                              # of the static step's x_in (per CFG half)
+        extras = None
+        if extra is not None:
+            if tuple(extra.shape[2:]) != in_shape[2:] or extra.shape[0] != n_img or extra[0].numel() % 8 != 0:
+                raise ValueError(f"fused=True: extra input channels {tuple(extra.shape)} do not fit latents {in_shape} "
+                                 "(one row of a multiple of 8 halfs per image)")
+            extra = extra.to(device=latents.device, dtype=latents.dtype).contiguous()
+            extras = [extra[j] for j in range(n_img)]
+            in_shape = (n_img, in_shape[1] + extra.shape[1]) + in_shape[2:]
+        key = (("slot", slot), n_img, in_shape, levels, tuple(text.shape), text.dtype,
                self._weight_func_key(weight_func), ip_key)
         if latents.is_cuda:
             # generation slots: each keeps its own static buffers, captured step, packed K/V and library-GEMM workspace, so
             # two generations can be in flight on two streams (one host thread per slot)
             _lib.check(_lib.load_library().dsc_set_workspace_slot(slot), "dsc_set_workspace_slot")
-        st = self._static_step(key, n_img, tuple(latents.shape), text, region_state, weight_func, cross_attention_kwargs)
+        st = self._static_step(key, n_img, in_shape, text, region_state, weight_func, cross_attention_kwargs)
         x = latents.contiguous().clone()
         old = torch.zeros_like(x)
         if prof:
@@ -1511,7 +1557,12 @@ class StableDiffusionPipeline:
                 st["temb_tab"] = self.unet.temb_add_table(torch.tensor(ts, dtype=torch.float32, device=x.device))
                 st["temb_key"] = tkey
             tab = st["temb_tab"]
-        ops.prepare_unet_input(x, c_in, t, sig[0], st["x_in"], st["t"], st["sigma"], row=None if tab is None else (tab[0], st["tadd"]))
+        if extras is not None:
+            # the first model input: JOIN records (dsc_prepare_unet_input's line per row, plus the extra channels), no source bucket
+            join = {"mode": ops.ROW_JOIN, "c_in_next": c_in, "t_next": t, "sigma_next": sig[0], "temb_row": None if tab is None else tab[0]}
+            ops.cfg_linear_step_rows_cat(x, None, old, 0, st["x_in"], st["t"], st["sigma_rows"], [join] * n_img, extras, tadd=st["tadd"])
+        else:
+            ops.prepare_unet_input(x, c_in, t, sig[0], st["x_in"], st["t"], st["sigma"], row=None if tab is None else (tab[0], st["tadd"]))
         if rows_path:
             noise = None
             if any(c4[3] != 0.0 for c4 in coeffs):
@@ -1519,7 +1570,7 @@ class StableDiffusionPipeline:
                     sampling.step_noise_table(family, x, sigmas, eta=sargs.get("eta", 1.0), noise_sampler=noise_sampler)
                 noise = self._check_step_noise(noise, len(coeffs), x)
             self._linear_fused_loop(st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout,
-                                    rescale=guidance_rescale)
+                                    rescale=guidance_rescale, extras=extras)
             coeffs = []
         for i, (a, b, c) in enumerate(coeffs):
             if start_time > 0 and timeout > 0:

@@ -41,7 +41,7 @@ from .. import sampling
 from ..encode_region_map_function import encode_region_map
 from . import requests
 from .executor import _GraphExecutor, step_launch
-from .requests import MAX_TEXT_KEYS, _Request, _ip_layers
+from .requests import MAX_TEXT_KEYS, _InpaintRequest, _Request, _ip_layers
 
 
 def _conv_out_hw(conv, h, w):
@@ -55,7 +55,7 @@ class ServingBatcher:
 
     def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
                  t2i_adapter=False, controlnet=False, control_slots=None, decode=False, decode_batch=2, previews=False,
-                 preview_scale=8, preview_coef=None, preview_ring=8):
+                 preview_scale=8, preview_coef=None, preview_ring=8, inpaint_unet=False):
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
             raise ValueError(f"serve: buckets {buckets} must cover max_batch={max_batch}")
@@ -78,6 +78,11 @@ class ServingBatcher:
                                           linear_transitions=0, handoffs=0, adapter_gate_updates=0, control_steps=0,
                                           control_gate_updates=0)
         self._hires = None                     # the chained batcher of the hires pass (chain_hires)
+        # a 9-channel inpainting UNet: every request is an inpainting request, and every transition writes each member's mask and
+        # masked-image latents behind its latent row (dsc_cfg_linear_step_rows_cat; package docstring)
+        self.inpaint = bool(inpaint_unet)
+        if self.inpaint:
+            self._inpaint_setup(controlnet, t2i_adapter)
         # requests may ask for images ("pil" / "np" / "uint8"): a decode lane beside the step finishes them (decode_lane.py)
         self.decode = bool(decode)
         self.decode_batch = 0
@@ -129,11 +134,26 @@ class ServingBatcher:
         self._cstate = {}                      # bucket -> (dst, gather, gates) last uploaded for it (absent: as captured)
         self.exec = executor if executor is not None else _GraphExecutor(self)
 
+    def _inpaint_setup(self, controlnet, t2i_adapter):
+        """`inpaint_unet=True` against the UNet and this batcher's size, at construction"""
+        c = int(self.pipe.unet.config.in_channels)
+        if c != 9:
+            raise ValueError(f"serve: `inpaint_unet=True` serves the 9-channel inpainting UNets ([latents | mask | masked-image "
+                             f"latents]); this pipeline's UNet has in_channels = {c}")
+        if controlnet or t2i_adapter:
+            raise ValueError("serve: `inpaint_unet=True` and `controlnet=True` / `t2i_adapter=True` are not served together yet")
+        h, w = self.height // 8, self.width // 8
+        if (h * w) % 8 != 0:
+            raise ValueError(f"serve: `inpaint_unet=True`: this batcher's {h}x{w} latent has h * w % 8 != 0; the 9-channel input "
+                             "row (4 + 5 maps of h * w halfs) must stay 16-byte aligned (use inpaiting)")
+        self._stats["cat_transitions"] = 0
+
     def _preview_setup(self, scale, coef, ring):
         """the preview arguments against this batcher's latent, at construction"""
         from ...latent_preview import preview_coef
         from .preview_lane import preview_scales_for
-        C, w = int(self.pipe.unet.config.in_channels), self.width // 8
+        # (the latent a preview reads has 4 channels whatever else an inpainting UNet's input carries)
+        C, w = 4 if self.inpaint else int(self.pipe.unet.config.in_channels), self.width // 8
         if self.max_batch > ops.PREVIEW_MAX_ROWS or C > ops.PREVIEW_MAX_CHANNELS:
             raise ValueError(f"serve: `previews=True` takes at most {ops.PREVIEW_MAX_ROWS} slots and {ops.PREVIEW_MAX_CHANNELS} latent "
                              f"channels (dsc_latent_preview), got max_batch = {self.max_batch}, {C} channels")
@@ -261,6 +281,8 @@ class ServingBatcher:
         (executor.py); `hi` keeps serving ordinary requests of its size.  Returns self."""
         if not isinstance(hi, ServingBatcher):
             raise TypeError("serve: chain_hires takes the ServingBatcher of the hires pass")
+        if self.inpaint or hi.inpaint:
+            raise ValueError("serve: a batcher built with `inpaint_unet=True` is not chained (inpaiting refuses the hires pass too)")
         if hi is self:
             raise ValueError("serve: a batcher cannot be chained to itself (the hires pass runs at another image size)")
         if hi.slot == self.slot:
@@ -298,7 +320,10 @@ class ServingBatcher:
         `controlnet=True`: `control_img` (a PIL image or a [1, 3, H, W] tensor in [0, 1]; a list with one per net when
         pipe.controlnet is a MultiControlNetModel), `controlnet_conditioning_scale` (default 1.0), `control_guidance_start` (0.0)
         and `control_guidance_end` (1.0) (numbers, or lists with one entry per net) - the pipeline methods' own keys; not with
-        `upscale` or `mask_image`.  On a batcher built with `previews=True`: `preview_every` (an int k >= 1; absent, None or 0: no
+        `upscale` or `mask_image`.  On a batcher built with `inpaint_unet=True` every request carries `image` (pixels, which needs
+        a VAE encoder, or [1, 4, h, w] latents together with `masked_image_latents` [1, 4, h, w]) and `mask_image`, optionally
+        `strength`; `sampler_name`, v-prediction and `guidance_rescale` combine with them.
+        On a batcher built with `previews=True`: `preview_every` (an int k >= 1; absent, None or 0: no
         previews) and `on_preview` (a callable f(step, steps, image)): after every k-th of the request's steps but the last, f
         receives the count of steps applied, the steps of this pass and an np.uint8 [h * scale, w * scale, 3] thumbnail of the
         denoised estimate (preview_lane.py); f runs on the thread that steps the batcher.  Returns a Future of the final output."""
@@ -381,9 +406,10 @@ class ServingBatcher:
         steps = int(request.get("num_inference_steps", 25))
         if steps < 1:
             raise ValueError("serve: num_inference_steps must be >= 1")
-        r = _Request(req=request, future=concurrent.futures.Future(), steps=steps, second=second, ip_embeds=ip_embeds,
-                     ip_scale=ip_scale, ip_weights=ip_weights, adapter=adapter, control=control, guidance=g, output_type=out_type,
-                     family=family, rescale=phi, eta=float(request.get("eta", 1.0)), text=text)
+        record = _InpaintRequest if self.inpaint else _Request           # (the former: one more field, `extra`)
+        r = record(req=request, future=concurrent.futures.Future(), steps=steps, second=second, ip_embeds=ip_embeds,
+                   ip_scale=ip_scale, ip_weights=ip_weights, adapter=adapter, control=control, guidance=g, output_type=out_type,
+                   family=family, rescale=phi, eta=float(request.get("eta", 1.0)), text=text)
         t_start = requests.image_request(self, r)
         dev, dt = self.exec.device, self.exec.dtype
         r.sig_dev = pipe._schedule(r.steps, request.get("sampler_opt") or {}, dev, dt)      # txt2img's schedule, fp16-rounded
@@ -586,7 +612,10 @@ class ServingBatcher:
         nd = n_dst if n_dst is not None else self.buckets[0]
         recs, known = self._records(max(n_src, nd), stepping, joins, leaving)
         self._load_joins(n_dst, joins)
-        self._transition(n_src, nd, recs, known)
+        if self.inpaint:
+            self._transition_cat(n_src, nd, recs)
+        else:
+            self._transition(n_src, nd, recs, known)
         if self.previews:
             self._preview(stepping, leaving)         # reads `old` of the step just applied, before the next transition
         self._leave(leaving)
@@ -685,6 +714,13 @@ class ServingBatcher:
         if kind == "linear":                         # a slot steps another sampler / a v-prediction model / with a rescale
             self._stats["linear_transitions"] += 1
 
+    def _transition_cat(self, n_src, n_dst, recs):
+        """the ONE launch of a step on a batcher built with `inpaint_unet=True`: always dsc_cfg_linear_step_rows_cat, with one
+        entry of extra input channels per slot - a member's row (its mask and masked-image latents), None for an idle slot"""
+        extras = [None if rec["req"] is None else rec["req"].extra for rec in recs]
+        self.exec.transition(n_src, n_dst, recs, extras=extras)
+        self._stats["cat_transitions"] += 1
+
     def _preview(self, stepping, leaving):
         """the slots whose request is due a preview after the step just applied (every preview_every-th of its steps, never its
         last) go to ONE launch; with no free ring entry it is skipped and counted - the step does not wait"""
@@ -728,6 +764,8 @@ class ServingBatcher:
                 self._done.append((r, self.exec.finish(r)))
             r.hnoise = None                          # (a second-pass record: its start noise was read before it joined)
             r.known = None                           # its image / noise / mask rows go back to the allocator (stream-ordered)
+            if self.inpaint:
+                r.extra = None                       # ... and its mask + masked-image latents row (inpaint_unet)
             r.noise = None                           # ... and its noise table
             r.adapter_feats = None                   # ... and its adapter features
             if r.lane is not None:                   # ... and its ControlNet lane goes to whoever waits for one

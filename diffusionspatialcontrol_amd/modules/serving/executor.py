@@ -51,17 +51,23 @@ from .decode_lane import _DecodeLane, _LaneHandle
 from .preview_lane import _PreviewLane
 
 _EMBED_LOCK = threading.Lock()       # around the process-wide deterministic switch in _GraphExecutor._control_embedding
-_STEP_ROWS = {"rows": "cfg_dpmpp2m_step_rows", "linear": "cfg_linear_step_rows", "known": "cfg_dpmpp2m_step_rows_known"}     # in ops
+_STEP_ROWS = {"rows": "cfg_dpmpp2m_step_rows", "linear": "cfg_linear_step_rows", "known": "cfg_dpmpp2m_step_rows_known",
+              "cat": "cfg_linear_step_rows_cat"}     # in ops
 
 
-def step_launch(recs, known=None):
+def step_launch(recs, known=None, extras=None):
     """which ONE launch of the per-row sampler step serves a transition with these records:
+    "cat"    - the batcher serves a 9-channel inpainting UNet (`extras` is a list, one entry per slot - every transition of a
+               batcher built with `inpaint_unet=True`): dsc_cfg_linear_step_rows_cat, which carries every sampler, both
+               parameterisations and the rescale, and writes the extra input channels behind each latent row;
     "known"  - an inpainting slot steps (some entry of `known` is a record): dsc_cfg_dpmpp2m_step_rows_known;
     "linear" - a slot steps another sampler, a v-prediction model or with a guidance rescale (a STEP record carries c_skip /
                c_out): dsc_cfg_linear_step_rows, whose wrapper picks the rescale entry from the records (records without
                c_skip / c_out are DPM++ 2M's: same bits);
     "rows"   - every stepping slot is DPM++ 2M on an eps-prediction model (and IDLE / JOIN-only transitions):
                dsc_cfg_dpmpp2m_step_rows."""
+    if extras is not None:
+        return "cat"
     if known is not None and any(k is not None for k in known):
         return "known"
     if any(rec["mode"] == ops.ROW_STEP and "c_skip" in rec for rec in recs):
@@ -123,7 +129,10 @@ class _GraphExecutor:
             raise NotImplementedError("serve: every cross-attention head dim must run the prepared-operand kernels "
                                       "(d % 8 == 0, d <= 160)")
         c = unet.config.in_channels
-        self.lat_shape = (c, batcher.height // 8, batcher.width // 8)
+        # lat_shape: a request's latent (x / old, noise, outputs); in_shape: a row of the bucket's model input - the same, but
+        # [latents | mask | masked-image latents] on a batcher built with `inpaint_unet=True` (reference :1617-1619)
+        self.in_shape = (c, batcher.height // 8, batcher.width // 8)
+        self.lat_shape = (4,) + self.in_shape[1:] if getattr(batcher, "inpaint", False) else self.in_shape
         self.ctx = unet.config.cross_attention_dim
         self.tw = unet.temb_width()
         mb = max(batcher.max_batch, batcher.buckets[-1])
@@ -370,7 +379,9 @@ class _GraphExecutor:
         latents_in = torch.is_tensor(image) and image.shape[1] == 4
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(self.stream):
-            if r.kind == "img2img":
+            if r.kind == "inpaint_unet":
+                self._prepare_inpaint_unet(r, image, latents_in)
+            elif r.kind == "img2img":
                 lat = image if latents_in else pipe._encode_vae_image(pipe._image_tensor(image, H, W), gen)     # :600-606
                 lat = lat.to(dev, dtype=dt)
                 noise = req.get("latents")
@@ -392,6 +403,28 @@ class _GraphExecutor:
                 raise ValueError(f"serve: start latent {tuple(r.lat.shape)}, this batcher needs {(1,) + self.lat_shape}")
             r.lat = r.lat.to(dt)
             self._tables_and_text(r)
+
+    def _prepare_inpaint_unet(self, r, image, latents_in):
+        """a request of a batcher built with `inpaint_unet=True`, as `inpaiting` prepares it for a 9-channel UNet and in its order
+        (start latent, mask, masked-image latents): r.lat, and r.extra - the fp16 [5, h, w] row cat([nearest-downsampled mask,
+        masked_image_latents]) (reference :1253-1290) the sampler launch scales and writes behind the latent, built once, on
+        this stream, and held until the request leaves"""
+        pipe, dev, dt = self.pipe, self.device, self.dtype
+        req, H, W = r.req, self.b.height, self.b.width
+        gen = req.get("generator")
+        init = image.float() if latents_in else pipe._image_tensor(image, H, W)
+        r.lat = pipe.prepare_latents_inpating(1, 4, H, W, dt, dev, gen, req.get("latents"), image=init, sigma=r.sig_dev[0],
+                                              is_strength_max=r.strength == 1.0, return_noise=True,
+                                              return_image_latents=True)[0]                              # :1459-1478
+        mask = pipe._image_tensor(req["mask_image"], H, W, mask=True)
+        mil = req.get("masked_image_latents")
+        if mil is None:
+            mil = pipe._encode_vae_image(init * (mask < 0.5), gen)
+        mil = mil.to(device=dev, dtype=dt)
+        mask = torch.nn.functional.interpolate(mask, size=self.lat_shape[1:]).to(device=dev, dtype=dt)    # :1253-1257
+        if tuple(mil.shape) != (1,) + self.lat_shape:
+            raise ValueError(f"serve: masked-image latents {tuple(mil.shape)}, this batcher needs {(1,) + self.lat_shape}")
+        r.extra = torch.cat([mask[0], mil[0]], dim=0).contiguous()
 
     def prepare_noise(self, r, eta):
         """the request's noise table on the device, [steps, 1, c, h, w]: `step_noise`, or the draws its sampler would make"""
@@ -529,7 +562,7 @@ class _GraphExecutor:
         rows = 2 * n
         S = self.b.text_len
         with torch.cuda.stream(self.stream):
-            st = {"x_in": torch.zeros((rows,) + self.lat_shape, device=dev, dtype=dt),
+            st = {"x_in": torch.zeros((rows,) + self.in_shape, device=dev, dtype=dt),
                   "t": torch.zeros(rows, device=dev, dtype=torch.float32),
                   "sigma": torch.ones(n, device=dev, dtype=torch.float32),
                   "text": torch.zeros((rows, S, self.ctx), device=dev, dtype=dt),
@@ -656,16 +689,18 @@ class _GraphExecutor:
                 raise RuntimeError("serve: the admitted requests' tables do not compress (admission check bypassed)")
             self.pipe._upload_tables(st, comp, dense)
 
-    def transition(self, n_src, n_dst, recs, known=None):
+    def transition(self, n_src, n_dst, recs, known=None, extras=None):
         """ONE launch of the per-row sampler step - the one step_launch names for these records - takes the eps of bucket
-        n_src and writes bucket n_dst's input; `known`: per slot the known-region record of an inpainting slot that steps"""
-        kind = step_launch(recs, known)
+        n_src and writes bucket n_dst's input; `known`: per slot the known-region record of an inpainting slot that steps;
+        `extras` (a batcher built with `inpaint_unet=True`): per slot the member's extra input channels, None for an idle slot"""
+        kind = step_launch(recs, known, extras)
         st_d = self.st.get(n_dst)
         if st_d is None:
             self.ensure(n_dst)
             st_d = self.st[n_dst]
         eps = self.st[n_src]["eps"] if n_src else None
-        args = (self.x, eps, self.old, n_src, st_d["x_in"], st_d["t"], st_d["sigma"], recs) + ((known,) if kind == "known" else ())
+        args = (self.x, eps, self.old, n_src, st_d["x_in"], st_d["t"], st_d["sigma"], recs) + \
+            ((known,) if kind == "known" else (extras,) if kind == "cat" else ())
         with torch.cuda.stream(self.stream):
             getattr(ops, _STEP_ROWS[kind])(*args, tadd=st_d["tadd"])
 

@@ -7,6 +7,14 @@ UNet: its image latents, noise and mask rows stay on the device while it runs, a
 the model input of every model call after its first (dsc_cfg_dpmpp2m_step_rows_known, what `inpaiting`'s eager hook does per
 call).  That launch replaces the plain one only for transitions in which an inpainting slot steps.
 
+9-channel inpainting UNets.  A batcher built with `inpaint_unet=True` serves the inpainting checkpoints, whose UNet reads
+`[latents | mask | masked-image latents]` (reference model_k_diffusion.py:1617-1619): every request of it carries `image` and
+`mask_image` (kind "inpaint_unet"), as pixels or as [1, 4, h, w] latents with `masked_image_latents`.  It has no known region to
+blend: admission builds `r.extra`, the request's fp16 [5, h, w] row cat([mask, masked-image latents]), and every transition is ONE
+dsc_cfg_linear_step_rows_cat launch that writes each member's row, times the coming c_in, behind its latent.  That launch carries
+the whole linear family, both parameterisations and the rescale, so the two refusals of `mask_image` above apply to 4-channel
+batchers only.
+
 Region masks of image prompts.  A batcher built with `ip_masks=True` takes the reference's
 `cross_attention_kwargs={"ip_adapter_masks": [n_adapters, 1, Hm, Wm]}` (app.py:1077-1091; both IP-Adapter processors multiply the
 adapter's output by the down-sampled mask, attention_modify.py:371-385 / :676-685).  After down-sampling a mask is one number per
@@ -44,11 +52,18 @@ class _Request:
                  "second": False, "adapter_limit": 0}
 
     def __init__(self, **given):
-        unknown = set(given) - set(self.__slots__)
+        fields = [name for cls in type(self).__mro__ for name in getattr(cls, "__slots__", ())]
+        unknown = set(given) - set(fields)
         if unknown:
             raise TypeError(f"_Request has no field {sorted(unknown)}")
-        for name in self.__slots__:
+        for name in fields:
             setattr(self, name, given.get(name, self._DEFAULTS.get(name)))
+
+
+class _InpaintRequest(_Request):
+    """a request of a batcher built with `inpaint_unet=True`: the record plus `extra`, its fp16 [5, h, w] row
+    cat([nearest-downsampled mask, masked-image latents]) on the device from admission until it leaves"""
+    __slots__ = ("extra",)
 
 
 # ---------------------------------------------------------------------- one copy of each small check
@@ -149,12 +164,13 @@ def common_request(b, request):
     if family is None:
         raise ValueError(f"serve: `sampler_name` {getattr(sampler, '__name__', sampler)!r} has no per-row step (supported: "
                          f"{', '.join(sampling.LINEAR_FAMILY)}; use txt2img)")
-    if request.get("mask_image") is not None and (family != "dpmpp_2m" or v_pred):
+    # (a batcher built with `inpaint_unet=True` has no known-region step: its launch carries every sampler, v and the rescale)
+    if request.get("mask_image") is not None and not b.inpaint and (family != "dpmpp_2m" or v_pred):
         raise ValueError("serve: `mask_image` (inpainting) runs DPM++ 2M on an eps-prediction model only (the known-region "
                          "step, dsc_cfg_dpmpp2m_step_rows_known); drop `sampler_name` or use inpaiting")
     phi = request.get("guidance_rescale", 0.0)
     phi = fraction("guidance_rescale", 0.0 if phi is None else phi)
-    if request.get("mask_image") is not None and phi > 0.0:
+    if request.get("mask_image") is not None and not b.inpaint and phi > 0.0:
         raise ValueError("serve: `mask_image` (inpainting) with `guidance_rescale` > 0 is not served (the known-region step "
                          "has no rescale); use inpaiting")
     if (request.get("height", b.height), request.get("width", b.width)) != (b.height, b.width):
@@ -383,6 +399,9 @@ def image_request(b, r):
     image, mask = req.get("image"), req.get("mask_image")
     if req.get("padding_mask_crop") is not None:
         raise ValueError("serve: `padding_mask_crop` is not supported (use inpaiting)")
+    if b.inpaint and (image is None or mask is None):
+        raise ValueError("serve: a batcher built with `inpaint_unet=True` serves inpainting requests only - every request needs "
+                         "`image` and `mask_image` (an inpainting UNet has no txt2img)")
     if r.second:                             # the hires pass: img2img from the latent the hand-off writes
         r.kind = "img2img"
         r.strength = float(req.get("strength", 0.7))
@@ -397,7 +416,8 @@ def image_request(b, r):
         if req.get("strength") is not None:
             raise ValueError("serve: `strength` needs `image` (txt2img starts from pure noise)")
         return 0
-    r.kind = "img2img" if mask is None else "inpaint"
+    # "inpaint_unet": the 9-channel UNet reads the mask and the masked image as input channels - no known region, no blend
+    r.kind = "img2img" if mask is None else "inpaint_unet" if b.inpaint else "inpaint"
     r.strength = float(req.get("strength", 1.0))
     if not 0.0 < r.strength <= 1.0:
         raise ValueError(f"serve: `strength` must be in (0, 1], got {r.strength}")
@@ -415,9 +435,18 @@ def image_request(b, r):
             raise ValueError(f"serve: `image` is {size}, this batcher runs one {b.height}x{b.width} image per request")
         if pipe.vae is None or not hasattr(pipe.vae, "encode"):
             raise ValueError("serve: `image` given as pixels needs a VAE with an encoder; pass [1, 4, h, w] latents")
+    if b.inpaint:
+        mil = req.get("masked_image_latents")
+        if mil is None and latents_in:
+            raise ValueError(f"serve: `image` given as latents needs `masked_image_latents` ([1, 4, {h}, {w}]: the masked image "
+                             "cannot be built from latents); pass pixels, or both")
+        if mil is not None and (not torch.is_tensor(mil) or tuple(mil.shape) != (1, 4, h, w)):
+            raise ValueError(f"serve: `masked_image_latents` must be a {[1, 4, h, w]} tensor, got "
+                             f"{list(mil.shape) if torch.is_tensor(mil) else type(mil).__name__}")
     if mask is not None:
-        if pipe.unet.config.in_channels != 4:
-            raise ValueError("serve: `mask_image` on a 9-channel inpainting UNet is not supported (use inpaiting)")
+        if pipe.unet.config.in_channels != 4 and not b.inpaint:
+            raise ValueError("serve: `mask_image` on a 9-channel inpainting UNet is not supported by this batcher (use inpaiting, "
+                             "or build the batcher with pipe.serve(..., inpaint_unet=True))")
         if _spatial_size(mask) not in ((b.height, b.width), (h, w)):
             raise ValueError(f"serve: `mask_image` is {_spatial_size(mask)}, this batcher needs {b.height}x{b.width} "
                              f"(or the latent size {h}x{w})")

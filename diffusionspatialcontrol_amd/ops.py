@@ -1210,9 +1210,9 @@ class RowLinear(ctypes.Structure):
                                         ("temb_row", ctypes.c_void_p), ("noise", ctypes.c_void_p)]
 
 
-def _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=False):
+def _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=False, cat=False):
     """shape / dtype / device validation shared by the per-row sampler steps -> (n_dst, n_slots, chw, dsc_row_step array, or
-    dsc_row_linear array with linear=True)"""
+    dsc_row_linear array with linear=True).  cat: x_in rows may be longer than a latent (cfg_linear_step_rows_cat checks them)."""
     _require_gpu(x, old, x_in, t_buf, sigma_groups)
     n_dst = t_buf.numel() // 2
     n_slots = len(rows)
@@ -1228,7 +1228,7 @@ def _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, t
             raise ValueError(f"{what}: {name} must be dense fp16 on {x.device}")
         if nr is not None and t.shape[0] != nr:
             raise ValueError(f"{what}: {name} has {t.shape[0]} rows, need {nr}")
-        if name in ("x_in", "eps") and t.numel() != nr * chw:
+        if name in ("x_in", "eps") and t.numel() != nr * chw and not (cat and name == "x_in"):
             raise ValueError(f"{what}: {name} rows are not [{chw}] latents")
     for name, t, n in (("t_buf", t_buf, 2 * n_dst), ("sigma_groups", sigma_groups, n_dst)):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device or t.numel() != n:
@@ -1307,6 +1307,44 @@ def cfg_linear_step_rows_rescale(x, eps, old, n_src, x_in, t_buf, sigma_groups, 
     rc = _lib.load_library().dsc_cfg_linear_step_rows_rescale(
         _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
         0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), ctypes.cast(phi, ctypes.c_void_p),
+        n_slots, chw, 0, _stream_ptr(x))
+    _lib.check(rc, what)
+
+
+class RowExtra(ctypes.Structure):
+    """dsc_row_extra (include/dsc_hip.h)"""
+    _fields_ = [("extra", ctypes.c_void_p)]
+
+
+def cfg_linear_step_rows_cat(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, extras, tadd=None):
+    """cfg_linear_step_rows for a UNet whose input carries more channels than the latent - the 9-channel inpainting checkpoints,
+    `[latents | mask | masked-image latents]` (dsc_cfg_linear_step_rows_cat).  x_in: contiguous [2 n', chw + extra_halfs] (or a
+    view of that shape, [2 n', 9, h, w]); the first chw halfs of a row are cfg_linear_step_rows' (with a `rescale` > 0 in some
+    record: cfg_linear_step_rows_rescale's) bits, the rest is the slot's `extras` entry times the record's c_in_next.  extras: one
+    entry per record of `rows` - an fp16 [extra_halfs] tensor on x's device (unscaled, step-invariant), or None: zeros.  IDLE
+    slots get a zero row whatever their entry.  The library refuses extra_halfs % 8 != 0, chw % 8 != 0 and rows that are not
+    16-byte aligned before it launches anything."""
+    what = "cfg_linear_step_rows_cat"
+    phis = _row_rescales(what, rows)
+    n_dst, n_slots, chw, recs = _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=True, cat=True)
+    if x_in.numel() % (2 * n_dst) != 0 or x_in.numel() // (2 * n_dst) < chw:
+        raise ValueError(f"{what}: x_in has shape {tuple(x_in.shape)}, need {2 * n_dst} rows of [{chw}] latents plus the extra channels")
+    extra_halfs = x_in.numel() // (2 * n_dst) - chw
+    if len(extras) != n_slots:
+        raise ValueError(f"{what}: {len(extras)} extras for {n_slots} slots")
+    ex = (RowExtra * n_slots)()
+    for i, t in enumerate(extras):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float16 or t.device != x.device or not t.is_contiguous() \
+                or t.numel() != extra_halfs:
+            raise ValueError(f"{what}: extras[{i}] must be a dense fp16 [{extra_halfs}] row on {x.device}")
+        ex[i] = RowExtra(t.data_ptr())
+    phi = (ctypes.c_float * n_slots)(*phis) if any(p > 0.0 for p in phis) else None
+    rc = _lib.load_library().dsc_cfg_linear_step_rows_cat(
+        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
+        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p),
+        None if phi is None else ctypes.cast(phi, ctypes.c_void_p), ctypes.cast(ex, ctypes.c_void_p), extra_halfs,
         n_slots, chw, 0, _stream_ptr(x))
     _lib.check(rc, what)
 

@@ -295,6 +295,31 @@ int dsc_cfg_linear_step_rows_rescale(void* x, const void* eps, void* old, int n_
                                      float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
                                      const dsc_row_linear* rows /* host */, const float* rescale /* host, n_slots */, int n_slots,
                                      int chw, int dtype, void* stream);
+/*
+ * dsc_cfg_linear_step_rows for a UNet that reads more channels than the latent has: the 9-channel inpainting checkpoints take
+ * `[latents | mask | masked-image latents]` (reference model_k_diffusion.py:1617-1619), and the denoiser's c_in scales all nine
+ * (external_k_diffusion.py:94-97).  Same launch contract as dsc_cfg_linear_step_rows, with two differences: a row of x_in is
+ * chw + extra_halfs halfs long (slot i owns rows {i, n_dst + i} at that stride; x, old, eps and noise rows stay chw), and there
+ * is one more record per slot, passed by value (8 bytes each): the slot's step-invariant extra channels.
+ *   x_in row [0, chw)                  : exactly what dsc_cfg_linear_step_rows / _rescale write there
+ *   x_in row [chw, chw + extra_halfs)  : STEP / JOIN: fp16((float)extra[k] * c_in_next), fp32 with one rounding, the same value in
+ *                                        both rows; zeros where extra == NULL.  IDLE: zeros (the whole row is).
+ * Slots i >= n_dst write no destination row.  rescale: one phi per slot on the host, or NULL (no slot rescales).  With NULL or
+ * every STEP slot's phi == 0 this is ONE launch whose x, old, t_buf, sigma_groups, tadd and x_in[:, :chw] are
+ * dsc_cfg_linear_step_rows' bits; with some phi > 0 it is one launch with dsc_cfg_linear_step_rows_rescale's bits and its
+ * fixed-order sums.  Plain vector stores, no atomics, nothing crosses workgroups.
+ * Status: what dsc_cfg_linear_step_rows checks (and, with rescale != NULL, the phi range of the rescale entry); extras == NULL,
+ * extra_halfs <= 0, extra_halfs % 8 != 0, chw % 8 != 0 or a non-NULL extra that is not 16-byte aligned: DSC_ERR_BAD_ARG.  All
+ * checks run before the launch: nothing is written on failure.
+ */
+typedef struct {
+    const void* extra;      /* fp16 [extra_halfs] extra input channels of this slot (unscaled), or NULL: zeros */
+} dsc_row_extra;
+int dsc_cfg_linear_step_rows_cat(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
+                                 float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
+                                 const dsc_row_linear* rows /* host */, const float* rescale /* host, n_slots, or NULL */,
+                                 const dsc_row_extra* extras /* host, n_slots */, int extra_halfs, int n_slots,
+                                 int chw, int dtype, void* stream);
 /* out = a*x + b*denoised + c*old  (old may be NULL when c == 0): the sampler update alone, for callers that keep
  * the reference's `sampler(model_fn, x, sigmas=...)` control flow.  n elements, n % 4 == 0 (8-byte accesses unless n % 8 == 0). */
 int dsc_dpmpp2m_update(const void* x, const void* denoised, const void* old, float a, float b, float c,

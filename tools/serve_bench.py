@@ -2,7 +2,7 @@
 
     python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
                                 [--hires X] [--ip-adapter [--ip-masks]] [--t2i-adapter] [--controlnet [--control-slots C]]
-                                [--images uint8|pil|np [--decode-batch D]] [--previews K [--preview-scale S]]
+                                [--images uint8|pil|np [--decode-batch D]] [--previews K [--preview-scale S]] [--inpaint-unet]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -58,6 +58,13 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
               requests on the previews batcher (no slot is ever due: the price of the flag), (c) every request with
               `preview_every=K` and a no-op callback; images/s and p50 / p95 latency for each, with the previews launched,
               their rows, the callbacks made and the previews dropped; then (c) with the batcher driven by its own thread
+  inpaint_unet (--inpaint-unet: this leg only) a second SD1.5-shape UNet with `in_channels=9` and seeded random weights, and two
+              batchers on two slots: the plain one on the 4-channel pipeline, and one built with `inpaint_unet=True` on the
+              9-channel pipeline, every request of it an inpainting request (4-channel latents as `image`, its own mask and
+              `masked_image_latents`).  8 slots kept full, three alternating rounds: images/s and steps/s of both; then
+              one-at-a-time `inpaiting(fused=True)` beside `fused=False` at 512x512 for 25 steps, ms per image, three runs of
+              four; then the device time of dsc_cfg_linear_step_rows_cat beside dsc_cfg_linear_step_rows at 8 slots of 64x64
+              latents (a captured graph of 100 launches each, three replays)
 """
 import argparse
 import json
@@ -120,6 +127,44 @@ def make_mixed(reqs, seed):
             x0 = 64 * (i % 7)
             m[..., x0:x0 + 192] = 1.0                       # repaint a 192-pixel column band, elsewhere keep the image
             out.append(dict(r, image=img, mask_image=m, strength=1.0))
+    return out
+
+
+def make_inpaint(reqs, seed):
+    """every request an inpainting request of a 9-channel UNet: its own image latents, mask and masked-image latents"""
+    out = []
+    for i, r in enumerate(reqs):
+        g = torch.Generator().manual_seed(seed * 1000 + 6000 + i)
+        img = (torch.randn(1, 4, 64, 64, generator=g) * 0.8).half().cuda()
+        mil = (torch.randn(1, 4, 64, 64, generator=g) * 0.8).half().cuda()
+        m = torch.zeros(1, 1, 512, 512)
+        x0 = 64 * (i % 6)
+        m[..., x0:x0 + 192] = 1.0                           # repaint a 192-pixel column band
+        out.append(dict(r, image=img, mask_image=m, masked_image_latents=mil, strength=1.0))
+    return out
+
+
+def graph_launch_us(fn, launches=100, replays=3):
+    """device microseconds per launch of `fn` (one sampler launch): a captured graph of `launches` of them, timed per replay"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(launches):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(replays):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(round(1e3 * e0.elapsed_time(e1) / launches, 3))
     return out
 
 
@@ -197,6 +242,8 @@ def main():
     ap.add_argument("--previews", type=int, default=None, metavar="K",
                     help="only the previews leg: every request with preview_every = K and a no-op callback")
     ap.add_argument("--preview-scale", type=int, default=8, help="with --previews: the thumbnails' enlargement (1, 2, 4, 8)")
+    ap.add_argument("--inpaint-unet", action="store_true",
+                    help="only the 9-channel inpainting UNet leg: a batcher built with inpaint_unet=True, every request inpainting")
     a = ap.parse_args()
     if a.ip_masks and not a.ip_adapter:
         ap.error("--ip-masks goes with --ip-adapter")
@@ -209,6 +256,62 @@ def main():
     opt = {"scheduler": "karras"}
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    if a.inpaint_unet:
+        import dataclasses
+        from diffusionspatialcontrol_amd import ops
+        torch.manual_seed(1)
+        with torch.device("cuda"):
+            unet9 = UNet2DConditionModel(dataclasses.replace(UNetConfig.sd15(), in_channels=9))
+        pipe9 = StableDiffusionPipeline(None, None, FakeTokenizer(), unet9.half().eval(), SD15Scheduler())
+        plain = pipe.serve(512, 512, max_batch=8, slot=0).warm()
+        inp = pipe9.serve(512, 512, max_batch=8, slot=1, inpaint_unet=True).warm()
+        ireqs = make_inpaint(reqs, a.seed)
+        for b, group in ((plain, reqs[:8]), (inp, ireqs[:8])):      # one untimed pass each
+            run_full(b, group, kw25)
+        runs = []
+        for _ in range(3):                                # alternating, so that a drift of the box hits both alike
+            runs.append((run_full(plain, reqs, kw25), run_full(inp, ireqs, kw25)))
+        emit(leg="inpaint_unet", requests=len(reqs), steps=25,
+             four_channel_txt2img_img_s=[round(t[0][0], 2) for t in runs], four_channel_txt2img_steps_s=[round(t[0][1], 1) for t in runs],
+             nine_channel_inpaint_img_s=[round(t[1][0], 2) for t in runs], nine_channel_inpaint_steps_s=[round(t[1][1], 1) for t in runs],
+             cat_transitions=inp.stats()["cat_transitions"], captures_after_warm=inp.stats()["captures_after_warm"],
+             note="three alternating rounds in one process, two UNets of the same shape but for conv_in (36 against 81 taps)")
+        r = ireqs[0]
+        one = dict(height=512, width=512, sampler_name="sample_dpmpp_2m", image=r["image"], mask_image=r["mask_image"],
+                   masked_image_latents=r["masked_image_latents"], latents=r["latents"], region_map_state=r["region_map_state"],
+                   prompt_embeds=r["prompt_embeds"], negative_prompt_embeds=r["negative_prompt_embeds"],
+                   text_input_ids=r["text_input_ids"], output_type="latent", **kw25)
+        ms = {True: [], False: []}
+        for mode in (True, False):
+            pipe9.inpaiting(None, fused=mode, **one)
+        for _ in range(3):
+            for mode in (True, False):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(4):
+                    pipe9.inpaiting(None, fused=mode, **one)
+                torch.cuda.synchronize()
+                ms[mode].append(round(1e3 * (time.perf_counter() - t0) / 4, 2))
+        emit(leg="inpaint_unet_one_at_a_time", steps=25, size="512x512", fused_ms_per_image=ms[True], protocol_ms_per_image=ms[False],
+             note="inpaiting(fused=True) against fused=False (eager protocol mode) on the 9-channel UNet, three alternating runs of four")
+        n, chw, eh = 8, 4 * 64 * 64, 5 * 64 * 64
+        h = lambda *shape: torch.randn(*shape, device="cuda").half()      # noqa: E731
+        x, eps, old = h(n, chw), h(2 * n, chw), h(n, chw)
+        t, sg = torch.zeros(2 * n, device="cuda"), torch.ones(n, device="cuda")
+        x4, x9 = torch.zeros(2 * n, chw, device="cuda").half(), torch.zeros(2 * n, chw + eh, device="cuda").half()
+        ex = [h(eh) for _ in range(n)]
+        recs = [{"mode": ops.ROW_STEP, "sigma": 2.0, "guidance": 7.5, "a": 1.0, "b": 0.0, "c": 0.0, "c_skip": 1.0, "c_out": -2.0,
+                 "c_in_next": 0.4, "t_next": 500.0, "sigma_next": 1.5} for _ in range(n)]      # (a = 1, b = c = 0: x stays x)
+        us = {"cfg_linear_step_rows": [], "cfg_linear_step_rows_cat": []}
+        for _ in range(3):
+            us["cfg_linear_step_rows"] += graph_launch_us(lambda: ops.cfg_linear_step_rows(x, eps, old, n, x4, t, sg, recs), replays=1)
+            us["cfg_linear_step_rows_cat"] += graph_launch_us(lambda: ops.cfg_linear_step_rows_cat(x, eps, old, n, x9, t, sg, recs, ex),
+                                                              replays=1)
+        emit(leg="inpaint_unet_kernel", slots=n, latent="4x64x64", extra_halfs=eh, device_us_per_launch=us,
+             note="a captured graph of 100 launches per figure, alternating; the cat entry reads 5/4 and writes 10/4 of a latent more")
+        emit(leg="stats", four_channel=plain.stats(), nine_channel=inp.stats())
+        return
 
     if a.previews:
         plain = pipe.serve(512, 512, max_batch=8, slot=0).warm()
