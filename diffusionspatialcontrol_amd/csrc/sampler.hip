@@ -125,7 +125,7 @@ __device__ __forceinline__ float as_f32(float v) {
     return v;
 }
 
-// ---- what the per-row kernels below share (slot i = blockIdx.y; T: the workgroup size, 256 for the first three)
+// ---- the helpers of the per-row step below (slot i = blockIdx.y; T: the workgroup size)
 // the slot's time-embedding row -> both of its CFG rows of the destination bucket
 template <int T = 256>
 __device__ __forceinline__ void rows_copy_temb(const void* temb_row, half_t* tadd, int tadd_halfs, int n_dst, int i) {
@@ -186,261 +186,100 @@ __device__ __forceinline__ void rows_cat_extra(const void* extra, bool idle, flo
     }
 }
 
-// dsc_cfg_dpmpp2m_step_rows: the records ride in the kernel arguments (kernarg segment, read through scalar loads: the slot is
-// blockIdx.y, uniform per workgroup)
-struct RowSteps { dsc_row_step r[DSC_ROW_STEP_MAX_SLOTS]; };
-
-template <int V>
-__global__ __launch_bounds__(256) void step_rows_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
-                                                        float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
-                                                        int n_dst, int chw, const RowSteps rs) {
-    const int i = blockIdx.y;
-    const dsc_row_step& r = rs.r[i];
-    const bool dst = i < n_dst;
-    const long long v8 = chw / V;
-    if (dst) rows_copy_temb(r.temb_row, tadd, tadd_halfs, n_dst, i);
-    half_t* xi_u = x_in + (long long)i * chw;
-    half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
-    if (r.mode == DSC_ROW_STEP) {
-        const float sigma = r.sigma, g = r.guidance, a = r.a, b = r.b, c = r.c, c_in_next = r.c_in_next;
-        half_t* xr = x + (long long)i * chw;
-        half_t* orow = old + (long long)i * chw;
-        const half_t* eur = eps + (long long)i * chw;
-        const half_t* ecr = eps + (long long)(n_src + i) * chw;
-        for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
-            float xv[V], eu[V], ec[V], ov[V], dn[V], xn[V], xi[V];
-            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(xr + k * V), xv);
-            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eur + k * V), eu);
-            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(ecr + k * V), ec);
-            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(orow + k * V), ov);
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                // step_kernel's arithmetic with the fused multiply-adds it compiles to, spelled out (the contraction of a
-                // plain expression depends on the surrounding code, and the per-row step must give the same bits):
-                // e = fma(g, ec - eu, eu), D = fma(-sigma, e, x), x' = fma(c, old, fma(a, x, b * D))
-                const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
-                dn[j] = (float)(half_t)as_f32(__builtin_fmaf(-sigma, e, xv[j]));
-                const float bd = as_f32(b * dn[j]);
-                xn[j] = (float)(half_t)as_f32(__builtin_fmaf(c, ov[j], as_f32(__builtin_fmaf(a, xv[j], bd))));
-                xi[j] = as_f32(xn[j] * c_in_next);
-            }
-            *reinterpret_cast<hv_t<V>*>(orow + k * V) = packv<V>(dn);
-            *reinterpret_cast<hv_t<V>*>(xr + k * V) = packv<V>(xn);
-            if (dst) {
-                const hv_t<V> o = packv<V>(xi);
-                *reinterpret_cast<hv_t<V>*>(xi_u + k * V) = o;
-                *reinterpret_cast<hv_t<V>*>(xi_c + k * V) = o;
-            }
-        }
-    } else if (dst) {
-        rows_join_or_idle<256, V>(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
-    }
-    if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
-}
-
-// dsc_cfg_dpmpp2m_step_rows_known: step_rows_kernel plus, per slot, the known region of an inpainting request blended into the
-// model input (what the eager hook of `inpaiting` did per model call, reference model_k_diffusion.py:1599-1612).  A slot whose
-// record has no image runs step_rows_kernel's arithmetic unchanged (same bits); JOIN / IDLE slots never look at the record.
+// ---- the per-row step: ONE body behind the five dsc_cfg_*_step_rows* entries.  What every kernel takes, by value in the kernel
+// arguments (kernarg segment, read through scalar loads: the slot is blockIdx.y, uniform per workgroup): the buffers and one
+// dsc_row_linear per slot - the dsc_cfg_dpmpp2m_* entries fill c_skip = 1, c_out = -sigma, noise = NULL on the host.
+struct RowArgs {
+    half_t* x; const half_t* eps; half_t* old; int n_src; half_t* x_in; float* t_buf; float* sigma_groups; half_t* tadd;
+    int tadd_halfs, n_dst, chw;
+    dsc_row_linear r[DSC_ROW_STEP_MAX_SLOTS];
+};
+// the optional parts, each passed only to the kernels compiled with its flag:
+// KNOWN (dsc_cfg_dpmpp2m_step_rows_known): the known region of an inpainting request blended into the model input (what the eager
+// hook of `inpaiting` did per model call, reference model_k_diffusion.py:1599-1612); a slot without an image is unblended
 struct RowKnowns { dsc_row_known r[DSC_ROW_STEP_MAX_SLOTS]; };
-
-template <int V>
-__global__ __launch_bounds__(256) void step_rows_known_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
-                                                              float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
-                                                              int n_dst, int chw, const RowSteps rs, const RowKnowns ks) {
-    const int i = blockIdx.y;
-    const dsc_row_step& r = rs.r[i];
-    const dsc_row_known& kr = ks.r[i];
-    const bool dst = i < n_dst;
-    const long long v8 = chw / V;
-    if (dst) rows_copy_temb(r.temb_row, tadd, tadd_halfs, n_dst, i);
-    half_t* xi_u = x_in + (long long)i * chw;
-    half_t* xi_c = x_in + (long long)(n_dst + i) * chw;
-    if (r.mode == DSC_ROW_STEP) {
-        const float sigma = r.sigma, g = r.guidance, a = r.a, b = r.b, c = r.c, c_in_next = r.c_in_next;
-        const float sigma_next = r.sigma_next;
-        const half_t* img = static_cast<const half_t*>(kr.image);
-        const half_t* nse = static_cast<const half_t*>(kr.noise);
-        const half_t* msk = static_cast<const half_t*>(kr.mask);
-        const bool now = img && kr.blend_now, next = img && kr.blend_next && dst;
-        half_t* xr = x + (long long)i * chw;
-        half_t* orow = old + (long long)i * chw;
-        const half_t* eur = eps + (long long)i * chw;
-        const half_t* ecr = eps + (long long)(n_src + i) * chw;
-        for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
-            float xv[V], eu[V], ec[V], ov[V], dn[V], xn[V], xi[V], im[V], nz[V], mk[V];
-            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(xr + k * V), xv);
-            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eur + k * V), eu);
-            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(ecr + k * V), ec);
-            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(orow + k * V), ov);
-            if (now || next) {
-                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(img + k * V), im);
-                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(nse + k * V), nz);
-                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(msk + k * V), mk);
-            }
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                // step_rows_kernel's lines; the model input xh replaces x in D only - the sampler's own state stays unblended
-                const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
-                float xh = xv[j];
-                if (now) {
-                    const float kn = as_f32(__builtin_fmaf(sigma, nz[j], im[j]));          // known region at this sigma
-                    xh = as_f32(__builtin_fmaf(mk[j], xv[j], as_f32((1.0f - mk[j]) * kn)));
-                }
-                dn[j] = (float)(half_t)as_f32(__builtin_fmaf(-sigma, e, xh));
-                const float bd = as_f32(b * dn[j]);
-                xn[j] = (float)(half_t)as_f32(__builtin_fmaf(c, ov[j], as_f32(__builtin_fmaf(a, xv[j], bd))));
-                float xo = xn[j];
-                if (next) {
-                    const float kn = as_f32(__builtin_fmaf(sigma_next, nz[j], im[j]));     // ... and at the coming one
-                    xo = as_f32(__builtin_fmaf(mk[j], xn[j], as_f32((1.0f - mk[j]) * kn)));
-                }
-                xi[j] = as_f32(xo * c_in_next);
-            }
-            *reinterpret_cast<hv_t<V>*>(orow + k * V) = packv<V>(dn);
-            *reinterpret_cast<hv_t<V>*>(xr + k * V) = packv<V>(xn);
-            if (dst) {
-                const hv_t<V> o = packv<V>(xi);
-                *reinterpret_cast<hv_t<V>*>(xi_u + k * V) = o;
-                *reinterpret_cast<hv_t<V>*>(xi_c + k * V) = o;
-            }
-        }
-    } else if (dst) {
-        rows_join_or_idle<256, V>(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
-    }
-    if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
-}
-
-// dsc_cfg_linear_step_rows: step_rows_kernel with the denoised estimate affine in (x, model output) - D = c_skip x + c_out m, eps- or
-// v-prediction - and an optional per-slot noise row: x' = a x + b D + c D_old + s xi, the one-model-call-per-step samplers of
-// modules/sampling.py (sample_euler, sample_euler_ancestral, sample_dpmpp_2m, sample_dpmpp_2m_sde, sample_lcm of
-// samplers_extra_k_diffusion.py) with their scalars computed on the host (sampling.linear_step_coefficients).  A slot with
-// c_skip = 1, c_out = -sigma and no noise row runs step_rows_kernel's arithmetic (same bits); JOIN / IDLE slots are its lines.
-struct RowLinears { dsc_row_linear r[DSC_ROW_STEP_MAX_SLOTS]; };
-// CAT (dsc_cfg_linear_step_rows_cat): an x_in row is chw + extra_halfs halfs long and ends with the slot's extra channels
-struct RowExtras { dsc_row_extra r[DSC_ROW_STEP_MAX_SLOTS]; };
-
-template <bool CAT>
-__device__ __forceinline__ void linear_rows_body(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
-                                                 float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
-                                                 int n_dst, int chw, const RowLinears& rs, int extra_halfs, const RowExtras* es) {
-    const int i = blockIdx.y;
-    const dsc_row_linear& r = rs.r[i];
-    const bool dst = i < n_dst;
-    const long long v8 = chw / 8;
-    if (dst) rows_copy_temb(r.temb_row, tadd, tadd_halfs, n_dst, i);
-    const long long xs = CAT ? (long long)chw + extra_halfs : chw;         // halfs per x_in row
-    half_t* xi_u = x_in + (long long)i * xs;
-    half_t* xi_c = x_in + (long long)(n_dst + i) * xs;
-    if (CAT && dst) rows_cat_extra(es->r[i].extra, r.mode == DSC_ROW_IDLE, r.c_in_next, xi_u + chw, xi_c + chw, extra_halfs / 8);
-    if (r.mode == DSC_ROW_STEP) {
-        const float g = r.guidance, a = r.a, b = r.b, c = r.c, c_in_next = r.c_in_next;
-        const float c_skip = r.c_skip, c_out = r.c_out, s = r.s;
-        const half_t* nse = static_cast<const half_t*>(r.noise);            // per slot: the branch below is uniform per workgroup
-        half_t* xr = x + (long long)i * chw;
-        half_t* orow = old + (long long)i * chw;
-        const half_t* eur = eps + (long long)i * chw;
-        const half_t* ecr = eps + (long long)(n_src + i) * chw;
-        for (long long k = blockIdx.x * 256ll + threadIdx.x; k < v8; k += (long long)gridDim.x * 256) {
-            float xv[8], eu[8], ec[8], ov[8], dn[8], xn[8], xi[8], nz[8];
-            unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), xv);
-            unpack8(*reinterpret_cast<const h8_t*>(eur + k * 8), eu);
-            unpack8(*reinterpret_cast<const h8_t*>(ecr + k * 8), ec);
-            unpack8(*reinterpret_cast<const h8_t*>(orow + k * 8), ov);
-            if (nse) unpack8(*reinterpret_cast<const h8_t*>(nse + k * 8), nz);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                // e = fma(g, ec - eu, eu), D = fma(c_out, e, c_skip * x), x' = fma(s, xi, fma(c, old, fma(a, x, b * D)))
-                const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
-                const float sx = as_f32(c_skip * xv[j]);
-                dn[j] = (float)(half_t)as_f32(__builtin_fmaf(c_out, e, sx));
-                const float bd = as_f32(b * dn[j]);
-                float xo = as_f32(__builtin_fmaf(c, ov[j], as_f32(__builtin_fmaf(a, xv[j], bd))));
-                if (nse) xo = as_f32(__builtin_fmaf(s, nz[j], xo));
-                xn[j] = (float)(half_t)xo;
-                xi[j] = as_f32(xn[j] * c_in_next);
-            }
-            *reinterpret_cast<h8_t*>(orow + k * 8) = pack8(dn);
-            *reinterpret_cast<h8_t*>(xr + k * 8) = pack8(xn);
-            if (dst) {
-                const h8_t o = pack8(xi);
-                *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
-                *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
-            }
-        }
-    } else if (dst) {
-        rows_join_or_idle(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
-    }
-    if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
-}
-
-__global__ __launch_bounds__(256) void linear_rows_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
-                                                          float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
-                                                          int n_dst, int chw, const RowLinears rs) {
-    linear_rows_body<false>(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, chw, rs, 0, nullptr);
-}
-__global__ __launch_bounds__(256) void linear_rows_cat_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
-                                                              float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
-                                                              int n_dst, int chw, const RowLinears rs, int extra_halfs,
-                                                              const RowExtras es) {
-    linear_rows_body<true>(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, chw, rs, extra_halfs, &es);
-}
-
-// dsc_cfg_linear_step_rows_rescale: linear_rows_kernel with the guidance rescale of arXiv 2305.08891 sec. 3.4 per slot, applied
-// - as the reference does - to the denoised estimate: D' = K D, K = phi sqrt(SSD(D_c) / SSD(D)) + (1 - phi), the two sums of
-// squared deviations taken over the slot's whole row.  x is updated in place, so a slot with phi > 0 belongs to ONE workgroup
-// (blockIdx.x == 0; the slot's other workgroups leave once the embedding row is copied): it reads x / m_u / m_c for the four
-// sums, meets at the workgroup barrier of the across-wave sum - after which no thread reads the old x of an element it does
-// not own - and then updates the row, every thread the elements it alone reads and writes.  Slots with phi == 0 and JOIN /
-// IDLE slots keep linear_rows_kernel's striding over gridDim.x and its bits.  No atomics, nothing crosses workgroups.
+// RESCALE (dsc_cfg_linear_step_rows_rescale): the guidance rescale of arXiv 2305.08891 sec. 3.4 per slot, applied - as the
+// reference does - to the denoised estimate: D' = K D, K = phi sqrt(SSD(D_c) / SSD(D)) + (1 - phi), the two sums of squared
+// deviations taken over the slot's whole row.  x is updated in place, so a slot with phi > 0 belongs to ONE workgroup
+// (blockIdx.x == 0; the slot's other workgroups leave once the embedding row and the extra channels are copied): it reads
+// x / m_u / m_c for the four sums, meets at the workgroup barrier of the across-wave sum - after which no thread reads the old x
+// of an element it does not own - and then updates the row, every thread the elements it alone reads and writes.  Slots with
+// phi == 0 and JOIN / IDLE slots stride over gridDim.x like everyone else.  No atomics, nothing crosses workgroups.
 // The sums have one fixed order: per thread over k = tid, tid + T, ... (8 halfs in order each), a 6-stage xor butterfly in the
 // wave (32, 16, .. 1: every lane ends with the same value), then waves 0 .. T/64 - 1 in order out of LDS.
 #ifndef DSC_RESCALE_THREADS
 #define DSC_RESCALE_THREADS 1024
 #endif
 struct RowRescales { float phi[DSC_ROW_STEP_MAX_SLOTS]; };
+// CAT (dsc_cfg_linear_step_rows_cat): an x_in row is chw + halfs halfs long and ends with the slot's extra channels
+struct RowExtras { int halfs; dsc_row_extra r[DSC_ROW_STEP_MAX_SLOTS]; };
 
-template <int T, bool CAT>
-__device__ __forceinline__ void linear_rows_rescale_body(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
-                                                         float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
-                                                         int n_dst, int chw, const RowLinears& rs, const RowRescales& ps,
-                                                         int extra_halfs, const RowExtras* es) {
+// T threads, V halfs per access.  A flag that is off compiles its part out; LINEAR off: the record is a DPM++ 2M one, c_skip == 1
+// and no noise row by construction (x for 1 x: the same bits, one multiply and a row of registers less).  Per element of a STEP
+// slot, all fp32:
+//   e = fma(g, m_c - m_u, m_u), D = fp16([K] fma(c_out, e, c_skip xh)), x' = fp16([fma(s, noise,] fma(c, old, fma(a, x, b D))[)]),
+//   x_in = fp16(xh' c_in_next) - xh, xh': x, x' with the known region blended in (KNOWN), else x, x' themselves.
+// These are step_kernel's lines with the fused multiply-adds it compiles to spelled out, every intermediate pinned to fp32 by
+// as_f32 (the contraction of a plain expression depends on the surrounding code, and every instantiation must give the same bits).
+template <int T, int V, bool LINEAR, bool KNOWN, bool RESCALE, bool CAT>
+__device__ __forceinline__ void rows_body(const RowArgs& p, const RowKnowns* ks, const RowRescales* ps, const RowExtras* es) {
     static_assert(T % 64 == 0 && T <= 1024, "whole waves");
-    __shared__ double red[T / 64][4];
-    const int i = blockIdx.y;
-    const dsc_row_linear& r = rs.r[i];
+    static_assert(!(KNOWN && RESCALE), "the row sums read x: they would have to read the blended model input");
+    static_assert(V == 8 || !(RESCALE || CAT), "8-byte rows: the sums and the extra channels move 8 halfs");
+    const int i = blockIdx.y, n_dst = p.n_dst, chw = p.chw;
+    const dsc_row_linear& r = p.r[i];
+    const int mode = r.mode;
     const bool dst = i < n_dst;
-    const long long v8 = chw / 8;
-    if (dst) rows_copy_temb<T>(r.temb_row, tadd, tadd_halfs, n_dst, i);
-    const long long xs = CAT ? (long long)chw + extra_halfs : chw;         // halfs per x_in row
-    half_t* xi_u = x_in + (long long)i * xs;
-    half_t* xi_c = x_in + (long long)(n_dst + i) * xs;
+    const long long nv = chw / V;
+    if (dst) rows_copy_temb<T>(r.temb_row, p.tadd, p.tadd_halfs, n_dst, i);
+    const long long xs = CAT ? (long long)chw + es->halfs : chw;           // halfs per x_in row
+    half_t* xi_u = p.x_in + (long long)i * xs;
+    half_t* xi_c = p.x_in + (long long)(n_dst + i) * xs;
+    half_t* xr = p.x + (long long)i * chw;
+    half_t* orow = p.old + (long long)i * chw;
     // (before an owned slot's other workgroups leave: the extra channels stride over the whole grid)
-    if (CAT && dst) rows_cat_extra<T>(es->r[i].extra, r.mode == DSC_ROW_IDLE, r.c_in_next, xi_u + chw, xi_c + chw, extra_halfs / 8);
-    if (r.mode == DSC_ROW_STEP) {
-        const float phi = ps.phi[i];
-        const bool owned = phi > 0.0f;                                      // per slot: uniform per workgroup
-        if (owned && blockIdx.x != 0) return;
+    if constexpr (CAT) if (dst) rows_cat_extra<T>(es->r[i].extra, mode == DSC_ROW_IDLE, r.c_in_next, xi_u + chw, xi_c + chw, es->halfs / 8);
+    if (mode == DSC_ROW_STEP) {
+        bool owned = false;                                                 // per slot: uniform per workgroup, like every branch below
+        if constexpr (RESCALE) {
+            owned = ps->phi[i] > 0.0f;
+            if (owned && blockIdx.x != 0) return;
+        }
         const float g = r.guidance, a = r.a, b = r.b, c = r.c, c_in_next = r.c_in_next;
-        const float c_skip = r.c_skip, c_out = r.c_out, s = r.s;
-        const half_t* nse = static_cast<const half_t*>(r.noise);
-        half_t* xr = x + (long long)i * chw;
-        half_t* orow = old + (long long)i * chw;
-        const half_t* eur = eps + (long long)i * chw;
-        const half_t* ecr = eps + (long long)(n_src + i) * chw;
+        const float c_skip = r.c_skip, c_out = r.c_out, s = r.s, sigma = r.sigma, sigma_next = r.sigma_next;   // (KNOWN's)
+        const half_t* nse = LINEAR ? static_cast<const half_t*>(r.noise) : nullptr;
+        const half_t* eur = p.eps + (long long)i * chw;
+        const half_t* ecr = p.eps + (long long)(p.n_src + i) * chw;
+        const auto combine = [&](float mu, float mc) { return as_f32(__builtin_fmaf(g, mc - mu, mu)); };
+        const auto skip = [&](float v) { return LINEAR ? as_f32(c_skip * v) : v; };
+        const auto estimate = [&](float m, float sx) { return as_f32(__builtin_fmaf(c_out, m, sx)); };      // D in fp32
+        const half_t *img = nullptr, *knz = nullptr, *msk = nullptr;
+        bool now = false, next = false;
+        if constexpr (KNOWN) {
+            const dsc_row_known& kr = ks->r[i];
+            img = static_cast<const half_t*>(kr.image), knz = static_cast<const half_t*>(kr.noise), msk = static_cast<const half_t*>(kr.mask);
+            now = img && kr.blend_now, next = img && kr.blend_next && dst;
+        }
+        // v with the known region at noise level sg in the place of what the mask keeps
+        const auto blend = [](float v, float sg, float im, float nz, float mk) {
+            const float kn = as_f32(__builtin_fmaf(sg, nz, im));
+            return as_f32(__builtin_fmaf(mk, v, as_f32((1.0f - mk) * kn)));
+        };
         float K = 1.0f;
-        if (owned) {
+        if constexpr (RESCALE) if (owned) {
+            __shared__ double red[T / 64][4];
             double sc = 0.0, qc = 0.0, sg = 0.0, qg = 0.0;                   // sum Dc, sum Dc^2, sum Dg, sum Dg^2
-            for (long long k = threadIdx.x; k < v8; k += T) {
-                float xv[8], eu[8], ec[8];
-                unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), xv);
-                unpack8(*reinterpret_cast<const h8_t*>(eur + k * 8), eu);
-                unpack8(*reinterpret_cast<const h8_t*>(ecr + k * 8), ec);
+            for (long long k = threadIdx.x; k < nv; k += T) {
+                float xv[V], eu[V], ec[V];
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(xr + k * V), xv);
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eur + k * V), eu);
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(ecr + k * V), ec);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
-                    const float sx = as_f32(c_skip * xv[j]);
-                    const double dc = (double)as_f32(__builtin_fmaf(c_out, ec[j], sx));
-                    const double dg = (double)as_f32(__builtin_fmaf(c_out, e, sx));
+                for (int j = 0; j < V; ++j) {
+                    const float e = combine(eu[j], ec[j]);
+                    const float sx = skip(xv[j]);
+                    const double dc = (double)estimate(ec[j], sx);
+                    const double dg = (double)estimate(e, sx);
                     sc += dc;
                     qc = __builtin_fma(dc, dc, qc);
                     sg += dg;
@@ -468,59 +307,76 @@ __device__ __forceinline__ void linear_rows_rescale_body(half_t* x, const half_t
             }
             const double n = (double)chw;
             const double ssd_c = qc - sc * sc / n, ssd_g = qg - sg * sg / n;   // (the n - 1 of both stds cancels)
+            const float phi = ps->phi[i];
             K = (float)((double)phi * __builtin_sqrt(ssd_c / ssd_g) + (1.0 - (double)phi));
         }
-        const long long k0 = owned ? threadIdx.x : blockIdx.x * (long long)T + threadIdx.x;
-        const long long dk = owned ? T : (long long)gridDim.x * T;
-        for (long long k = k0; k < v8; k += dk) {
-            float xv[8], eu[8], ec[8], ov[8], dn[8], xn[8], xi[8], nz[8];
-            unpack8(*reinterpret_cast<const h8_t*>(xr + k * 8), xv);
-            unpack8(*reinterpret_cast<const h8_t*>(eur + k * 8), eu);
-            unpack8(*reinterpret_cast<const h8_t*>(ecr + k * 8), ec);
-            unpack8(*reinterpret_cast<const h8_t*>(orow + k * 8), ov);
-            if (nse) unpack8(*reinterpret_cast<const h8_t*>(nse + k * 8), nz);
+        // an owned slot's row is this workgroup's alone; any other strides over the slot's workgroups
+        for (long long k = owned ? threadIdx.x : blockIdx.x * (long long)T + threadIdx.x; k < nv;
+             k += owned ? T : (long long)gridDim.x * T) {
+            float xv[V], eu[V], ec[V], ov[V], dn[V], xn[V], xi[V], nz[V], im[V], kz[V], mk[V];
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(xr + k * V), xv);
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eur + k * V), eu);
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(ecr + k * V), ec);
+            unpackv<V>(*reinterpret_cast<const hv_t<V>*>(orow + k * V), ov);
+            if (nse) unpackv<V>(*reinterpret_cast<const hv_t<V>*>(nse + k * V), nz);
+            if constexpr (KNOWN) if (now || next) {
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(img + k * V), im);
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(knz + k * V), kz);
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(msk + k * V), mk);
+            }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                // linear_rows_kernel's lines, D scaled by K before its fp16 rounding in an owned slot
-                const float e = as_f32(__builtin_fmaf(g, ec[j] - eu[j], eu[j]));
-                const float sx = as_f32(c_skip * xv[j]);
-                float dg = as_f32(__builtin_fmaf(c_out, e, sx));
-                if (owned) dg = as_f32(K * dg);
-                dn[j] = (float)(half_t)dg;
+            for (int j = 0; j < V; ++j) {
+                const float e = combine(eu[j], ec[j]);
+                float xh = xv[j];                                           // the model input replaces x in D only - the
+                if constexpr (KNOWN) if (now) xh = blend(xv[j], sigma, im[j], kz[j], mk[j]);   // sampler's own state stays unblended
+                float d = estimate(e, skip(xh));
+                if constexpr (RESCALE) if (owned) d = as_f32(K * d);        // before D's fp16 rounding
+                dn[j] = (float)(half_t)d;
                 const float bd = as_f32(b * dn[j]);
                 float xo = as_f32(__builtin_fmaf(c, ov[j], as_f32(__builtin_fmaf(a, xv[j], bd))));
                 if (nse) xo = as_f32(__builtin_fmaf(s, nz[j], xo));
                 xn[j] = (float)(half_t)xo;
-                xi[j] = as_f32(xn[j] * c_in_next);
+                float xm = xn[j];
+                if constexpr (KNOWN) if (next) xm = blend(xn[j], sigma_next, im[j], kz[j], mk[j]);
+                xi[j] = as_f32(xm * c_in_next);
             }
-            *reinterpret_cast<h8_t*>(orow + k * 8) = pack8(dn);
-            *reinterpret_cast<h8_t*>(xr + k * 8) = pack8(xn);
+            *reinterpret_cast<hv_t<V>*>(orow + k * V) = packv<V>(dn);
+            *reinterpret_cast<hv_t<V>*>(xr + k * V) = packv<V>(xn);
             if (dst) {
-                const h8_t o = pack8(xi);
-                *reinterpret_cast<h8_t*>(xi_u + k * 8) = o;
-                *reinterpret_cast<h8_t*>(xi_c + k * 8) = o;
+                const hv_t<V> o = packv<V>(xi);
+                *reinterpret_cast<hv_t<V>*>(xi_u + k * V) = o;
+                *reinterpret_cast<hv_t<V>*>(xi_c + k * V) = o;
             }
         }
     } else if (dst) {
-        rows_join_or_idle<T>(r.mode == DSC_ROW_JOIN, r.c_in_next, x + (long long)i * chw, old + (long long)i * chw, xi_u, xi_c, v8);
+        rows_join_or_idle<T, V>(mode == DSC_ROW_JOIN, r.c_in_next, xr, orow, xi_u, xi_c, nv);
     }
-    if (dst) rows_write_scalars(t_buf, sigma_groups, n_dst, i, r.t_next, r.mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
+    if (dst) rows_write_scalars(p.t_buf, p.sigma_groups, n_dst, i, r.t_next, mode == DSC_ROW_IDLE ? 1.0f : r.sigma_next);
 }
 
-template <int T>
-__global__ __launch_bounds__(T) void linear_rows_rescale_kernel(half_t* x, const half_t* eps, half_t* old, int n_src, half_t* x_in,
-                                                                float* t_buf, float* sigma_groups, half_t* tadd, int tadd_halfs,
-                                                                int n_dst, int chw, const RowLinears rs, const RowRescales ps) {
-    linear_rows_rescale_body<T, false>(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, chw, rs, ps, 0, nullptr);
+template <int V>
+__global__ __launch_bounds__(256) void step_rows_kernel(const RowArgs p) {
+    rows_body<256, V, false, false, false, false>(p, nullptr, nullptr, nullptr);
+}
+template <int V>
+__global__ __launch_bounds__(256) void step_rows_known_kernel(const RowArgs p, const RowKnowns ks) {
+    rows_body<256, V, false, true, false, false>(p, &ks, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void linear_rows_kernel(const RowArgs p) {
+    rows_body<256, 8, true, false, false, false>(p, nullptr, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void linear_rows_cat_kernel(const RowArgs p, const RowExtras es) {
+    rows_body<256, 8, true, false, false, true>(p, nullptr, nullptr, &es);
 }
 template <int T>
-__global__ __launch_bounds__(T) void linear_rows_rescale_cat_kernel(half_t* x, const half_t* eps, half_t* old, int n_src,
-                                                                    half_t* x_in, float* t_buf, float* sigma_groups, half_t* tadd,
-                                                                    int tadd_halfs, int n_dst, int chw, const RowLinears rs,
-                                                                    const RowRescales ps, int extra_halfs, const RowExtras es) {
-    linear_rows_rescale_body<T, true>(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, chw, rs, ps,
-                                      extra_halfs, &es);
+__global__ __launch_bounds__(T) void linear_rows_rescale_kernel(const RowArgs p, const RowRescales ps) {
+    rows_body<T, 8, true, false, true, false>(p, nullptr, &ps, nullptr);
 }
+template <int T>
+__global__ __launch_bounds__(T) void linear_rows_rescale_cat_kernel(const RowArgs p, const RowRescales ps, const RowExtras es) {
+    rows_body<T, 8, true, false, true, true>(p, nullptr, &ps, &es);
+}
+
 
 int grid_for(long long n8) {
     long long g = (n8 + 255) / 256;
@@ -551,6 +407,78 @@ int row_record_status(int mode, int i, int n_src, int n_dst, const void* eps, co
         *any_row = true;
     }
     return DSC_OK;
+}
+
+// ---- the host side of the per-row entries: one check, one grid rule, one launch
+struct RowLaunch { RowArgs a; RowKnowns ks; RowRescales ps; RowExtras es; bool any_phi; };
+
+// What the five entries check, in the order of their status paragraphs (include/dsc_hip.h); fills the by-value structs.  Records:
+// `steps` (the dsc_cfg_dpmpp2m_* entries: chw % 4 == 0, D = x - sigma e written as a dsc_row_linear) or `linears` (chw % 8 == 0).
+// need_known / need_rescale / need_extras: the entry has that argument and refuses NULL; rescale is also read where it is merely
+// given (dsc_cfg_linear_step_rows_cat's may be NULL).
+int rows_check(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf, float* sigma_groups, void* tadd,
+               int tadd_halfs, int n_dst, const dsc_row_step* steps, const dsc_row_linear* linears, int n_slots, int chw, int dtype,
+               bool need_known, const dsc_row_known* known, bool need_rescale, const float* rescale,
+               bool need_extras, const dsc_row_extra* extras, int extra_halfs, RowLaunch* L) {
+    if (!x || !old || !x_in || !t_buf || !sigma_groups || !(steps || linears) || (need_known && !known) ||
+        (need_rescale && !rescale) || (need_extras && !extras) || n_src < 0 || n_dst <= 0 || chw <= 0)
+        return DSC_ERR_BAD_ARG;
+    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
+    if (extras && (extra_halfs <= 0 || extra_halfs % 8 != 0 || chw % 8 != 0)) return DSC_ERR_BAD_ARG;  // 16-byte rows of chw + extra_halfs
+    if (dtype != DSC_F16 || chw % (steps ? 4 : 8) != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps)))
+        return DSC_ERR_UNSUPPORTED;
+    *L = RowLaunch{};
+    L->a = RowArgs{static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src, static_cast<half_t*>(x_in),
+                   t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, {}};
+    L->es.halfs = extra_halfs;
+    bool any_row = false;
+    for (int i = 0; i < n_slots; ++i) {
+        dsc_row_linear r;
+        if (steps) {
+            const dsc_row_step& q = steps[i];
+            r = dsc_row_linear{q.mode, q.sigma, q.guidance, q.a, q.b, q.c, q.c_in_next, q.t_next, q.sigma_next,
+                               /* c_skip, c_out, s */ 1.0f, -q.sigma, 0.0f, q.temb_row, /* noise */ nullptr};
+        } else {
+            r = linears[i];
+        }
+        const bool step = r.mode == DSC_ROW_STEP;
+        if (known && step) {
+            if (!eps || i >= n_src) return DSC_ERR_BAD_ARG;                 // (row_record_status' line, ahead of the record's own)
+            const dsc_row_known& k = known[i];
+            const int set = (k.image != nullptr) + (k.noise != nullptr) + (k.mask != nullptr);
+            if (set != 0 && set != 3) return DSC_ERR_BAD_ARG;
+            if (set && (!al16(k.image) || !al16(k.noise) || !al16(k.mask))) return DSC_ERR_UNSUPPORTED;
+            L->ks.r[i] = k;
+        }
+        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
+        if (step && r.noise && !al16(r.noise)) return DSC_ERR_UNSUPPORTED;
+        if (step && rescale) {
+            if (!(rescale[i] >= 0.0f && rescale[i] <= 1.0f)) return DSC_ERR_BAD_ARG;      // (NaN lands here too)
+            L->ps.phi[i] = rescale[i];
+            L->any_phi |= rescale[i] > 0.0f;
+        }
+        if (extras) {
+            if (extras[i].extra && !al16(extras[i].extra)) return DSC_ERR_BAD_ARG;
+            L->es.r[i] = extras[i];
+        }
+        L->a.r[i] = r;
+    }
+    if (any_row) {
+        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
+        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
+    }
+    return DSC_OK;
+}
+
+// workgroups per slot: a row's vectors over T threads, at most 256 (the rest is strided)
+unsigned rows_grid(long long vectors, int T) {
+    const long long g = (vectors + T - 1) / T;
+    return (unsigned)(g < 1 ? 1 : (g > 256 ? 256 : g));
+}
+template <int T, int V, typename... Parts>
+int rows_launch(void (*kernel)(RowArgs, Parts...), const RowArgs& a, int n_slots, void* stream, const Parts&... parts) {
+    DSC_LAUNCH(kernel, dim3(rows_grid(a.chw / V, T), (unsigned)n_slots), dim3(T), 0, static_cast<hipStream_t>(stream), a, parts...);
+    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
 }
 }  // namespace
 
@@ -604,183 +532,52 @@ extern "C" int dsc_dpmpp2m_update(const void* x, const void* denoised, const voi
 extern "C" int dsc_cfg_dpmpp2m_step_rows(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
                                          float* sigma_groups, void* tadd, int tadd_halfs, int n_dst, const dsc_row_step* rows,
                                          int n_slots, int chw, int dtype, void* stream) {
-    if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || n_src < 0 || n_dst <= 0 || chw <= 0) return DSC_ERR_BAD_ARG;
-    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16 || chw % 4 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
-    RowSteps rs{};
-    bool any_row = false;
-    for (int i = 0; i < n_slots; ++i) {
-        const dsc_row_step& r = rows[i];
-        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
-        rs.r[i] = r;
-    }
-    if (any_row) {
-        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
-        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
-    }
-    const int V = chw % 8 == 0 ? 8 : 4;
-    const long long v8 = chw / V;
-    long long gx = (v8 + 255) / 256;
-    gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-#define DSC_STEP_ROWS(VV) DSC_LAUNCH(step_rows_kernel<VV>, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream), \
-               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src, \
-               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs)
-    if (V == 8) DSC_STEP_ROWS(8); else DSC_STEP_ROWS(4);
-#undef DSC_STEP_ROWS
-    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+    RowLaunch L;
+    if (const int st = rows_check(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, rows, nullptr, n_slots, chw,
+                                  dtype, false, nullptr, false, nullptr, false, nullptr, 0, &L)) return st;
+    return chw % 8 == 0 ? rows_launch<256, 8>(step_rows_kernel<8>, L.a, n_slots, stream)
+                        : rows_launch<256, 4>(step_rows_kernel<4>, L.a, n_slots, stream);
 }
 
 extern "C" int dsc_cfg_dpmpp2m_step_rows_known(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
                                                float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
                                                const dsc_row_step* rows, const dsc_row_known* known, int n_slots, int chw,
                                                int dtype, void* stream) {
-    if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || !known || n_src < 0 || n_dst <= 0 || chw <= 0)
-        return DSC_ERR_BAD_ARG;
-    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16 || chw % 4 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
-    RowSteps rs{};
-    RowKnowns ks{};
-    bool any_row = false;
-    for (int i = 0; i < n_slots; ++i) {
-        const dsc_row_step& r = rows[i];
-        if (r.mode == DSC_ROW_STEP) {
-            if (!eps || i >= n_src) return DSC_ERR_BAD_ARG;
-            const dsc_row_known& k = known[i];
-            const int set = (k.image != nullptr) + (k.noise != nullptr) + (k.mask != nullptr);
-            if (set != 0 && set != 3) return DSC_ERR_BAD_ARG;
-            if (set && (!al16(k.image) || !al16(k.noise) || !al16(k.mask))) return DSC_ERR_UNSUPPORTED;
-            ks.r[i] = k;
-        }
-        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
-        rs.r[i] = r;
-    }
-    if (any_row) {
-        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
-        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
-    }
-    const int V = chw % 8 == 0 ? 8 : 4;
-    const long long v8 = chw / V;
-    long long gx = (v8 + 255) / 256;
-    gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-#define DSC_STEP_KNOWN(VV) DSC_LAUNCH(step_rows_known_kernel<VV>, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream), \
-               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src, \
-               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs, ks)
-    if (V == 8) DSC_STEP_KNOWN(8); else DSC_STEP_KNOWN(4);
-#undef DSC_STEP_KNOWN
-    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+    RowLaunch L;
+    if (const int st = rows_check(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, rows, nullptr, n_slots, chw,
+                                  dtype, true, known, false, nullptr, false, nullptr, 0, &L)) return st;
+    return chw % 8 == 0 ? rows_launch<256, 8>(step_rows_known_kernel<8>, L.a, n_slots, stream, L.ks)
+                        : rows_launch<256, 4>(step_rows_known_kernel<4>, L.a, n_slots, stream, L.ks);
 }
 
 extern "C" int dsc_cfg_linear_step_rows(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
                                         float* sigma_groups, void* tadd, int tadd_halfs, int n_dst, const dsc_row_linear* rows,
                                         int n_slots, int chw, int dtype, void* stream) {
-    if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || n_src < 0 || n_dst <= 0 || chw <= 0) return DSC_ERR_BAD_ARG;
-    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16 || chw % 8 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
-    RowLinears rs{};
-    bool any_row = false;
-    for (int i = 0; i < n_slots; ++i) {
-        const dsc_row_linear& r = rows[i];
-        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
-        if (r.mode == DSC_ROW_STEP && r.noise && !al16(r.noise)) return DSC_ERR_UNSUPPORTED;
-        rs.r[i] = r;
-    }
-    if (any_row) {
-        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
-        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
-    }
-    const long long v8 = chw / 8;
-    long long gx = (v8 + 255) / 256;
-    gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-    DSC_LAUNCH(linear_rows_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
-               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
-               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs);
-    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+    RowLaunch L;
+    if (const int st = rows_check(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, nullptr, rows, n_slots, chw,
+                                  dtype, false, nullptr, false, nullptr, false, nullptr, 0, &L)) return st;
+    return rows_launch<256, 8>(linear_rows_kernel, L.a, n_slots, stream);
 }
 
 extern "C" int dsc_cfg_linear_step_rows_rescale(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
                                                 float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
                                                 const dsc_row_linear* rows, const float* rescale, int n_slots, int chw, int dtype,
                                                 void* stream) {
-    if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || !rescale || n_src < 0 || n_dst <= 0 || chw <= 0)
-        return DSC_ERR_BAD_ARG;
-    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
-    if (dtype != DSC_F16 || chw % 8 != 0 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
-    RowLinears rs{};
-    RowRescales ps{};
-    bool any_row = false;
-    for (int i = 0; i < n_slots; ++i) {
-        const dsc_row_linear& r = rows[i];
-        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
-        if (r.mode == DSC_ROW_STEP) {
-            if (r.noise && !al16(r.noise)) return DSC_ERR_UNSUPPORTED;
-            if (!(rescale[i] >= 0.0f && rescale[i] <= 1.0f)) return DSC_ERR_BAD_ARG;      // (NaN lands here too)
-            ps.phi[i] = rescale[i];
-        }
-        rs.r[i] = r;
-    }
-    if (any_row) {
-        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
-        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
-    }
-    constexpr int T = DSC_RESCALE_THREADS;
-    const long long v8 = chw / 8;
-    long long gx = (v8 + T - 1) / T;
-    gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-    DSC_LAUNCH(linear_rows_rescale_kernel<T>, dim3((unsigned)gx, (unsigned)n_slots), dim3(T), 0, static_cast<hipStream_t>(stream),
-               static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
-               static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs, ps);
-    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+    RowLaunch L;
+    if (const int st = rows_check(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, nullptr, rows, n_slots, chw,
+                                  dtype, false, nullptr, true, rescale, false, nullptr, 0, &L)) return st;
+    return rows_launch<DSC_RESCALE_THREADS, 8>(linear_rows_rescale_kernel<DSC_RESCALE_THREADS>, L.a, n_slots, stream, L.ps);
 }
 
+// the grid and the kernel of the entry this one shares its arithmetic with (the extra channels stride over the same grid)
 extern "C" int dsc_cfg_linear_step_rows_cat(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
                                             float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
                                             const dsc_row_linear* rows, const float* rescale, const dsc_row_extra* extras,
                                             int extra_halfs, int n_slots, int chw, int dtype, void* stream) {
-    if (!x || !old || !x_in || !t_buf || !sigma_groups || !rows || !extras || n_src < 0 || n_dst <= 0 || chw <= 0)
-        return DSC_ERR_BAD_ARG;
-    if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
-    if (extra_halfs <= 0 || extra_halfs % 8 != 0 || chw % 8 != 0) return DSC_ERR_BAD_ARG;     // 16-byte rows of chw + extra_halfs
-    if (dtype != DSC_F16 || !al16(x) || !al16(old) || !al16(x_in) || (eps && !al16(eps))) return DSC_ERR_UNSUPPORTED;
-    RowLinears rs{};
-    RowRescales ps{};
-    RowExtras es{};
-    bool any_row = false, any_phi = false;
-    for (int i = 0; i < n_slots; ++i) {
-        const dsc_row_linear& r = rows[i];
-        if (const int st = row_record_status(r.mode, i, n_src, n_dst, eps, r.temb_row, &any_row)) return st;
-        if (r.mode == DSC_ROW_STEP) {
-            if (r.noise && !al16(r.noise)) return DSC_ERR_UNSUPPORTED;
-            if (rescale) {
-                if (!(rescale[i] >= 0.0f && rescale[i] <= 1.0f)) return DSC_ERR_BAD_ARG;      // (NaN lands here too)
-                ps.phi[i] = rescale[i];
-                any_phi |= rescale[i] > 0.0f;
-            }
-        }
-        if (extras[i].extra && !al16(extras[i].extra)) return DSC_ERR_BAD_ARG;
-        rs.r[i] = r;
-        es.r[i] = extras[i];
-    }
-    if (any_row) {
-        if (!tadd || tadd_halfs <= 0) return DSC_ERR_BAD_ARG;
-        if (tadd_halfs % 8 != 0 || !al16(tadd)) return DSC_ERR_UNSUPPORTED;
-    }
-    // the grids of the two entries this one shares its arithmetic with (the extra channels stride over the same grid)
-    const long long v8 = chw / 8;
-    if (!any_phi) {
-        long long gx = (v8 + 255) / 256;
-        gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-        DSC_LAUNCH(linear_rows_cat_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream),
-                   static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src,
-                   static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, rs,
-                   extra_halfs, es);
-    } else {
-        constexpr int T = DSC_RESCALE_THREADS;
-        long long gx = (v8 + T - 1) / T;
-        gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-        DSC_LAUNCH(linear_rows_rescale_cat_kernel<T>, dim3((unsigned)gx, (unsigned)n_slots), dim3(T), 0,
-                   static_cast<hipStream_t>(stream), static_cast<half_t*>(x), static_cast<const half_t*>(eps),
-                   static_cast<half_t*>(old), n_src, static_cast<half_t*>(x_in), t_buf, sigma_groups, static_cast<half_t*>(tadd),
-                   tadd_halfs, n_dst, chw, rs, ps, extra_halfs, es);
-    }
-    return hipGetLastError() == hipSuccess ? DSC_OK : DSC_ERR_LAUNCH;
+    RowLaunch L;
+    if (const int st = rows_check(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, nullptr, rows, n_slots, chw,
+                                  dtype, false, nullptr, false, rescale, true, extras, extra_halfs, &L)) return st;
+    return L.any_phi ? rows_launch<DSC_RESCALE_THREADS, 8>(linear_rows_rescale_cat_kernel<DSC_RESCALE_THREADS>, L.a, n_slots, stream, L.ps, L.es)
+                     : rows_launch<256, 8>(linear_rows_cat_kernel, L.a, n_slots, stream, L.es);
 }
+

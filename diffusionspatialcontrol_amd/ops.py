@@ -1245,15 +1245,32 @@ def _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, t
         if not linear:
             recs[i] = RowStep(*head, None if tr is None else tr.data_ptr())
             continue
-        nz = r.get("noise")
-        if nz is not None and (nz.dtype != torch.float16 or nz.device != x.device or not nz.is_contiguous() or nz.numel() != chw):
-            raise ValueError(f"{what}: rows[{i}]['noise'] must be a dense fp16 [{chw}] row on {x.device}")
         # eps-prediction unless the record says otherwise: D = x - sigma * e
         recs[i] = RowLinear(*head, float(r.get("c_skip", 1.0)), float(r.get("c_out", -float(r.get("sigma", 0.0)))),
-                            float(r.get("s", 0.0)), None if tr is None else tr.data_ptr(), None if nz is None else nz.data_ptr())
+                            float(r.get("s", 0.0)), None if tr is None else tr.data_ptr(),
+                            _slot_row(what, f"rows[{i}]['noise']", r.get("noise"), chw, x.device))
     for t in (x, old, x_in, t_buf, sigma_groups, tadd):
         _drop_gn_partials(t)
     return n_dst, n_slots, chw, recs
+
+
+def _slot_row(what, name, t, n, device):
+    """address of an optional per-slot row of the per-row sampler steps - a dense fp16 [n] row on x's device - or None for None"""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float16 or t.device != device or not t.is_contiguous() or t.numel() != n:
+        raise ValueError(f"{what}: {name} must be a dense fp16 [{n}] row on {device}")
+    return t.data_ptr()
+
+
+def _step_rows_call(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, n_dst, n_slots, chw, recs, *more):
+    """the library call every per-row sampler step ends in (entry dsc_<what>); more: the entry's own arguments, which follow the
+    records (ctypes arrays go as pointers)"""
+    more = [ctypes.cast(m, ctypes.c_void_p) if isinstance(m, ctypes.Array) else m for m in more]
+    rc = getattr(_lib.load_library(), "dsc_" + what)(
+        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
+        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), *more, n_slots, chw, 0, _stream_ptr(x))
+    _lib.check(rc, "dsc_" + what)
 
 
 def cfg_dpmpp2m_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=None):
@@ -1262,11 +1279,9 @@ def cfg_dpmpp2m_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, t
     tadd (the bucket that runs next, n' = t_buf.numel() // 2); sigma_groups [n'] fp32.  rows: one dict per slot with `mode`
     (ROW_STEP / ROW_JOIN / ROW_IDLE), the scalars of dsc_row_step and `temb_row` (an fp16 [tadd width] tensor or None); at least
     n' of them.  x / old hold at least len(rows) latent rows."""
-    n_dst, n_slots, chw, recs = _step_rows_args("cfg_dpmpp2m_step_rows", x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd)
-    rc = _lib.load_library().dsc_cfg_dpmpp2m_step_rows(
-        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
-        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), n_slots, chw, 0, _stream_ptr(x))
-    _lib.check(rc, "dsc_cfg_dpmpp2m_step_rows")
+    what = "cfg_dpmpp2m_step_rows"
+    _step_rows_call(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd,
+                    *_step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd))
 
 
 def cfg_linear_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=None):
@@ -1278,11 +1293,8 @@ def cfg_linear_step_rows(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, ta
     what = "cfg_linear_step_rows"
     if any(phi > 0.0 for phi in _row_rescales(what, rows)):
         return cfg_linear_step_rows_rescale(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=tadd)
-    n_dst, n_slots, chw, recs = _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=True)
-    rc = _lib.load_library().dsc_cfg_linear_step_rows(
-        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
-        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), n_slots, chw, 0, _stream_ptr(x))
-    _lib.check(rc, what)
+    _step_rows_call(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd,
+                    *_step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=True))
 
 
 def _row_rescales(what, rows):
@@ -1302,13 +1314,8 @@ def cfg_linear_step_rows_rescale(x, eps, old, n_src, x_in, t_buf, sigma_groups, 
     whole row inside the same launch; a slot with phi == 0 carries cfg_linear_step_rows' bits."""
     what = "cfg_linear_step_rows_rescale"
     phis = _row_rescales(what, rows)
-    n_dst, n_slots, chw, recs = _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=True)
-    phi = (ctypes.c_float * n_slots)(*phis)
-    rc = _lib.load_library().dsc_cfg_linear_step_rows_rescale(
-        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
-        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), ctypes.cast(phi, ctypes.c_void_p),
-        n_slots, chw, 0, _stream_ptr(x))
-    _lib.check(rc, what)
+    args = _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=True)
+    _step_rows_call(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, *args, (ctypes.c_float * len(phis))(*phis))
 
 
 class RowExtra(ctypes.Structure):
@@ -1332,21 +1339,9 @@ def cfg_linear_step_rows_cat(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows
     extra_halfs = x_in.numel() // (2 * n_dst) - chw
     if len(extras) != n_slots:
         raise ValueError(f"{what}: {len(extras)} extras for {n_slots} slots")
-    ex = (RowExtra * n_slots)()
-    for i, t in enumerate(extras):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float16 or t.device != x.device or not t.is_contiguous() \
-                or t.numel() != extra_halfs:
-            raise ValueError(f"{what}: extras[{i}] must be a dense fp16 [{extra_halfs}] row on {x.device}")
-        ex[i] = RowExtra(t.data_ptr())
+    ex = (RowExtra * n_slots)(*(RowExtra(_slot_row(what, f"extras[{i}]", t, extra_halfs, x.device)) for i, t in enumerate(extras)))
     phi = (ctypes.c_float * n_slots)(*phis) if any(p > 0.0 for p in phis) else None
-    rc = _lib.load_library().dsc_cfg_linear_step_rows_cat(
-        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
-        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p),
-        None if phi is None else ctypes.cast(phi, ctypes.c_void_p), ctypes.cast(ex, ctypes.c_void_p), extra_halfs,
-        n_slots, chw, 0, _stream_ptr(x))
-    _lib.check(rc, what)
+    _step_rows_call(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, n_dst, n_slots, chw, recs, phi, ex, extra_halfs)
 
 
 class RowKnown(ctypes.Structure):
@@ -1369,18 +1364,9 @@ def cfg_dpmpp2m_step_rows_known(x, eps, old, n_src, x_in, t_buf, sigma_groups, r
     for i, k in enumerate(known):
         if k is None:
             continue
-        ptrs = []
-        for name in ("image", "noise", "mask"):
-            t = k.get(name)
-            if t is not None and (t.dtype != torch.float16 or t.device != x.device or not t.is_contiguous() or t.numel() != chw):
-                raise ValueError(f"{what}: known[{i}][{name!r}] must be a dense fp16 [{chw}] row on {x.device}")
-            ptrs.append(None if t is None else t.data_ptr())
+        ptrs = [_slot_row(what, f"known[{i}][{name!r}]", k.get(name), chw, x.device) for name in ("image", "noise", "mask")]
         kn[i] = RowKnown(*ptrs, int(bool(k.get("blend_now"))), int(bool(k.get("blend_next"))))
-    rc = _lib.load_library().dsc_cfg_dpmpp2m_step_rows_known(
-        _p(x), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
-        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), ctypes.cast(kn, ctypes.c_void_p),
-        n_slots, chw, 0, _stream_ptr(x))
-    _lib.check(rc, what)
+    _step_rows_call(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, n_dst, n_slots, chw, recs, kn)
 
 
 def dpmpp2m_update(x, denoised, old, a, b, c):

@@ -37,7 +37,9 @@ def _gen(seed):
 # slot:  0 STEP (eps scalars)   1 STEP + noise (v scalars)   2 JOIN   3 IDLE (handed a row all the same: zeros)
 #        4 STEP, extra = None (v scalars)   5 STEP at i >= n_dst (a request that leaves; eps scalars)
 MODES, N_SRC, N_DST = "SSJISS", 6, 5
-SHAPES = [(64, 80), (288, 360), (1024, 1280), (16384, 20480)]
+# (2056, 8): 257 latent vectors - a second workgroup with one live lane - and a single vector of extra channels;
+# (8200, 16): 1025 vectors - the second pass of an owned slot's 1024-thread loop with one live lane
+SHAPES = [(64, 80), (288, 360), (1024, 1280), (16384, 20480), (2056, 8), (8200, 16)]
 
 
 def _case(ops, chw, eh, rescale=()):

@@ -53,7 +53,7 @@ def _recs(ops, modes, tabs):
     return recs
 
 
-@pytest.mark.parametrize("chw", [1024, 16384])
+@pytest.mark.parametrize("chw", [1024, 2056, 16384])
 @pytest.mark.parametrize("n_src, n_dst, modes", [(2, 4, "SSJI"), (4, 2, "SISI"), (4, 4, "JSIS"), (3, 3, "SSS")])
 def test_eps_prediction_without_noise_is_the_dpmpp2m_op(ops, chw, n_src, n_dst, modes):
     """c_skip = 1, c_out = -sigma, no noise row (spelled out, and as the wrapper's defaults): every output buffer carries the
@@ -83,7 +83,7 @@ def _restate(x, eu, ec, old, p, noise):
     return xn.half(), d.half(), (xn * cn).half()
 
 
-@pytest.mark.parametrize("chw", [1024, 16384])
+@pytest.mark.parametrize("chw", [1024, 2056, 16384])
 def test_noise_and_v_scalars_against_the_formulas(ops, chw):
     """slots: v-prediction scalars with noise, v without noise, JOIN, eps-prediction with noise, IDLE, a leaving slot at
     i >= n_dst with noise.  STEP slots: at most 1 fp16 ulp from the restated formulas (the bound of the known-region kernel's
@@ -145,6 +145,24 @@ def test_argument_status(ops):
     assert call([rec(ops.ROW_STEP, temb=0x2000), step], tadd=None) == -1                    # a row but no destination
     assert call([rec(ops.ROW_STEP, temb=0x2000), step], tw=100) == -2
     assert ctypes.sizeof(ops.RowLinear) == 64 and 16 * ctypes.sizeof(ops.RowLinear) <= 1024  # well inside the 4 KB kernarg segment
+
+
+def test_linear_entries_refuse_8_byte_rows(ops):
+    """chw = 1444 (19 x 19 latents: 361 four-half vectors).  The linear, rescale and cat entries move 8 halfs per lane: each is
+    refused before any launch, nothing written - such rows stay with dsc_cfg_dpmpp2m_step_rows and its known-region form"""
+    chw, n = 1444, 2
+    x, eps, old = _h(n, chw, seed=81), _h(2 * n, chw, seed=82), _h(n, chw, seed=83)
+    recs = [_params(i) for i in range(n)]
+    rescaled = [dict(r, rescale=0.7) for r in recs]
+    for fn, rs, more, row in ((ops.cfg_linear_step_rows, recs, (), chw), (ops.cfg_linear_step_rows_rescale, rescaled, (), chw),
+                              (ops.cfg_linear_step_rows_cat, recs, ([None, None],), chw + 8)):
+        xr, oldr = x.clone(), old.clone()
+        x_in = torch.full((2 * n, row), 7.0, dtype=torch.float16, device="cuda")
+        t, s = torch.full((2 * n,), -1.0, device="cuda"), torch.full((n,), -1.0, device="cuda")
+        with pytest.raises(dsc.DscLibraryError):
+            fn(xr, eps, oldr, n, x_in, t, s, rs, *more)
+        torch.cuda.synchronize()
+        assert torch.equal(xr, x) and torch.equal(oldr, old) and (x_in == 7.0).all() and (t == -1.0).all() and (s == -1.0).all()
 
 
 def test_code_object_has_no_scratch_or_spill():

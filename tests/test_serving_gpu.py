@@ -41,7 +41,7 @@ def _scalar_step(ops, x, eps_u, eps_c, old, p, tab_row):
 
 
 def _rows_call(ops, x, eps, old, n_src, n_dst, recs):
-    x_in = torch.full((2 * n_dst, 4, 16, 16), 7.0, dtype=torch.float16, device="cuda")
+    x_in = torch.full((2 * n_dst, *x.shape[1:]), 7.0, dtype=torch.float16, device="cuda")
     t = torch.full((2 * n_dst,), -1.0, device="cuda")
     s = torch.full((n_dst,), -1.0, device="cuda")
     tadd = torch.zeros(2 * n_dst, TW, dtype=torch.float16, device="cuda")
@@ -74,13 +74,20 @@ def test_step_rows_uniform_equals_scalar_kernel(ops):
     assert torch.equal(got[2], s.expand(n))
 
 
-@pytest.mark.parametrize("n_src, n_dst, modes", [(2, 4, "SSJI"), (4, 2, "SIS I".replace(" ", "")), (4, 4, "JSIS")])
-def test_step_rows_mixed_modes_equal_per_slot_kernels(ops, n_src, n_dst, modes):
+# rows of 1024 halfs, and two lengths with a partial tail: 1444 = 361 four-half vectors (19 x 19 latents: 8-byte rows, a second
+# workgroup with 105 live lanes), 2056 = 257 eight-half vectors (a second workgroup with one live lane)
+MIXED = [pytest.param(*m, shape, id="-".join(map(str, m)) + tag)
+         for shape, tag in (((4, 16, 16), ""), ((4, 19, 19), "-1444"), ((4, 2, 257), "-2056"))
+         for m in [(2, 4, "SSJI"), (4, 2, "SISI"), (4, 4, "JSIS")]]
+
+
+@pytest.mark.parametrize("n_src, n_dst, modes, shape", MIXED)
+def test_step_rows_mixed_modes_equal_per_slot_kernels(ops, n_src, n_dst, modes, shape):
     """STEP / JOIN / IDLE mix with distinct scalars per slot, including bucket changes (n_src != n_dst): every slot equals the
     scalar kernel (or prepare_unet_input) run on that slot alone; IDLE slots write zeros and sigma 1"""
     n_slots = len(modes)
-    x, old = _h(n_slots, 4, 16, 16, seed=11), _h(n_slots, 4, 16, 16, seed=12)
-    eps = _h(2 * n_src, 4, 16, 16, seed=13)
+    x, old = _h(n_slots, *shape, seed=11), _h(n_slots, *shape, seed=12)
+    eps = _h(2 * n_src, *shape, seed=13)
     tabs = [_h(TW, seed=20 + i) for i in range(n_slots)]
     recs = []
     for i, m in enumerate(modes):
@@ -101,7 +108,7 @@ def test_step_rows_mixed_modes_equal_per_slot_kernels(ops, n_src, n_dst, modes):
                 assert torch.equal(x_in[rows], ex[2]) and torch.equal(t[rows], ex[3]), (modes, i)
                 assert s[i].item() == ex[4].item() and torch.equal(tadd[rows], ex[5]), (modes, i)
         elif m == "J":
-            x_in1 = torch.empty(2, 4, 16, 16, dtype=torch.float16, device="cuda")
+            x_in1 = torch.empty(2, *shape, dtype=torch.float16, device="cuda")
             t1, s1 = torch.empty(2, device="cuda"), torch.empty(1, device="cuda")
             ops.prepare_unet_input(x[i:i + 1].clone(), p["c_in_next"], p["t_next"], p["sigma_next"], x_in1, t1, s1)
             torch.cuda.synchronize()
@@ -112,6 +119,39 @@ def test_step_rows_mixed_modes_equal_per_slot_kernels(ops, n_src, n_dst, modes):
             assert torch.equal(xr[i], x[i]) and torch.equal(oldr[i], old[i]), (modes, i)
             if i < n_dst:
                 assert not x_in[rows].any() and s[i].item() == 1.0 and not tadd[rows].any(), (modes, i)
+
+
+def test_step_rows_clamped_grid_every_entry_equals_the_scalar_kernel(ops):
+    """chw = 524296: 65537 eight-half vectors per row, so the grid clamps at 256 workgroups per slot and one of them strides a
+    second time.  Two STEP slots: dsc_cfg_dpmpp2m_step_rows, dsc_cfg_linear_step_rows, the known-region entry without a known
+    region and x_in[:, :chw] of dsc_cfg_linear_step_rows_cat carry the same bits - those of the scalar kernel on each slot alone"""
+    chw, n, eh = 524296, 2, 8
+    x, old, eps = _h(n, chw, seed=91), _h(n, chw, seed=92), _h(2 * n, chw, seed=93)
+    tabs = [_h(TW, seed=94 + i) for i in range(n)]
+    recs = [dict(_params(i), temb_row=tabs[i]) for i in range(n)]
+
+    def run(fn, *more, row=chw):
+        xr, oldr = x.clone(), old.clone()
+        x_in = torch.full((2 * n, row), 7.0, dtype=torch.float16, device="cuda")
+        t, s = torch.full((2 * n,), -1.0, device="cuda"), torch.full((n,), -1.0, device="cuda")
+        tadd = torch.zeros(2 * n, TW, dtype=torch.float16, device="cuda")
+        fn(xr, eps, oldr, n, x_in, t, s, recs, *more, tadd=tadd)
+        torch.cuda.synchronize()
+        return xr, oldr, x_in[:, :chw], t, s, tadd
+
+    rows = run(ops.cfg_dpmpp2m_step_rows)
+    others = {"linear": run(ops.cfg_linear_step_rows), "known": run(ops.cfg_dpmpp2m_step_rows_known, [None, None]),
+              "cat": run(ops.cfg_linear_step_rows_cat, [_h(eh, seed=96), None], row=chw + eh)}
+    for entry, got in others.items():
+        for name, a, b in zip(("x", "old", "x_in", "t", "sigma_groups", "tadd"), got, rows):
+            assert torch.equal(a, b), (entry, name)
+    for i in range(n):
+        pair = [i, n + i]
+        ex = _scalar_step(ops, x[i:i + 1], eps[i:i + 1], eps[n + i:n + i + 1], old[i:i + 1], recs[i], tabs[i])
+        torch.cuda.synchronize()
+        assert torch.equal(rows[0][i:i + 1], ex[0]) and torch.equal(rows[1][i:i + 1], ex[1]), i
+        assert torch.equal(rows[2][pair], ex[2]) and torch.equal(rows[3][pair], ex[3]), i
+        assert rows[4][i].item() == ex[4].item() and torch.equal(rows[5][pair], ex[5]), i
 
 
 # ----------------------------------------------------------------------------- per-group sigma in the region cross-attention

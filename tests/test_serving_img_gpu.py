@@ -91,7 +91,7 @@ def _ulps(a, b):
     return (key(a) - key(b)).abs().max().item()
 
 
-@pytest.mark.parametrize("chw", [1024, 16384])
+@pytest.mark.parametrize("chw", [1024, 1444, 2056, 16384])
 @pytest.mark.parametrize("n_src, n_dst, modes", [(2, 4, "SSJI"), (4, 2, "SISI"), (4, 4, "JSIS")])
 def test_known_all_null_is_the_plain_op(ops, chw, n_src, n_dst, modes):
     """no slot has a known region: every output buffer carries the bits of dsc_cfg_dpmpp2m_step_rows"""
@@ -135,7 +135,7 @@ def test_known_mask_of_ones_and_mask_of_zeros(ops, chw):
     assert not torch.equal(got[0], other[0])
 
 
-@pytest.mark.parametrize("chw", [1024, 16384])
+@pytest.mark.parametrize("chw", [1024, 1444, 2056, 16384])
 def test_known_mixed_slots_against_the_formulas(ops, chw):
     """half / half 0-1 mask; slots: known (both blends), plain STEP, JOIN, a known slot on its first step (blend_next only)
     IDLE, and a known slot at i >= n_dst that leaves (blend_now only).  Known slots: at most 1 fp16 ulp from the restated
@@ -149,8 +149,8 @@ def test_known_mixed_slots_against_the_formulas(ops, chw):
     mask[chw // 2:] = 1.0
     flags = {0: (True, True), 3: (False, True), 5: (True, False)}
     known = [None] * 6
-    for i, (now, nxt) in flags.items():
-        known[i] = {"image": img[i], "noise": noise[i], "mask": mask, "blend_now": now, "blend_next": nxt}
+    for i, (now, nxt) in flags.items():       # (clones: row i of a [6, 1444] tensor is 8-byte aligned only, the entry wants 16)
+        known[i] = {"image": img[i].clone(), "noise": noise[i].clone(), "mask": mask, "blend_now": now, "blend_next": nxt}
     known[2] = {"image": img[2], "noise": noise[2], "mask": mask, "blend_now": True, "blend_next": True}      # JOIN ignores it
     plain = _call(ops, chw, x, eps, old, n_src, n_dst, recs)
     got = _call(ops, chw, x, eps, old, n_src, n_dst, recs, known=known)

@@ -168,6 +168,34 @@ def graph_launch_us(fn, launches=100, replays=3):
     return out
 
 
+def step_rows_kernel_us(rounds=3):
+    """device microseconds per launch of the five per-row sampler entries on 8 STEP slots of a 4 x 64 x 64 latent, `rounds`
+    alternating figures each -> (slots, extra_halfs, {entry: [us, ...]}).  One slot of the rescale entry has phi > 0 (its row
+    belongs to one workgroup), one slot of the known entry a known region with both blends on"""
+    from diffusionspatialcontrol_amd import ops
+    n, chw, eh = 8, 4 * 64 * 64, 5 * 64 * 64
+    h = lambda *shape: torch.randn(*shape, device="cuda").half()      # noqa: E731
+    x, eps, old = h(n, chw), h(2 * n, chw), h(n, chw)
+    t, sg = torch.zeros(2 * n, device="cuda"), torch.ones(n, device="cuda")
+    x4, x9 = torch.zeros(2 * n, chw, device="cuda").half(), torch.zeros(2 * n, chw + eh, device="cuda").half()
+    ex = [h(eh) for _ in range(n)]
+    recs = [{"mode": ops.ROW_STEP, "sigma": 2.0, "guidance": 7.5, "a": 1.0, "b": 0.0, "c": 0.0, "c_skip": 1.0, "c_out": -2.0,
+             "c_in_next": 0.4, "t_next": 500.0, "sigma_next": 1.5} for _ in range(n)]      # (a = 1, b = c = 0: x stays x)
+    resc = [dict(recs[0], rescale=0.7)] + recs[1:]
+    known = [{"image": h(chw), "noise": h(chw), "mask": (torch.rand(chw, device="cuda") < 0.5).half(), "blend_now": True,
+              "blend_next": True}] + [None] * (n - 1)
+    entries = {"cfg_dpmpp2m_step_rows": lambda: ops.cfg_dpmpp2m_step_rows(x, eps, old, n, x4, t, sg, recs),
+               "cfg_dpmpp2m_step_rows_known": lambda: ops.cfg_dpmpp2m_step_rows_known(x, eps, old, n, x4, t, sg, recs, known),
+               "cfg_linear_step_rows": lambda: ops.cfg_linear_step_rows(x, eps, old, n, x4, t, sg, recs),
+               "cfg_linear_step_rows_rescale": lambda: ops.cfg_linear_step_rows_rescale(x, eps, old, n, x4, t, sg, resc),
+               "cfg_linear_step_rows_cat": lambda: ops.cfg_linear_step_rows_cat(x, eps, old, n, x9, t, sg, recs, ex)}
+    us = {name: [] for name in entries}
+    for _ in range(rounds):
+        for name, fn in entries.items():
+            us[name] += graph_launch_us(fn, replays=1)
+    return n, eh, us
+
+
 def run_full(b, reqs, kw):
     """(images/s, sampler steps/s) of one batcher with its slots kept full by these requests"""
     torch.cuda.synchronize()
@@ -259,7 +287,6 @@ def main():
 
     if a.inpaint_unet:
         import dataclasses
-        from diffusionspatialcontrol_amd import ops
         torch.manual_seed(1)
         with torch.device("cuda"):
             unet9 = UNet2DConditionModel(dataclasses.replace(UNetConfig.sd15(), in_channels=9))
@@ -295,21 +322,10 @@ def main():
                 ms[mode].append(round(1e3 * (time.perf_counter() - t0) / 4, 2))
         emit(leg="inpaint_unet_one_at_a_time", steps=25, size="512x512", fused_ms_per_image=ms[True], protocol_ms_per_image=ms[False],
              note="inpaiting(fused=True) against fused=False (eager protocol mode) on the 9-channel UNet, three alternating runs of four")
-        n, chw, eh = 8, 4 * 64 * 64, 5 * 64 * 64
-        h = lambda *shape: torch.randn(*shape, device="cuda").half()      # noqa: E731
-        x, eps, old = h(n, chw), h(2 * n, chw), h(n, chw)
-        t, sg = torch.zeros(2 * n, device="cuda"), torch.ones(n, device="cuda")
-        x4, x9 = torch.zeros(2 * n, chw, device="cuda").half(), torch.zeros(2 * n, chw + eh, device="cuda").half()
-        ex = [h(eh) for _ in range(n)]
-        recs = [{"mode": ops.ROW_STEP, "sigma": 2.0, "guidance": 7.5, "a": 1.0, "b": 0.0, "c": 0.0, "c_skip": 1.0, "c_out": -2.0,
-                 "c_in_next": 0.4, "t_next": 500.0, "sigma_next": 1.5} for _ in range(n)]      # (a = 1, b = c = 0: x stays x)
-        us = {"cfg_linear_step_rows": [], "cfg_linear_step_rows_cat": []}
-        for _ in range(3):
-            us["cfg_linear_step_rows"] += graph_launch_us(lambda: ops.cfg_linear_step_rows(x, eps, old, n, x4, t, sg, recs), replays=1)
-            us["cfg_linear_step_rows_cat"] += graph_launch_us(lambda: ops.cfg_linear_step_rows_cat(x, eps, old, n, x9, t, sg, recs, ex),
-                                                              replays=1)
+        n, eh, us = step_rows_kernel_us()
         emit(leg="inpaint_unet_kernel", slots=n, latent="4x64x64", extra_halfs=eh, device_us_per_launch=us,
-             note="a captured graph of 100 launches per figure, alternating; the cat entry reads 5/4 and writes 10/4 of a latent more")
+             note="a captured graph of 100 launches per figure, alternating; one slot of the rescale entry has phi > 0 and one of the "
+                  "known entry a known region; the cat entry reads 5/4 and writes 10/4 of a latent more")
         emit(leg="stats", four_channel=plain.stats(), nine_channel=inp.stats())
         return
 
