@@ -329,29 +329,22 @@ class _RegionProcessor:
             # self-attention: q, k, v from ONE [3C, C] GEMM; the three [B, L, H, d] operands are strided views of it
             B, L, _ = hidden_states.shape
             wq = fused_qkv()
+            w2, b2, ln = _ln_fold.folded(attn, "qkv", wq) if _ln_fold is not None else (wq, None, None)
             if ops.linear_qkv_covers(hidden_states, wq, H):
                 # the GEMM's epilogue writes K / V head-major: the flash kernel's key tiles are then contiguous DMA pieces
-                if _ln_fold is not None:
-                    w2, b2, cvec = _ln_fold.folded(attn, "qkv", wq)
-                    q4, k4, v4 = ops.linear_qkv(hidden_states, w2, b2, H, ln=(_ln_fold.stats, cvec, _ln_fold.norm.eps))
-                else:
-                    q4, k4, v4 = ops.linear_qkv(hidden_states, wq, None, H)
+                q4, k4, v4 = ops.linear_qkv(hidden_states, w2, b2, H, ln=ln)
                 C = wq.shape[0] // 3
                 d = C // H
             else:
-                if _ln_fold is not None:
-                    w2, b2, cvec = _ln_fold.folded(attn, "qkv", wq)
-                    qkv = ops.linear_ln(hidden_states, w2, b2, ln=(_ln_fold.stats, cvec, _ln_fold.norm.eps))
-                else:
-                    qkv = ops.linear(hidden_states, wq)
+                qkv = ops.linear_ln(hidden_states, w2, b2, ln=ln) if ln is not None else ops.linear(hidden_states, wq)
                 C = qkv.shape[-1] // 3
                 d = C // H
                 q4, k4, v4 = (qkv[..., i * C:(i + 1) * C].unflatten(-1, (H, d)) for i in range(3))
             S = L
         else:
             if _ln_fold is not None:
-                w2, b2, cvec = _ln_fold.folded(attn, "q", attn.to_q.weight, attn.to_q.bias)
-                query = ops.linear_ln(hidden_states, w2, b2, ln=(_ln_fold.stats, cvec, _ln_fold.norm.eps))
+                w2, b2, ln = _ln_fold.folded(attn, "q", attn.to_q.weight, attn.to_q.bias)
+                query = ops.linear_ln(hidden_states, w2, b2, ln=ln)
             else:
                 query = ops.linear(hidden_states, attn.to_q.weight, attn.to_q.bias) if type(attn.to_q) is nn.Linear \
                     else attn.to_q(hidden_states)
@@ -420,11 +413,7 @@ class _RegionProcessor:
         to_out = attn.to_out[0]
         if _ln_fold is not None:
             # the block's `x = attn(norm(x)) + x` add and the next LayerNorm's row statistics ride in this GEMM's epilogue
-            res = _ln_fold.residual
-            if res.shape[0] != hidden_states.shape[0] and ((res.shape[0] * res.shape[1]) % 128 != 0 or not ops.USE_RESIDUAL_WRAP):
-                # shared CFG prefix: the residual stream was computed once per image.  The GEMM wraps a residual of fewer rows
-                # itself (dsc_linear_f16: row m adds residual row m % R) when R is a multiple of its row tiles; else repeat
-                res = res.repeat(hidden_states.shape[0] // res.shape[0], 1, 1)
+            res = ops.residual_for_batch(_ln_fold.residual, hidden_states.shape[0])    # shared CFG prefix: computed once per image
             return ops.linear_ln(hidden_states, to_out.weight, to_out.bias, residual=res, ln_stats=True)
         hidden_states = ops.linear(hidden_states, to_out.weight, to_out.bias) if type(to_out) is nn.Linear \
             else to_out(hidden_states)

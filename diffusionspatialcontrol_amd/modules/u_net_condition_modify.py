@@ -305,7 +305,7 @@ def _with_gn(img, part):
 
 
 class Conv1x1(nn.Conv2d):
-    """1x1 convolution run as a token-major GEMM (hipBLASLt) instead of a MIOpen convolution: same parameters and
+    """1x1 convolution run as a token-major GEMM (ops.linear / ops.linear_gn) instead of a MIOpen convolution: same parameters and
     state_dict keys as nn.Conv2d(cin, cout, 1).  With channels-last activations the [B, h*w, C] token view is free,
     and MIOpen's 1x1 kernels at small spatial sizes accumulate with atomics (measured: run-to-run differences of 3e-2
     at 128->64 @ 2x2) while the GEMM is bit-reproducible."""
@@ -459,10 +459,12 @@ class LNFold:
         self.norm, self.stats, self.residual = norm, stats, residual
 
     def folded(self, owner, key, weight, bias=None):
-        """(W diag(gamma), W beta + b, row sums) of `weight` under self.norm, cached on `owner`"""
+        """(W diag(gamma), W beta + b) of `weight` under self.norm, cached on `owner`, and the `ln=` argument of ops.linear_ln /
+        linear_qkv that goes with them: (self.stats, the row sums of the folded weight, eps)"""
         n = self.norm
         deps = (weight, n.weight, n.bias) + (() if bias is None else (bias,))
-        return _derived(owner, "lnfold_" + key, deps, lambda: ops.fold_layernorm(weight, bias, n.weight, n.bias))
+        w2, b2, cvec = _derived(owner, "lnfold_" + key, deps, lambda: ops.fold_layernorm(weight, bias, n.weight, n.bias))
+        return w2, b2, (self.stats, cvec, n.eps)
 
 
 class BasicTransformerBlock(nn.Module):
@@ -500,9 +502,8 @@ class BasicTransformerBlock(nn.Module):
         if ops.USE_LN_FOLD and self._can_fold(x, stats, prepared_ip_rows(kw.get("region_prompt")) is not None):
             x, st = self.attn1(x, None, _ln_fold=LNFold(self.norm1, stats, x), **kw)
             x, st = self.attn2(x, encoder_hidden_states, _ln_fold=LNFold(self.norm2, st, x), **kw)
-            f = LNFold(self.norm3, st, None)
-            w2, b2, cvec = f.folded(self.ff, "geglu", self.ff.net[0].proj.weight, self.ff.net[0].proj.bias)
-            h = ops.linear_ln(x, w2, b2, geglu=True, ln=(st, cvec, self.norm3.eps))
+            w2, b2, ln = LNFold(self.norm3, st, None).folded(self.ff, "geglu", self.ff.net[0].proj.weight, self.ff.net[0].proj.bias)
+            h = ops.linear_ln(x, w2, b2, geglu=True, ln=ln)
             return ops.linear(h, self.ff.net[2].weight, self.ff.net[2].bias, residual=x)
         # `x = attn(norm(x)) + x; h = next_norm(x)` pairs run as ONE add+LayerNorm launch (the same kwargs reach self-
         # and cross-attention, as in diffusers' BasicTransformerBlock)
@@ -540,11 +541,7 @@ class Transformer2DModel(nn.Module):
             t = self.proj_in(t) if self.use_linear_projection else self.proj_in.tokens(t)
         for i, blk in enumerate(self.transformer_blocks):
             t = blk(t, encoder_hidden_states, cross_attention_kwargs, stats=st if i == 0 else None)
-        res = _tokens(x)
-        if res.shape[0] != t.shape[0] and not (res.is_cuda and ops.USE_RESIDUAL_WRAP and (res.shape[0] * res.shape[1]) % 128 == 0):
-            # shared CFG prefix: x came in once per image.  (On the GPU the GEMM wraps a residual of fewer rows itself:
-            # ops.linear / linear_gn, dsc_linear_f16.)
-            res = res.repeat(t.shape[0] // res.shape[0], 1, 1)
+        res = ops.residual_for_batch(_tokens(x), t.shape[0])    # shared CFG prefix: x came in once per image
         if self.use_linear_projection:
             t = ops.linear(t, self.proj_out.weight, self.proj_out.bias, residual=res)
             return _image(t, h, w)

@@ -1,6 +1,7 @@
 """Thin torch-tensor wrappers over the C ABI (include/dsc_hip.h).  torch is plumbing here: device memory,
 the current HIP stream and strides; all arithmetic happens in libdsc_hip.so."""
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -524,19 +525,17 @@ def conv3x3_gn(x, weight, groups, bias=None, add=None, residual=None, upsample=F
 def linear_gn(x, weight, bias, residual, rows_per_image, groups):
     """x [B, L, K] @ weight.T (+ bias) (+ residual) -> [B, L, N] with the GroupNorm partial sums of the result (a 1x1 convolution
     in token-major form: proj_out, conv_shortcut), or None when dsc_linear_gn_f16 does not cover the shape"""
-    if not USE_GN_FUSE or not x.is_cuda or x.dtype != torch.float16 or x.dim() != 3:
+    got = USE_GN_FUSE and x.is_cuda and x.dim() == 3 and x.shape[1] == rows_per_image and _gemm_operands(x, weight, bias, residual)
+    if not got:
         return None
+    x2, r2, ldr = got
     lib = _lib.load_library()
     B, L, K = x.shape
     N = weight.shape[0]
     M = B * L
-    if L != rows_per_image or not weight.is_contiguous() or weight.dtype != torch.float16:
-        return None
     rows = int(lib.dsc_linear_gn_rows(M, N, K, rows_per_image, groups))
-    if rows <= 0 or not linear_kernel_can(x, weight, bias, residual):
+    if rows <= 0:
         return None
-    x2 = x.reshape(M, K)
-    r2, ldr = _residual_2d(residual, M, N) if residual is not None else (None, 0)
     out = torch.empty((M, N), dtype=x.dtype, device=x.device)
     part = torch.empty((B, rows, groups, 2, 2), dtype=torch.float32, device=x.device)
     rc = lib.dsc_linear_gn_f16(_p(x2), _p(weight), _p(bias), _p(r2), _p(out), M, N, K, x2.stride(0),
@@ -548,38 +547,60 @@ def linear_gn(x, weight, bias, residual, rows_per_image, groups):
 USE_RESIDUAL_WRAP = os.environ.get("DSC_RESIDUAL_WRAP", "1") != "0"   # (A/B switch: 0 = repeat a shorter residual on the host, as before)
 
 
+def _residual_wraps(R):
+    """the GEMM kernels add residual row m % R to row m themselves when R is a multiple of their 128-row tile"""
+    return USE_RESIDUAL_WRAP and R % 128 == 0
+
+
+def residual_for_batch(residual, batch):
+    """the [b, L, N] residual stream of a GEMM whose result has `batch` = k b images (shared CFG prefix: the stream was computed
+    once per image): itself where the kernels wrap its rows, else repeated k times"""
+    b, L = residual.shape[:2]
+    return residual if b == batch or _residual_wraps(b * L) else residual.repeat(batch // b, 1, 1)
+
+
 def _residual_2d(residual, M, N):
-    """(r2, ldr) for the GEMM entry points: the residual as [R, N] rows and its row stride, with R << 32 in the stride's high
-    bits when it has fewer rows than the result (include/dsc_hip.h, dsc_linear_f16: row m adds residual row m % R - a residual
-    stream computed once per image under the shared CFG prefix); None when the shape is not one the kernels take."""
+    """(r2, ldr) for the GEMM entry points: the residual as [R, N] rows and its row stride, with R << 32 in the stride's high bits
+    when it has fewer rows than the result (include/dsc_hip.h, dsc_linear_f16); None when the kernels do not take the shape."""
     R = residual.numel() // N
-    if R * N != residual.numel() or R <= 0 or M % R != 0:
+    if R * N != residual.numel() or R <= 0 or M % R != 0 or not (R == M or _residual_wraps(R)):
         return None
     r2 = residual.reshape(R, N)
     if r2.stride(1) != 1 or r2.stride(0) % 8 != 0 or r2.data_ptr() % 16 != 0:
         return None
-    if R == M:
-        return r2, r2.stride(0)
-    if R % 128 != 0 or not USE_RESIDUAL_WRAP:
-        return None
-    return r2, r2.stride(0) | (R << 32)
+    return r2, r2.stride(0) | (R << 32 if R != M else 0)
+
+
+def _gemm_shape(N, K, dtype, geglu=False):
+    """the shapes gemm_tn_f16 is built for: fp16, 64-column tiles, 64-deep K steps, a GEGLU pair in one 64-column tile"""
+    return dtype == torch.float16 and K % 64 == 0 and N % 64 == 0 and (not geglu or (N // 2) % 32 == 0)
+
+
+def _gemm_operands(x, weight, bias=None, residual=None, geglu=False, must=None):
+    """(x2, r2, ldr) when the package's GEMM entry points (gemm.hip: dsc_linear_f16 / _ln_f16 / _qkv_f16 / _gn_f16 / _splitk_f16)
+    can read these operands, else None - or a ValueError in the name of `must`, an entry point with no other route: fp16 only (the
+    C ABI sees no dtypes), _gemm_shape, unit inner strides, row strides in 8s, 16-byte aligned pointers, a contiguous weight, GEGLU
+    only with a bias and no residual, the residual as in _residual_2d.  x2 = x as [M, K]: a copy only where x does not collapse.
+    An x whose last dimension is not the weight's K is a RuntimeError for every caller, as from the reshape or F.linear before."""
+    N, K = weight.shape
+    if x.shape[-1] != K:
+        raise RuntimeError(f"{must or 'linear'}: x {tuple(x.shape)} does not multiply with weight {tuple(weight.shape)}")
+    got, at_fault = None, "x, weight or bias (fp16, K and N in 64s, unit-stride rows in 8s at 16 bytes, GEGLU with a bias)"
+    if (_gemm_shape(N, K, x.dtype, geglu) and weight.dtype == torch.float16 and x.stride(-1) == 1 and weight.is_contiguous()
+            and (bias is None or (bias.dtype == torch.float16 and bias.data_ptr() % 16 == 0))
+            and (not geglu or (bias is not None and residual is None))):
+        x2 = x.reshape(math.prod(x.shape[:-1]), K)
+        if x2.stride(1) == 1 and x2.stride(0) % 8 == 0 and x2.data_ptr() % 16 == 0:
+            got = (None, 0) if residual is None else _residual_2d(residual, x2.shape[0], N)
+            got, at_fault = got and (x2, *got), "the residual (M rows, or M / k rows in 128s; unit-stride rows in 8s at 16 bytes)"
+    if got is None and must:
+        raise ValueError(f"{must}: the GEMM kernels cannot read {at_fault}")
+    return got
 
 
 def linear_kernel_can(x, weight, bias, residual):
-    """dsc_linear_f16's operand constraints (not its row / K preferences): K, N multiples of 64, 16-byte aligned unit-stride rows"""
-    N, K = weight.shape
-    M = x.numel() // K
-    if not (x.dtype == torch.float16 and weight.dtype == torch.float16 and K % 64 == 0 and N % 64 == 0 and x.stride(-1) == 1
-            and weight.is_contiguous()):
-        return False
-    x2 = x.reshape(M, K)
-    if not (x2.stride(1) == 1 and x2.stride(0) % 8 == 0 and x2.data_ptr() % 16 == 0):
-        return False
-    if bias is not None and (bias.dtype != torch.float16 or bias.data_ptr() % 16 != 0):
-        return False
-    if residual is not None and _residual_2d(residual, M, N) is None:
-        return False
-    return True
+    """dsc_linear_f16's operand constraints (_gemm_operands), not its row / K preferences"""
+    return _gemm_operands(x, weight, bias, residual) is not None
 
 
 USE_GN_CAT = os.environ.get("DSC_GN_CAT", "1") != "0"   # up blocks: the skip concatenation is written by the GroupNorm that reads it
@@ -618,41 +639,40 @@ def groupnorm_silu_nhwc_cat(x1, x2, groups, weight, bias, eps, act, add=None):
     return y, cat
 
 
-# Library GEMMs (hipBLASLt through dsc_linear_lt_f16) are OFF by default since round 3: every linear of the step runs on the
-# package's own kernels (gemm_tn_f16, split-K for the few-row long-K shapes).  Per step that costs ~20 us against the best of
-# both per shape (tools/mb_gemm_cold.py) and buys: the same bits in every process, on every rank and under both tuning profiles
-# (the library's algorithm was timed per process and differed per profile), no 0.3 s of algorithm timing at start-up, and no
-# stream-K kernels in a step that runs on two streams.  DSC_LIBRARY_GEMM=1 restores the round-2 routing for A/B measurements.
+# Library GEMMs (hipBLASLt through dsc_linear_lt_f16) are OFF by default: every linear of the step runs on the package's own kernels
+# (gemm_tn_f16, split-K for the few-row long-K shapes).  Per step that costs ~20 us against the best of both per shape
+# (tools/mb_gemm_cold.py) and buys: the same bits in every process, rank and tuning profile (the library's algorithm was timed per
+# process and differed per profile), no 0.3 s of algorithm timing at start-up, no stream-K kernels in a step on two streams.
 USE_LIBRARY_GEMM = os.environ.get("DSC_LIBRARY_GEMM", "0") != "0"
 USE_LT_RESIDUAL = USE_LIBRARY_GEMM and os.environ.get("DSC_LT_RESIDUAL", "1") != "0"   # bias + residual in the library launch (dsc_linear_lt_f16)
 USE_LT_ALL = USE_LIBRARY_GEMM and os.environ.get("DSC_LT_ALL", "1") != "0"   # ... and the ones without a residual go the same way
-USE_DSC_GEMM = True        # route qualifying linears to dsc_linear_f16 (False: always hipBLASLt through torch)
-DSC_GEMM_MIN_ROWS = 1024   # measured (tools/mb_gemm.py): the 128x64x64-tile kernel beats hipBLASLt + separate epilogue
-DSC_GEMM_MAX_K = int(os.environ.get("DSC_GEMM_MAX_K", "640"))       # kernels for >= 1024 token rows and K <= 640; hipBLASLt's larger macro-tiles win beyond
+USE_DSC_GEMM = True        # False: no linear reaches dsc_linear_f16 / dsc_linear_splitk_f16 (library, else torch)
 USE_LN_FOLD = os.environ.get("DSC_LN_FOLD", "1") != "0"   # BasicTransformerBlock: LayerNorms folded into the GEMMs (dsc_linear_ln_f16)
-
-
-DSC_GEMM_MID_ROWS = int(os.environ.get("DSC_GEMM_MID_ROWS", "128")) if os.environ.get("DSC_GEMM_MID", "1") != "0" else 1 << 30    # 128 <= rows < 1024 (the 16x16 and 8x8 levels at batch 1): the kernel up to K = 1280 - a wash per GEMM against the
-DSC_GEMM_MID_K = int(os.environ.get("DSC_GEMM_MID_K", "1280"))      # library (QKV 14.0 vs 15.4 us, C->C 11.8 vs 11.1), but it lets the block's three LayerNorms fold into
-#                            its GEMMs (three add+LayerNorm launches of 6.5 us fewer) and K / V leave the QKV GEMM head-major; the 8x8 level
-#                            (128 rows) the same: equal time in the step and in images/s, three launches fewer (tools/ab_bench.sh)
+# The window (_gemm_rows_k_preferred): >= MIN_ROWS rows with K <= MAX_K, MID_ROWS <= rows < MIN_ROWS with K <= MID_K (DSC_GEMM_MID=0
+# closes that half), GEGLU with K <= 1280.  Measured against the library (tools/mb_gemm.py: the mid rows a wash per GEMM, QKV 14.0
+# vs 15.4 us, C->C 11.8 vs 11.1; GEGLU at M=512 N=10240 K=1280 22.2 vs 23.2 us + the GEGLU launch); with the library on it still
+# decides between the two.  With it off (the default) every linear the kernels can read runs on them, inside the window or not,
+# and the window decides (_linear_plan): outside it few rows with a long K go to split-K (SPLITK_*) and a residual of fewer rows is
+# repeated, inside it (or with prefer_kernel) dsc_linear_f16 wraps those rows; and (linear_kernel_covers) only inside it the
+# LayerNorms fold into the GEMMs (three add+LayerNorm launches fewer per block) and K / V leave the QKV GEMM head-major.
+DSC_GEMM_MIN_ROWS = 1024
+DSC_GEMM_MAX_K = int(os.environ.get("DSC_GEMM_MAX_K", "640"))
+DSC_GEMM_MID_ROWS = int(os.environ.get("DSC_GEMM_MID_ROWS", "128")) if os.environ.get("DSC_GEMM_MID", "1") != "0" else 1 << 30
+DSC_GEMM_MID_K = int(os.environ.get("DSC_GEMM_MID_K", "1280"))
 
 
 def _gemm_rows_k_preferred(M, K, geglu=False):
-    """row / K window in which the hand-written GEMM is the faster (or launch-saving) choice; tools/mb_gemm.py"""
+    """the row / K window of the comment above"""
     if M >= DSC_GEMM_MIN_ROWS and K <= DSC_GEMM_MAX_K:
         return True
     if DSC_GEMM_MID_ROWS <= M < DSC_GEMM_MIN_ROWS and K <= DSC_GEMM_MID_K:
         return True
-    # GEGLU: the fused epilogue beats library GEMM + separate GEGLU launch at every row count of the UNet (M=512 N=10240
-    # K=1280 22.2 vs 23.2 + the launch; M=128 12.5 vs 14.9)
     return bool(geglu) and K <= 1280
 
 
 def linear_kernel_covers(M, N, K, dtype, geglu=False):
-    """True when dsc_linear_f16 (the hand-written MFMA GEMM with fused epilogues) takes this shape"""
-    return (USE_DSC_GEMM and dtype == torch.float16 and K % 64 == 0 and N % 64 == 0 and _gemm_rows_k_preferred(M, K, geglu)
-            and (not geglu or (N // 2) % 32 == 0))
+    """True for gemm_tn_f16's shapes inside the window: asked before dsc_linear_ln_f16 / _qkv_f16, which have no other route"""
+    return USE_DSC_GEMM and _gemm_shape(N, K, dtype, geglu) and _gemm_rows_k_preferred(M, K, geglu)
 
 
 def fold_layernorm(weight, bias, gamma, beta):
@@ -666,39 +686,31 @@ def fold_layernorm(weight, bias, gamma, beta):
     return w2, b2.to(weight.dtype).contiguous(), w2.float().sum(dim=1).contiguous()
 
 
+def _ln_args(what, ln, M, N):
+    """dsc_linear_ln_f16 / _qkv_f16's four LayerNorm arguments from ln = (partials [M, nb, 2] fp32, cvec [N] fp32, eps) or None"""
+    if ln is None:
+        return None, 0, None, 0.0
+    part, cvec, eps = ln
+    if part.shape[0] != M or part.dtype != torch.float32 or not part.is_contiguous() or cvec.numel() != N:
+        raise ValueError(f"{what}: statistics / cvec do not match the operands")
+    return _p(part), part.shape[1], _p(cvec), float(eps)
+
+
 def linear_ln(x, weight, bias, *, residual=None, geglu=False, ln=None, ln_stats=False):
     """dsc_linear_ln_f16 (no library fallback: call only when linear_kernel_covers() says so).
     ln = (partials [M, nb, 2] fp32, cvec [N] fp32, eps): x is the un-normalised stream, weight / bias come from
     fold_layernorm().  ln_stats=True additionally returns the [M, N/64, 2] row partials of the output."""
     _require_gpu(x, weight)
+    x2, r2, ldr = _gemm_operands(x, weight, bias, residual, geglu, must="linear_ln")
     N, K = weight.shape
-    lead = x.shape[:-1]
-    M = 1
-    for v in lead:
-        M *= v
-    x2 = x.reshape(M, K)
-    if x2.stride(1) != 1 or x2.stride(0) % 8 != 0 or not weight.is_contiguous():
-        raise ValueError("linear_ln: unit inner stride, 16-byte aligned rows and a contiguous weight are required")
-    r2, ldr = None, 0
-    if residual is not None:
-        got = _residual_2d(residual, M, N)
-        if got is None:
-            raise ValueError("linear_ln: residual rows must be 16-byte aligned with unit inner stride (M rows, or M / k rows in multiples of 128)")
-        r2, ldr = got
+    M = x2.shape[0]
     n_out = N // 2 if geglu else N
     out = torch.empty((M, n_out), dtype=x.dtype, device=x.device)
     stats = torch.empty((M, N // 64, 2), dtype=torch.float32, device=x.device) if ln_stats else None
-    part, cvec, eps, nb = None, None, 0.0, 0
-    if ln is not None:
-        part, cvec, eps = ln
-        nb = part.shape[1]
-        if part.shape[0] != M or part.dtype != torch.float32 or not part.is_contiguous() or cvec.numel() != N:
-            raise ValueError("linear_ln: statistics / cvec do not match the operands")
-    rc = _lib.load_library().dsc_linear_ln_f16(_p(x2), _p(weight), _p(bias), _p(r2), _p(out), M, N, K, x2.stride(0),
-                                               ldr, n_out, 1 if geglu else 0,
-                                               _p(part), nb, _p(cvec), float(eps), _p(stats), 0, _stream_ptr(x))
+    rc = _lib.load_library().dsc_linear_ln_f16(_p(x2), _p(weight), _p(bias), _p(r2), _p(out), M, N, K, x2.stride(0), ldr, n_out,
+                                               1 if geglu else 0, *_ln_args("linear_ln", ln, M, N), _p(stats), 0, _stream_ptr(x))
     _lib.check(rc, "dsc_linear_ln_f16")
-    out = out.reshape(*lead, n_out)
+    out = out.reshape(*x.shape[:-1], n_out)
     return (out, stats) if ln_stats else out
 
 
@@ -707,12 +719,10 @@ USE_QKV_HEAD_MAJOR = os.environ.get("DSC_QKV_HEAD_MAJOR", "1") != "0"
 
 def linear_qkv_covers(x, weight, heads):
     """True when dsc_linear_qkv_f16 takes the fused self-attention projection of x [B, L, K] by weight [3C, K]"""
-    if not (USE_QKV_HEAD_MAJOR and x.dim() == 3 and x.dtype == torch.float16 and weight.dtype == torch.float16):
-        return False
-    B, L, K = x.shape
     C = weight.shape[0] // 3
-    return (weight.shape[0] == 3 * C and C % 64 == 0 and C % heads == 0 and (C // heads) % 8 == 0
-            and linear_kernel_covers(B * L, 3 * C, K, x.dtype) and x.stride(-1) == 1 and weight.is_contiguous())
+    return (USE_QKV_HEAD_MAJOR and x.dim() == 3 and weight.dtype == torch.float16 and weight.shape[0] == 3 * C and C % heads == 0
+            and (C // heads) % 8 == 0 and linear_kernel_covers(x.shape[0] * x.shape[1], 3 * C, x.shape[2], x.dtype)
+            and x.stride(-1) == 1 and weight.is_contiguous())
 
 
 def linear_qkv(x, weight, bias, heads, ln=None):
@@ -724,19 +734,11 @@ def linear_qkv(x, weight, bias, heads, ln=None):
     C = weight.shape[0] // 3
     d = C // heads
     M = B * L
-    x2 = x.reshape(M, K)
-    if x2.stride(1) != 1 or x2.stride(0) % 8 != 0:
-        raise ValueError("linear_qkv: unit inner stride and 16-byte aligned rows are required")
+    x2 = _gemm_operands(x, weight, bias, must="linear_qkv")[0]
     q = torch.empty((B, L, C), dtype=x.dtype, device=x.device)
     kv = torch.empty((2, B, heads, L, d), dtype=x.dtype, device=x.device)
-    part, cvec, eps, nb = None, None, 0.0, 0
-    if ln is not None:
-        part, cvec, eps = ln
-        nb = part.shape[1]
-        if part.shape[0] != M or part.dtype != torch.float32 or not part.is_contiguous() or cvec.numel() != 3 * C:
-            raise ValueError("linear_qkv: statistics / cvec do not match the operands")
     rc = _lib.load_library().dsc_linear_qkv_f16(_p(x2), _p(weight), _p(bias), _p(q), _p(kv), M, C, K, x2.stride(0), C, heads, L,
-                                                _p(part), nb, _p(cvec), float(eps), 0, _stream_ptr(x))
+                                                *_ln_args("linear_qkv", ln, M, 3 * C), 0, _stream_ptr(x))
     _lib.check(rc, "dsc_linear_qkv_f16")
     return q.view(B, L, heads, d), kv[0].permute(0, 2, 1, 3), kv[1].permute(0, 2, 1, 3)
 
@@ -761,75 +763,86 @@ def linear_splitk(x2, weight, bias, r2, splits=0):
     return out
 
 
+# _linear_plan's routes: dsc_linear_f16 (epilogue fused, fewer residual rows wrapped); dsc_linear_splitk_f16 (epilogue in its reduce
+# launch); dsc_linear_lt_f16 (hipBLASLt: bias epilogue, residual as beta * C; it may decline); F.linear, then the epilogue as separate ops
+LINEAR_KERNEL, LINEAR_SPLITK, LINEAR_LIBRARY, LINEAR_TORCH = range(4)
+
+
+def _linear_plan(x, weight, bias, residual, geglu, prefer_kernel):
+    """Where ops.linear sends these operands, from shapes, strides, dtypes, pointers and the module's switches alone (no launch;
+    the only allocations are the [M, K] form of an x and, for the library, the [M, N] form of a residual whose leading dimensions
+    do not collapse) -> (route, fallback, x2, r2, ldr, repeat): a LINEAR_* route and the one to take if LINEAR_LIBRARY declines; x
+    as [M, K] and the residual as rows with their stride (_residual_2d), None / 0 where no entry point reads them; repeat = k:
+    first repeat the residual's M / k rows k times."""
+    N, K = weight.shape
+    M = math.prod(x.shape[:-1])
+    inside = prefer_kernel or _gemm_rows_k_preferred(M, K, geglu)
+    x2, r2, ldr = (USE_DSC_GEMM and _gemm_operands(x, weight, bias, None, geglu)) or (None, None, 0)
+    can, repeat = x2 is not None, None            # the package's kernels can read x, weight and bias ...
+    if residual is not None:
+        rows = _residual_2d(residual, M, N) if can else None
+        if residual.numel() != M * N and (rows is None or not inside):
+            # fewer rows (shared CFG prefix), not wrapped: outside the window even where dsc_linear_f16 then runs (2048 rows, K = 1280)
+            repeat = M // (residual.numel() // N)
+        else:
+            can = rows is not None                # ... and the residual
+            r2, ldr = rows or (None, 0)
+    # outside the window the kernel still takes what it can read: no GEMM of the step reaches a library algorithm nobody vetted
+    route = fallback = LINEAR_KERNEL if can else LINEAR_TORCH
+    if can and inside:
+        return route, fallback, x2, r2, ldr, repeat
+    if can and not geglu and USE_SPLITK and not USE_LIBRARY_GEMM and M <= SPLITK_MAX_ROWS and K >= SPLITK_MIN_K:
+        # few rows, long K (the 16x16 / 8x8 levels' feed-forward output projections and shortcut 1x1s): weight-streaming bound, split
+        # over K + an ordered reduce launch; measured against the library per shape in the step's cache state (tools/mb_gemm_cold.py)
+        route = LINEAR_SPLITK
+    elif (USE_LT_RESIDUAL if residual is not None else USE_LT_ALL) and x.dtype == torch.float16 and K % 8 == 0 and N % 8 == 0 and M >= 8:
+        if not can:                               # the library asks less of its operands than the kernels: no 64s, no pointers
+            x2 = x.reshape(M, K) if x2 is None else x2
+            if residual is not None and repeat is None:
+                r2 = residual.reshape(M, N)       # (a copy where the residual's leading dimensions do not collapse)
+                ldr = r2.stride(0)
+        if (x2.stride(1) == 1 and x2.stride(0) % 8 == 0 and weight.is_contiguous() and weight.dtype == torch.float16
+                and (bias is None or bias.dtype == torch.float16) and (r2 is None or (r2.stride(1) == 1 and ldr % 8 == 0))):
+            route = LINEAR_LIBRARY
+    return route, fallback, x2, r2, ldr, repeat
+
+
+def _unfused_epilogue(y, residual, gated):
+    """what dsc_linear_f16 fuses, after a GEMM that has no such epilogue"""
+    return geglu(y) if gated else y if residual is None else y + residual
+
+
 def linear(x, weight, bias=None, residual=None, geglu=False, prefer_kernel=False):
     """x @ weight.T (+ bias) (+ residual), or the fused GEGLU of [x @ weight.T + bias]; x [..., K], weight [N, K].
-    prefer_kernel: take the hand-written GEMM whenever it CAN run the shape, whatever the row / K thresholds say.
-
-    Shapes the hand-written MFMA kernel covers (fp16, K % 64 == 0, N % 64 == 0, >= DSC_GEMM_MIN_ROWS rows, unit inner
-    stride) go to dsc_linear_f16 with the epilogue fused; everything else is a plain library GEMM through torch
-    (hipBLASLt) followed by the separate epilogue ops."""
+    prefer_kernel: as if the shape lay inside the row / K window (DSC_GEMM_*).
+    Every linear the package's kernels can read (_gemm_operands: fp16, K and N multiples of 64, aligned unit-stride rows) runs on
+    dsc_linear_f16 with the epilogue fused, or outside the window, with few rows and a long K, on split-K; DSC_LIBRARY_GEMM=1
+    sends those outside the window to dsc_linear_lt_f16 first.  What no entry point can read is F.linear and separate ops."""
+    if geglu and residual is not None:
+        raise ValueError("linear: the GEGLU epilogue takes no residual")
     _require_gpu(x, weight)
+    route, fallback, x2, r2, ldr, repeat = _linear_plan(x, weight, bias, residual, geglu, prefer_kernel)
     N, K = weight.shape
     lead = x.shape[:-1]
-    M = 1
-    for v in lead:
-        M *= v
-    # `can`: dsc_linear_f16 is ABLE to run the shape; `ok`: it is also the faster choice (row / K thresholds)
-    can = (USE_DSC_GEMM and x.dtype == torch.float16 and weight.dtype == torch.float16 and K % 64 == 0 and N % 64 == 0
-           and x.stride(-1) == 1 and weight.is_contiguous()
-           and (not geglu or (bias is not None and residual is None and (N // 2) % 32 == 0)))
-    x2 = None
-    if can:
-        x2 = x.reshape(M, K)                      # a view when the leading dims collapse (the token-major case)
-        can = x2.stride(1) == 1 and x2.stride(0) % 8 == 0 and x2.data_ptr() % 16 == 0
-    ldr = 0
-    if residual is not None and residual.numel() != M * N:
-        # fewer residual rows than result rows (shared CFG prefix): the kernel wraps them (dsc_linear_f16), every other route
-        # gets them repeated
-        got = _residual_2d(residual, M, N) if can and not geglu else None
-        if got is None or not (prefer_kernel or _gemm_rows_k_preferred(M, K, geglu)):
-            residual = residual.reshape(-1, N).repeat(M // (residual.numel() // N), 1).reshape(*lead, N)
-    if can and residual is not None:
-        got = _residual_2d(residual, M, N)
-        can = got is not None
-        if can:
-            r2, ldr = got
-    ok = can and (prefer_kernel or _gemm_rows_k_preferred(M, K, geglu))
-    if can and not ok and not geglu and USE_SPLITK and not USE_LIBRARY_GEMM and M <= SPLITK_MAX_ROWS and K >= SPLITK_MIN_K \
-            and (bias is None or (bias.dtype == torch.float16 and bias.data_ptr() % 16 == 0)):
-        # few rows, long K (the 16x16 / 8x8 levels' feed-forward output projections and shortcut 1x1s): weight-streaming bound,
-        # split-K over workgroups + an ordered reduce launch (bias / residual there) - measured against the library per shape
-        # in the step's cache state (tools/mb_gemm_cold.py)
-        return linear_splitk(x2, weight, bias, residual.reshape(M, N) if residual is not None else None).reshape(*lead, N)
-    if not ok:
-        if ((USE_LT_RESIDUAL if residual is not None else USE_LT_ALL) and x.dtype == torch.float16 and K % 8 == 0
-                and N % 8 == 0 and M >= 8 and not (geglu and residual is not None)):
-            # library GEMM with the bias epilogue AND the residual as beta*C: one launch instead of GEMM + add; the
-            # algorithm is the fastest of the heuristic's candidates, timed on the first call of a shape
-            xl = x.reshape(M, K)
-            rl = residual.reshape(M, N) if residual is not None else None
-            if (xl.stride(1) == 1 and xl.stride(0) % 8 == 0 and weight.is_contiguous() and weight.dtype == torch.float16
-                    and (bias is None or bias.dtype == torch.float16)
-                    and (rl is None or (rl.stride(1) == 1 and rl.stride(0) % 8 == 0))):
-                out = torch.empty((M, N), dtype=x.dtype, device=x.device)
-                rc = _lib.load_library().dsc_linear_lt_f16(_p(xl), _p(weight), _p(bias), _p(rl), _p(out), M, N, K,
-                                                           xl.stride(0), rl.stride(0) if rl is not None else 0, N, 0,
-                                                           _stream_ptr(x))
-                if rc == 0:
-                    out = out.reshape(*lead, N)
-                    return globals()["geglu"](out) if geglu else out
-        # dsc_linear_lt_f16 declined (no workspace-free library algorithm for the shape, linear_lt.hip): the hand-written
-        # kernel takes it when it can, so that no GEMM of the step reaches a library algorithm this package did not vet
-        ok = can
-    if not ok:
-        y = torch.nn.functional.linear(x, weight, bias)
-        if geglu:
-            return globals()["geglu"](y)
-        return y if residual is None else y + residual
+    M = math.prod(lead)
+    if repeat is not None:
+        residual = residual.reshape(-1, N).repeat(repeat, 1).reshape(*lead, N)
+        r2, ldr = residual.reshape(M, N), N
+    if route == LINEAR_LIBRARY:
+        # one launch instead of GEMM + add, by the fastest of the heuristic's candidates, timed on a shape's first call (linear_lt.hip)
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+        rc = _lib.load_library().dsc_linear_lt_f16(_p(x2), _p(weight), _p(bias), _p(r2), _p(out), M, N, K, x2.stride(0), ldr, N, 0,
+                                                   _stream_ptr(x))
+        if rc == 0:
+            return _unfused_epilogue(out.reshape(*lead, N), None, geglu)
+        route = fallback
+    if route == LINEAR_TORCH:
+        return _unfused_epilogue(torch.nn.functional.linear(x, weight, bias), residual, geglu)
+    if route == LINEAR_SPLITK:
+        return linear_splitk(x2, weight, bias, r2).reshape(*lead, N)
     n_out = N // 2 if geglu else N
     out = torch.empty((M, n_out), dtype=x.dtype, device=x.device)
-    rc = _lib.load_library().dsc_linear_f16(_p(x2), _p(weight), _p(bias), _p(r2) if residual is not None else None, _p(out),
-                                            M, N, K, x2.stride(0), ldr if residual is not None else 0, n_out,
+    rc = _lib.load_library().dsc_linear_f16(_p(x2), _p(weight), _p(bias), _p(r2), _p(out), M, N, K, x2.stride(0), ldr, n_out,
                                             1 if geglu else 0, 0, _stream_ptr(x))
     _lib.check(rc, "dsc_linear_f16")
     return out.reshape(*lead, n_out)

@@ -262,6 +262,20 @@ def test_linear_kernel(ops, M, N, K):
     assert torch.all((o3.float().cpu() - ref3).abs() <= 1.5e-3 * ref3.abs() + 2e-3)
 
 
+@pytest.mark.parametrize("M,N,K", [(128, 64, 64), (128, 64, 1920)])
+def test_linear_with_a_bias_the_kernels_cannot_read(ops, M, N, K):
+    """a bias at a 2-byte offset (the library refuses it) takes the torch route instead of raising, at dsc_linear_f16's shape and at
+    the split-K one; test_linear_kernel's bound (one fp16 rounding of the fp32 result)"""
+    g = torch.Generator().manual_seed(M + N + K)
+    x = torch.randn(M, K, generator=g).half()
+    w = (torch.randn(N, K, generator=g) / math.sqrt(K)).half()
+    b = (torch.randn(N + 1, generator=g) * 0.2).half()
+    ref = x.float() @ w.float().t() + b[1:].float()
+    out = ops.linear(x.cuda(), w.cuda(), b.cuda()[1:])
+    assert out.shape == (M, N)
+    assert torch.all((out.float().cpu() - ref).abs() <= 1.5e-3 * ref.abs() + 2e-3)
+
+
 @pytest.mark.parametrize("B,Cin,Cout,H,W,splits", [
     (2, 320, 320, 64, 64, 0), (2, 640, 320, 64, 64, 0), (2, 640, 640, 32, 32, 0), (2, 640, 640, 32, 32, 1),
     (2, 1920, 640, 32, 32, 0), (2, 1280, 1280, 16, 16, 0), (2, 2560, 1280, 16, 16, 0), (2, 1280, 1280, 8, 8, 0),
