@@ -471,90 +471,21 @@ class StableDiffusionPipeline:
                 prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
                 text_input_ids=None, fused: Optional[bool] = None, slot: int = 0, step_noise: Optional[torch.Tensor] = None,
                 **unsupported):
-        hires = dict(prompt=prompt, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                     negative_prompt=negative_prompt, generator=generator, strength=upscale_denoising_strength,
-                     sampler_name=sampler_name_hires or sampler_name, sampler_opt=sampler_opt_hires or sampler_opt,
-                     region_map_state=region_map_state, seed=seed, control_img=control_img,
-                     latent_processing=unsupported.get("latent_upscale_processing", False),
-                     controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
-                     control_guidance_end=control_guidance_end, image_t2i_adapter=image_t2i_adapter,
-                     adapter_conditioning_scale=adapter_conditioning_scale, adapter_conditioning_factor=adapter_conditioning_factor,
-                     guidance_rescale=guidance_rescale, cross_attention_kwargs=cross_attention_kwargs, clip_skip=clip_skip,
-                     long_encode=long_encode, num_images_per_prompt=num_images_per_prompt, weight_func=weight_func,
-                     ip_adapter_image_embeds=ip_adapter_image_embeds, prompt_embeds=prompt_embeds,
-                     negative_prompt_embeds=negative_prompt_embeds, text_input_ids=text_input_ids, output_type=output_type,
-                     start_time=start_time, timeout=timeout) if upscale else None
-        if image_t2i_adapter is not None:
+        """reference :943-1231.  What is txt2img's own stands here; the rest is the shared path below (_text_and_schedule,
+        _conditioning, _denoise_and_finish)."""
+        a = dict(locals())                       # this call's arguments by name, as given: what the shared path reads
+        if image_t2i_adapter is not None:        # (before any prompt work)
             if getattr(self, "adapter", None) is None:
                 raise ValueError("image_t2i_adapter needs an adapter: modules.t2i_adapter.setup_model_t2i_adapter(pipe, adapter)")
             from .t2i_adapter import default_height_width
             height, width = default_height_width(self, height, width, image_t2i_adapter)              # :990-991
-        sampler = self.get_scheduler(sampler_name) if isinstance(sampler_name, str) else sampler_name
-        device = self._execution_device
-        self._do_classifier_free_guidance = guidance_scale > 1.0
-        cfg = self._do_classifier_free_guidance
-        if prompt_embeds is None:                                                                            # :1006-1019
-            if prompt is None or self.tokenizer is None or self.text_encoder is None:
-                raise NotImplementedError("pass prompt_embeds / negative_prompt_embeds / text_input_ids, or construct the "
-                                          "pipeline with a tokenizer and a CLIP text encoder and pass `prompt`")
-            from .encoder_prompt_modify import encode_prompt_function
-            prompt_embeds, negative_prompt_embeds, text_input_ids = encode_prompt_function(
-                self, prompt, device, 1, cfg, negative_prompt, clip_skip=clip_skip, long_encode=long_encode)
-        n_img = prompt_embeds.shape[0] * num_images_per_prompt
-        text = prompt_embeds.repeat_interleave(num_images_per_prompt, dim=0)
-        if cfg:
-            if negative_prompt_embeds is None:
-                raise ValueError("classifier-free guidance needs negative_prompt_embeds")
-            text = torch.cat([negative_prompt_embeds.repeat_interleave(num_images_per_prompt, dim=0), text])   # :1021
-        text = text.to(device=device, dtype=self.unet.dtype)
-        # sigmas are cast to the model dtype on the device (:1027-1029): fp16 rounding is part of the schedule
-        sigmas = self._schedule(num_inference_steps, sampler_opt, device, text.dtype)
-        latents = self.prepare_latents(n_img, self.unet.config.in_channels, height, width, text.dtype, device,
-                                       generator, latents)
+        sampler, text, text_input_ids, n_img, sigmas = self._text_and_schedule(a)
+        latents = self.prepare_latents(n_img, self.unet.config.in_channels, height, width, text.dtype, self._execution_device,
+                                       generator, latents)           # the only generator draw of the call
         latents = latents * (sigmas[0] ** 2 + 1) ** 0.5                                                      # :1043
-        if text_input_ids is None:
-            text_input_ids = [None, None]
-        region_state = encode_region_map(self, region_map_state, width=width, height=height,
-                                         num_images_per_prompt=num_images_per_prompt, text_ids=text_input_ids)  # :1050
-        cross_attention_kwargs = {} if cross_attention_kwargs is None else cross_attention_kwargs
-        added_cond_kwargs = None
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:                               # :1069-1082
-            embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, ip_adapter_image_embeds, device,
-                                                          num_images_per_prompt, cfg)
-            added_cond_kwargs = {"image_embeds": [e.to(device=device, dtype=text.dtype) for e in embeds]}
-        self._added_cond_kwargs = added_cond_kwargs
-        control_hook = self._controlnet_hook(control_img, controlnet_conditioning_scale, control_guidance_start,
-                                             control_guidance_end, width, height, num_inference_steps, n_img,
-                                             num_images_per_prompt, text)                                    # :1060-1061
-        control_hook = self._merge_hooks(control_hook, self._adapter_hook(
-            image_t2i_adapter, adapter_conditioning_scale, adapter_conditioning_factor, width, height, len(sigmas),
-            num_images_per_prompt))                                                                         # :1086-1089
-        preview = None
-        if latent_processing == 1:                               # :1083-1084: previews of every model call's estimate
-            latents_process = [self.latent_to_image(latents, output_type)]
-            preview = (latents_process, output_type)
-        if fused is None:
-            fused = sampler is sampling.sample_dpmpp_2m and guidance_rescale == 0.0 and cfg and not self.v_prediction \
-                and control_hook is None and preview is None
-        if fused:
-            if control_hook is not None or preview is not None:
-                raise NotImplementedError("ControlNet / T2I-Adapter / latent previews run in protocol mode (fused=False)")
-            latents = self._denoise_fused(latents, sigmas, text, region_state, weight_func, guidance_scale, n_img,
-                                          cross_attention_kwargs, start_time, timeout, slot=slot, sampler=sampler,
-                                          sampler_args=self._fused_sampler_args(sampler, sigmas, eta, num_inference_steps,
-                                                                                sampler_opt, latents, seed, step_noise),
-                                          step_noise=step_noise, guidance_rescale=guidance_rescale)
-        else:
-            latents = self._denoise_protocol(sampler, latents, sigmas, text, region_state, weight_func, guidance_scale,
-                                             guidance_rescale, n_img, cross_attention_kwargs, eta,
-                                             num_inference_steps, sampler_opt, seed, start_time, timeout,
-                                             control_hook=control_hook, preview=preview, slot=slot)
-        if upscale:                                                                                          # :1176-1228
-            res = self._hires_pass(latents, height, width, upscale_x, upscale_method, upscale_antialias, **hires)
-            return latents_process + res if latent_processing == 1 else res
-        if latent_processing == 1:                               # :1229-1230 (the list ends with the last model call's estimate)
-            return latents_process
-        return [self.latent_to_image(latents, output_type)]
+        cond = self._conditioning(a, text, text_input_ids, n_img, sigmas, width, height, num_inference_steps)
+        return self._denoise_and_finish(a, sampler, latents, sigmas, text, n_img, cond, height, width, num_inference_steps, eta,
+                                        fused_by_default=True, protocol_kw={"slot": slot}, fused_kw={"slot": slot})
 
     def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77,
               ip_masks: bool = False, t2i_adapter: bool = False, controlnet: bool = False, control_slots=None,
@@ -821,22 +752,8 @@ class StableDiffusionPipeline:
                 text_input_ids=None, fused: Optional[bool] = None, step_noise: Optional[torch.Tensor] = None, **unsupported):
         """reference :543-846: encode the image (or take `latents`), keep the last `strength` fraction of the schedule, add
         noise, denoise.  Reproduces the reference's start: `latents + noise * sqrt(sigma_0^2 + 1)` (:647 - sic, not
-        `noise * sigma_0`)."""
-        hires = dict(prompt=prompt, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                     negative_prompt=negative_prompt, generator=generator, strength=upscale_denoising_strength,
-                     sampler_name=sampler_name_hires or sampler_name, sampler_opt=sampler_opt_hires or sampler_opt,
-                     region_map_state=region_map_state, seed=seed, control_img=control_img,
-                     latent_processing=unsupported.get("latent_upscale_processing", False),
-                     controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
-                     control_guidance_end=control_guidance_end, image_t2i_adapter=image_t2i_adapter,
-                     adapter_conditioning_scale=adapter_conditioning_scale, adapter_conditioning_factor=adapter_conditioning_factor,
-                     guidance_rescale=guidance_rescale, cross_attention_kwargs=cross_attention_kwargs, clip_skip=clip_skip,
-                     long_encode=long_encode, num_images_per_prompt=num_images_per_prompt, weight_func=weight_func,
-                     ip_adapter_image_embeds=ip_adapter_image_embeds, prompt_embeds=prompt_embeds,
-                     negative_prompt_embeds=negative_prompt_embeds, text_input_ids=text_input_ids, output_type=output_type,
-                     start_time=start_time, timeout=timeout) if upscale else None
-        sampler = self.get_scheduler(sampler_name) if isinstance(sampler_name, str) else sampler_name
-        device = self._execution_device
+        `noise * sigma_0`).  Generator draws: the VAE posterior sample, then the noise; the image is encoded before the prompt."""
+        a = dict(locals())                       # this call's arguments by name, as given: what the shared path reads
         if image is not None:
             image = self.preprocess(image)
             latents = self._encode_vae_image(image, generator)                                       # :600-606
@@ -846,60 +763,18 @@ class StableDiffusionPipeline:
             height = int(latents.shape[-2]) * 8
         if width is None:
             width = int(latents.shape[-1]) * 8
+        device = self._execution_device
         latents = latents.to(device, dtype=self.unet.dtype)
-        self._do_classifier_free_guidance = guidance_scale > 1.0
-        text, text_input_ids, n_img = self._encode_text_rows(prompt, negative_prompt, prompt_embeds, negative_prompt_embeds,
-                                                             text_input_ids, num_images_per_prompt, clip_skip, long_encode,
-                                                             device)
+        sampler, text, text_input_ids, n_img, sigmas = self._text_and_schedule(a)
         if latents.shape[0] != n_img:
             latents = latents.repeat(n_img // latents.shape[0], 1, 1, 1)
         init_timestep = min(int(num_inference_steps * strength), num_inference_steps)                # :637-638
-        t_start = max(num_inference_steps - init_timestep, 0)
-        sigmas = self._schedule(num_inference_steps, sampler_opt, device, text.dtype)
-        sigma_sched = sigmas[t_start:]
+        sigma_sched = sigmas[max(num_inference_steps - init_timestep, 0):]
         noise = self._randn_like_ref(latents.shape, generator, device, text.dtype)
         latents = latents + noise * (sigma_sched[0] ** 2 + 1) ** 0.5                                 # :647
-        region_state = encode_region_map(self, region_map_state, width=width, height=height,
-                                         num_images_per_prompt=num_images_per_prompt, text_ids=text_input_ids)
-        cross_attention_kwargs = {} if cross_attention_kwargs is None else cross_attention_kwargs
-        self._added_cond_kwargs = None
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-            embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, ip_adapter_image_embeds, device,
-                                                          num_images_per_prompt, self.do_classifier_free_guidance)
-            self._added_cond_kwargs = {"image_embeds": [e.to(device=device, dtype=text.dtype) for e in embeds]}
-        control_hook = self._controlnet_hook(control_img, controlnet_conditioning_scale, control_guidance_start,
-                                             control_guidance_end, width, height, len(sigma_sched), n_img,
-                                             num_images_per_prompt, text)                                    # :675-676
-        control_hook = self._merge_hooks(control_hook, self._adapter_hook(
-            image_t2i_adapter, adapter_conditioning_scale, adapter_conditioning_factor, width, height, len(sigma_sched),
-            num_images_per_prompt))                                                                         # :700-703
-        preview = None
-        if latent_processing == 1:                               # :696-697
-            latents_process = [self.latent_to_image(latents, output_type)]
-            preview = (latents_process, output_type)
-        if fused is None:
-            fused = sampler is sampling.sample_dpmpp_2m and guidance_rescale == 0.0 and self.do_classifier_free_guidance \
-                and not self.v_prediction and control_hook is None and preview is None
-        if fused:
-            if control_hook is not None or preview is not None:
-                raise NotImplementedError("ControlNet / T2I-Adapter / latent previews run in protocol mode (fused=False)")
-            latents = self._denoise_fused(latents, sigma_sched, text, region_state, weight_func, guidance_scale, n_img,
-                                          cross_attention_kwargs, start_time, timeout, sampler=sampler,
-                                          sampler_args=self._fused_sampler_args(sampler, sigma_sched, None, len(sigma_sched),
-                                                                                sampler_opt, latents, seed, step_noise),
-                                          step_noise=step_noise, guidance_rescale=guidance_rescale)
-        else:
-            args = self.get_sampler_extra_args_i2i(sigma_sched, len(sigma_sched), sampler_opt, latents, seed, sampler)
-            latents = self._denoise_protocol(sampler, latents, sigma_sched, text, region_state, weight_func, guidance_scale,
-                                             guidance_rescale, n_img, cross_attention_kwargs, 0.0, len(sigma_sched),
-                                             sampler_opt, seed, start_time, timeout, sampler_args=args,
-                                             control_hook=control_hook, preview=preview)
-        if upscale:                                                                                          # :789-838
-            res = self._hires_pass(latents, height, width, upscale_x, upscale_method, upscale_antialias, **hires)
-            return latents_process + res if latent_processing == 1 else res
-        if latent_processing == 1:                               # :841-842
-            return latents_process
-        return [self.latent_to_image(latents, output_type)]
+        cond = self._conditioning(a, text, text_input_ids, n_img, sigma_sched, width, height, len(sigma_sched))
+        return self._denoise_and_finish(a, sampler, latents, sigma_sched, text, n_img, cond, height, width, len(sigma_sched), None,
+                                        fused_by_default=True)
 
     def _sigma_to_alpha_sigma_t(self, sigma):
         alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)                                                      # :1293-1297
@@ -956,8 +831,10 @@ class StableDiffusionPipeline:
         re-imposed on the model input before every model call after the first (:1599-1612).  9-channel UNet (the inpainting
         checkpoints): mask and masked-image latents are concatenated to the duplicated latent (:1617-1619) - eager protocol mode,
         or with fused=True the captured 9-channel step and one dsc_cfg_linear_step_rows_cat launch per step (_denoise_fused with
-        `extra`: every sampler of sampling.LINEAR_FAMILY, v-prediction, guidance_rescale; step_noise as in img2img)."""
-        if upscale or padding_mask_crop is not None:
+        `extra`: every sampler of sampling.LINEAR_FAMILY, v-prediction, guidance_rescale; step_noise as in img2img).  Generator
+        draws: everything inside prepare_latents_inpating, then the masked-image encode."""
+        a = dict(locals())                       # this call's arguments by name, as given: what the shared path reads
+        if upscale or padding_mask_crop is not None:             # (the refusals come before anything else)
             raise NotImplementedError("hires upscale after inpainting and mask cropping are outside the denoising hot path "
                                       "built here")
         num_channels_unet = self.unet.config.in_channels
@@ -965,16 +842,10 @@ class StableDiffusionPipeline:
             raise ValueError(f"The unet {self.unet.__class__} should have either 4 or 9 input channels, not {num_channels_unet}.")
         if image is None or mask_image is None:
             raise ValueError("inpaiting needs `image` and `mask_image`")
-        sampler = self.get_scheduler(sampler_name) if isinstance(sampler_name, str) else sampler_name
         device = self._execution_device
-        self._do_classifier_free_guidance = guidance_scale > 1.0
-        text, text_input_ids, n_img = self._encode_text_rows(prompt, negative_prompt, prompt_embeds, negative_prompt_embeds,
-                                                             text_input_ids, num_images_per_prompt, clip_skip, long_encode,
-                                                             device)
+        sampler, text, text_input_ids, n_img, sigmas = self._text_and_schedule(a)
         init_timestep = min(int(num_inference_steps * strength), num_inference_steps)                # :1432-1438
-        t_start = max(num_inference_steps - init_timestep, 0)
-        sigmas = self._schedule(num_inference_steps, sampler_opt, device, text.dtype)
-        sigmas = sigmas[t_start:] if 0 <= strength < 1.0 else sigmas
+        sigmas = sigmas[max(num_inference_steps - init_timestep, 0):] if 0 <= strength < 1.0 else sigmas
         is_strength_max = strength == 1.0
         init_image = self._image_tensor(image, height, width) if not (isinstance(image, torch.Tensor) and image.shape[1] == 4) \
             else image.float()
@@ -999,14 +870,6 @@ class StableDiffusionPipeline:
         if num_channels_unet == 9:
             rows = 2 if self.do_classifier_free_guidance else 1
             extra_input = torch.cat([torch.cat([mask] * rows), torch.cat([mil] * rows)], dim=1)
-        region_state = encode_region_map(self, region_map_state, width=width, height=height,
-                                         num_images_per_prompt=num_images_per_prompt, text_ids=text_input_ids)
-        cross_attention_kwargs = {} if cross_attention_kwargs is None else cross_attention_kwargs
-        self._added_cond_kwargs = None
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-            embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, ip_adapter_image_embeds, device,
-                                                          num_images_per_prompt, self.do_classifier_free_guidance)
-            self._added_cond_kwargs = {"image_embeds": [e.to(device=device, dtype=text.dtype) for e in embeds]}
         sig_last = float(sigmas[-1])
 
         def keep_known_region(x, sigma, call_index):                                                 # :1599-1612
@@ -1020,39 +883,139 @@ class StableDiffusionPipeline:
             rate = (s ** 2 + 1) ** 0.5
             return ((1 - mask) * known + mask * x / rate) * rate
 
-        preview = None
-        if latent_processing == 1:                               # :1584-1585
-            latents_process = [self.latent_to_image(latents, output_type)]
-            preview = (latents_process, output_type)
-        control_hook = self._controlnet_hook(control_img, controlnet_conditioning_scale, control_guidance_start,
-                                             control_guidance_end, width, height, num_inference_steps, n_img,
-                                             num_images_per_prompt, text)                                    # :1577-1578
-        control_hook = self._merge_hooks(control_hook, self._adapter_hook(
-            image_t2i_adapter, adapter_conditioning_scale, adapter_conditioning_factor, width, height, len(sigmas),
-            num_images_per_prompt))                                                                         # :1588-1591
+        cond = self._conditioning(a, text, text_input_ids, n_img, sigmas, width, height, num_inference_steps)
+        fused_kw = None
         if fused:
             if num_channels_unet != 9:
                 raise NotImplementedError("inpaiting(fused=True) runs the 9-channel inpainting UNets; the known-region blend of a "
                                           "4-channel UNet has no fused loop: run it with fused=False")
-            if control_hook is not None or preview is not None:
-                raise NotImplementedError("ControlNet / T2I-Adapter / latent previews run in protocol mode (fused=False)")
             if latents.shape[-2] * latents.shape[-1] % 8 != 0:
                 raise NotImplementedError(f"inpaiting(fused=True): the 9-channel input row must stay 16-byte aligned, which needs a "
                                           f"latent of h * w % 8 == 0, got {list(latents.shape[-2:])}; run it with fused=False")
+            fused_kw = {"extra": torch.cat([mask, mil], dim=1)}
+        return self._denoise_and_finish(a, sampler, latents, sigmas, text, n_img, cond, height, width, num_inference_steps, eta,
+                                        fused_by_default=False, fused_kw=fused_kw,
+                                        protocol_kw={"input_hook": keep_known_region, "extra_input": extra_input})
+
+    # ------------------------------------------------------------------ the generation path the three entries share
+    # Each entry keeps what is its own - its refusals, how the start latent is made (and with it the order of the generator's
+    # draws) and the strength cut of the schedule - and runs the rest here, in the reference's order:
+    #   _text_and_schedule -> [the entry's latents] -> _conditioning -> _denoise_and_finish.
+    # Where the entries differ on purpose (they mirror the reference), the difference is a parameter of these three methods and
+    # is written down at that parameter.  `a` is the entry's own `dict(locals())`, taken before it changes anything: the
+    # arguments as the caller gave them, by name.
+    def _text_and_schedule(self, a):
+        """-> (sampler, text rows, token ids, number of images, schedule).  Sets `_do_classifier_free_guidance` first: the text
+        rows, the region tables and the hooks read it when they are built.  The prompt is encoded here, i.e. before every
+        generator draw of txt2img and inpaiting and after img2img's image encode (:600-606)."""
+        sampler = self.get_scheduler(a["sampler_name"]) if isinstance(a["sampler_name"], str) else a["sampler_name"]
+        device = self._execution_device
+        self._do_classifier_free_guidance = a["guidance_scale"] > 1.0
+        text, text_input_ids, n_img = self._encode_text_rows(
+            a["prompt"], a["negative_prompt"], a["prompt_embeds"], a["negative_prompt_embeds"], a["text_input_ids"],
+            a["num_images_per_prompt"], a["clip_skip"], a["long_encode"], device)
+        # sigmas are cast to the model dtype on the device (:1027-1029): fp16 rounding is part of the schedule
+        return sampler, text, text_input_ids, n_img, self._schedule(a["num_inference_steps"], a["sampler_opt"], device, text.dtype)
+
+    def _conditioning(self, a, text, text_input_ids, n_img, sigmas, width, height, steps):
+        """-> (region_state, cross_attention_kwargs, control_hook): the region tables (:1050), the IP-Adapter embeds in
+        `self._added_cond_kwargs` (:1069-1082; reset on every call) and the ControlNet / T2I-Adapter hooks, merged.
+        sigmas: the schedule the entry will run, i.e. after img2img's and inpaiting's strength cut.  The T2I-Adapter hook counts
+        its steps as len(sigmas) in every entry (:1086-1089, :700-703, :1588-1591).
+        steps: what the ControlNet hook spreads its guidance window over - `num_inference_steps` in txt2img (:1060-1061) and
+        inpaiting (:1577-1578), cut or not; len(sigmas) in img2img (:675-676)."""
+        device, n_per = self._execution_device, a["num_images_per_prompt"]
+        region_state = encode_region_map(self, a["region_map_state"], width=width, height=height, num_images_per_prompt=n_per,
+                                         text_ids=text_input_ids)
+        self._added_cond_kwargs = None
+        if a["ip_adapter_image"] is not None or a["ip_adapter_image_embeds"] is not None:
+            embeds = self.prepare_ip_adapter_image_embeds(a["ip_adapter_image"], a["ip_adapter_image_embeds"], device, n_per,
+                                                          self.do_classifier_free_guidance)
+            self._added_cond_kwargs = {"image_embeds": [e.to(device=device, dtype=text.dtype) for e in embeds]}
+        control_hook = self._merge_hooks(
+            self._controlnet_hook(a["control_img"], a["controlnet_conditioning_scale"], a["control_guidance_start"],
+                                  a["control_guidance_end"], width, height, steps, n_img, n_per, text),
+            self._adapter_hook(a["image_t2i_adapter"], a["adapter_conditioning_scale"], a["adapter_conditioning_factor"], width,
+                               height, len(sigmas), n_per))
+        return region_state, {} if a["cross_attention_kwargs"] is None else a["cross_attention_kwargs"], control_hook
+
+    def _denoise_and_finish(self, a, sampler, latents, sigmas, text, n_img, cond, height, width, steps, eta, fused_by_default,
+                            protocol_kw=None, fused_kw=None):
+        """Choose the core, run it, and return what the entry returns.
+        steps, eta: what the sampler's arguments are built from.  txt2img and inpaiting: `num_inference_steps` and the caller's
+        eta, in both modes (protocol mode leaves the arguments to _denoise_protocol: get_sampler_extra_args_t2i).  img2img: len(sigmas)
+        and eta None - the fused loop then keeps the sampler's own default, and protocol mode gets the arguments of
+        get_sampler_extra_args_i2i (:916-941), which takes no eta (the core is handed 0.0).
+        fused_by_default: what `fused=None` means.  True (txt2img, img2img): the fused loop where it is the cheaper equal - DPM++ 2M,
+        guidance on and not rescaled, eps-prediction, no hook, no previews.  False (inpaiting): protocol mode.
+        protocol_kw / fused_kw: what only this entry hands the cores - txt2img its `slot` (to both), inpaiting `input_hook` and
+        `extra_input` (protocol) or `extra` (fused)."""
+        region_state, cross_attention_kwargs, control_hook = cond
+        output_type, sampler_opt, seed, step_noise = a["output_type"], a["sampler_opt"], a["seed"], a["step_noise"]
+        guidance_scale, guidance_rescale, weight_func = a["guidance_scale"], a["guidance_rescale"], a["weight_func"]
+        latent_processing, preview = a["latent_processing"], None
+        if latent_processing == 1:                               # :1083-1084, :696-697, :1584-1585: previews of every model call's estimate
+            latents_process = [self.latent_to_image(latents, output_type)]
+            preview = (latents_process, output_type)
+        fused = a["fused"]
+        if fused is None:
+            fused = fused_by_default and sampler is sampling.sample_dpmpp_2m and guidance_rescale == 0.0 \
+                and self.do_classifier_free_guidance and not self.v_prediction and control_hook is None and preview is None
+        if fused:
+            if control_hook is not None or preview is not None:
+                raise NotImplementedError("ControlNet / T2I-Adapter / latent previews run in protocol mode (fused=False)")
             latents = self._denoise_fused(latents, sigmas, text, region_state, weight_func, guidance_scale, n_img,
-                                          cross_attention_kwargs, start_time, timeout, sampler=sampler,
-                                          sampler_args=self._fused_sampler_args(sampler, sigmas, eta, num_inference_steps,
-                                                                                sampler_opt, latents, seed, step_noise),
-                                          step_noise=step_noise, guidance_rescale=guidance_rescale,
-                                          extra=torch.cat([mask, mil], dim=1))
+                                          cross_attention_kwargs, a["start_time"], a["timeout"], sampler=sampler,
+                                          sampler_args=self._fused_sampler_args(sampler, sigmas, eta, steps, sampler_opt, latents,
+                                                                                seed, step_noise),
+                                          step_noise=step_noise, guidance_rescale=guidance_rescale, **(fused_kw or {}))
         else:
+            protocol_kw = dict(protocol_kw or {})
+            if eta is None:
+                protocol_kw["sampler_args"] = self.get_sampler_extra_args_i2i(sigmas, steps, sampler_opt, latents, seed, sampler)
             latents = self._denoise_protocol(sampler, latents, sigmas, text, region_state, weight_func, guidance_scale,
-                                             guidance_rescale, n_img, cross_attention_kwargs, eta, num_inference_steps,
-                                             sampler_opt, seed, start_time, timeout, input_hook=keep_known_region,
-                                             control_hook=control_hook, extra_input=extra_input, preview=preview)
-        if latent_processing == 1:                               # :1759-1760
+                                             guidance_rescale, n_img, cross_attention_kwargs, 0.0 if eta is None else eta, steps,
+                                             sampler_opt, seed, a["start_time"], a["timeout"], control_hook=control_hook,
+                                             preview=preview, **protocol_kw)
+        if a["upscale"]:                                         # :1176-1228, :789-838 (inpaiting refuses it on entry)
+            hires = dict(strength=a["upscale_denoising_strength"], sampler_name=a["sampler_name_hires"] or a["sampler_name"],
+                         sampler_opt=a["sampler_opt_hires"] or sampler_opt,
+                         latent_processing=a["unsupported"].get("latent_upscale_processing", False),
+                         **{k: a[k] for k in self._HIRES_SAME})
+            res = self._hires_pass(latents, height, width, a["upscale_x"], a["upscale_method"], a["upscale_antialias"], **hires)
+            return latents_process + res if preview is not None else res
+        if preview is not None:                                  # :1229-1230, :841-842, :1759-1760 (the list ends with the last model call's estimate)
             return latents_process
         return [self.latent_to_image(latents, output_type)]
+
+    # what the hires pass (img2img on the enlarged latents) is given unchanged, as the caller gave it
+    _HIRES_SAME = ("prompt", "num_inference_steps", "guidance_scale", "negative_prompt", "generator", "region_map_state", "seed",
+                   "control_img", "controlnet_conditioning_scale", "control_guidance_start", "control_guidance_end",
+                   "image_t2i_adapter", "adapter_conditioning_scale", "adapter_conditioning_factor", "guidance_rescale",
+                   "cross_attention_kwargs", "clip_skip", "long_encode", "num_images_per_prompt", "weight_func",
+                   "ip_adapter_image_embeds", "prompt_embeds", "negative_prompt_embeds", "text_input_ids", "output_type",
+                   "start_time", "timeout")
+
+    # ---- what the two cores share
+    @staticmethod
+    def _check_timeout(start_time, timeout):
+        """before every model call and every fused step (reference :1094-1095, :707-708, :1596-1597)"""
+        if start_time > 0 and timeout > 0:
+            assert (time.time() - start_time) < timeout, "inference process timed out"
+
+    def _step_key(self, slot, n_img, in_shape, region_state, text, weight_func, ip_key):
+        """the key of a captured step: shapes only (and what the capture bakes in), see _build_or_refresh_step"""
+        levels = tuple(sorted((int(L), tuple(w.shape)) for L, w in region_state.items())) \
+            if isinstance(region_state, dict) else None
+        return (("slot", slot), n_img, in_shape, levels, tuple(text.shape), text.dtype, self._weight_func_key(weight_func), ip_key)
+
+    @staticmethod
+    def _record_done(st, device):
+        """the event a later generation on the same static buffers waits for (_build_or_refresh_step)"""
+        done = st.get("done")
+        if done is None:
+            done = st["done"] = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(device))
 
     # ---- protocol mode: the reference's model_fn closure (:1091-1171) + sampler call (:1172-1175)
     def _denoise_protocol(self, sampler, latents, sigmas, text, region_state, weight_func, guidance_scale,
@@ -1068,6 +1031,20 @@ class StableDiffusionPipeline:
         cfg = self.do_classifier_free_guidance
         kdm = self.k_diffusion_model
         calls = [0]
+
+        def enter(x, sigma):
+            """how both model_fn below begin: the timeout, the caller's input_hook, the call counter -> the model input"""
+            self._check_timeout(start_time, timeout)
+            if input_hook is not None:
+                x = input_hook(x, sigma, calls[0])
+            calls[0] += 1
+            return x
+
+        def sample(model_fn):
+            extra = sampler_args if sampler_args is not None else \
+                self.get_sampler_extra_args_t2i(sigmas, eta, steps, sampler_opt, latents, seed, sampler)
+            return sampler(model_fn, latents, **extra)
+
         # Graph-backed model calls: when nothing has to enter the UNet per call besides (x, sigma) - no ControlNet / adapter
         # residuals, eps-prediction, CFG without rescale, fp16 - the sampler's model call is: one launch that writes the
         # static inputs, ONE replay of the captured UNet step (the fused mode's graph), one launch for CFG + eps -> denoised.
@@ -1077,13 +1054,11 @@ class StableDiffusionPipeline:
                      and not self.v_prediction and latents.is_cuda and text.dtype == torch.float16 and extra_input is None
                      and self._added_cond_kwargs is None and latents.numel() // latents.shape[0] % 4 == 0)
         if use_graph:
-            levels = tuple(sorted((int(L), tuple(w.shape)) for L, w in region_state.items())) \
-                if isinstance(region_state, dict) else None
             ckey = None if control is None else tuple(
                 ("cn", id(self.controlnet), tuple(tuple(i.shape) for i in (p["image"] if isinstance(p["image"], list) else [p["image"]])))
                 if p["kind"] == "controlnet" else ("ad", tuple(tuple(v.shape) for v in p["state"])) for p in control)
-            key = (("slot", slot), n_img, tuple(latents.shape), levels, tuple(text.shape), text.dtype,
-                   self._weight_func_key(weight_func), None) + (() if ckey is None else (ckey,))
+            key = self._step_key(slot, n_img, tuple(latents.shape), region_state, text, weight_func, None) \
+                + (() if ckey is None else (ckey,))
             _lib.check(_lib.load_library().dsc_set_workspace_slot(slot), "dsc_set_workspace_slot")    # see _denoise_fused
             st = self._static_step(key, n_img, tuple(latents.shape), text, region_state, weight_func, cross_attention_kwargs,
                                    control=control)
@@ -1099,11 +1074,7 @@ class StableDiffusionPipeline:
                         st["ad"]["gate"].fill_(1.0 if v else 0.0)
 
             def model_fn(x, sigma):
-                if start_time > 0 and timeout > 0:
-                    assert (time.time() - start_time) < timeout, "inference process timed out"
-                if input_hook is not None:
-                    x = input_hook(x, sigma, calls[0])
-                calls[0] += 1
+                x = enter(x, sigma)
                 s = float(sigma[0])                              # the host needs sigma for (c_in, t): one sync per model call
                 c_in, _, t = kdm.step_scalars(s)
                 d = x.to(text.dtype).contiguous().clone()
@@ -1120,24 +1091,15 @@ class StableDiffusionPipeline:
                     preview[0].append(self.latent_to_image(d, preview[1]))
                 return d.to(x.dtype)
 
-            extra = sampler_args if sampler_args is not None else \
-                self.get_sampler_extra_args_t2i(sigmas, eta, steps, sampler_opt, latents, seed, sampler)
-            out = sampler(model_fn, latents, **extra)
-            done = st.get("done")
-            if done is None:
-                done = st["done"] = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(latents.device))
+            out = sample(model_fn)
+            self._record_done(st, latents.device)
             return out
         if slot:
             raise NotImplementedError("generation slots need the graph-backed model call (eps-prediction, CFG without rescale, "
                                       "fp16, no per-call UNet inputs)")
 
         def model_fn(x, sigma):
-            if start_time > 0 and timeout > 0:
-                assert (time.time() - start_time) < timeout, "inference process timed out"
-            if input_hook is not None:
-                x = input_hook(x, sigma, calls[0])
-            calls[0] += 1
+            x = enter(x, sigma)
             latent_model_input = torch.cat([x] * 2) if cfg else x
             if extra_input is not None:
                 latent_model_input = torch.cat([latent_model_input, extra_input.to(latent_model_input.dtype)], dim=1)
@@ -1162,9 +1124,7 @@ class StableDiffusionPipeline:
                 preview[0].append(self.latent_to_image(noise_pred, preview[1]))
             return noise_pred
 
-        extra = sampler_args if sampler_args is not None else \
-            self.get_sampler_extra_args_t2i(sigmas, eta, steps, sampler_opt, latents, seed, sampler)
-        return sampler(model_fn, latents, **extra)
+        return sample(model_fn)
 
     # ---- fused mode
     def _control_buffers(self, control, st=None):
@@ -1446,8 +1406,7 @@ class StableDiffusionPipeline:
         input channels of a 9-channel UNet (ops.cfg_linear_step_rows_cat writes them behind each latent row)"""
         kdm = self.k_diffusion_model
         for i, (a, b, c, s) in enumerate(coeffs):
-            if start_time > 0 and timeout > 0:
-                assert (time.time() - start_time) < timeout, "inference process timed out"
+            self._check_timeout(start_time, timeout)
             st["run"]()
             nxt = sig[i + 1]
             c_in_n, _, t_n = kdm.step_scalars(nxt) if nxt > 0 else (1.0, 0.0, 0.0)
@@ -1518,8 +1477,6 @@ class StableDiffusionPipeline:
         if family != "dpmpp_2m_sde":
             sargs.pop("solver_type", None)
         coeffs = sampling.linear_step_coefficients(family, sig, **sargs) if rows_path else sampling.dpmpp_2m_coefficients(sig)
-        levels = tuple(sorted((int(L), tuple(w.shape)) for L, w in region_state.items())) \
-            if isinstance(region_state, dict) else None
         ack = getattr(self, "_added_cond_kwargs", None)
         ip_key = None if ack is None else (tuple(tuple(e.shape) for e in ack["image_embeds"]),
                                            id(getattr(self.unet, "encoder_hid_proj", None)))
@@ -1535,8 +1492,7 @@ class StableDiffusionPipeline:
             extra = extra.to(device=latents.device, dtype=latents.dtype).contiguous()
             extras = [extra[j] for j in range(n_img)]
             in_shape = (n_img, in_shape[1] + extra.shape[1]) + in_shape[2:]
-        key = (("slot", slot), n_img, in_shape, levels, tuple(text.shape), text.dtype,
-               self._weight_func_key(weight_func), ip_key)
+        key = self._step_key(slot, n_img, in_shape, region_state, text, weight_func, ip_key)
         if latents.is_cuda:
             # generation slots: each keeps its own static buffers, captured step, packed K/V and library-GEMM workspace, so
             # two generations can be in flight on two streams (one host thread per slot)
@@ -1573,8 +1529,7 @@ class StableDiffusionPipeline:
                                     rescale=guidance_rescale, extras=extras)
             coeffs = []
         for i, (a, b, c) in enumerate(coeffs):
-            if start_time > 0 and timeout > 0:
-                assert (time.time() - start_time) < timeout, "inference process timed out"
+            self._check_timeout(start_time, timeout)
             st["run"]()
             nxt = sig[i + 1]
             c_in_n, _, t_n = kdm.step_scalars(nxt) if nxt > 0 else (1.0, 0.0, 0.0)
@@ -1583,10 +1538,7 @@ class StableDiffusionPipeline:
                                  st["x_in"], st["t"], st["sigma"],
                                  row=(tab[i + 1], st["tadd"]) if tab is not None and i + 1 < len(coeffs) else None)
         if x.is_cuda:
-            done = st.get("done")
-            if done is None:
-                done = st["done"] = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(x.device))
+            self._record_done(st, x.device)
         if prof:
             torch.cuda.synchronize()
             t2 = time.perf_counter()
