@@ -18,6 +18,9 @@ What changes underneath:
   * `weight_func` is a caller-supplied callable (app.py:1004 builds a fresh lambda per request): it is probed once
     with two tiny tensors; if it behaves as `w * sigma * qk.std()` the fused path runs, otherwise the scores are
     materialised, the callable is evaluated as the reference would, and its result is added by the same kernel.
+Which kernel runs a call is decided by `attention_plan` (the facts of the call -> a ROUTE_* constant or the refusal) and run by
+`run_attention`; the limits of the kernels are ops.XATTN_MAX_KEYS / XATTN_MAX_KEYS_PACKED / ATTN_MAX_HEAD_DIM (DESIGN.md
+"Attention routes" is the table; tests/golden/attention_routes.json pins it on the host).
 There is no CPU path: tensors must live on the GPU and libdsc_hip.so must be built.
 """
 import math
@@ -40,107 +43,150 @@ _PROBES = (
     (torch.tensor([[[-0.75, 0.125, 1.0], [4.0, -2.5, 0.0]]]), torch.tensor(0.3125),
      torch.tensor([[[7.0, 1.0, -1.0], [2.5, -4.0, 0.25]]])),
 )
-_WF_CACHE = OrderedDict()
 
 
-def weight_func_is_default(weight_func):
-    """True iff `weight_func(w, sigma, qk)` equals `w * sigma * qk.std()` on two probes (SURVEY.md 7)."""
-    key = id(weight_func)
-    hit = _WF_CACHE.get(key)
-    if hit is not None and hit[0] is weight_func:
-        return hit[1]
-    ok = True
+class _PerObjectCache:
+    """What was derived from an object, keyed by (id, in-place version, *extra): the entry holds the object, so its id cannot be
+    reused while the entry lives; the least recently used entry leaves when there are more than `size`."""
+
+    def __init__(self, size):
+        self.size, self.entries = size, OrderedDict()
+
+    def get(self, obj, make, *extra):
+        key = (id(obj), getattr(obj, "_version", None)) + extra
+        hit = self.entries.get(key)
+        if hit is not None and hit[0] is obj:
+            self.entries.move_to_end(key)
+            return hit[1]
+        value = make()
+        self.entries[key] = (obj, value)
+        while len(self.entries) > self.size:
+            self.entries.popitem(last=False)
+        return value
+
+
+_WF_CACHE, _TABLE_CACHE, _COMPRESSED_CACHE, _SIGMA_CACHE = _PerObjectCache(32), _PerObjectCache(64), _PerObjectCache(64), _PerObjectCache(8)
+
+
+def _probe_weight_func(weight_func):
     try:
         for w, s, qk in _PROBES:
             r = weight_func(w, s, qk)
             e = w * s * qk.std()
             if not (torch.is_tensor(r) and r.shape == e.shape and torch.allclose(r.float(), e, rtol=1e-6, atol=0.0)):
-                ok = False
-                break
+                return False
     except Exception:  # noqa: BLE001 - any failure on the probe means "not the default": take the generic path
-        ok = False
-    _WF_CACHE[key] = (weight_func, ok)          # keeps the callable alive so its id cannot be reused
-    while len(_WF_CACHE) > 32:
-        _WF_CACHE.popitem(last=False)
-    return ok
+        return False
+    return True
+
+
+def weight_func_is_default(weight_func):
+    """True iff `weight_func(w, sigma, qk)` equals `w * sigma * qk.std()` on two probes (SURVEY.md 7)."""
+    return _WF_CACHE.get(weight_func, lambda: _probe_weight_func(weight_func))
+
+
+def weight_func_fused(weight_func):
+    """None or default-equivalent: the fused kernels compute the bias themselves"""
+    return weight_func is None or weight_func_is_default(weight_func)
 
 
 # ----------------------------------------------------------------------------- region table residency
-_TABLE_CACHE = OrderedDict()
-
-
 def resident_table(w, device):
     """fp32 device copy of a region table, made once per (tensor object, version, device)."""
     if w.device == device and w.dtype == torch.float32 and w.is_contiguous():
         return w
-    key = (id(w), w._version, str(device))
-    hit = _TABLE_CACHE.get(key)
-    if hit is not None and hit[0] is w:
-        _TABLE_CACHE.move_to_end(key)
-        return hit[1]
-    dw = w.to(device=device, dtype=torch.float32).contiguous()
-    _TABLE_CACHE[key] = (w, dw)
-    while len(_TABLE_CACHE) > 64:
-        _TABLE_CACHE.popitem(last=False)
-    return dw
-
-
-_COMPRESSED_CACHE = OrderedDict()
+    return _TABLE_CACHE.get(w, lambda: w.to(device=device, dtype=torch.float32).contiguous(), str(device))
 
 
 def compressed_table(w, device):
-    """(ids, rows) of ops.compress_region_table for a region table, or None when it has too many distinct rows;
+    """(ids, rows) of ops.compress_region_table_for_kernel for a region table, or None when it has too many distinct rows;
     computed once per (tensor object, version, device) like resident_table."""
-    key = (id(w), w._version, str(device))
-    hit = _COMPRESSED_CACHE.get(key)
-    if hit is not None and hit[0] is w:
-        return hit[1]
-    comp = ops.compress_region_table(resident_table(w, device))
-    if comp is not None and comp[1].shape[1] <= 96:
-        comp = (comp[0], ops.pad_region_rows(comp[1]))
-    _COMPRESSED_CACHE[key] = (w, comp)
-    while len(_COMPRESSED_CACHE) > 64:
-        _COMPRESSED_CACHE.popitem(last=False)
-    return comp
+    return _COMPRESSED_CACHE.get(w, lambda: ops.compress_region_table_for_kernel(resident_table(w, device)), str(device))
 
 
-_SIGMA_CACHE = OrderedDict()
-
-
-def _sigma_arg(sigma, device):
-    """A python float (host scalar) or an fp32 device scalar (no host sync) for the kernel."""
-    if not torch.is_tensor(sigma):
-        return float(sigma)
-    if not sigma.is_cuda:
+def _sigma_arg(sigma):
+    """What ops.region_xattn[_packed] take as sigma without a host sync: a python float, or an fp32 device tensor - a device
+    scalar of another dtype is converted once per (tensor object, version)."""
+    if not torch.is_tensor(sigma) or not sigma.is_cuda:
         return float(sigma)
     if sigma.dtype == torch.float32:
         return sigma
-    key = (id(sigma), sigma._version)
-    hit = _SIGMA_CACHE.get(key)
-    if hit is not None and hit[0] is sigma:
-        return hit[1]
-    s32 = sigma.detach().float().reshape(1)
-    _SIGMA_CACHE[key] = (sigma, s32)
-    while len(_SIGMA_CACHE) > 8:
-        _SIGMA_CACHE.popitem(last=False)
-    return s32
+    return _SIGMA_CACHE.get(sigma, lambda: sigma.detach().float().reshape(1))
 
 
-_KERNEL_MAX_KEYS = 96      # xattn_shared.h kSMax: one 77-token text chunk (+ padding to three MFMA row tiles)
+# ----------------------------------------------------------------------------- the plan: which route runs an attention call
+ROUTE_FLASH = "flash"                      # dsc_self_attn_fwd: self-attention, and long keys without a table
+ROUTE_SDPA = "sdpa"                        # the library's scaled_dot_product_attention: what no kernel here can read
+ROUTE_PLAIN_KERNEL = "plain-kernel"        # dsc_region_xattn_fwd without a table
+ROUTE_PLAIN_PACKED = "plain-packed"        # dsc_region_xattn_fwd_packed without a table
+ROUTE_PLAIN_MASK = "plain-mask"            # dsc_region_xattn_fwd, the mask as its final bias
+ROUTE_REGION_PACKED = "region-packed"      # dsc_region_xattn_fwd_packed: packed text K/V + (ids, rows) table
+ROUTE_REGION_DENSE = "region-dense"        # dsc_region_xattn_fwd with the dense table
+ROUTE_REGION_GENERIC = "region-generic"    # scores materialised for a custom weight_func, its result the kernel's final bias
+ROUTE_REGION_LONG = "region-long"          # more keys than the kernels hold: the reference's op sequence on the library
+ROUTE_REGION_MASKED = "region-masked"      # dsc_region_xattn_std_masked, then mask + bias as the kernel's final bias
+ROUTES = (ROUTE_FLASH, ROUTE_SDPA, ROUTE_PLAIN_KERNEL, ROUTE_PLAIN_PACKED, ROUTE_PLAIN_MASK, ROUTE_REGION_PACKED, ROUTE_REGION_DENSE,
+          ROUTE_REGION_GENERIC, ROUTE_REGION_LONG, ROUTE_REGION_MASKED)
 
 
-def _region_attention_long(q, k, v, w, sigma, weight_func, layout, n_std_groups, scale):
+def attention_plan(*, S, d, dtype, is_self=False, layout="blhd", table=False, mask=False, packed=False, compressed=None,
+                   fused_weight_func=True, ref16=False, per_group_sigma=False, short_keys_unchecked=True):
+    """The route of one attention call, from its facts alone - decides (or refuses), launches nothing.
+    S keys of head dim d in `dtype`; table: a region table applies; mask: an additive mask applies; packed: the text K/V have a
+    packed image (ops.xattn_kv_pack); compressed: the table has an (ids, rows) form - True, None = not derived yet (assume it
+    has: the caller asks again with False if it turns out to have none), False = none, or the table is a static buffer that must
+    be read densely (region_prompt["compressed"] = False); fused_weight_func: weight_func_fused(); ref16: the reference's fp16
+    rounding; per_group_sigma: one sigma per std group (serving) - only the fused kernels take it.
+    short_keys_unchecked (no table): the sites WITHOUT a mask hand up to XATTN_MAX_KEYS keys to the region kernel whatever the
+    dtype and head dim, and what it cannot read is its refusal (TypeError for fp32); the site WITH a mask passes False and
+    asks first, because the library route takes the mask at any shape.  The difference is older than this plan and is kept."""
+    short = S <= ops.XATTN_MAX_KEYS
+    if table:
+        if per_group_sigma and mask:
+            raise NotImplementedError("per-group sigma: attention masks are not supported")
+        if per_group_sigma and not fused_weight_func:
+            raise NotImplementedError("per-group sigma: a custom weight_func is not supported")
+        if mask:
+            if not short:
+                raise NotImplementedError(f"attention masks with more than {ops.XATTN_MAX_KEYS} text keys")
+            return ROUTE_REGION_MASKED
+        can_pack = packed and compressed is not False and layout == "blhd" and fused_weight_func
+        if not short:
+            # the prepared-operand kernels walk the keys in chunks with an online softmax (fp32 scores, default weight_func,
+            # compressible table); anything else runs the reference's op sequence as library kernels
+            if can_pack and S <= ops.XATTN_MAX_KEYS_PACKED and not ref16:
+                return ROUTE_REGION_PACKED
+            if per_group_sigma:
+                raise NotImplementedError(f"per-group sigma: {S} text keys need the chunked prepared-operand kernels "
+                                          f"(<= {ops.XATTN_MAX_KEYS_PACKED} keys, packed text K/V, compressible table)")
+            return ROUTE_REGION_LONG
+        if not fused_weight_func:
+            return ROUTE_REGION_GENERIC
+        return ROUTE_REGION_PACKED if can_pack else ROUTE_REGION_DENSE
+    if is_self and not mask:
+        return ROUTE_FLASH
+    fits = ops.attn_kernel_takes(dtype, d)
+    if short and (fits or short_keys_unchecked):
+        return ROUTE_PLAIN_MASK if mask else ROUTE_PLAIN_PACKED if packed else ROUTE_PLAIN_KERNEL
+    return ROUTE_FLASH if fits and not mask else ROUTE_SDPA
+
+
+def _scores(q, k, layout, scale):
+    """scale * q k^T materialised by the library, [B, H, L, S]: what a custom weight_func is evaluated on (reference :90-95)"""
+    qh, kh = (q, k) if layout == "bhld" else (q.transpose(1, 2), k.transpose(1, 2))
+    return (qh @ kh.transpose(-2, -1)) * (scale if scale else 1.0 / math.sqrt(q.shape[-1]))
+
+
+def _region_attention_long(q, k, v, w, sigma, weight_func, fused, layout, n_std_groups, scale):
     """Prompts longer than one 77-token chunk (S = 154, 231, ... from the A1111-style encoder): the fused kernels hold
-    at most 96 keys, so the reference's op sequence (attention_modify.py:90-103) runs as library kernels on the GPU -
-    scores materialised once, the std over the std group(s), bias add, softmax, PV."""
-    qh, kh, vh = (q, k, v) if layout == "bhld" else (q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2))
-    B, H, L, d = qh.shape
-    S = kh.shape[2]
-    sf = scale if scale else 1.0 / math.sqrt(d)
-    scores = (qh @ kh.transpose(-2, -1)) * sf                                   # [B, H, L, S]
+    at most ops.XATTN_MAX_KEYS keys, so the reference's op sequence (attention_modify.py:90-103) runs as library kernels on
+    the GPU - scores materialised once, the std over the std group(s), bias add, softmax, PV."""
+    vh = v if layout == "bhld" else v.transpose(1, 2)
+    scores = _scores(q, k, layout, scale)
+    B, H, L, S = scores.shape
     w_dev = resident_table(w, q.device)
     sig = sigma.float() if (torch.is_tensor(sigma) and sigma.is_cuda) else float(sigma)   # device scalar: no host sync (graphs)
-    if weight_func is not None and not weight_func_is_default(weight_func):
+    if not fused:
         bias = torch.broadcast_to(weight_func(w_dev, sigma, scores.reshape(-1, L, S)), w_dev.shape)
     elif n_std_groups == 1:
         bias = w_dev * sig * scores.float().std()
@@ -154,24 +200,17 @@ def _region_attention_long(q, k, v, w, sigma, weight_func, layout, n_std_groups,
     return out if layout == "bhld" else out.transpose(1, 2).contiguous()
 
 
-_KERNEL_MAX_KEYS_PACKED = 384   # region_xattn_packed.hip kChunksMax x 96: long prompts (77 n tokens) on the chunked kernels
-
-
-def _region_attention_masked(q, k, v, w, sigma, weight_func, layout, n_std_groups, scale, ref16, mask):
+def _region_attention_masked(q, k, v, w, sigma, weight_func, fused, layout, n_std_groups, scale, ref16, mask):
     """The region path with an additive attention mask (reference :85-97 / :144-170): the mask enters the scores BEFORE the
     statistics, so the std comes from dsc_region_xattn_std_masked; mask + w * sigma * std is then the final bias of the
     forward kernel (one dense fp32 [Bc*H, L, S] tensor - this is the rarely-taken path, app.py never passes a mask)."""
-    qh = q if layout == "bhld" else q.transpose(1, 2)
-    Bc, H, L, d = qh.shape
+    Bc, H, L, _ = q.shape if layout == "bhld" else q.transpose(1, 2).shape
     S = k.shape[2 if layout == "bhld" else 1]
-    if S > _KERNEL_MAX_KEYS:
-        raise NotImplementedError("attention masks with more than 96 text keys")
-    m3 = mask.float()
-    while m3.dim() < 3:
-        m3 = m3.unsqueeze(0)
+    # a custom weight_func meets a mask of another shape in its own `scores + mask` below (RuntimeError, as the reference's)
+    m3 = ops.mask_3d(mask, Bc * H, L, S, check=fused)
     w_dev = resident_table(w, q.device)
     rep = (Bc * H) // w_dev.shape[0]
-    if weight_func is None or weight_func_is_default(weight_func):
+    if fused:
         std = ops.region_xattn_std(q, k, layout=layout, n_std_groups=n_std_groups, scale=scale, ref_fp16_rounding=ref16, mask=m3)
         sig = sigma.float() if (torch.is_tensor(sigma) and sigma.is_cuda) else float(sigma)
         if ref16:                                                                   # 0-dim fp16 tensors in the fp16 pipeline
@@ -180,64 +219,84 @@ def _region_attention_masked(q, k, v, w, sigma, weight_func, layout, n_std_group
         grp = (torch.arange(Bc * H, device=q.device) // H) % n_std_groups           # row bh = b * H + h belongs to group b % n
         region = torch.repeat_interleave(w_dev, rep, dim=0) * sig * std[grp].reshape(-1, 1, 1)
     else:
-        kh = k if layout == "bhld" else k.transpose(1, 2)
-        sf = scale if scale else 1.0 / math.sqrt(d)
-        scores = ((qh @ kh.transpose(-2, -1)) * sf).reshape(-1, L, S) + m3.to(qh.dtype)
+        scores = _scores(q, k, layout, scale).reshape(-1, L, S) + m3.to(q.dtype)
         region = torch.repeat_interleave(torch.broadcast_to(weight_func(w_dev, sigma, scores), w_dev.shape).float(), rep, dim=0)
     bias = (region + m3).contiguous()
     return ops.region_xattn(q, k, v, bias, 1.0, layout=layout, scale=scale, bias_is_final=True, ref_fp16_rounding=ref16)
 
 
-def _region_attention(q, k, v, w, sigma, weight_func, layout, n_std_groups, scale=None, ref16=False, packed_kv=None,
-                      comp=None, mask=None, per_group_sigma=False):
-    """comp: the caller's (ids, rows) of `w`, None = compress `w` here (cached per tensor version), False = `w` is a static
-    buffer whose CONTENTS change between replays of a captured step: read it densely, derive nothing from its values.
-    per_group_sigma: `sigma` is an [n_std_groups] fp32 device tensor, one sigma per std group (continuous batching,
-    modules/serving/) - only the fused default-weight_func kernels take it; every other route raises NotImplementedError."""
-    S = k.shape[2 if layout == "bhld" else 1]
-    if per_group_sigma:
-        if mask is not None:
-            raise NotImplementedError("per-group sigma: attention masks are not supported")
-        if weight_func is not None and not weight_func_is_default(weight_func):
-            raise NotImplementedError("per-group sigma: a custom weight_func is not supported")
-    if mask is not None:
-        return _region_attention_masked(q, k, v, w, sigma, weight_func, layout, n_std_groups, scale, ref16, mask)
-    if comp is False:
-        packed_kv, comp = None, None
-    if S > _KERNEL_MAX_KEYS:
-        # long prompts: the prepared-operand kernels walk the keys in chunks of 96 with an online softmax (fp32 scores, default
-        # weight_func, compressible table); anything else runs the reference's op sequence as library kernels
-        if (S <= _KERNEL_MAX_KEYS_PACKED and packed_kv is not None and layout == "blhd" and not ref16
-                and (weight_func is None or weight_func_is_default(weight_func))):
-            if comp is None:
-                comp = compressed_table(w, q.device)
-            if comp is not None:
-                return ops.region_xattn_packed(q, packed_kv, S, comp, _sigma_arg(sigma, q.device), n_std_groups=n_std_groups,
-                                               scale=scale, ref_fp16_rounding=False, per_group_sigma=per_group_sigma)
-        if per_group_sigma:
-            raise NotImplementedError(f"per-group sigma: {S} text keys need the chunked prepared-operand kernels "
-                                      f"(<= {_KERNEL_MAX_KEYS_PACKED} keys, packed text K/V, compressible table)")
-        return _region_attention_long(q, k, v, w, sigma, weight_func, layout, n_std_groups, scale)
-    if weight_func is None or weight_func_is_default(weight_func):
-        if packed_kv is not None and layout == "blhd":
-            if comp is None:
-                comp = compressed_table(w, q.device)
-            if comp is not None:                 # prepared operands: packed text K/V + row-id region table
-                return ops.region_xattn_packed(q, packed_kv, k.shape[1], comp, _sigma_arg(sigma, q.device),
-                                               n_std_groups=n_std_groups, scale=scale, ref_fp16_rounding=ref16,
-                                               per_group_sigma=per_group_sigma)
-        w_dev = resident_table(w, q.device)
-        return ops.region_xattn(q, k, v, w_dev, _sigma_arg(sigma, q.device), layout=layout, n_std_groups=n_std_groups,
-                                scale=scale, ref_fp16_rounding=ref16, per_group_sigma=per_group_sigma)
+def _region_attention_generic(q, k, v, w, sigma, weight_func, layout, scale, ref16):
+    """a custom weight_func: evaluate it the way the reference does (attention_modify.py:90-95), then let the kernel add its
+    result (flag BIAS_IS_FINAL).  Slow path by construction - the scores are materialised once."""
     w_dev = resident_table(w, q.device)
-    # generic weight_func: evaluate it the way the reference does (attention_modify.py:90-95), then let the kernel
-    # add its result (flag BIAS_IS_FINAL).  Slow path by construction - the scores are materialised once.
-    qh, kh = (q, k) if layout == "bhld" else (q.transpose(1, 2), k.transpose(1, 2))
-    sf = scale if scale else 1.0 / math.sqrt(q.shape[-1])
-    scores = (qh @ kh.transpose(-2, -1)) * sf
+    scores = _scores(q, k, layout, scale)
     bias = weight_func(w_dev, sigma, scores.reshape(-1, scores.shape[-2], scores.shape[-1]))
     bias = torch.broadcast_to(bias, w_dev.shape).float().contiguous()
     return ops.region_xattn(q, k, v, bias, 1.0, layout=layout, scale=scale, bias_is_final=True, ref_fp16_rounding=ref16)
+
+
+def run_attention(route, q, k, v, *, layout="blhd", scale=None, mask=None, packed_kv=None, table=None, comp=None, sigma=1.0,
+                  weight_func=None, fused=True, n_std_groups=1, ref16=False, per_group_sigma=False):
+    """Runs the route attention_plan chose.  q / k / v [B, L | S, H, d] ('blhd': views of the projection outputs, the only layout
+    of the routes without a table) or [B, H, L | S, d] ('bhld') -> the attention output in q's layout, contiguous.
+    mask: additive, [B*H, 1|L, S] without a table, anything ops.mask_3d takes with one; table: the region table, comp its
+    (ids, rows); the defaults are a call without a table (sigma 1, one std group, fp32 scores)."""
+    if route == ROUTE_FLASH:
+        return ops.self_attention(q, k, v, scale=scale)          # [B, L, H, d]; S != L: long keys without a table
+    S = k.shape[2 if layout == "bhld" else 1]
+    if route in (ROUTE_REGION_PACKED, ROUTE_PLAIN_PACKED):       # prepared operands: packed text K/V (+ row-id region table)
+        return ops.region_xattn_packed(q, packed_kv, S, comp, _sigma_arg(sigma), n_std_groups=n_std_groups, scale=scale,
+                                       ref_fp16_rounding=ref16, per_group_sigma=per_group_sigma)
+    if route in (ROUTE_REGION_DENSE, ROUTE_PLAIN_KERNEL):
+        w_dev = None if table is None else resident_table(table, q.device)
+        return ops.region_xattn(q, k, v, w_dev, _sigma_arg(sigma), layout=layout, n_std_groups=n_std_groups, scale=scale,
+                                ref_fp16_rounding=ref16, per_group_sigma=per_group_sigma)
+    if route == ROUTE_REGION_GENERIC:
+        return _region_attention_generic(q, k, v, table, sigma, weight_func, layout, scale, ref16)
+    if route == ROUTE_REGION_LONG:
+        return _region_attention_long(q, k, v, table, sigma, weight_func, fused, layout, n_std_groups, scale)
+    if route == ROUTE_REGION_MASKED:
+        return _region_attention_masked(q, k, v, table, sigma, weight_func, fused, layout, n_std_groups, scale, ref16, mask)
+    B, L, H, _ = q.shape
+    if route == ROUTE_PLAIN_MASK:                                # (:483-485 / :182-186) the mask is the forward kernel's final bias
+        bias = torch.broadcast_to(mask.float(), (B * H, L, S)).contiguous()
+        return ops.region_xattn(q, k, v, bias, 1.0, layout="blhd", scale=scale, bias_is_final=True, ref_fp16_rounding=False)
+    if route != ROUTE_SDPA:
+        raise ValueError(f"unknown attention route {route!r}")
+    m4 = None if mask is None else mask.view(B, H, -1, S).to(q.dtype)
+    return F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), attn_mask=m4,
+                                          scale=scale).transpose(1, 2).contiguous()
+
+
+def _plain_attention(q4, k4, v4, scale, *, mask3=None, packed_kv=None, is_self=False):
+    """Attention without a region table, q4 [B, L, H, d], k4 / v4 [B, S, H, d]: the flash kernel for self-attention; else the
+    region kernel (no table, or the mask as its final bias) when the keys fit it, the flash kernel when dtype and head dim fit,
+    the library's SDPA otherwise.  Only the call with a mask asks about dtype and head dim before it takes the region kernel
+    (attention_plan, short_keys_unchecked)."""
+    route = attention_plan(S=k4.shape[1], d=q4.shape[-1], dtype=q4.dtype, is_self=is_self, mask=mask3 is not None,
+                           packed=packed_kv is not None, short_keys_unchecked=mask3 is None)
+    return run_attention(route, q4, k4, v4, scale=scale, mask=mask3, packed_kv=packed_kv)
+
+
+def _region_attention(q, k, v, w, sigma, weight_func, layout, n_std_groups, scale=None, ref16=False, packed_kv=None,
+                      comp=None, mask=None, per_group_sigma=False):
+    """Attention with the region table `w`.  comp: the caller's (ids, rows) of `w`, None = compress `w` here when a route needs it
+    (cached per tensor version), False = `w` is a static buffer whose CONTENTS change between replays of a captured step: read it
+    densely, derive nothing from its values.
+    per_group_sigma: `sigma` is an [n_std_groups] fp32 device tensor, one sigma per std group (continuous batching,
+    modules/serving/) - only the fused default-weight_func kernels take it; every other route raises NotImplementedError."""
+    fused = weight_func_fused(weight_func)                       # asked once per call
+    facts = dict(S=k.shape[2 if layout == "bhld" else 1], d=q.shape[-1], dtype=q.dtype, layout=layout, table=True,
+                 mask=mask is not None, packed=packed_kv is not None, fused_weight_func=fused, ref16=ref16,
+                 per_group_sigma=per_group_sigma)
+    route = attention_plan(compressed=None if comp is None else comp is not False, **facts)
+    if route == ROUTE_REGION_PACKED and comp is None:
+        comp = compressed_table(w, q.device)
+        if comp is None:                                         # more distinct rows than the kernels' table holds
+            route = attention_plan(compressed=False, **facts)
+    return run_attention(route, q, k, v, layout=layout, scale=scale, mask=mask, packed_kv=packed_kv, table=w, comp=comp, sigma=sigma,
+                         weight_func=weight_func, fused=fused, n_std_groups=n_std_groups, ref16=ref16,
+                         per_group_sigma=per_group_sigma)
 
 
 def scaled_dot_product_attention_regionstate(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False,
@@ -300,7 +359,7 @@ class _RegionProcessor:
         # u_net_condition_modify.LNFold): hidden_states is the UN-normalised residual stream, the block's LayerNorm is
         # folded into the q / qkv projection, the block's residual add into to_out, and (output, row statistics) is returned
         residual = hidden_states
-        img_sequence_length = hidden_states.shape[1]              # :427 - dim 1 also for 4-D input
+        n_queries = hidden_states.shape[1]                        # :427 - dim 1 also for 4-D input
         ip_hidden_states = None
         # prepared rows (the continuous batcher's step, see prepared_ip_rows): the text arrives alone - no split, which in its
         # deprecated single-tensor form would cut the last num_tokens[0] text rows off
@@ -309,107 +368,93 @@ class _RegionProcessor:
             encoder_hidden_states, ip_hidden_states = self._split_ip(encoder_hidden_states)
         if attn.spatial_norm is not None:
             hidden_states = attn.spatial_norm(hidden_states, temb)
-        input_ndim = hidden_states.ndim
-        if input_ndim == 4:
-            batch_size, channel, height, width = hidden_states.shape
-            hidden_states = hidden_states.view(batch_size, channel, height * width).transpose(1, 2)
-        is_xattn = encoder_hidden_states is not None and region_prompt is not None
+        image_shape = hidden_states.shape if hidden_states.ndim == 4 else None
+        if image_shape is not None:
+            hidden_states = hidden_states.view(image_shape[0], image_shape[1], -1).transpose(1, 2)
+        is_self = encoder_hidden_states is None
         mask3 = None
         if attention_mask is not None:
             # reference :144 / :448-452: [B, 1|L, S_mask] -> padded to the key length and repeated per head -> [B*H, 1|L, S]
-            kv_len = hidden_states.shape[1] if encoder_hidden_states is None else encoder_hidden_states.shape[1]
+            kv_len = hidden_states.shape[1] if is_self else encoder_hidden_states.shape[1]
             mask3 = attn.prepare_attention_mask(attention_mask, kv_len, hidden_states.shape[0])
         if attn.group_norm is not None:
             hidden_states = attn.group_norm(hidden_states.transpose(1, 2)).transpose(1, 2)
-        is_self = encoder_hidden_states is None
-        H = attn.heads
-        packed_kv = None
-        fused_qkv = getattr(attn, "qkv_weight", None)
-        if is_self and fused_qkv is not None and attn.to_q.bias is None:
-            # self-attention: q, k, v from ONE [3C, C] GEMM; the three [B, L, H, d] operands are strided views of it
-            B, L, _ = hidden_states.shape
-            wq = fused_qkv()
-            w2, b2, ln = _ln_fold.folded(attn, "qkv", wq) if _ln_fold is not None else (wq, None, None)
-            if ops.linear_qkv_covers(hidden_states, wq, H):
-                # the GEMM's epilogue writes K / V head-major: the flash kernel's key tiles are then contiguous DMA pieces
-                q4, k4, v4 = ops.linear_qkv(hidden_states, w2, b2, H, ln=ln)
-                C = wq.shape[0] // 3
-                d = C // H
-            else:
-                qkv = ops.linear_ln(hidden_states, w2, b2, ln=ln) if ln is not None else ops.linear(hidden_states, wq)
-                C = qkv.shape[-1] // 3
-                d = C // H
-                q4, k4, v4 = (qkv[..., i * C:(i + 1) * C].unflatten(-1, (H, d)) for i in range(3))
-            S = L
-        else:
-            if _ln_fold is not None:
-                w2, b2, ln = _ln_fold.folded(attn, "q", attn.to_q.weight, attn.to_q.bias)
-                query = ops.linear_ln(hidden_states, w2, b2, ln=ln)
-            else:
-                query = ops.linear(hidden_states, attn.to_q.weight, attn.to_q.bias) if type(attn.to_q) is nn.Linear \
-                    else attn.to_q(hidden_states)
-            if is_self:
-                encoder_hidden_states = hidden_states
-            elif attn.norm_cross:
-                encoder_hidden_states = attn.norm_encoder_hidden_states(encoder_hidden_states)
-            cache = getattr(attn, "kv_cache", None)
-            if cache is not None and cache["src"] is not encoder_hidden_states:     # another generation slot's text buffer?
-                cache = next((c for c in getattr(attn, "kv_caches", ()) if c["src"] is encoder_hidden_states), None)
-            if cache is not None and cache["src"] is encoder_hidden_states:
-                key, value = cache["k"], cache["v"]          # text K/V: once per generation, not once per step
-                packed_kv = cache.get("packed")
-            else:
-                key = attn.to_k(encoder_hidden_states)
-                value = attn.to_v(encoder_hidden_states)
-            if not is_self and key.shape[0] != query.shape[0] and key.shape[0] % query.shape[0] == 0:
-                # shared CFG prefix (UNet2DConditionModel.forward): up to the first cross-attention the unconditional and
-                # the conditional rows of the batch are the same numbers and were computed once - from here on they differ
-                # (one image: a stride-0 batch dimension - the kernels take the query's strides - instead of a 5 MB copy launch)
-                query = query.expand(key.shape[0], -1, -1) if query.shape[0] == 1 else query.repeat(key.shape[0] // query.shape[0], 1, 1)
-            B, L, C = query.shape
-            d = C // H
-            S = key.shape[1]
-            q4, k4, v4 = query.view(B, L, H, d), key.view(B, S, H, d), value.view(B, S, H, d)
+        q4, k4, v4, packed_kv = self._project_qkv(attn, hidden_states, encoder_hidden_states, _ln_fold)
         sc = attn.scale if self.honours_attn_scale else None
-        if is_xattn and isinstance(region_prompt["region_state"], dict):
-            w = region_prompt["region_state"][img_sequence_length]          # KeyError when L is not a level (:481)
-            groups = region_prompt.get("n_std_groups", self.n_std_groups)
-            pre = region_prompt.get("compressed")                           # the pipeline's static (ids, rows) buffers
-            comp = pre.get(img_sequence_length) if isinstance(pre, dict) else (False if pre is False else None)
-            if mask3 is not None and not self.honours_attn_scale:
-                # AttnProcessor2_0 hands the [B, H, ., S] view of the mask to scaled_dot_product_attention_regionstate, whose
-                # in-place `attn_bias += attn_mask` into an [L, S] tensor torch refuses for any 4-D mask (:89): the
-                # reference raises here - so does this (same exception type)
-                torch.zeros(L, S, dtype=q4.dtype, device=q4.device).add_(mask3.view(B, H, -1, S))
-            out = _region_attention(q4, k4, v4, w, region_prompt["sigma"], region_prompt["weight_func"], "blhd",
-                                    groups, sc, ref16=self.ref_fp16_rounding, packed_kv=packed_kv, comp=comp, mask=mask3,
-                                    per_group_sigma=bool(region_prompt.get("sigma_per_group", False)))
-        elif mask3 is not None:
-            # no region table: plain masked attention (:483-485 / :182-186) - the mask is the forward kernel's final bias when
-            # the keys fit it, else the library's SDPA
-            if S <= _KERNEL_MAX_KEYS and q4.dtype == torch.float16 and d % 8 == 0 and d <= 160:
-                bias = torch.broadcast_to(mask3.float(), (B * H, L, S)).contiguous()
-                out = ops.region_xattn(q4, k4, v4, bias, 1.0, layout="blhd", scale=sc, bias_is_final=True, ref_fp16_rounding=False)
-            else:
-                out = F.scaled_dot_product_attention(q4.transpose(1, 2), k4.transpose(1, 2), v4.transpose(1, 2),
-                                                     attn_mask=mask3.view(B, H, -1, S).to(q4.dtype), scale=sc).transpose(1, 2).contiguous()
-        elif not is_self:
-            if S > _KERNEL_MAX_KEYS and q4.dtype == torch.float16 and d % 8 == 0 and d <= 160:
-                out = ops.self_attention(q4, k4, v4, scale=sc)      # long prompt without a region table: the flash kernel (S != L)
-            elif S > _KERNEL_MAX_KEYS:
-                out = F.scaled_dot_product_attention(q4.transpose(1, 2), k4.transpose(1, 2), v4.transpose(1, 2),
-                                                     scale=sc).transpose(1, 2).contiguous()
-            elif packed_kv is not None:
-                out = ops.region_xattn_packed(q4, packed_kv, S, None, scale=sc, ref_fp16_rounding=False)
-            else:
-                out = ops.region_xattn(q4, k4, v4, None, layout="blhd", scale=sc, ref_fp16_rounding=False)
-        else:
-            out = ops.self_attention(q4, k4, v4, scale=sc)                  # [B, L, H, d]
-        hidden_states = out.reshape(B, L, C)
+        out = self._attend(q4, k4, v4, sc, packed_kv, mask3, None if is_self else region_prompt, n_queries, is_self)
+        hidden_states = out.reshape(q4.shape[0], q4.shape[1], -1)
         if ip_rows is not None:
             hidden_states = self._ip_rows_branch(q4, hidden_states, ip_rows[self], ip_adapter_masks, sc)
         elif self.is_ip_adapter:
             hidden_states = self._ip_branch(attn, q4, hidden_states, ip_hidden_states, ip_adapter_masks, sc)
+        return self._project_out(attn, hidden_states, residual, image_shape, _ln_fold)
+
+    @staticmethod
+    def _project_qkv(attn, hidden_states, encoder_hidden_states, _ln_fold):
+        """-> q4 [B, L, H, d], k4 / v4 [B, S, H, d] (views) and the packed image of the text K/V, or None"""
+        is_self = encoder_hidden_states is None
+        H = attn.heads
+        fused_qkv = getattr(attn, "qkv_weight", None)
+        if is_self and fused_qkv is not None and attn.to_q.bias is None:
+            # self-attention: q, k, v from ONE [3C, C] GEMM; the three [B, L, H, d] operands are strided views of it
+            wq = fused_qkv()
+            w2, b2, ln = _ln_fold.folded(attn, "qkv", wq) if _ln_fold is not None else (wq, None, None)
+            if ops.linear_qkv_covers(hidden_states, wq, H):
+                # the GEMM's epilogue writes K / V head-major: the flash kernel's key tiles are then contiguous DMA pieces
+                return (*ops.linear_qkv(hidden_states, w2, b2, H, ln=ln), None)
+            qkv = ops.linear_ln(hidden_states, w2, b2, ln=ln) if ln is not None else ops.linear(hidden_states, wq)
+            C = qkv.shape[-1] // 3
+            return (*(qkv[..., i * C:(i + 1) * C].unflatten(-1, (H, C // H)) for i in range(3)), None)
+        if _ln_fold is not None:
+            w2, b2, ln = _ln_fold.folded(attn, "q", attn.to_q.weight, attn.to_q.bias)
+            query = ops.linear_ln(hidden_states, w2, b2, ln=ln)
+        else:
+            query = ops.linear(hidden_states, attn.to_q.weight, attn.to_q.bias) if type(attn.to_q) is nn.Linear \
+                else attn.to_q(hidden_states)
+        if is_self:
+            encoder_hidden_states = hidden_states
+        elif attn.norm_cross:
+            encoder_hidden_states = attn.norm_encoder_hidden_states(encoder_hidden_states)
+        packed_kv = None
+        cache = getattr(attn, "kv_cache", None)
+        if cache is not None and cache["src"] is not encoder_hidden_states:     # another generation slot's text buffer?
+            cache = next((c for c in getattr(attn, "kv_caches", ()) if c["src"] is encoder_hidden_states), None)
+        if cache is not None and cache["src"] is encoder_hidden_states:
+            key, value = cache["k"], cache["v"]          # text K/V: once per generation, not once per step
+            packed_kv = cache.get("packed")
+        else:
+            key = attn.to_k(encoder_hidden_states)
+            value = attn.to_v(encoder_hidden_states)
+        if not is_self and key.shape[0] != query.shape[0] and key.shape[0] % query.shape[0] == 0:
+            # shared CFG prefix (UNet2DConditionModel.forward): up to the first cross-attention the unconditional and
+            # the conditional rows of the batch are the same numbers and were computed once - from here on they differ
+            # (one image: a stride-0 batch dimension - the kernels take the query's strides - instead of a 5 MB copy launch)
+            query = query.expand(key.shape[0], -1, -1) if query.shape[0] == 1 else query.repeat(key.shape[0] // query.shape[0], 1, 1)
+        B, L, C = query.shape
+        S = key.shape[1]
+        return query.view(B, L, H, C // H), key.view(B, S, H, C // H), value.view(B, S, H, C // H), packed_kv
+
+    def _attend(self, q4, k4, v4, sc, packed_kv, mask3, region_prompt, n_queries, is_self):
+        """the text (or self-) attention -> [B, L, H, d]: with the region table of the level when the call carries one"""
+        if region_prompt is None or not isinstance(region_prompt["region_state"], dict):
+            return _plain_attention(q4, k4, v4, sc, mask3=mask3, packed_kv=packed_kv, is_self=is_self)
+        w = region_prompt["region_state"][n_queries]                    # KeyError when L is not a level (:481)
+        pre = region_prompt.get("compressed")                           # the pipeline's static (ids, rows) buffers
+        comp = pre.get(n_queries) if isinstance(pre, dict) else (False if pre is False else None)
+        if mask3 is not None and not self.honours_attn_scale:
+            # AttnProcessor2_0 hands the [B, H, ., S] view of the mask to scaled_dot_product_attention_regionstate, whose
+            # in-place `attn_bias += attn_mask` into an [L, S] tensor torch refuses for any 4-D mask (:89): the
+            # reference raises here - so does this (same exception type)
+            B, L, H, _ = q4.shape
+            S = k4.shape[1]
+            torch.zeros(L, S, dtype=q4.dtype, device=q4.device).add_(mask3.view(B, H, -1, S))
+        return _region_attention(q4, k4, v4, w, region_prompt["sigma"], region_prompt["weight_func"], "blhd",
+                                 region_prompt.get("n_std_groups", self.n_std_groups), sc, ref16=self.ref_fp16_rounding,
+                                 packed_kv=packed_kv, comp=comp, mask=mask3,
+                                 per_group_sigma=bool(region_prompt.get("sigma_per_group", False)))
+
+    @staticmethod
+    def _project_out(attn, hidden_states, residual, image_shape, _ln_fold):
         to_out = attn.to_out[0]
         if _ln_fold is not None:
             # the block's `x = attn(norm(x)) + x` add and the next LayerNorm's row statistics ride in this GEMM's epilogue
@@ -418,8 +463,8 @@ class _RegionProcessor:
         hidden_states = ops.linear(hidden_states, to_out.weight, to_out.bias) if type(to_out) is nn.Linear \
             else to_out(hidden_states)
         hidden_states = attn.to_out[1](hidden_states)
-        if input_ndim == 4:
-            hidden_states = hidden_states.transpose(-1, -2).reshape(batch_size, channel, height, width)
+        if image_shape is not None:
+            hidden_states = hidden_states.transpose(-1, -2).reshape(image_shape)
         if attn.residual_connection:
             hidden_states = hidden_states + residual
         if attn.rescale_output_factor != 1.0:
@@ -534,14 +579,7 @@ class _IPAdapterProcessor(_RegionProcessor, nn.Module):
             T = cur.shape[1]
             k4 = to_k_ip(cur).view(B, T, H, d)
             v4 = to_v_ip(cur).view(B, T, H, d)
-            if T <= 96:
-                o = ops.region_xattn(q4, k4, v4, None, layout="blhd", scale=sc, ref_fp16_rounding=False)
-            elif q4.dtype == torch.float16 and d % 8 == 0 and d <= 160:
-                o = ops.self_attention(q4, k4, v4, scale=sc)          # 257-token variants (Full / Plus): the flash kernel, S != L
-            else:
-                o = F.scaled_dot_product_attention(q4.transpose(1, 2), k4.transpose(1, 2), v4.transpose(1, 2),
-                                                   scale=sc).transpose(1, 2)
-            o = o.reshape(B, L, H * d)
+            o = _plain_attention(q4, k4, v4, sc).reshape(B, L, H * d)    # 257-token variants (Full / Plus): the flash kernel
             if mask is not None:
                 md = IPAdapterMaskProcessor.downsample(mask, B, o.shape[1], o.shape[2])
                 o = o * md.to(dtype=o.dtype, device=o.device)

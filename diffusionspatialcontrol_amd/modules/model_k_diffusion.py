@@ -39,7 +39,7 @@ import torch
 from .. import _lib, ops
 from . import sampling
 from .encode_region_map_function import encode_region_map
-from .attention_modify import weight_func_is_default
+from .attention_modify import weight_func_fused
 from .external_k_diffusion import CompVisDenoiser, CompVisVDenoiser
 
 
@@ -1177,8 +1177,8 @@ class StableDiffusionPipeline:
         # kernels) reads the DENSE table - so the graph must be given a static device copy that each generation refreshes in
         # place, never the first generation's own tensors (a later generation with the same shapes would replay old masks).
         need_dense = isinstance(region_state, dict) and bool(region_state) and (
-            comp_cpu is None or self._weight_func_key(weight_func) != "default" or text.shape[1] > 384
-            or not self._all_cross_attention_packable())         # (<= 384 text keys: the chunked prepared-operand kernels)
+            comp_cpu is None or self._weight_func_key(weight_func) != "default" or text.shape[1] > ops.XATTN_MAX_KEYS_PACKED
+            or not self._all_cross_attention_packable())         # (beyond the chunked prepared-operand kernels)
         if (st is not None and (st["compressed"] is None) == (comp_cpu is None)
                 and (st["dense"] is None) == (not need_dense) and st["profile"] == ops.tuning_profile()):
             done = st.get("done")
@@ -1273,8 +1273,7 @@ class StableDiffusionPipeline:
         from .u_net_condition_modify import Attention
         for m in self.unet.modules():
             if isinstance(m, Attention) and m.is_cross_attention:
-                d = m.to_q.weight.shape[0] // m.heads
-                if d % 8 != 0 or d > 160:
+                if not ops.xattn_kv_packable(1, m.to_q.weight.shape[0] // m.heads):      # the head dim alone: whatever the keys
                     return False
         return True
 
@@ -1286,7 +1285,7 @@ class StableDiffusionPipeline:
         warm-up steps and a capture under the capture lock per request - and by object identity otherwise: a captured MUTABLE
         object hashes by identity, two closures over it would share one captured step whose baked-in scalars go stale when the
         object changes, and the key would keep the object alive as long as the graph cache."""
-        if weight_func is None or weight_func_is_default(weight_func):
+        if weight_func_fused(weight_func):
             return "default"
 
         def immutable(v):
@@ -1316,11 +1315,9 @@ class StableDiffusionPipeline:
             return None
         out = {}
         for L, w in region_state.items():
-            c = ops.compress_region_table(w.float().cpu() if w.is_cuda else w.float(), pad_rows=True)
+            c = ops.compress_region_table_for_kernel(w.float().cpu() if w.is_cuda else w.float(), pad_rows=True)
             if c is None:
                 return None
-            if c[1].shape[1] <= 96:            # one text chunk: the rows in the forward kernel's own table shape (flat 16-byte copy)
-                c = (c[0], ops.pad_region_rows(c[1]))
             out[L] = c
         return out
 
@@ -1366,7 +1363,7 @@ class StableDiffusionPipeline:
                     slots[:] = [e for e in others if e.get("pin")] + [e for e in others if not e.get("pin")][-3:] + [c]
                 m.kv_cache = c
                 # MFMA-fragment image of K / V^T for the fused kernel (rewritten in place: captured graphs keep reading it)
-                if S <= 384 and d % 8 == 0 and d <= 160:          # > 96 keys: one image per 96-key chunk (long prompts)
+                if ops.xattn_kv_packable(S, d):                  # long prompts: one image per chunk of ops.XATTN_MAX_KEYS keys
                     c["packed"] = ops.xattn_kv_pack(c["k"].view(B, S, m.heads, d), c["v"].view(B, S, m.heads, d),
                                                     out=c.get("packed"))
 

@@ -127,7 +127,7 @@ class _GraphExecutor:
             raise NotImplementedError("serve: needs the UNet's per-step time-embedding tables (temb_add_table)")
         if not pipe._all_cross_attention_packable():
             raise NotImplementedError("serve: every cross-attention head dim must run the prepared-operand kernels "
-                                      "(d % 8 == 0, d <= 160)")
+                                      f"(a multiple of 8, at most {ops.ATTN_MAX_HEAD_DIM})")
         c = unet.config.in_channels
         # lat_shape: a request's latent (x / old, noise, outputs); in_shape: a row of the bucket's model input - the same, but
         # [latents | mask | masked-image latents] on a batcher built with `inpaint_unet=True` (reference :1617-1619)

@@ -28,12 +28,13 @@ down-samples the same mask at the target size's levels.
 """
 import torch
 
+from ... import ops
 from .. import sampling
-from ..attention_modify import weight_func_is_default
+from ..attention_modify import weight_func_fused
 from ..external_k_diffusion import DiscreteVDDPMDenoiser
 from ..latent_resample import MODES as _RESAMPLE_MODES, hires_target_size
 
-MAX_TEXT_KEYS = 384                  # the chunked prepared-operand kernels (ops.region_xattn_packed)
+MAX_TEXT_KEYS = ops.XATTN_MAX_KEYS_PACKED     # the chunked prepared-operand kernels (ops.region_xattn_packed)
 _UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter")
 _IMAGE_TYPES = ("pil", "np", "numpy", "uint8")      # what a batcher built with `decode=True` hands out besides "latent"
 _FLAG_HINT = {"image_t2i_adapter": "; a batcher built with `t2i_adapter=True` (pipe.serve(..., t2i_adapter=True)) serves it",
@@ -186,7 +187,7 @@ def common_request(b, request):
     if g <= 1.0:
         raise ValueError("serve: guidance_scale must be > 1 (classifier-free guidance rows u_i / c_i)")
     wf = request.get("weight_func")
-    if wf is not None and not weight_func_is_default(wf):
+    if not weight_func_fused(wf):
         raise ValueError("serve: a custom weight_func is not supported (use txt2img)")
     for k in _UNSUPPORTED_KEYS:
         if request.get(k) is not None and not (b.t2i and k == "image_t2i_adapter") and not (b.cn and k == "control_img"):

@@ -15,6 +15,26 @@ FLAG_REUSE_STATS = 4
 FLAG_ROWS_PADDED = 256
 FLAG_SIGMA_PER_GROUP = 512
 REGION_ROW_STRIDE = 100    # region_xattn_packed.hip kBP: the forward kernel's LDS bias-table row stride (floats)
+# What the attention kernels can read - stated here once; every Python site that routes by a key count or a head dim asks these
+XATTN_MAX_KEYS = 96            # xattn_shared.h kSMax: one 77-token text chunk, padded to three MFMA row tiles
+XATTN_MAX_KEYS_PACKED = 384    # region_xattn_packed.hip kSMax x kChunksMax: long prompts (77 n tokens) on the chunked kernels
+ATTN_MAX_HEAD_DIM = 160        # the `d > 160` of check_common (csrc/region_xattn.hip), dsc_self_attn_fwd and dsc_ip_xattn_add_f16
+
+
+def attn_head_dim_ok(d):
+    """a head dim the attention kernels take: a multiple of 8 (16-byte pieces of fp16), at most ATTN_MAX_HEAD_DIM"""
+    return d % 8 == 0 and 8 <= d <= ATTN_MAX_HEAD_DIM
+
+
+def attn_kernel_takes(dtype, d):
+    """fp16 with a head dim the kernels take: what check_common, dsc_self_attn_fwd and dsc_ip_xattn_add_f16 all require"""
+    return dtype == torch.float16 and attn_head_dim_ok(d)
+
+
+def xattn_kv_packable(S, d):
+    """this (S, d) has a packed K/V image (dsc_xattn_kv_pack_bytes != 0)"""
+    return S <= XATTN_MAX_KEYS_PACKED and attn_head_dim_ok(d)
+
 
 def _stream_ptr(t):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
@@ -124,18 +144,8 @@ def region_xattn(q, k, v, region=None, sigma=1.0, *, layout="bhld", n_std_groups
             raise ValueError(f"region table {tuple(region.shape)} does not match L={L}, S={S}")
         Bw = region.shape[0]
         rptr = ctypes.c_void_p(region.data_ptr())
-    sig_host, sig_dev = 0.0, None
-    if per_group_sigma:
-        sig_dev = _group_sigma_ptr(sigma, n_std_groups, q.device, "region_xattn")
-    elif isinstance(sigma, torch.Tensor):
-        if sigma.is_cuda and sigma.dtype == torch.float32:
-            sig_dev = ctypes.c_void_p(sigma.data_ptr())
-        else:
-            sig_host = float(sigma)
-    else:
-        sig_host = float(sigma)
-    flags = (FLAG_REF_FP16_ROUNDING if ref_fp16_rounding else 0) | (FLAG_BIAS_IS_FINAL if bias_is_final else 0) \
-        | (FLAG_REUSE_STATS if reuse_stats else 0) | (FLAG_SIGMA_PER_GROUP if per_group_sigma else 0) | debug_flags
+    sig_host, sig_dev = _sigma_args(sigma, per_group_sigma, n_std_groups, q.device, "region_xattn")
+    flags = _xattn_flags(ref_fp16_rounding, reuse_stats, per_group_sigma, debug_flags) | (FLAG_BIAS_IS_FINAL if bias_is_final else 0)
     nbytes = lib.dsc_region_xattn_workspace_bytes(Bc, H, L, S, d, n_std_groups)
     ws = _workspace(q.device, nbytes)
     rc = lib.dsc_region_xattn_fwd(
@@ -148,12 +158,21 @@ def region_xattn(q, k, v, region=None, sigma=1.0, *, layout="bhld", n_std_groups
     return out
 
 
-def _group_sigma_ptr(sigma, n_std_groups, device, what):
-    """per_group_sigma=True: one fp32 sigma per std group, dense on the attention's device"""
-    if not (isinstance(sigma, torch.Tensor) and sigma.is_cuda and sigma.dtype == torch.float32 and sigma.dim() == 1
-            and sigma.numel() == n_std_groups and sigma.is_contiguous() and sigma.device == device):
-        raise ValueError(f"{what}: per_group_sigma needs a dense [n_std_groups={n_std_groups}] fp32 tensor on {device}")
-    return ctypes.c_void_p(sigma.data_ptr())
+def _sigma_args(sigma, per_group, n_std_groups, device, what):
+    """(sigma_host, sigma_dev) of the region kernels: an fp32 device tensor goes by pointer (no host sync), anything else as a host
+    float; per_group: one fp32 sigma per std group, dense on the attention's device"""
+    if per_group:
+        if not (isinstance(sigma, torch.Tensor) and sigma.is_cuda and sigma.dtype == torch.float32 and sigma.dim() == 1
+                and sigma.numel() == n_std_groups and sigma.is_contiguous() and sigma.device == device):
+            raise ValueError(f"{what}: per_group_sigma needs a dense [n_std_groups={n_std_groups}] fp32 tensor on {device}")
+    elif not (isinstance(sigma, torch.Tensor) and sigma.is_cuda and sigma.dtype == torch.float32):
+        return float(sigma), None
+    return 0.0, ctypes.c_void_p(sigma.data_ptr())
+
+
+def _xattn_flags(ref_fp16_rounding, reuse_stats, per_group_sigma, debug_flags):
+    return (FLAG_REF_FP16_ROUNDING if ref_fp16_rounding else 0) | (FLAG_REUSE_STATS if reuse_stats else 0) \
+        | (FLAG_SIGMA_PER_GROUP if per_group_sigma else 0) | debug_flags
 
 
 def xattn_kv_pack(k, v, *, layout="blhd", out=None):
@@ -211,13 +230,22 @@ def compress_region_table(w, pad_rows=False):
 
 def pad_region_rows(rows):
     """distinct region rows [NU, S] (compress_region_table) -> [NU, 100] fp32, zero padded: the shape of the forward kernel's LDS
-    table, which it then fills with a flat 16-byte copy (DSC_FLAG_ROWS_PADDED).  S <= 96."""
+    table, which it then fills with a flat 16-byte copy (DSC_FLAG_ROWS_PADDED).  S <= XATTN_MAX_KEYS."""
     NU, S = rows.shape
-    if S > 96:
-        raise ValueError("pad_region_rows: at most 96 keys (one text chunk)")
+    if S > XATTN_MAX_KEYS:
+        raise ValueError(f"pad_region_rows: at most {XATTN_MAX_KEYS} keys (one text chunk)")
     out = rows.new_zeros((NU, REGION_ROW_STRIDE), dtype=torch.float32)
     out[:, :S] = rows
     return out
+
+
+def compress_region_table_for_kernel(w, pad_rows=False):
+    """compress_region_table, with the rows in the forward kernel's own table shape (pad_region_rows) when the keys are one text
+    chunk: what region_xattn_packed takes as `region`, or None"""
+    comp = compress_region_table(w, pad_rows)
+    if comp is not None and comp[1].shape[1] <= XATTN_MAX_KEYS:
+        comp = (comp[0], pad_region_rows(comp[1]))
+    return comp
 
 
 def region_xattn_packed(q, packed_kv, S, region=None, sigma=1.0, *, n_std_groups=1, scale=None, ref_fp16_rounding=True,
@@ -238,16 +266,9 @@ def region_xattn_packed(q, packed_kv, S, region=None, sigma=1.0, *, n_std_groups
     if region is not None:
         ids, rows = region
         Bw, nrows = ids.shape[0], rows.shape[0]
-    sig_host, sig_dev = 0.0, None
-    if per_group_sigma:
-        sig_dev = _group_sigma_ptr(sigma, n_std_groups, q.device, "region_xattn_packed")
-    elif isinstance(sigma, torch.Tensor) and sigma.is_cuda and sigma.dtype == torch.float32:
-        sig_dev = ctypes.c_void_p(sigma.data_ptr())
-    else:
-        sig_host = float(sigma)
-    flags = (FLAG_REF_FP16_ROUNDING if ref_fp16_rounding else 0) | (FLAG_REUSE_STATS if reuse_stats else 0) \
-        | (FLAG_SIGMA_PER_GROUP if per_group_sigma else 0) | debug_flags
-    if rows is not None and rows.shape[1] == REGION_ROW_STRIDE and S <= 96:      # pad_region_rows() form ([NU, S] has S <= 96 columns)
+    sig_host, sig_dev = _sigma_args(sigma, per_group_sigma, n_std_groups, q.device, "region_xattn_packed")
+    flags = _xattn_flags(ref_fp16_rounding, reuse_stats, per_group_sigma, debug_flags)
+    if rows is not None and rows.shape[1] == REGION_ROW_STRIDE and S <= XATTN_MAX_KEYS:      # pad_region_rows() form
         flags |= FLAG_ROWS_PADDED
     ws = _workspace(q.device, lib.dsc_region_xattn_workspace_bytes(Bc, H, L, S, d, n_std_groups))
     rc = lib.dsc_region_xattn_fwd_packed(_p(q), _p(packed_kv), _p(out), _p(ids), _p(rows), nrows, Bc, H, L, S, d, Bw,
@@ -255,6 +276,17 @@ def region_xattn_packed(q, packed_kv, S, region=None, sigma=1.0, *, n_std_groups
                                          float(scale) if scale else 0.0, 0, flags, _p(ws), ws.numel() * 8, _stream_ptr(q))
     _lib.check(rc, "dsc_region_xattn_fwd_packed")
     return out
+
+
+def mask_3d(mask, BH, L, S, check=True):
+    """an additive attention mask as the kernels read it: fp32 [1 | BH, 1 | L, S] (leading dimensions added as needed).
+    check=False: the caller adds the mask to [BH, L, S] scores with torch first, whose broadcast error is then the refusal"""
+    m3 = mask.float()
+    while m3.dim() < 3:
+        m3 = m3.unsqueeze(0)
+    if check and (m3.dim() != 3 or m3.shape[2] != S or m3.shape[1] not in (1, L) or m3.shape[0] not in (1, BH)):
+        raise ValueError(f"mask {tuple(mask.shape)} does not broadcast to [{BH}, {L}, {S}]")
+    return m3
 
 
 def region_xattn_std(q, k, *, layout="bhld", n_std_groups=1, scale=None, ref_fp16_rounding=True, mask=None):
@@ -276,12 +308,7 @@ def region_xattn_std(q, k, *, layout="bhld", n_std_groups=1, scale=None, ref_fp1
             ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, _stream_ptr(q))
         _lib.check(rc, "dsc_region_xattn_std")
         return out
-    m3 = mask.float()
-    while m3.dim() < 3:
-        m3 = m3.unsqueeze(0)
-    if m3.dim() != 3 or m3.shape[2] != S or m3.shape[1] not in (1, L) or m3.shape[0] not in (1, Bc * H):
-        raise ValueError(f"mask {tuple(mask.shape)} does not broadcast to [{Bc * H}, {L}, {S}]")
-    m3 = m3.contiguous()
+    m3 = mask_3d(mask, Bc * H, L, S).contiguous()
     ms = (ctypes.c_int64 * 2)(0 if m3.shape[0] == 1 else m3.stride(0), 0 if m3.shape[1] == 1 else m3.stride(1))
     rc = lib.dsc_region_xattn_std_masked(
         ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(k.data_ptr()), Bc, H, L, S, d, n_std_groups,
@@ -334,8 +361,8 @@ def ip_xattn_add(q4, k_ip, v_ip, row_scale, io, scale=None, q_weight=None):
         raise ValueError(f"ip_xattn_add: q4 is [B, L, H, d] and k_ip / v_ip [B, T, H, d], got {tuple(q4.shape)} / {tuple(k_ip.shape)}")
     (sb, sl, sh), (B, H, L, d) = _blhd_strides(q4, "blc")
     T = k_ip.shape[1]
-    if d % 8 != 0 or not 8 <= d <= 160:
-        raise ValueError(f"ip_xattn_add: head dim {d} is not a multiple of 8 in [8, 160]")
+    if not attn_head_dim_ok(d):
+        raise ValueError(f"ip_xattn_add: head dim {d} is not a multiple of 8 in [8, {ATTN_MAX_HEAD_DIM}]")
     if not 1 <= T <= IP_MAX_TOKENS:
         raise ValueError(f"ip_xattn_add: {T} image tokens; the kernel takes 1 .. {IP_MAX_TOKENS} (IP_MAX_TOKENS)")
     skb = k_ip.stride(0) if B > 1 else T * H * d
