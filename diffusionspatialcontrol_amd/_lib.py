@@ -124,7 +124,8 @@ _SIGNATURES = {
     "dsc_ip_xattn_add_masked_f16": (ctypes.c_int, [_vp] + [ctypes.c_longlong] * 3 + [_vp, _vp, ctypes.c_longlong, _vp, _vp] +
                                     [_vp, ctypes.c_longlong] + [ctypes.c_int] * 5 + [ctypes.c_float, _vp]),
     "dsc_add_rows_gated_f16": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _vp]),
-    "dsc_scatter_add_rows_f16": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 3 + [ctypes.c_longlong, _vp]),
+    "dsc_freeu_rows_f16": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int] + [ctypes.c_int] * 3 + [_vp, ctypes.c_int, _vp]),
+    "dsc_scatter_add_rows_f16":(ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 3 + [ctypes.c_longlong, _vp]),
     "dsc_image_finish": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [_vp]),
     "dsc_latent_preview": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 4 +
                            [ctypes.POINTER(ctypes.c_float), ctypes.c_int, _vp, _vp]),

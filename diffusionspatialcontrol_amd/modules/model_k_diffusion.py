@@ -490,7 +490,7 @@ class StableDiffusionPipeline:
     def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77,
               ip_masks: bool = False, t2i_adapter: bool = False, controlnet: bool = False, control_slots=None,
               decode: bool = False, decode_batch: int = 2, previews: bool = False, preview_scale: int = 8, preview_coef=None,
-              preview_ring: int = 8, inpaint_unet: bool = False):
+              preview_ring: int = 8, inpaint_unet: bool = False, freeu: bool = False):
         """Continuous-batching server (modules/serving/): requests join a running batch at any step boundary, each at its own
         point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
         stats / warm).  `ip_masks=True` (IP-Adapters loaded): requests may carry the reference's
@@ -511,11 +511,16 @@ class StableDiffusionPipeline:
         is dropped, never waited for.  `inpaint_unet=True` (a 9-channel inpainting UNet; not together with `controlnet` /
         `t2i_adapter`): every request is an inpainting request (`image`, `mask_image`, optional `masked_image_latents` /
         `strength`) with any served sampler, v-prediction and `guidance_rescale`; every step writes the request's mask and
-        masked-image latents behind its latent row (dsc_cfg_linear_step_rows_cat)."""
+        masked-image latents behind its latent row (dsc_cfg_linear_step_rows_cat).  `freeu=True`: requests may carry
+        `freeu=(s1, s2, b1, b2)` (or a dict with those names), FreeU per request: the captured steps hold the six FreeU launches
+        (dsc_freeu_rows_f16), which read each row's values from a table and leave rows without the key as they are; it combines
+        with every other flag.  Any batcher is refused while the UNet-level setting (unet.enable_freeu) is on."""
         from .serving import ServingBatcher
         kw = dict(previews=True, preview_scale=preview_scale, preview_coef=preview_coef, preview_ring=preview_ring) if previews else {}
         if inpaint_unet:                         # (a batcher built without the flag is constructed exactly as before)
             kw["inpaint_unet"] = True
+        if freeu:
+            kw["freeu"] = True
         return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len,
                               ip_masks=ip_masks, t2i_adapter=t2i_adapter, controlnet=controlnet, control_slots=control_slots,
                               decode=decode, decode_batch=decode_batch, **kw)
@@ -523,7 +528,7 @@ class StableDiffusionPipeline:
     def serve_hires(self, height: int = 512, width: int = 512, upscale_x: float = 1.25, max_batch: int = 8, buckets=(1, 2, 4, 8),
                     text_len: int = 77, slots=(0, 1), ip_masks: bool = False, decode: bool = False, decode_batch: int = 2,
                     previews: bool = False, preview_scale: int = 8, preview_coef=None, preview_ring: int = 8,
-                    inpaint_unet: bool = False):
+                    inpaint_unet: bool = False, freeu: bool = False):
         """Continuous-batching server for requests with a hires pass (reference :1176-1228): a batcher at `height` x `width`
         chained to one at the target size of `upscale_x` (_hires_pass's expression), on two workspace slots.  A request with
         `upscale=True` runs its first pass on the one, is enlarged and re-noised on the device (dsc_latent_resample_noise) and
@@ -532,7 +537,8 @@ class StableDiffusionPipeline:
         `ip_adapter_masks` (see `serve`); the second pass down-samples a request's mask at its own levels.  `decode=True` gives
         each batcher a decode lane at its own image size (see `serve`): a request without `upscale` finishes on the base batcher.
         `previews=True` gives both batchers the preview path (see `serve`): each pass of a request with `upscale` counts its own
-        steps, and the second pass previews at its own size."""
+        steps, and the second pass previews at its own size.  `freeu=True` builds both batchers for per-request FreeU (see
+        `serve`): both passes of a request get its values."""
         from .latent_resample import hires_target_size
         from .serving import HiresPair, ServingBatcher
         if inpaint_unet:
@@ -560,6 +566,8 @@ class StableDiffusionPipeline:
             kw.update(decode=True, decode_batch=decode_batch)
         if previews:
             kw.update(previews=True, preview_scale=preview_scale, preview_coef=preview_coef, preview_ring=preview_ring)
+        if freeu:
+            kw["freeu"] = True
         return HiresPair(ServingBatcher(self, height, width, slot=slots[0], **kw), ServingBatcher(self, th, tw, slot=slots[1], **kw))
 
     def txt2img_coalesced(self, requests, height: int = 512, width: int = 512, num_inference_steps: int = 50,
@@ -1007,7 +1015,12 @@ class StableDiffusionPipeline:
         """the key of a captured step: shapes only (and what the capture bakes in), see _build_or_refresh_step"""
         levels = tuple(sorted((int(L), tuple(w.shape)) for L, w in region_state.items())) \
             if isinstance(region_state, dict) else None
-        return (("slot", slot), n_img, in_shape, levels, tuple(text.shape), text.dtype, self._weight_func_key(weight_func), ip_key)
+        # ("freeu", on): whether the capture holds the UNet's FreeU launches (unet.enable_freeu) - the VALUES are data the launches
+        # read from the UNet's persistent table, so changing them keeps the capture; enabling builds a second one beside the
+        # plain step's, and disabling finds the plain one again (_build_or_refresh_step keeps one of each per slot)
+        freeu = ("freeu", getattr(self.unet, "freeu_setting", lambda: None)() is not None)
+        return (("slot", slot), n_img, in_shape, levels, tuple(text.shape), text.dtype, self._weight_func_key(weight_func), ip_key,
+                freeu)
 
     @staticmethod
     def _record_done(st, device):
@@ -1261,9 +1274,9 @@ class StableDiffusionPipeline:
                 st["eps"] = step()
             st["graph"] = g
             st["run"] = g.replay
-        # keep one captured step per generation slot
-        tag = self._slot_of(key)
-        self._graphs = {k: v for k, v in self._graphs.items() if self._slot_of(k) != tag}
+        # keep one captured step per generation slot (and one more with the FreeU launches, once FreeU has been enabled)
+        tag = (self._slot_of(key), ("freeu", True) in key)
+        self._graphs = {k: v for k, v in self._graphs.items() if (self._slot_of(k), ("freeu", True) in k) != tag}
         self._graphs[key] = st
         return st
 
@@ -1350,8 +1363,9 @@ class StableDiffusionPipeline:
                     k, v = m.to_k(text), m.to_v(text)
                 B, S, C = k.shape
                 d = C // m.heads
-                # one entry per static text buffer (= per generation slot); the newest few are kept, and every entry a serving
-                # batcher pinned (its bucket graphs read those buffers for as long as the batcher lives, modules/serving/)
+                # one entry per static text buffer (= per captured step: a generation slot's, and its twin with the FreeU launches
+                # once FreeU has been enabled); the newest few are kept, and every entry a serving batcher pinned (its bucket graphs
+                # read those buffers for as long as the batcher lives, modules/serving/)
                 slots = m.__dict__.setdefault("kv_caches", [])
                 c = next((e for e in slots if e["src"] is text and e["k"].shape == k.shape), None)
                 if c is not None:
@@ -1360,7 +1374,7 @@ class StableDiffusionPipeline:
                 else:
                     c = {"src": text, "k": k, "v": v, "packed": None}
                     others = [e for e in slots if e["src"] is not text]
-                    slots[:] = [e for e in others if e.get("pin")] + [e for e in others if not e.get("pin")][-3:] + [c]
+                    slots[:] = [e for e in others if e.get("pin")] + [e for e in others if not e.get("pin")][-7:] + [c]
                 m.kv_cache = c
                 # MFMA-fragment image of K / V^T for the fused kernel (rewritten in place: captured graphs keep reading it)
                 if ops.xattn_kv_packable(S, d):                  # long prompts: one image per chunk of ops.XATTN_MAX_KEYS keys

@@ -41,7 +41,7 @@ from .. import sampling
 from ..encode_region_map_function import encode_region_map
 from . import requests
 from .executor import _GraphExecutor, step_launch
-from .requests import MAX_TEXT_KEYS, _InpaintRequest, _Request, _ip_layers
+from .requests import MAX_TEXT_KEYS, _FreeuRequest, _InpaintFreeuRequest, _InpaintRequest, _Request, _ip_layers
 
 
 def _conv_out_hw(conv, h, w):
@@ -55,7 +55,8 @@ class ServingBatcher:
 
     def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
                  t2i_adapter=False, controlnet=False, control_slots=None, decode=False, decode_batch=2, previews=False,
-                 preview_scale=8, preview_coef=None, preview_ring=8, inpaint_unet=False):
+                 preview_scale=8, preview_coef=None, preview_ring=8, inpaint_unet=False, freeu=False):
+        requests.check_freeu_off(pipe)
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
             raise ValueError(f"serve: buckets {buckets} must cover max_batch={max_batch}")
@@ -78,6 +79,11 @@ class ServingBatcher:
                                           linear_transitions=0, handoffs=0, adapter_gate_updates=0, control_steps=0,
                                           control_gate_updates=0)
         self._hires = None                     # the chained batcher of the hires pass (chain_hires)
+        # requests may carry `freeu`: the step holds the FreeU launches, which read (s1, s2, b1, b2) per row from a table (executor.py)
+        self.freeu = bool(freeu)
+        self._freeu_rows = {}                  # bucket -> the table last uploaded for it (absent: ones, as captured)
+        if self.freeu:
+            self._stats["freeu_updates"] = 0
         # a 9-channel inpainting UNet: every request is an inpainting request, and every transition writes each member's mask and
         # masked-image latents behind its latent row (dsc_cfg_linear_step_rows_cat; package docstring)
         self.inpaint = bool(inpaint_unet)
@@ -392,6 +398,8 @@ class ServingBatcher:
             raise TypeError("serve: a request is a dict (txt2img_coalesced's request + num_inference_steps / sampler_opt / "
                             "guidance_scale)")
         requests.check_ip_current(self)
+        requests.check_freeu_off(self.pipe)
+        freeu = requests.freeu_request(self, request)
         adapter = requests.adapter_request(self, request)
         control = requests.control_request(self, request, second)
         if request.get("upscale") and not second:
@@ -407,9 +415,12 @@ class ServingBatcher:
         if steps < 1:
             raise ValueError("serve: num_inference_steps must be >= 1")
         record = _InpaintRequest if self.inpaint else _Request           # (the former: one more field, `extra`)
+        more = {}
+        if self.freeu:                                                   # (one more field, `freeu`)
+            record, more = (_InpaintFreeuRequest if self.inpaint else _FreeuRequest), {"freeu": freeu}
         r = record(req=request, future=concurrent.futures.Future(), steps=steps, second=second, ip_embeds=ip_embeds,
                    ip_scale=ip_scale, ip_weights=ip_weights, adapter=adapter, control=control, guidance=g, output_type=out_type,
-                   family=family, rescale=phi, eta=float(request.get("eta", 1.0)), text=text)
+                   family=family, rescale=phi, eta=float(request.get("eta", 1.0)), text=text, **more)
         t_start = requests.image_request(self, r)
         dev, dt = self.exec.device, self.exec.dtype
         r.sig_dev = pipe._schedule(r.steps, request.get("sampler_opt") or {}, dev, dt)      # txt2img's schedule, fp16-rounded
@@ -484,6 +495,16 @@ class ServingBatcher:
             if r is not None and r.adapter is not None and r.i < r.adapter_limit:
                 gates[i] = gates[n + i] = 1.0
         return gates
+
+    @staticmethod
+    def _freeu_table(n, members):
+        """the FreeU table of bucket n, [2 n][4]: a member's (s1, s2, b1, b2) at rows {i, n + i}; ones (the launches leave such a
+        row as it is) for idle slots and members without `freeu`"""
+        table = [[1.0] * 4 for _ in range(2 * n)]
+        for i, r in enumerate(members):
+            if r is not None and r.freeu is not None:
+                table[i] = table[n + i] = list(r.freeu)
+        return table
 
     @staticmethod
     def control_keep(n_steps, starts, ends):
@@ -793,6 +814,13 @@ class ServingBatcher:
                 self.exec.set_adapter_gates(n_dst, gates)
                 self._gates[n_dst] = gates
                 self._stats["adapter_gate_updates"] += 1
+        if self.freeu:
+            # the values are a member's for its whole stay: the table changes with the membership only
+            table = self._freeu_table(n_dst, rows)
+            if self._freeu_rows.get(n_dst, [[1.0] * 4] * (2 * n_dst)) != table:
+                self.exec.set_freeu(n_dst, table)
+                self._freeu_rows[n_dst] = table
+                self._stats["freeu_updates"] += 1
         if self.cn:
             # (after r.i moved on, as above.)  Each of the three is uploaded only when it differs from what the bucket holds;
             # the ControlNet itself runs only when some member's gate is open in the coming call

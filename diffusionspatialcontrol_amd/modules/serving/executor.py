@@ -351,6 +351,11 @@ class _GraphExecutor:
         with torch.cuda.stream(self.stream):
             _upload(self.st[n]["adapter"]["gate"], gates, torch.float32)
 
+    def set_freeu(self, n, table):
+        """the bucket's FreeU table (read by the captured dsc_freeu_rows_f16 launches) <- these [2 n][4] values"""
+        with torch.cuda.stream(self.stream):
+            _upload(self.st[n]["freeu"], table, torch.float32)
+
     @torch.no_grad()
     def _ip_request_rows(self, r):
         """once per request: its image tokens (unet.encoder_hid_proj on its own [2, ...] embeds: txt2img's call shape) through
@@ -590,6 +595,9 @@ class _GraphExecutor:
             st["control"] = {"dst": torch.full((lanes,), -1, device=dev, dtype=torch.int32),
                              "gather": torch.zeros(lanes, device=dev, dtype=torch.int64),
                              "gate": torch.zeros((len(self.cn_nets), lanes), device=dev, dtype=torch.float32)} if self.b.cn else None
+            # (freeu) (s1, s2, b1, b2) per batch row: ones until a member with `freeu` is refreshed in, and a row of ones is
+            # neither read nor written by the FreeU launches
+            st["freeu"] = torch.ones((rows, 4), device=dev, dtype=torch.float32) if getattr(self.b, "freeu", False) else None
         kw = {"region_prompt": {"region_state": zero, "compressed": st["compressed"], "sigma": st["sigma"], "weight_func": None,
                                 "n_std_groups": n, "sigma_per_group": True}}
         if self.ip_layers:
@@ -608,6 +616,9 @@ class _GraphExecutor:
         gated = {"down_intrablock_gated": (st["adapter"]["feats"], st["adapter"]["gate"])} if st["adapter"] is not None else {}
         if st["control"] is not None:                # ... or the `controlnet` flag (the two are not built together)
             gated = {"down_block_scattered": (self.cn["down"], self.cn["mid"], st["control"]["gate"], st["control"]["dst"])}
+
+        if st["freeu"] is not None:                  # a batcher built without `freeu` calls the UNet exactly as it did before
+            gated = dict(gated, freeu_rows=st["freeu"])
 
         def step():                                  # (every run binds the eps the next transition reads)
             st["eps"] = unet(st["x_in"], st["t"], encoder_hidden_states=st["text"], cross_attention_kwargs=kw,

@@ -38,7 +38,8 @@ MAX_TEXT_KEYS = ops.XATTN_MAX_KEYS_PACKED     # the chunked prepared-operand ker
 _UNSUPPORTED_KEYS = ("control_img", "image_t2i_adapter")
 _IMAGE_TYPES = ("pil", "np", "numpy", "uint8")      # what a batcher built with `decode=True` hands out besides "latent"
 _FLAG_HINT = {"image_t2i_adapter": "; a batcher built with `t2i_adapter=True` (pipe.serve(..., t2i_adapter=True)) serves it",
-              "control_img": "; a batcher built with `controlnet=True` (pipe.serve(..., controlnet=True)) serves it"}
+              "control_img": "; a batcher built with `controlnet=True` (pipe.serve(..., controlnet=True)) serves it",
+              "freeu": "; a batcher built with `freeu=True` (pipe.serve(..., freeu=True)) serves it"}
 
 
 class _Request:
@@ -65,6 +66,16 @@ class _InpaintRequest(_Request):
     """a request of a batcher built with `inpaint_unet=True`: the record plus `extra`, its fp16 [5, h, w] row
     cat([nearest-downsampled mask, masked-image latents]) on the device from admission until it leaves"""
     __slots__ = ("extra",)
+
+
+class _FreeuRequest(_Request):
+    """a request of a batcher built with `freeu=True`: the record plus `freeu`, its (s1, s2, b1, b2) or None"""
+    __slots__ = ("freeu",)
+
+
+class _InpaintFreeuRequest(_InpaintRequest):
+    """... of a batcher built with `inpaint_unet=True` and `freeu=True`"""
+    __slots__ = ("freeu",)
 
 
 # ---------------------------------------------------------------------- one copy of each small check
@@ -213,6 +224,28 @@ def preview_request(b, request):
     if call is None:
         raise ValueError("serve: `preview_every` needs `on_preview`, a callable f(step, steps, image)")
     return every, call
+
+
+def check_freeu_off(pipe):
+    """a batcher's steps take FreeU per request (`freeu=True`) or not at all: the UNet-level setting would enter every capture made
+    from here on, for every row"""
+    setting = getattr(getattr(pipe, "unet", None), "freeu_setting", None)
+    if setting is not None and setting() is not None:
+        raise ValueError("serve: the UNet-level FreeU setting is on (unet.enable_freeu); a batcher takes FreeU per request: call "
+                         "unet.disable_freeu(), build the batcher with `freeu=True` and pass `freeu=(s1, s2, b1, b2)` in the requests")
+
+
+def freeu_request(b, request):
+    """submit-time check of `freeu` -> (s1, s2, b1, b2) as four finite floats, or None (absent)"""
+    v = request.get("freeu")
+    if v is None:
+        return None
+    if not getattr(b, "freeu", False):
+        raise ValueError("serve: `freeu` (FreeU per request) is not supported by this batcher" + _FLAG_HINT["freeu"])
+    try:
+        return ops.freeu_values(v)
+    except ValueError as e:
+        raise ValueError(f"serve: `freeu` must be four finite numbers (s1, s2, b1, b2) or a dict with those names: {e}") from None
 
 
 def text_request(b, request):

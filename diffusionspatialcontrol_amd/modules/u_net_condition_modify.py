@@ -925,6 +925,9 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
             self.up_blocks.append(_Block(io, td, cfg, rev_heads[i], rev_depth[i], up=i < n - 1))
             prev = c
         assert not skip
+        for blk in self.up_blocks:                   # FreeU's per-block attributes, as diffusers' blocks carry them (enable_freeu)
+            blk.s1 = blk.s2 = blk.b1 = blk.b2 = None
+        self._freeu_tables = {}                      # (batch rows, device) -> [fp32 [rows, 4] table, the values it holds]
         self._channels_last = False
         self.conv_norm_out = GroupNormAct(cfg.norm_num_groups, ch[0], cfg.norm_eps, act=True)
         self.conv_out = nn.Conv2d(ch[0], cfg.out_channels, 3, padding=1)
@@ -936,6 +939,55 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
         from .attention_modify import _RegionProcessor
         blk = self.down_blocks[0].attentions[0].transformer_blocks[0]
         return isinstance(blk.attn1.processor, _RegionProcessor) and isinstance(blk.attn2.processor, _RegionProcessor)
+
+    # ---- FreeU (reference :835-865; what diffusers' up blocks then do with the attributes: _freeu)
+    def enable_freeu(self, s1, s2, b1, b2):
+        """FreeU (arXiv 2309.11497): s1 / b1 act in up block 0, s2 / b2 in up block 1 - before each of their ResNets the first
+        half of the hidden channels is scaled by b and the skip tensor's four lowest frequencies by s.  The four values are set
+        on every up block, as the reference does.  Tables a captured step already reads are refilled in place: the step stays
+        valid and sees the new values at its next replay."""
+        vals = ops.freeu_values((s1, s2, b1, b2))
+        for blk in self.up_blocks:
+            blk.s1, blk.s2, blk.b1, blk.b2 = vals
+        for (rows, _), ent in self._freeu_tables.items():
+            self._fill_freeu_table(ent, rows, vals)
+
+    def disable_freeu(self):
+        for blk in self.up_blocks:
+            blk.s1 = blk.s2 = blk.b1 = blk.b2 = None
+
+    def freeu_setting(self):
+        """(s1, s2, b1, b2) of the module-level setting, or None when FreeU is disabled"""
+        blk = self.up_blocks[0]
+        vals = (blk.s1, blk.s2, blk.b1, blk.b2)
+        return None if any(v is None for v in vals) else tuple(float(v) for v in vals)
+
+    @staticmethod
+    def _fill_freeu_table(ent, rows, vals):
+        ent[0].copy_(torch.tensor([vals] * rows, dtype=torch.float32))
+        ent[1] = vals
+
+    def _freeu_table(self, rows, device):
+        """the persistent fp32 [rows, 4] table of the module-level setting on `device`: one per (rows, device), allocated at the
+        first forward that needs it (a captured step's warm-up runs, outside the capture) and only ever rewritten in place"""
+        vals = self.freeu_setting()
+        ent = self._freeu_tables.get((rows, device))
+        if ent is None:
+            ent = self._freeu_tables[(rows, device)] = [torch.ones((rows, 4), dtype=torch.float32, device=device), None]
+        if ent[1] != vals:
+            self._fill_freeu_table(ent, rows, vals)
+        return ent[0]
+
+    @staticmethod
+    def _freeu(x, skip, table, stage):
+        """diffusers' `apply_freeu` for one ResNet of up block `stage` (0 / 1), per batch row from table [B, 4] = (s1, s2, b1, b2):
+        -> (x, skip) as the ResNet's concatenation and shortcut must see them.  The kernel route works IN PLACE, which is safe
+        here: each skip tensor of these blocks is popped once and its producers' other readers (the next down ResNet, the mid
+        block) ran before the up path; x is the fresh output of the mid block, a ResNet, a transformer or the upsampler, held
+        by nobody else; GroupNorm partial sums a producer attached are dropped by the op, and of_cat takes none from x anyway."""
+        if ops.freeu_covers(x, skip):
+            return ops.freeu_rows_(x, skip, table, stage)
+        return ops.freeu_eager(x, skip, table[:, stage], table[:, 2 + stage])
 
     def _resnets(self):
         out = []
@@ -950,7 +1002,7 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
                 attention_mask=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
                 down_intrablock_additional_residuals=None, encoder_attention_mask=None, return_dict=True, temb_adds=None,
-                cfg_shared_prefix=False, down_intrablock_gated=None, down_block_scattered=None):
+                cfg_shared_prefix=False, down_intrablock_gated=None, down_block_scattered=None, freeu_rows=None):
         if attention_mask is not None or encoder_attention_mask is not None:
             raise NotImplementedError("attention masks are not on the hot path (never passed by app.py)")
         # down_block_scattered = (down_feats, mid_feat, gate, dst): the static form of down_block_additional_residuals /
@@ -986,6 +1038,16 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
                 raise ValueError(f"down_intrablock_gated: {len(g_feats)} feature maps for {len(self.down_blocks)} down blocks")
             if not torch.is_tensor(g_gate) or tuple(g_gate.shape) != (sample.shape[0],) or g_gate.dtype != torch.float32:
                 raise ValueError(f"down_intrablock_gated: gate must be an fp32 [{sample.shape[0]}] tensor (one per batch row)")
+        # freeu_rows: fp32 [B, 4] in device memory, (s1, s2, b1, b2) per batch row - the static form of enable_freeu for a captured
+        # step that serves a batch of which only some rows have FreeU (a row of ones is left as it is); it takes precedence over
+        # the module-level setting, which is served by a persistent table of its own (_freeu_table)
+        if freeu_rows is not None:
+            if not torch.is_tensor(freeu_rows) or tuple(freeu_rows.shape) != (sample.shape[0], 4) \
+                    or freeu_rows.dtype != torch.float32 or freeu_rows.device != sample.device or not freeu_rows.is_contiguous():
+                raise ValueError(f"freeu_rows: must be a contiguous fp32 [{sample.shape[0]}, 4] tensor on {sample.device} "
+                                 "(s1, s2, b1, b2 per batch row)")
+        elif self.freeu_setting() is not None:
+            freeu_rows = self._freeu_table(sample.shape[0], sample.device)
         # temb_adds: a [B, temb_width()] buffer holding this timestep's rows of temb_add_table() - the time-embedding path
         # is then not run (the captured step of the fused loop: its caller refreshes the buffer between replays)
         temb_act = None if temb_adds is not None else self._time_act(sample, timestep)
@@ -1034,9 +1096,12 @@ class UNet2DConditionModel(_EncoderHalf, nn.Module, UNet2DConditionLoadersMixin_
         # is concatenated with.  Sides that divide: nothing is forwarded and the upsamplers double, as before.
         factor = 2 ** sum(1 for blk in self.up_blocks if hasattr(blk, "upsamplers"))
         forward_size = any(int(d) % factor != 0 for d in sample.shape[-2:])
-        for blk in self.up_blocks:
+        for i, blk in enumerate(self.up_blocks):
             for j, res in enumerate(blk.resnets):
-                x = res((x, skips.pop()), temb_act, tadd[res])
+                skip = skips.pop()
+                if freeu_rows is not None and i < 2:             # diffusers' apply_freeu: resolution_idx 0 and 1 only
+                    x, skip = self._freeu(x, skip, freeu_rows, i)
+                x = res((x, skip), temb_act, tadd[res])
                 if blk.has_attn:
                     x = blk.attentions[j](x, encoder_hidden_states, cross_attention_kwargs)
             if hasattr(blk, "upsamplers"):

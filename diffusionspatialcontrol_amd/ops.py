@@ -1446,3 +1446,9 @@ from .image_finish import IMAGE_KINDS, image_finish, image_finish_torch  # noqa:
 # live previews of running requests (dsc_latent_preview: up to 16 fp16 latent rows -> uint8 RGB thumbnails): wrapper beside its
 # kernel's name, reached as ops.latent_preview; latent_preview_numpy restates its arithmetic in numpy float32, op by op
 from .latent_preview import LATENT_RGB_SD15, PREVIEW_MAX_CHANNELS, PREVIEW_MAX_ROWS, PREVIEW_SCALES, latent_preview, latent_preview_numpy  # noqa: E402,F401
+
+# FreeU on an up-block ResNet's (hidden, skip) pair (dsc_freeu_rows_f16: the half-channel scale and the four-frequency Fourier
+# filter, per batch row, in one launch): wrapper beside its kernel's name, reached as ops.freeu_rows_ / ops.freeu_covers;
+# freeu_eager is diffusers' algorithm with torch.fft in fp32 (the CPU / fp32 route and the tests' restatement)
+USE_FREEU_KERNEL = os.environ.get("DSC_FREEU", "1") != "0"   # A/B switch: 0 = FreeU through freeu_eager (torch.fft) everywhere
+from .freeu import FREEU_MAX_SIDE, fourier_filter_eager, freeu_covers, freeu_eager, freeu_rows_, freeu_values  # noqa: E402,F401

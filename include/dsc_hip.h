@@ -719,6 +719,37 @@ int dsc_add_rows_gated_f16(const void* x, const void* feat, const void* gate, vo
                            long long row_elems, void* stream);
 
 /*
+ * FreeU (arXiv 2309.11497) on the two inputs of one up-block ResNet, per batch row, in place, in one launch.  Replaces what
+ * modules/u_net_condition_modify.py:835-865 of the reference (`enable_freeu` / `disable_freeu`, the up blocks built with
+ * `resolution_idx`, :445) switches on: diffusers' `apply_freeu` and `fourier_filter(x, threshold=1, scale)` (fftn, fftshift, a
+ * mask multiply, ifftshift, ifftn, .real, a cast) in front of every ResNet of up blocks 0 and 1, with "this row has FreeU" a
+ * device value, not Python control flow:
+ *     hidden[r][p][c] = fp16( float(hidden[r][p][c]) * b[r] )                       c < C_h / 2
+ *     skip[r][p][c]   = fp16( x + (s[r] - 1) / (H W) * [ S0 + Ach cos th + Ash sin th + Acw cos tw + Asw sin tw
+ *                                                        + Ac2 cos(th + tw) + As2 sin(th + tw) ] )
+ * with th = 2 pi h / H, tw = 2 pi w / W of pixel p = (h, w), x = float(skip[r][p][c]) and the seven sums over the H * W pixels
+ * of (r, c): S0 = sum x, Ach / Ash = sum x cos th / sin th, Acw / Asw = sum x cos tw / sin tw, Ac2 / As2 = sum x cos(th + tw) /
+ * sin(th + tw) - the scaling of the frequencies {0, -1} x {0, -1}, which is all the filter does at threshold 1.
+ * hidden [B, H, W, C_h] and skip [B, H, W, C_s]: fp16, channels-last, dense, both updated IN PLACE.  params [B][4] fp32 =
+ * (s1, s2, b1, b2) per batch row, read from DEVICE memory (never by value): a captured launch sees the values of the moment it
+ * replays.  stage 0 (up block 0) reads s = params[r][0], b = params[r][2]; stage 1 reads s = params[r][1], b = params[r][3].
+ * b[r] == 1: the hidden row is neither read nor written; s[r] == 1: the skip row is neither read nor written (such rows may
+ * hold anything).  The batch row is a grid coordinate (B <= 65535).
+ * Hidden: one fp32 product, rounded to fp32 and then to fp16, per element: `fp16(fp32(x) * b)`, the bits of torch's fp16 `x * b`
+ * on the CPU and of `(x.float() * b).half()` anywhere.  Skip: fp64 sums in a fixed order (per lane, a wave butterfly, the waves
+ * through LDS), the formula in fp64, one rounding to fp16 (with s2 = 0.2 the result crosses zero, where fp32 sums were up to 9 fp16
+ * ulps off); one workgroup owns all pixels of its channels, with a barrier between its reads and its writes.  No workspace, no allocation, no synchronisation, no atomics:
+ * deterministic and safe under graph capture.
+ * DSC_ERR_BAD_ARG: null pointer, B < 1, H < 2 or W < 2 (diffusers' slice means something else on a side of 1), C_h / C_s < 1,
+ * stage not 0 / 1, any overlap among hidden, skip and params.  DSC_ERR_UNSUPPORTED: C_s % 8 != 0, C_h % 16 != 0, C_h or C_s above
+ * 2^20, hidden / skip not 16-byte or params not 4-byte aligned, B > 65535, H or W above DSC_FREEU_MAX_SIDE (the cos / sin tables
+ * live in LDS; it also keeps a row's H * W inside an int).
+ */
+#define DSC_FREEU_MAX_SIDE 512
+int dsc_freeu_rows_f16(void* hidden, int C_h, void* skip, int C_s, int B, int H, int W, const float* params, int stage,
+                       void* stream);
+
+/*
  * Residuals of a compact ControlNet batch ("lanes") added into the batch rows they belong to: the ControlNet hook of the
  * continuous batcher's captured step.  Replaces, in one launch per skip tensor, ControlNetModel.forward's
  * `d * conditioning_scale`, MultiControlNetModel.forward's sum over the nets and modules/u_net_condition_modify.py:1236-1245 of

@@ -65,6 +65,10 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
               one-at-a-time `inpaiting(fused=True)` beside `fused=False` at 512x512 for 25 steps, ms per image, three runs of
               four; then the device time of dsc_cfg_linear_step_rows_cat beside dsc_cfg_linear_step_rows at 8 slots of 64x64
               latents (a captured graph of 100 launches each, three replays)
+  freeu       (--freeu: this leg only) two batchers on two slots: one built without `freeu`, one with it.  8 slots kept full, three
+              alternating rounds of (a) the flagless batcher, (b) the same requests on the freeu=True batcher (every row's values
+              are ones: the six launches per step return at once - the price of the flag), (c) every other request with
+              `freeu=(0.9, 0.2, 1.5, 1.6)`; images/s and steps/s for each
 """
 import argparse
 import json
@@ -272,6 +276,9 @@ def main():
     ap.add_argument("--preview-scale", type=int, default=8, help="with --previews: the thumbnails' enlargement (1, 2, 4, 8)")
     ap.add_argument("--inpaint-unet", action="store_true",
                     help="only the 9-channel inpainting UNet leg: a batcher built with inpaint_unet=True, every request inpainting")
+    ap.add_argument("--freeu", action="store_true",
+                    help="only the FreeU leg: a flagless batcher, a freeu=True batcher without FreeU requests, and the same with "
+                         "freeu=(0.9, 0.2, 1.5, 1.6) on every other request")
     a = ap.parse_args()
     if a.ip_masks and not a.ip_adapter:
         ap.error("--ip-masks goes with --ip-adapter")
@@ -284,6 +291,26 @@ def main():
     opt = {"scheduler": "karras"}
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    if a.freeu:
+        plain = pipe.serve(512, 512, max_batch=8, slot=0).warm()
+        on = pipe.serve(512, 512, max_batch=8, slot=1, freeu=True).warm()
+        every_other = [dict(r, freeu=(0.9, 0.2, 1.5, 1.6)) if i % 2 else r for i, r in enumerate(reqs)]
+        for b in (plain, on):                             # one untimed pass each
+            run_full(b, reqs[:8], kw25)
+        runs = []
+        for _ in range(3):                                # alternating, so that a drift of the box hits all three alike
+            runs.append((run_full(plain, reqs, kw25), run_full(on, reqs, kw25), run_full(on, every_other, kw25)))
+        emit(leg="freeu", requests=len(reqs), steps=25,
+             flagless_img_s=[round(t[0][0], 2) for t in runs], flag_no_freeu_requests_img_s=[round(t[1][0], 2) for t in runs],
+             flag_every_other_request_img_s=[round(t[2][0], 2) for t in runs],
+             flagless_steps_s=[round(t[0][1], 1) for t in runs], flag_no_freeu_requests_steps_s=[round(t[1][1], 1) for t in runs],
+             flag_every_other_request_steps_s=[round(t[2][1], 1) for t in runs],
+             freeu_updates=on.stats()["freeu_updates"], captures_after_warm=on.stats()["captures_after_warm"],
+             note="three alternating rounds in one process, 8 slots kept full; the freeu=True step holds six dsc_freeu_rows_f16 "
+                  "launches, which skip rows whose values are (1, 1, 1, 1)")
+        emit(leg="stats", flagless=plain.stats(), freeu=on.stats())
+        return
 
     if a.inpaint_unet:
         import dataclasses
