@@ -30,6 +30,19 @@ def declared_symbols():
 _i64p = ctypes.POINTER(ctypes.c_int64)
 _vp = ctypes.c_void_p
 
+
+class ImagePrepareRow(ctypes.Structure):
+    """dsc_image_prepare_row (include/dsc_hip.h)"""
+    _fields_ = [("image", _vp), ("mask", _vp), ("image_kind", ctypes.c_int), ("mask_kind", ctypes.c_int), ("out_image", _vp),
+                ("out_masked", _vp), ("out_mask", _vp), ("mask_rep", ctypes.c_int)]
+
+
+class LatentStartRow(ctypes.Structure):
+    """dsc_latent_start_row (include/dsc_hip.h)"""
+    _fields_ = [("kind", ctypes.c_int), ("moments_row", ctypes.c_int), ("eps", _vp), ("noise", _vp), ("scaling", ctypes.c_float),
+                ("coef", ctypes.c_float), ("start", _vp), ("keep", _vp), ("keep_noise", _vp)]
+
+
 _SIGNATURES = {
     "dsc_abi_version": (ctypes.c_int, []),
     "dsc_target_arch": (ctypes.c_char_p, []),
@@ -129,6 +142,8 @@ _SIGNATURES = {
     "dsc_image_finish": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [_vp]),
     "dsc_latent_preview": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 4 +
                            [ctypes.POINTER(ctypes.c_float), ctypes.c_int, _vp, _vp]),
+    "dsc_image_prepare": (ctypes.c_int, [ctypes.POINTER(ImagePrepareRow)] + [ctypes.c_int] * 3 + [_vp]),
+    "dsc_latent_start_rows": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(LatentStartRow)] + [ctypes.c_int] * 3 + [_vp]),
 }
 
 

@@ -490,7 +490,7 @@ class StableDiffusionPipeline:
     def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77,
               ip_masks: bool = False, t2i_adapter: bool = False, controlnet: bool = False, control_slots=None,
               decode: bool = False, decode_batch: int = 2, previews: bool = False, preview_scale: int = 8, preview_coef=None,
-              preview_ring: int = 8, inpaint_unet: bool = False, freeu: bool = False):
+              preview_ring: int = 8, inpaint_unet: bool = False, freeu: bool = False, encode: bool = False, encode_batch: int = 2):
         """Continuous-batching server (modules/serving/): requests join a running batch at any step boundary, each at its own
         point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
         stats / warm).  `ip_masks=True` (IP-Adapters loaded): requests may carry the reference's
@@ -514,13 +514,20 @@ class StableDiffusionPipeline:
         masked-image latents behind its latent row (dsc_cfg_linear_step_rows_cat).  `freeu=True`: requests may carry
         `freeu=(s1, s2, b1, b2)` (or a dict with those names), FreeU per request: the captured steps hold the six FreeU launches
         (dsc_freeu_rows_f16), which read each row's values from a table and leave rows without the key as they are; it combines
-        with every other flag.  Any batcher is refused while the UNet-level setting (unet.enable_freeu) is on."""
+        with every other flag.  `encode=True` (a pipeline whose VAE has an encoder, in fp16 on the GPU): requests whose `image` /
+        `mask_image` are pixels are encoded on an encode lane - a second stream with one captured `vae.encode` per bucket, up to
+        `encode_batch` (in [1, max_batch]) rows per encode, between one dsc_image_prepare and one dsc_latent_start_rows launch -
+        beside the step: `submit` does host work and the request's draws only, and the request is admitted when its encode has
+        completed; without it pixel inputs are prepared inline inside `submit`, as before.  Any batcher is refused while the
+        UNet-level setting (unet.enable_freeu) is on."""
         from .serving import ServingBatcher
         kw = dict(previews=True, preview_scale=preview_scale, preview_coef=preview_coef, preview_ring=preview_ring) if previews else {}
         if inpaint_unet:                         # (a batcher built without the flag is constructed exactly as before)
             kw["inpaint_unet"] = True
         if freeu:
             kw["freeu"] = True
+        if encode:
+            kw.update(encode=True, encode_batch=encode_batch)
         return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len,
                               ip_masks=ip_masks, t2i_adapter=t2i_adapter, controlnet=controlnet, control_slots=control_slots,
                               decode=decode, decode_batch=decode_batch, **kw)
@@ -528,7 +535,7 @@ class StableDiffusionPipeline:
     def serve_hires(self, height: int = 512, width: int = 512, upscale_x: float = 1.25, max_batch: int = 8, buckets=(1, 2, 4, 8),
                     text_len: int = 77, slots=(0, 1), ip_masks: bool = False, decode: bool = False, decode_batch: int = 2,
                     previews: bool = False, preview_scale: int = 8, preview_coef=None, preview_ring: int = 8,
-                    inpaint_unet: bool = False, freeu: bool = False):
+                    inpaint_unet: bool = False, freeu: bool = False, encode: bool = False, encode_batch: int = 2):
         """Continuous-batching server for requests with a hires pass (reference :1176-1228): a batcher at `height` x `width`
         chained to one at the target size of `upscale_x` (_hires_pass's expression), on two workspace slots.  A request with
         `upscale=True` runs its first pass on the one, is enlarged and re-noised on the device (dsc_latent_resample_noise) and
@@ -538,7 +545,8 @@ class StableDiffusionPipeline:
         each batcher a decode lane at its own image size (see `serve`): a request without `upscale` finishes on the base batcher.
         `previews=True` gives both batchers the preview path (see `serve`): each pass of a request with `upscale` counts its own
         steps, and the second pass previews at its own size.  `freeu=True` builds both batchers for per-request FreeU (see
-        `serve`): both passes of a request get its values."""
+        `serve`): both passes of a request get its values.  `encode=True` gives the encode lane (see `serve`) to the base-size batcher
+        only: the second pass starts from the hand-off's latent, never from pixels."""
         from .latent_resample import hires_target_size
         from .serving import HiresPair, ServingBatcher
         if inpaint_unet:
@@ -568,7 +576,8 @@ class StableDiffusionPipeline:
             kw.update(previews=True, preview_scale=preview_scale, preview_coef=preview_coef, preview_ring=preview_ring)
         if freeu:
             kw["freeu"] = True
-        return HiresPair(ServingBatcher(self, height, width, slot=slots[0], **kw), ServingBatcher(self, th, tw, slot=slots[1], **kw))
+        base_kw = dict(kw, encode=True, encode_batch=encode_batch) if encode else kw
+        return HiresPair(ServingBatcher(self, height, width, slot=slots[0], **base_kw), ServingBatcher(self, th, tw, slot=slots[1], **kw))
 
     def txt2img_coalesced(self, requests, height: int = 512, width: int = 512, num_inference_steps: int = 50,
                           guidance_scale: float = 7.5, sampler_opt=None, output_type: Optional[str] = "latent",

@@ -24,10 +24,12 @@ The seam is host scheduling against a replaceable device executor:
   executor.py     _GraphExecutor, the capture sequence, step_launch (which launch serves a transition); image prompts,
                   T2I-Adapter, ControlNet
   decode_lane.py  the decode lane that finishes images beside the step
+  encode_lane.py  the encode lane that encodes pixel inputs beside the step
   preview_lane.py the preview path: thumbnails of running requests' denoised estimates, beside the step
 """
 # every name that is imported from `modules.serving`
 from .batcher import HiresPair, ServingBatcher
 from .decode_lane import decode_buckets
+from .encode_lane import encode_buckets, encode_roles
 from .executor import _GraphExecutor, step_launch
 from .requests import MAX_TEXT_KEYS, _ip_layers

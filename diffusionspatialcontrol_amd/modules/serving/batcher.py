@@ -40,6 +40,7 @@ from ... import ops
 from .. import sampling
 from ..encode_region_map_function import encode_region_map
 from . import requests
+from .encode_lane import _EncodeHandle, encode_roles
 from .executor import _GraphExecutor, step_launch
 from .requests import MAX_TEXT_KEYS, _FreeuRequest, _InpaintFreeuRequest, _InpaintRequest, _Request, _ip_layers
 
@@ -55,7 +56,7 @@ class ServingBatcher:
 
     def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
                  t2i_adapter=False, controlnet=False, control_slots=None, decode=False, decode_batch=2, previews=False,
-                 preview_scale=8, preview_coef=None, preview_ring=8, inpaint_unet=False, freeu=False):
+                 preview_scale=8, preview_coef=None, preview_ring=8, inpaint_unet=False, freeu=False, encode=False, encode_batch=2):
         requests.check_freeu_off(pipe)
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
@@ -100,6 +101,17 @@ class ServingBatcher:
                 raise ValueError(f"serve: `decode_batch` must be an integer in [1, max_batch = {self.max_batch}], got {decode_batch!r}")
             self.decode_batch = decode_batch
             self._stats["decodes"] = self._stats["decode_rows"] = 0
+        # pixel inputs (`image` / `mask_image` as pixels) are encoded on an encode lane beside the step (encode_lane.py)
+        self.encode = bool(encode)
+        self.encode_batch = 0
+        if self.encode:
+            if getattr(pipe, "vae", None) is None or not hasattr(pipe.vae, "encode"):
+                raise ValueError("serve: `encode=True` on a pipeline without a VAE encoder (construct it with a "
+                                 "modules.vae_decoder.AutoencoderKL, or pass [1, 4, h, w] latents as `image`)")
+            if isinstance(encode_batch, bool) or not isinstance(encode_batch, int) or not 1 <= encode_batch <= self.max_batch:
+                raise ValueError(f"serve: `encode_batch` must be an integer in [1, max_batch = {self.max_batch}], got {encode_batch!r}")
+            self.encode_batch = encode_batch
+            self._stats["encodes"] = self._stats["encode_rows"] = 0
         # requests may carry `preview_every` / `on_preview`: thumbnails of the denoised estimate leave beside the step
         # (preview_lane.py)
         self.previews = bool(previews)
@@ -277,6 +289,8 @@ class ServingBatcher:
                 self._ensure(n)
             if self.decode:
                 self._ensure_decode()                # the lane's stream, static buffers, graphs and pinned ring
+            if self.encode:
+                self._ensure_encode()                # the encode lane's stream, static buffers, graphs, staging and pinned ring
             if self.previews:
                 self.exec.ensure_preview()           # the preview stream and its ring of device / pinned buffers
             self._warm_captures = self._stats["captures"]
@@ -332,7 +346,11 @@ class ServingBatcher:
         On a batcher built with `previews=True`: `preview_every` (an int k >= 1; absent, None or 0: no
         previews) and `on_preview` (a callable f(step, steps, image)): after every k-th of the request's steps but the last, f
         receives the count of steps applied, the steps of this pass and an np.uint8 [h * scale, w * scale, 3] thumbnail of the
-        denoised estimate (preview_lane.py); f runs on the thread that steps the batcher.  Returns a Future of the final output."""
+        denoised estimate (preview_lane.py); f runs on the thread that steps the batcher.
+        On a batcher built with `encode=True`: `image` / `mask_image` given as pixels (a PIL image, a numpy array or a tensor, of
+        this batcher's size) are encoded on the encode lane (encode_lane.py): submit normalises them on the host and makes the
+        request's draws, and the request joins the batch once its encode has completed; its result has the bits the inline path
+        gives at the same encode batch size.  Returns a Future of the final output."""
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -418,10 +436,15 @@ class ServingBatcher:
         more = {}
         if self.freeu:                                                   # (one more field, `freeu`)
             record, more = (_InpaintFreeuRequest if self.inpaint else _FreeuRequest), {"freeu": freeu}
+        if self.encode:                                                  # (one more field, `enc`)
+            record = requests._ENCODE_RECORD[record]
         r = record(req=request, future=concurrent.futures.Future(), steps=steps, second=second, ip_embeds=ip_embeds,
                    ip_scale=ip_scale, ip_weights=ip_weights, adapter=adapter, control=control, guidance=g, output_type=out_type,
                    family=family, rescale=phi, eta=float(request.get("eta", 1.0)), text=text, **more)
         t_start = requests.image_request(self, r)
+        if self.encode:                              # its rows on the encode lane; None: the request does not touch it
+            roles = encode_roles(self, r)
+            r.enc = _EncodeHandle(roles) if roles else None
         dev, dt = self.exec.device, self.exec.dtype
         r.sig_dev = pipe._schedule(r.steps, request.get("sampler_opt") or {}, dev, dt)      # txt2img's schedule, fp16-rounded
         sig = getattr(r.sig_dev, "_dsc_host", None)
@@ -545,6 +568,8 @@ class ServingBatcher:
             self.exec.prepare_hires(r)
         elif r.kind == "txt2img":
             self.exec.prepare(r)
+        elif self.encode and r.enc is not None:
+            self.exec.prepare_encode(r)              # host pixels and draws only: the lane encodes it beside the step
         else:
             self.exec.prepare_image(r)
         if any(v != 0.0 for v in r.snoise):
@@ -617,12 +642,18 @@ class ServingBatcher:
         return True
 
     def _step_locked(self):
-        """one step, as phases in the order the device sees them: admit, build the records, ensure the next bucket and load the
-        joins, ONE transition launch, (previews) the launch for the slots that are due, let the finished leave, advance, refresh /
-        upload / run the next bucket, flush decodes"""
+        """one step, as phases in the order the device sees them: (encode) send queued pixel inputs to the lane, admit, build the
+        records, ensure the next bucket and load the joins, ONE transition launch, (previews) the launch for the slots that are
+        due, let the finished leave, advance, refresh / upload / run the next bucket, flush decodes"""
         slots = self._slots
         stepping = [r for r in slots if r is not None and r.i < len(r.coeffs) and self._n is not None]
+        if self.encode:
+            self._dispatch_encodes()
         joins = self._admit()
+        if self.encode and not stepping and not joins and self._queue and self._queue[0].enc is not None:
+            # nothing steps and the head is still encoding: wait for its event instead of reporting idle with a request queued
+            self.exec.encode_wait(self._queue[0])
+            joins = self._admit()
         if not stepping and not joins:
             return False
         # who leaves after this transition: a request whose last step is the one being applied now
@@ -665,6 +696,8 @@ class ServingBatcher:
                 break
             if not self._launch_compatible(head, [r for r in slots if r is not None]):
                 break
+            if self.encode and head.enc is not None and not self.exec.encode_ready(head):
+                break                                # still encoding: it waits although a slot is free, and nobody overtakes it
             if head.control is not None:
                 # a ControlNet lane, the lowest free one, kept until the request leaves; with none free the request waits at the
                 # head of the queue although a slot is free (FIFO, the rule of _launch_compatible)
@@ -678,6 +711,15 @@ class ServingBatcher:
             slots[free] = head
             joins.append(head)
         return joins
+
+    def _dispatch_encodes(self):
+        """queued requests whose pixel inputs have not been sent to the encode lane go there now, in FIFO order"""
+        todo = [r for r in self._queue if r.enc is not None and r.enc.sent < r.enc.rows]
+        if todo:
+            self._ensure_encode()
+            encodes, rows = self.exec.dispatch_encodes(todo)
+            self._stats["encodes"] += encodes
+            self._stats["encode_rows"] += rows
 
     def _records(self, n_slots, stepping, joins, leaving):
         """the per-slot records of this transition's launch and, per slot, the known-region record of an inpainting slot that
@@ -788,6 +830,8 @@ class ServingBatcher:
             if self.inpaint:
                 r.extra = None                       # ... and its mask + masked-image latents row (inpaint_unet)
             r.noise = None                           # ... and its noise table
+            if self.encode:
+                r.enc = None                         # ... and its draws and host pixels (encode)
             r.adapter_feats = None                   # ... and its adapter features
             if r.lane is not None:                   # ... and its ControlNet lane goes to whoever waits for one
                 self._lanes[r.lane] = None
@@ -866,6 +910,9 @@ class ServingBatcher:
 
     def _ensure_decode(self):
         self._stats["captures"] += self.exec.ensure_decode()
+
+    def _ensure_encode(self):
+        self._stats["captures"] += self.exec.ensure_encode()
 
     def _poll(self, wait=False):
         """resolve the futures of requests whose final row copy has completed (in completion order); on a previews batcher the

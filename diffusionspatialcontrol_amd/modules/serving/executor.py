@@ -48,6 +48,7 @@ from ... import _lib, ops
 from .. import sampling
 from ..latent_resample import MODES as _RESAMPLE_MODES, device_taps
 from .decode_lane import _DecodeLane, _LaneHandle
+from .encode_lane import _EncodeLane
 from .preview_lane import _PreviewLane
 
 _EMBED_LOCK = threading.Lock()       # around the process-wide deterministic switch in _GraphExecutor._control_embedding
@@ -158,6 +159,8 @@ class _GraphExecutor:
         self.cn = None
         # (decode) the lane that finishes images beside the step; its stream and buffers are built by ensure_decode
         self.lane = _DecodeLane(self, batcher.decode_batch) if getattr(batcher, "decode", False) else None
+        # (encode) the lane that encodes pixel inputs beside the step; its stream and buffers are built by ensure_encode
+        self.enc_lane = _EncodeLane(self, batcher.encode_batch) if getattr(batcher, "encode", False) else None
         # (previews) the path that turns rows of `old` into thumbnails beside the step; its stream and ring are built by ensure_preview
         self.previews = _PreviewLane(self, batcher.preview_scale, batcher.preview_coef, batcher.preview_ring) \
             if getattr(batcher, "previews", False) else None
@@ -497,6 +500,8 @@ class _GraphExecutor:
         with torch.cuda.stream(self.stream):
             if r.ready is not None:                  # a hires second pass: its start latent is written on another stream
                 self.stream.wait_event(r.ready)
+            if self.enc_lane is not None and r.enc is not None:      # a pixel input: its rows are written on the lane's stream
+                self.stream.wait_event(r.enc.ev)
             self.x[r.slot].copy_(r.lat[0])
 
     def finish(self, r):
@@ -521,6 +526,26 @@ class _GraphExecutor:
     def flush_decodes(self):
         """the pending rows to the lane, up to decode_batch at a time -> (decodes queued, rows in them)"""
         return self.lane.dispatch()
+
+    def prepare_encode(self, r):
+        """submit's half of a pixel-input request on a batcher built with `encode=True`: host pixels, draws, allocations"""
+        self.enc_lane.prepare(r)
+
+    def ensure_encode(self):
+        """the encode lane's stream, per-bucket static buffers and graphs, staging and pinned ring -> how many graphs this call
+        captured"""
+        return self.enc_lane.ensure()
+
+    def dispatch_encodes(self, requests):
+        """these queued requests' rows to the lane, up to encode_batch per encode -> (encodes queued, rows in them)"""
+        return self.enc_lane.dispatch(requests)
+
+    def encode_ready(self, r):
+        self.enc_lane.reclaim()
+        return self.enc_lane.ready(r)
+
+    def encode_wait(self, r):
+        self.enc_lane.wait(r)
 
     def ensure_preview(self):
         """the preview path's stream and its ring of device / pinned buffers (preview_lane.py)"""

@@ -78,6 +78,28 @@ class _InpaintFreeuRequest(_InpaintRequest):
     __slots__ = ("freeu",)
 
 
+# a request of a batcher built with `encode=True`: the record of its kind plus `enc`, its handle on the encode lane
+# (encode_lane._EncodeHandle) from submit until it leaves, or None when it does not touch the lane
+class _EncodeRequest(_Request):
+    __slots__ = ("enc",)
+
+
+class _InpaintEncodeRequest(_InpaintRequest):
+    __slots__ = ("enc",)
+
+
+class _FreeuEncodeRequest(_FreeuRequest):
+    __slots__ = ("enc",)
+
+
+class _InpaintFreeuEncodeRequest(_InpaintFreeuRequest):
+    __slots__ = ("enc",)
+
+
+_ENCODE_RECORD = {_Request: _EncodeRequest, _InpaintRequest: _InpaintEncodeRequest, _FreeuRequest: _FreeuEncodeRequest,
+                  _InpaintFreeuRequest: _InpaintFreeuEncodeRequest}
+
+
 # ---------------------------------------------------------------------- one copy of each small check
 def finite(v):
     """a python number (no bool) that is neither NaN nor infinite"""

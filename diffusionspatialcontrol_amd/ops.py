@@ -1452,3 +1452,8 @@ from .latent_preview import LATENT_RGB_SD15, PREVIEW_MAX_CHANNELS, PREVIEW_MAX_R
 # freeu_eager is diffusers' algorithm with torch.fft in fp32 (the CPU / fp32 route and the tests' restatement)
 USE_FREEU_KERNEL = os.environ.get("DSC_FREEU", "1") != "0"   # A/B switch: 0 = FreeU through freeu_eager (torch.fft) everywhere
 from .freeu import FREEU_MAX_SIDE, fourier_filter_eager, freeu_covers, freeu_eager, freeu_rows_, freeu_values  # noqa: E402,F401
+
+# pixel inputs of served requests (dsc_image_prepare: request images -> the VAE encoder's fp16 input, the masked image and the
+# latent mask; dsc_latent_start_rows: the encoder's moments -> latents and start latents, per row): wrappers beside their kernels'
+# names, reached as ops.image_prepare / ops.latent_start; the *_torch functions are the literal eager chains they replace
+from .image_prepare import image_prepare, image_prepare_torch, latent_start, latent_start_torch, start_form  # noqa: E402,F401

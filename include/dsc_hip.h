@@ -832,6 +832,85 @@ int dsc_image_finish(const void* img, void* out, int n, int H, int W, int out_ki
 int dsc_latent_preview(const void* lat, long long row_stride, const int* rows, int n, int C, int h, int w, const float* coef,
                        int up, void* out, void* stream);
 
+/*
+ * Pixel inputs of served requests, the reverse direction of dsc_image_finish: the two launches around the VAE encoder's captured
+ * graph on the encode lane of the continuous batcher (modules/serving/encode_lane.py).
+ *
+ * dsc_image_prepare: up to DSC_IMAGE_PREPARE_MAX_ROWS request images become what `vae.encode` and the sampler step read, in one
+ * launch.  Replaces, per request, the reference's VaeImageProcessor.preprocess at its call sites
+ * modules/model_k_diffusion.py:1447-1449 (the image: bytes / 255, `2 x - 1`, channel-major float32) and :1480-1482 (the mask,
+ * binarised at 0.5, and the masked image `init_image * (mask < 0.5)`), the conversion to the VAE's fp16 inside
+ * `_encode_vae_image` (:1234-1246) and `F.interpolate(mask, size=(h, w))` (:1253-1257; default nearest: pixel (8 i, 8 j)).
+ * rows: a HOST array of n records, read at the call and passed to the kernel by value (the caller may reuse it at once).  Per row:
+ *     image      uint8 [H, W, 3] (DSC_PIXELS_U8: the bytes of a PIL image) or float32 [3, H, W] in [-1, 1] (DSC_PIXELS_F32), dense
+ *     mask       uint8 [H, W] or float32 [H, W], dense; NULL when the row has none
+ *     out_image  fp16 [3, H, W]: fp16(v), v = 2.0f * (float(b) / 255.0f) - 1.0f (an IEEE division) / v = x;  NULL: not wanted
+ *     out_masked fp16 [3, H, W]: fp16(v * (m ? 0.0f : 1.0f)), the literal fp32 product (-0.0 under a negative v);  NULL: not wanted
+ *     out_mask   fp16 [mask_rep, H / 8, W / 8]: fp16(m) of pixel (8 i, 8 j), mask_rep (1 or 4) times;  NULL: not wanted
+ * with m = b >= 128 (uint8) / x >= 0.5f (float32; a NaN compares false).  Bit for bit the torch chain for every input.  A row
+ * whose three destinations are NULL is neither read nor written; with no destination in any row nothing is launched.
+ * H % 8 == 0 and W % 8 == 0: one lane owns 16 consecutive pixels of the dense plane - 48 interleaved bytes as three 16-byte loads
+ * split into planes in registers (four 16-byte loads per float32 plane), two 16-byte stores per channel; the lane whose 8-pixel
+ * half starts a latent cell stores its mask sample.  image, mask, out_image, out_masked 16-byte aligned; out_mask 2-byte.
+ * No workspace, no LDS, no allocation, no synchronisation, no atomics, every element written by the one lane that owns it and
+ * nothing behind the last one: deterministic and safe beside captured graphs.
+ * DSC_ERR_BAD_ARG (before any GPU call): rows NULL; n < 1 or > 16; H / W < 1; a wanted destination without its source; an
+ * unknown kind; mask_rep not 1 or 4; out_image == out_masked.  DSC_ERR_UNSUPPORTED: a side that is no multiple of 8, alignment,
+ * 2^31 pieces of 16 pixels and more.
+ *
+ * dsc_latent_start_rows: after the encode, every row of it in one launch.  Replaces DiagonalGaussianDistribution.sample and
+ * `_encode_vae_image`'s product (:1234-1246), img2img's start latent (:647) and prepare_latents_inpating's branches (:1306-1362),
+ * with an fp16 rounding wherever that chain holds an fp16 tensor:
+ *     lv  = clamp(logvar, -30, 20);   std = fp16(expf(float(fp16(0.5f * lv))))
+ *     lat = fp16(scaling * float(fp16(mean + fp16(std * eps))))
+ *     DSC_START_ADD:   start = fp16(lat + fp16(noise * coef))    (img2img: coef = fp16 sqrt(sigma_0^2 + 1); inpainting below
+ *                                                                  strength 1: coef = sigma_0, both fp16 values)
+ *     DSC_START_SCALE: start = fp16(noise * coef)                (inpainting at strength 1 / with given latents:
+ *                                                                  coef = fp32(sqrt(sigma_0^2 + 1)) of the python float)
+ *     DSC_START_NONE:  no start latent                           (the masked image of a 9-channel request)
+ * moments: fp16 [m, 8, h, w] dense (`vae.encode(x).latent_dist.parameters`: mean | logvar).  rows: a HOST array of n records, by
+ * value as above.  Per row: kind (DSC_START_IDLE: neither read nor written), moments_row in [0, m), eps (the posterior draw) and
+ * noise, fp16 [4, h, w]; start fp16 [4, h, w]; keep (optional) receives lat - r.known["image"] of 4-channel inpainting, rows 1..4
+ * of r.extra for a masked-image row; keep_noise (optional) receives the noise row as it is.
+ * One lane owns 8 consecutive halfs of a row's 4 h w: 16-byte loads and stores when 4 h w % 8 == 0 and every pointer is 16-byte
+ * aligned, otherwise element by element with a bound check (any h, w; pointers 2-byte aligned).
+ * No workspace, no LDS, no allocation, no synchronisation, no atomics: deterministic and safe beside captured graphs.
+ * DSC_ERR_BAD_ARG: NULL moments / rows; m / n / h / w < 1; n > 16; an unknown kind; moments_row outside [0, m); NULL eps; a start
+ * kind without noise or start; DSC_START_NONE without keep; keep_noise without noise; two destinations of a row that are one.
+ * DSC_ERR_UNSUPPORTED: an odd pointer; 2^30 halfs and more per row.
+ */
+#define DSC_IMAGE_PREPARE_MAX_ROWS 16
+#define DSC_PIXELS_U8  0
+#define DSC_PIXELS_F32 1
+typedef struct {
+    const void* image;
+    const void* mask;
+    int image_kind;
+    int mask_kind;
+    void* out_image;
+    void* out_masked;
+    void* out_mask;
+    int mask_rep;
+} dsc_image_prepare_row;
+int dsc_image_prepare(const dsc_image_prepare_row* rows, int n, int H, int W, void* stream);
+
+#define DSC_START_IDLE  0
+#define DSC_START_ADD   1
+#define DSC_START_SCALE 2
+#define DSC_START_NONE  3
+typedef struct {
+    int kind;
+    int moments_row;
+    const void* eps;
+    const void* noise;
+    float scaling;
+    float coef;
+    void* start;
+    void* keep;
+    void* keep_noise;
+} dsc_latent_start_row;
+int dsc_latent_start_rows(const void* moments, int m, const dsc_latent_start_row* rows, int n, int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
     python tools/serve_bench.py [--requests 16] [--rates 2,6] [--seed 0] [--mix] [--sampler NAME] [--guidance-rescale PHI]
                                 [--hires X] [--ip-adapter [--ip-masks]] [--t2i-adapter] [--controlnet [--control-slots C]]
                                 [--images uint8|pil|np [--decode-batch D]] [--previews K [--preview-scale S]] [--inpaint-unet]
+                                [--pixels [--encode-batch E] [--inpaint-unet]]
 
 Legs (SD1.5-shape UNet with seeded random weights at 512x512, heterogeneous requests: 1/2/4 masks, distinct prompts and
 latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
@@ -69,6 +70,14 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
               alternating rounds of (a) the flagless batcher, (b) the same requests on the freeu=True batcher (every row's values
               are ones: the six launches per step return at once - the price of the flag), (c) every other request with
               `freeu=(0.9, 0.2, 1.5, 1.6)`; images/s and steps/s for each
+  pixels      (--pixels [--encode-batch E, default 2] [--inpaint-unet]: this leg only) an SD1.x-size VAE with seeded random
+              weights in the pipeline, then two batchers on two slots: one built without `encode` (pixel inputs are prepared inline
+              inside submit, on the batch's stream) and one built with `encode=True, encode_batch=E` (the encode lane).  Every
+              request is img2img at strength 0.6 (with --inpaint-unet: an inpainting request of a 9-channel UNet without
+              `masked_image_latents`, two encodes each).  8 slots kept full, three alternating rounds of (a) 4-channel latents as
+              `image` on the flagless batcher, (b) the same requests with a PIL image (and PIL mask) on the flagless batcher, (c)
+              the same on the encode-lane batcher; images/s, p50 / p95 of submit -> resolved and the wall time of `submit` itself
+              for each; then the same three legs with each batcher driven by its own thread
 """
 import argparse
 import json
@@ -243,6 +252,53 @@ def run_started_latency(b, reqs, kw):
     return len(reqs) / dt, pct(lat, 50), pct(lat, 95)
 
 
+def run_submit_latency(b, reqs, kw, started=False):
+    """run_full_latency / run_started_latency, also timing every `submit` call on the caller's thread:
+    (images/s, p50 s, p95 s, mean submit ms, max submit ms)"""
+    torch.cuda.synchronize()
+    if started:
+        b.start()
+    t0 = time.perf_counter()
+    futs, took = [], []
+    for r in reqs:
+        s0 = time.perf_counter()
+        futs.append(b.submit(dict(r, **kw)))
+        took.append(1e3 * (time.perf_counter() - s0))
+    if started:
+        for f in futs:
+            f.result()
+    else:
+        b.run_until_idle()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if started:
+        b.stop()
+    lat = [f.dsc_latency_s for f in futs]
+    return len(reqs) / dt, pct(lat, 50), pct(lat, 95), sum(took) / len(took), max(took)
+
+
+def make_pixels(reqs, seed, inpaint):
+    """(latent-input requests, the same requests with PIL pixels): img2img at strength 0.6, or (`inpaint`) inpainting requests of
+    a 9-channel UNet - latents with `masked_image_latents` against a PIL image and a PIL mask"""
+    from PIL import Image
+    lat, pix = [], []
+    for i, r in enumerate(reqs):
+        g = torch.Generator().manual_seed(seed * 1000 + 8000 + i)
+        img = (torch.randn(1, 4, 64, 64, generator=g) * 0.8).half().cuda()
+        pil = Image.fromarray(torch.randint(96, 160, (512, 512, 3), generator=g, dtype=torch.uint8).numpy())
+        if inpaint:
+            mil = (torch.randn(1, 4, 64, 64, generator=g) * 0.8).half().cuda()
+            m = torch.zeros(512, 512, dtype=torch.uint8)
+            x0 = 64 * (i % 6)
+            m[:, x0:x0 + 192] = 255
+            lat.append(dict(r, image=img, mask_image=m[None, None].float() / 255, masked_image_latents=mil, strength=1.0))
+            pix.append(dict(r, image=pil, mask_image=Image.fromarray(m.numpy(), "L"), strength=1.0))
+        else:
+            lat.append(dict(r, image=img, strength=0.6))
+            pix.append(dict(r, image=pil, strength=0.6))
+    return lat, pix
+
+
 def pct(v, p):
     return float(np.percentile(np.array(v), p)) if v else None
 
@@ -276,6 +332,10 @@ def main():
     ap.add_argument("--preview-scale", type=int, default=8, help="with --previews: the thumbnails' enlargement (1, 2, 4, 8)")
     ap.add_argument("--inpaint-unet", action="store_true",
                     help="only the 9-channel inpainting UNet leg: a batcher built with inpaint_unet=True, every request inpainting")
+    ap.add_argument("--pixels", action="store_true",
+                    help="only the pixel-input leg: latents as `image`, pixels inline on a flagless batcher, pixels on the encode lane "
+                         "(with --inpaint-unet: inpainting requests of a 9-channel UNet)")
+    ap.add_argument("--encode-batch", type=int, default=2, help="with --pixels: rows per captured encode of the lane")
     ap.add_argument("--freeu", action="store_true",
                     help="only the FreeU leg: a flagless batcher, a freeu=True batcher without FreeU requests, and the same with "
                          "freeu=(0.9, 0.2, 1.5, 1.6) on every other request")
@@ -291,6 +351,62 @@ def main():
     opt = {"scheduler": "karras"}
     reqs = make_requests(a.requests, a.seed)
     kw25 = dict(num_inference_steps=25, guidance_scale=7.5, sampler_opt=opt)
+
+    if a.pixels:
+        from diffusionspatialcontrol_amd.modules.vae_decoder import AutoencoderKL
+        serving = pipe
+        more = {}
+        if a.inpaint_unet:
+            import dataclasses
+            torch.manual_seed(1)
+            with torch.device("cuda"):
+                unet9 = UNet2DConditionModel(dataclasses.replace(UNetConfig.sd15(), in_channels=9))
+            serving = StableDiffusionPipeline(None, None, FakeTokenizer(), unet9.half().eval(), SD15Scheduler())
+            more = {"inpaint_unet": True}
+        torch.manual_seed(a.seed + 13)
+        with torch.device("cuda"):
+            vae = AutoencoderKL()
+        serving.vae = vae.half().eval()
+        plain = serving.serve(512, 512, max_batch=8, slot=0, **more).warm()
+        lane = serving.serve(512, 512, max_batch=8, slot=1, encode=True, encode_batch=a.encode_batch, **more).warm()
+        lat_reqs, pix_reqs = make_pixels(reqs, a.seed, a.inpaint_unet)
+        legs = (("a_latents_flagless", plain, lat_reqs), ("b_pixels_inline", plain, pix_reqs), ("c_pixels_encode_lane", lane, pix_reqs))
+        for started, name in ((False, "pixels"), (True, "pixels_driver_thread")):
+            for _, b, group in legs:                      # one untimed pass each (allocator, kernel selection, the inline encoder)
+                run_submit_latency(b, group[:8], kw25, started)
+            before = lane.stats()
+            runs = []
+            for _ in range(3):                            # alternating, so that a drift of the box hits all alike
+                runs.append({leg: run_submit_latency(b, group, kw25, started) for leg, b, group in legs})
+            after = lane.stats()
+            emit(leg=name, requests=len(reqs), steps=25, kind="inpaint_unet 1.0" if a.inpaint_unet else "img2img 0.6",
+                 encode_batch=a.encode_batch,
+                 **{f"{leg}_img_s": [round(r[leg][0], 3) for r in runs] for leg, _, _ in legs},
+                 **{f"{leg}_p50_s": [round(r[leg][1], 3) for r in runs] for leg, _, _ in legs},
+                 **{f"{leg}_p95_s": [round(r[leg][2], 3) for r in runs] for leg, _, _ in legs},
+                 **{f"{leg}_submit_ms_mean": [round(r[leg][3], 2) for r in runs] for leg, _, _ in legs},
+                 **{f"{leg}_submit_ms_max": [round(r[leg][4], 2) for r in runs] for leg, _, _ in legs},
+                 encodes=after["encodes"] - before["encodes"], encode_rows=after["encode_rows"] - before["encode_rows"],
+                 captures_after_warm=after["captures_after_warm"],
+                 note="three alternating rounds in one process, 8 slots kept full; " +
+                      ("each batcher driven by its own thread (start / stop)" if started else
+                       "each batcher stepped by the caller's thread (run_until_idle)") +
+                      "; latency = submit -> future resolved (dsc_latency_s); submit_ms = wall time of the submit call itself")
+        per = {}
+        for m, st in lane.exec.enc_lane.st.items():      # one captured encode, device time
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(lane.exec.enc_lane.stream):
+                st["run"]()
+                e0.record()
+                for _ in range(10):
+                    st["run"]()
+                e1.record()
+            torch.cuda.synchronize()
+            per[m] = round(e0.elapsed_time(e1) / 10, 3)
+        emit(leg="pixels_encode_replay", encode_graph_gpu_ms_per_bucket=per,
+             note="ten back-to-back replays on the lane's stream with nothing else running")
+        emit(leg="stats", flagless=plain.stats(), encode_lane=lane.stats())
+        return
 
     if a.freeu:
         plain = pipe.serve(512, 512, max_batch=8, slot=0).warm()
