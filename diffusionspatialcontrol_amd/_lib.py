@@ -79,6 +79,8 @@ _SIGNATURES = {
                                          ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "dsc_cfg_linear_step_rows_cat": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
                                      ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "dsc_cfg_staged_step_rows": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                 ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "dsc_dpmpp2m_update": (ctypes.c_int, [_vp, _vp, _vp] + [ctypes.c_float] * 3 + [_vp, ctypes.c_int64, ctypes.c_int, _vp]),
     "dsc_groupnorm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "dsc_groupnorm_silu": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_int, ctypes.c_int,

@@ -186,7 +186,7 @@ __device__ __forceinline__ void rows_cat_extra(const void* extra, bool idle, flo
     }
 }
 
-// ---- the per-row step: ONE body behind the five dsc_cfg_*_step_rows* entries.  What every kernel takes, by value in the kernel
+// ---- the per-row step: ONE body behind the six dsc_cfg_*_step_rows* entries.  What every kernel takes, by value in the kernel
 // arguments (kernarg segment, read through scalar loads: the slot is blockIdx.y, uniform per workgroup): the buffers and one
 // dsc_row_linear per slot - the dsc_cfg_dpmpp2m_* entries fill c_skip = 1, c_out = -sigma, noise = NULL on the host.
 struct RowArgs {
@@ -213,17 +213,25 @@ struct RowKnowns { dsc_row_known r[DSC_ROW_STEP_MAX_SLOTS]; };
 struct RowRescales { float phi[DSC_ROW_STEP_MAX_SLOTS]; };
 // CAT (dsc_cfg_linear_step_rows_cat): an x_in row is chw + halfs halfs long and ends with the slot's extra channels
 struct RowExtras { int halfs; dsc_row_extra r[DSC_ROW_STEP_MAX_SLOTS]; };
+// STAGED (dsc_cfg_staged_step_rows): the two-call samplers (modules/sampling.py call_plan).  A slot's step is two transitions:
+// PREDICT writes the intermediate point into the slot's row of `mid` and leaves x alone; CORRECT - the model ran on mid - takes
+// D (and the rescale's sums) from mid and adds m * mid to the update of x.  A FULL slot is the linear step: mid is not touched.
+struct RowStages { half_t* mid; dsc_row_stage r[DSC_ROW_STEP_MAX_SLOTS]; };
 
 // T threads, V halfs per access.  A flag that is off compiles its part out; LINEAR off: the record is a DPM++ 2M one, c_skip == 1
 // and no noise row by construction (x for 1 x: the same bits, one multiply and a row of registers less).  Per element of a STEP
 // slot, all fp32:
 //   e = fma(g, m_c - m_u, m_u), D = fp16([K] fma(c_out, e, c_skip xh)), x' = fp16([fma(s, noise,] fma(c, old, fma(a, x, b D))[)]),
 //   x_in = fp16(xh' c_in_next) - xh, xh': x, x' with the known region blended in (KNOWN), else x, x' themselves.
+// STAGED, PREDICT: x' = fp16([fma(s, noise,] fma(a, x, b D)[)]) goes to mid and into x_in, x stays; CORRECT: xh = mid and
+//   x' = fp16([fma(s, noise,] fma(m, mid, fma(c, old, fma(a, x, b D)))[)]).
 // These are step_kernel's lines with the fused multiply-adds it compiles to spelled out, every intermediate pinned to fp32 by
 // as_f32 (the contraction of a plain expression depends on the surrounding code, and every instantiation must give the same bits).
-template <int T, int V, bool LINEAR, bool KNOWN, bool RESCALE, bool CAT>
-__device__ __forceinline__ void rows_body(const RowArgs& p, const RowKnowns* ks, const RowRescales* ps, const RowExtras* es) {
+template <int T, int V, bool LINEAR, bool KNOWN, bool RESCALE, bool CAT, bool STAGED = false>
+__device__ __forceinline__ void rows_body(const RowArgs& p, const RowKnowns* ks, const RowRescales* ps, const RowExtras* es,
+                                          const RowStages* ss = nullptr) {
     static_assert(T % 64 == 0 && T <= 1024, "whole waves");
+    static_assert(!STAGED || (LINEAR && !KNOWN && !CAT && V == 8), "the staged entry is the linear one, without KNOWN and CAT");
     static_assert(!(KNOWN && RESCALE), "the row sums read x: they would have to read the blended model input");
     static_assert(V == 8 || !(RESCALE || CAT), "8-byte rows: the sums and the extra channels move 8 halfs");
     const int i = blockIdx.y, n_dst = p.n_dst, chw = p.chw;
@@ -253,6 +261,17 @@ __device__ __forceinline__ void rows_body(const RowArgs& p, const RowKnowns* ks,
         const auto combine = [&](float mu, float mc) { return as_f32(__builtin_fmaf(g, mc - mu, mu)); };
         const auto skip = [&](float v) { return LINEAR ? as_f32(c_skip * v) : v; };
         const auto estimate = [&](float m, float sx) { return as_f32(__builtin_fmaf(c_out, m, sx)); };      // D in fp32
+        // (STAGED) the row the model call saw: mid in CORRECT, else x
+        bool predict = false, correct = false;
+        float sm = 0.0f;
+        const half_t* srow = xr;
+        half_t* midr = nullptr;
+        if constexpr (STAGED) {
+            predict = ss->r[i].stage == DSC_ROW_STAGE_PREDICT, correct = ss->r[i].stage == DSC_ROW_STAGE_CORRECT;
+            sm = ss->r[i].m;
+            midr = ss->mid + (long long)i * chw;
+            if (correct) srow = midr;
+        }
         const half_t *img = nullptr, *knz = nullptr, *msk = nullptr;
         bool now = false, next = false;
         if constexpr (KNOWN) {
@@ -271,7 +290,7 @@ __device__ __forceinline__ void rows_body(const RowArgs& p, const RowKnowns* ks,
             double sc = 0.0, qc = 0.0, sg = 0.0, qg = 0.0;                   // sum Dc, sum Dc^2, sum Dg, sum Dg^2
             for (long long k = threadIdx.x; k < nv; k += T) {
                 float xv[V], eu[V], ec[V];
-                unpackv<V>(*reinterpret_cast<const hv_t<V>*>(xr + k * V), xv);
+                unpackv<V>(*reinterpret_cast<const hv_t<V>*>((STAGED ? srow : xr) + k * V), xv);
                 unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eur + k * V), eu);
                 unpackv<V>(*reinterpret_cast<const hv_t<V>*>(ecr + k * V), ec);
 #pragma unroll
@@ -313,8 +332,9 @@ __device__ __forceinline__ void rows_body(const RowArgs& p, const RowKnowns* ks,
         // an owned slot's row is this workgroup's alone; any other strides over the slot's workgroups
         for (long long k = owned ? threadIdx.x : blockIdx.x * (long long)T + threadIdx.x; k < nv;
              k += owned ? T : (long long)gridDim.x * T) {
-            float xv[V], eu[V], ec[V], ov[V], dn[V], xn[V], xi[V], nz[V], im[V], kz[V], mk[V];
+            float xv[V], eu[V], ec[V], ov[V], dn[V], xn[V], xi[V], nz[V], im[V], kz[V], mk[V], mv[V];
             unpackv<V>(*reinterpret_cast<const hv_t<V>*>(xr + k * V), xv);
+            if constexpr (STAGED) if (correct) unpackv<V>(*reinterpret_cast<const hv_t<V>*>(midr + k * V), mv);
             unpackv<V>(*reinterpret_cast<const hv_t<V>*>(eur + k * V), eu);
             unpackv<V>(*reinterpret_cast<const hv_t<V>*>(ecr + k * V), ec);
             unpackv<V>(*reinterpret_cast<const hv_t<V>*>(orow + k * V), ov);
@@ -329,11 +349,14 @@ __device__ __forceinline__ void rows_body(const RowArgs& p, const RowKnowns* ks,
                 const float e = combine(eu[j], ec[j]);
                 float xh = xv[j];                                           // the model input replaces x in D only - the
                 if constexpr (KNOWN) if (now) xh = blend(xv[j], sigma, im[j], kz[j], mk[j]);   // sampler's own state stays unblended
+                if constexpr (STAGED) if (correct) xh = mv[j];
                 float d = estimate(e, skip(xh));
                 if constexpr (RESCALE) if (owned) d = as_f32(K * d);        // before D's fp16 rounding
                 dn[j] = (float)(half_t)d;
                 const float bd = as_f32(b * dn[j]);
-                float xo = as_f32(__builtin_fmaf(c, ov[j], as_f32(__builtin_fmaf(a, xv[j], bd))));
+                float xo = as_f32(__builtin_fmaf(a, xv[j], bd));
+                if (!(STAGED && predict)) xo = as_f32(__builtin_fmaf(c, ov[j], xo));
+                if constexpr (STAGED) if (correct) xo = as_f32(__builtin_fmaf(sm, mv[j], xo));
                 if (nse) xo = as_f32(__builtin_fmaf(s, nz[j], xo));
                 xn[j] = (float)(half_t)xo;
                 float xm = xn[j];
@@ -341,7 +364,7 @@ __device__ __forceinline__ void rows_body(const RowArgs& p, const RowKnowns* ks,
                 xi[j] = as_f32(xm * c_in_next);
             }
             *reinterpret_cast<hv_t<V>*>(orow + k * V) = packv<V>(dn);
-            *reinterpret_cast<hv_t<V>*>(xr + k * V) = packv<V>(xn);
+            *reinterpret_cast<hv_t<V>*>((STAGED && predict ? midr : xr) + k * V) = packv<V>(xn);
             if (dst) {
                 const hv_t<V> o = packv<V>(xi);
                 *reinterpret_cast<hv_t<V>*>(xi_u + k * V) = o;
@@ -375,6 +398,13 @@ __global__ __launch_bounds__(T) void linear_rows_rescale_kernel(const RowArgs p,
 template <int T>
 __global__ __launch_bounds__(T) void linear_rows_rescale_cat_kernel(const RowArgs p, const RowRescales ps, const RowExtras es) {
     rows_body<T, 8, true, false, true, true>(p, nullptr, &ps, &es);
+}
+__global__ __launch_bounds__(256) void staged_rows_kernel(const RowArgs p, const RowStages ss) {
+    rows_body<256, 8, true, false, false, false, true>(p, nullptr, nullptr, nullptr, &ss);
+}
+template <int T>
+__global__ __launch_bounds__(T) void staged_rows_rescale_kernel(const RowArgs p, const RowRescales ps, const RowStages ss) {
+    rows_body<T, 8, true, false, true, false, true>(p, nullptr, &ps, nullptr, &ss);
 }
 
 
@@ -410,18 +440,20 @@ int row_record_status(int mode, int i, int n_src, int n_dst, const void* eps, co
 }
 
 // ---- the host side of the per-row entries: one check, one grid rule, one launch
-struct RowLaunch { RowArgs a; RowKnowns ks; RowRescales ps; RowExtras es; bool any_phi; };
+struct RowLaunch { RowArgs a; RowKnowns ks; RowRescales ps; RowExtras es; RowStages ss; bool any_phi; };
 
-// What the five entries check, in the order of their status paragraphs (include/dsc_hip.h); fills the by-value structs.  Records:
+// What the six entries check, in the order of their status paragraphs (include/dsc_hip.h); fills the by-value structs.  Records:
 // `steps` (the dsc_cfg_dpmpp2m_* entries: chw % 4 == 0, D = x - sigma e written as a dsc_row_linear) or `linears` (chw % 8 == 0).
 // need_known / need_rescale / need_extras: the entry has that argument and refuses NULL; rescale is also read where it is merely
-// given (dsc_cfg_linear_step_rows_cat's may be NULL).
+// given (dsc_cfg_linear_step_rows_cat's may be NULL).  need_stages (dsc_cfg_staged_step_rows): `stages` is refused when NULL, and a
+// STEP slot's stage is read: one of the three, and PREDICT / CORRECT need the 16-byte aligned `mid`.
 int rows_check(void* x, const void* eps, void* old, int n_src, void* x_in, float* t_buf, float* sigma_groups, void* tadd,
                int tadd_halfs, int n_dst, const dsc_row_step* steps, const dsc_row_linear* linears, int n_slots, int chw, int dtype,
                bool need_known, const dsc_row_known* known, bool need_rescale, const float* rescale,
-               bool need_extras, const dsc_row_extra* extras, int extra_halfs, RowLaunch* L) {
+               bool need_extras, const dsc_row_extra* extras, int extra_halfs, RowLaunch* L,
+               bool need_stages = false, const dsc_row_stage* stages = nullptr, void* mid = nullptr) {
     if (!x || !old || !x_in || !t_buf || !sigma_groups || !(steps || linears) || (need_known && !known) ||
-        (need_rescale && !rescale) || (need_extras && !extras) || n_src < 0 || n_dst <= 0 || chw <= 0)
+        (need_rescale && !rescale) || (need_extras && !extras) || (need_stages && !stages) || n_src < 0 || n_dst <= 0 || chw <= 0)
         return DSC_ERR_BAD_ARG;
     if (n_slots < n_dst || n_slots > DSC_ROW_STEP_MAX_SLOTS) return DSC_ERR_BAD_ARG;
     if (extras && (extra_halfs <= 0 || extra_halfs % 8 != 0 || chw % 8 != 0)) return DSC_ERR_BAD_ARG;  // 16-byte rows of chw + extra_halfs
@@ -431,6 +463,7 @@ int rows_check(void* x, const void* eps, void* old, int n_src, void* x_in, float
     L->a = RowArgs{static_cast<half_t*>(x), static_cast<const half_t*>(eps), static_cast<half_t*>(old), n_src, static_cast<half_t*>(x_in),
                    t_buf, sigma_groups, static_cast<half_t*>(tadd), tadd_halfs, n_dst, chw, {}};
     L->es.halfs = extra_halfs;
+    L->ss.mid = static_cast<half_t*>(mid);
     bool any_row = false;
     for (int i = 0; i < n_slots; ++i) {
         dsc_row_linear r;
@@ -456,6 +489,15 @@ int rows_check(void* x, const void* eps, void* old, int n_src, void* x_in, float
             if (!(rescale[i] >= 0.0f && rescale[i] <= 1.0f)) return DSC_ERR_BAD_ARG;      // (NaN lands here too)
             L->ps.phi[i] = rescale[i];
             L->any_phi |= rescale[i] > 0.0f;
+        }
+        if (stages && step) {
+            const int stage = stages[i].stage;
+            if (stage != DSC_ROW_STAGE_FULL && stage != DSC_ROW_STAGE_PREDICT && stage != DSC_ROW_STAGE_CORRECT) return DSC_ERR_BAD_ARG;
+            if (stage != DSC_ROW_STAGE_FULL) {
+                if (!mid) return DSC_ERR_BAD_ARG;
+                if (!al16(mid)) return DSC_ERR_UNSUPPORTED;
+            }
+            L->ss.r[i] = stages[i];
         }
         if (extras) {
             if (extras[i].extra && !al16(extras[i].extra)) return DSC_ERR_BAD_ARG;
@@ -581,3 +623,15 @@ extern "C" int dsc_cfg_linear_step_rows_cat(void* x, const void* eps, void* old,
                      : rows_launch<256, 8>(linear_rows_cat_kernel, L.a, n_slots, stream, L.es);
 }
 
+// the kernels of the two linear entries this one shares its arithmetic with, each with the STAGED flag: without a phi > 0 the 256-thread
+// grid of dsc_cfg_linear_step_rows, with one the single-workgroup sums of dsc_cfg_linear_step_rows_rescale
+extern "C" int dsc_cfg_staged_step_rows(void* x, void* mid, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
+                                        float* sigma_groups, void* tadd, int tadd_halfs, int n_dst, const dsc_row_linear* rows,
+                                        const dsc_row_stage* stages, const float* rescale, int n_slots, int chw, int dtype,
+                                        void* stream) {
+    RowLaunch L;
+    if (const int st = rows_check(x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, tadd_halfs, n_dst, nullptr, rows, n_slots, chw,
+                                  dtype, false, nullptr, false, rescale, false, nullptr, 0, &L, true, stages, mid)) return st;
+    return L.any_phi ? rows_launch<DSC_RESCALE_THREADS, 8>(staged_rows_rescale_kernel<DSC_RESCALE_THREADS>, L.a, n_slots, stream, L.ps, L.ss)
+                     : rows_launch<256, 8>(staged_rows_kernel, L.a, n_slots, stream, L.ss);
+}

@@ -470,7 +470,7 @@ class StableDiffusionPipeline:
                 # build-specific inputs (the prompt encoders are a "next" row):
                 prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
                 text_input_ids=None, fused: Optional[bool] = None, slot: int = 0, step_noise: Optional[torch.Tensor] = None,
-                **unsupported):
+                two_call: bool = False, **unsupported):
         """reference :943-1231.  What is txt2img's own stands here; the rest is the shared path below (_text_and_schedule,
         _conditioning, _denoise_and_finish)."""
         a = dict(locals())                       # this call's arguments by name, as given: what the shared path reads
@@ -490,7 +490,8 @@ class StableDiffusionPipeline:
     def serve(self, height: int = 512, width: int = 512, max_batch: int = 8, slot: int = 0, buckets=(1, 2, 4, 8), text_len: int = 77,
               ip_masks: bool = False, t2i_adapter: bool = False, controlnet: bool = False, control_slots=None,
               decode: bool = False, decode_batch: int = 2, previews: bool = False, preview_scale: int = 8, preview_coef=None,
-              preview_ring: int = 8, inpaint_unet: bool = False, freeu: bool = False, encode: bool = False, encode_batch: int = 2):
+              preview_ring: int = 8, inpaint_unet: bool = False, freeu: bool = False, encode: bool = False, encode_batch: int = 2,
+              two_call: bool = False):
         """Continuous-batching server (modules/serving/): requests join a running batch at any step boundary, each at its own
         point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
         stats / warm).  `ip_masks=True` (IP-Adapters loaded): requests may carry the reference's
@@ -518,7 +519,11 @@ class StableDiffusionPipeline:
         `mask_image` are pixels are encoded on an encode lane - a second stream with one captured `vae.encode` per bucket, up to
         `encode_batch` (in [1, max_batch]) rows per encode, between one dsc_image_prepare and one dsc_latent_start_rows launch -
         beside the step: `submit` does host work and the request's draws only, and the request is admitted when its encode has
-        completed; without it pixel inputs are prepared inline inside `submit`, as before.  Any batcher is refused while the
+        completed; without it pixel inputs are prepared inline inside `submit`, as before.  `two_call=True` (not together with
+        `inpaint_unet`): requests may name a sampler of sampling.TWO_CALL_FAMILY (Heun, DPM2, DPM2 a, DPM++ 2S a, DPM++ SDE) with
+        `eta` / `s_noise` / `seed` / `step_noise` (one row per model call, sampling.call_noise_table); such a request advances by
+        one model call per transition, two per sampler step (dsc_cfg_staged_step_rows), beside requests of the one-call samplers;
+        not with `control_img` / `image_t2i_adapter`.  Any batcher is refused while the
         UNet-level setting (unet.enable_freeu) is on."""
         from .serving import ServingBatcher
         kw = dict(previews=True, preview_scale=preview_scale, preview_coef=preview_coef, preview_ring=preview_ring) if previews else {}
@@ -528,6 +533,8 @@ class StableDiffusionPipeline:
             kw["freeu"] = True
         if encode:
             kw.update(encode=True, encode_batch=encode_batch)
+        if two_call:
+            kw["two_call"] = True
         return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len,
                               ip_masks=ip_masks, t2i_adapter=t2i_adapter, controlnet=controlnet, control_slots=control_slots,
                               decode=decode, decode_batch=decode_batch, **kw)
@@ -535,7 +542,8 @@ class StableDiffusionPipeline:
     def serve_hires(self, height: int = 512, width: int = 512, upscale_x: float = 1.25, max_batch: int = 8, buckets=(1, 2, 4, 8),
                     text_len: int = 77, slots=(0, 1), ip_masks: bool = False, decode: bool = False, decode_batch: int = 2,
                     previews: bool = False, preview_scale: int = 8, preview_coef=None, preview_ring: int = 8,
-                    inpaint_unet: bool = False, freeu: bool = False, encode: bool = False, encode_batch: int = 2):
+                    inpaint_unet: bool = False, freeu: bool = False, encode: bool = False, encode_batch: int = 2,
+                    two_call: bool = False):
         """Continuous-batching server for requests with a hires pass (reference :1176-1228): a batcher at `height` x `width`
         chained to one at the target size of `upscale_x` (_hires_pass's expression), on two workspace slots.  A request with
         `upscale=True` runs its first pass on the one, is enlarged and re-noised on the device (dsc_latent_resample_noise) and
@@ -549,6 +557,9 @@ class StableDiffusionPipeline:
         only: the second pass starts from the hand-off's latent, never from pixels."""
         from .latent_resample import hires_target_size
         from .serving import HiresPair, ServingBatcher
+        if two_call:
+            raise ValueError("serve_hires: `two_call=True` is not served (the two-call samplers run on a batcher built with "
+                             "pipe.serve(..., two_call=True))")
         if inpaint_unet:
             raise ValueError("serve_hires: `inpaint_unet=True` is not served (inpaiting refuses the hires pass too); build the "
                              "batcher with pipe.serve(..., inpaint_unet=True)")
@@ -766,7 +777,8 @@ class StableDiffusionPipeline:
                 guidance_rescale: float = 0.0, cross_attention_kwargs=None, clip_skip=None, long_encode=0,
                 num_images_per_prompt=1, ip_adapter_image_embeds=None,
                 prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
-                text_input_ids=None, fused: Optional[bool] = None, step_noise: Optional[torch.Tensor] = None, **unsupported):
+                text_input_ids=None, fused: Optional[bool] = None, step_noise: Optional[torch.Tensor] = None,
+                two_call: bool = False, **unsupported):
         """reference :543-846: encode the image (or take `latents`), keep the last `strength` fraction of the schedule, add
         noise, denoise.  Reproduces the reference's start: `latents + noise * sqrt(sigma_0^2 + 1)` (:647 - sic, not
         `noise * sigma_0`).  Generator draws: the VAE posterior sample, then the noise; the image is encoded before the prompt."""
@@ -985,7 +997,8 @@ class StableDiffusionPipeline:
                                           cross_attention_kwargs, a["start_time"], a["timeout"], sampler=sampler,
                                           sampler_args=self._fused_sampler_args(sampler, sigmas, eta, steps, sampler_opt, latents,
                                                                                 seed, step_noise),
-                                          step_noise=step_noise, guidance_rescale=guidance_rescale, **(fused_kw or {}))
+                                          step_noise=step_noise, guidance_rescale=guidance_rescale,
+                                          **({"two_call": True} if a.get("two_call") else {}), **(fused_kw or {}))
         else:
             protocol_kw = dict(protocol_kw or {})
             if eta is None:
@@ -1405,7 +1418,8 @@ class StableDiffusionPipeline:
         if eta is not None:
             args["eta"] = eta
         if step_noise is None and sampler_opt.get("brownian_noise", False) \
-                and sampling.linear_family(sampler) in ("euler_ancestral", "dpmpp_2m_sde", "lcm"):
+                and (sampling.linear_family(sampler) in ("euler_ancestral", "dpmpp_2m_sde", "lcm")
+                     or sampling.two_call_family(sampler) in ("dpm_2_ancestral", "dpmpp_2s_ancestral", "dpmpp_sde")):
             args["noise_sampler"] = self.create_noise_sampler(latents, sigmas, steps, seed)
         return args
 
@@ -1443,10 +1457,34 @@ class StableDiffusionPipeline:
             else:
                 ops.cfg_linear_step_rows(x, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, tadd=st["tadd"])
 
+    def _staged_fused_loop(self, st, x, old, calls, noise, tab, guidance_scale, n_img, start_time, timeout, rescale=0.0):
+        """_linear_fused_loop for a two-call sampler: one model call and one dsc_cfg_staged_step_rows launch per entry of `calls`,
+        [(the sigma the call's model runs at, its sampling.Call)]; every image is on the same call of the same plan"""
+        kdm = self.k_diffusion_model
+        mid = torch.zeros_like(x)
+        for k, (sigma, call) in enumerate(calls):
+            self._check_timeout(start_time, timeout)
+            st["run"]()
+            nxt = calls[k + 1][0] if k + 1 < len(calls) else 0.0
+            c_in_n, _, t_n = kdm.step_scalars(nxt) if nxt > 0 else (1.0, 0.0, 0.0)
+            a, m, b, c, s = call.coeffs
+            rec = {"mode": ops.ROW_STEP, "stage": call.stage, "sigma": sigma, "guidance": guidance_scale, "a": a, "m": m, "b": b,
+                   "c": c, "s": s, "c_skip": kdm.step_skip(sigma), "c_out": kdm.step_scalars(sigma)[1], "c_in_next": c_in_n,
+                   "t_next": t_n, "sigma_next": max(nxt, 1e-10),
+                   "temb_row": tab[k + 1] if tab is not None and k + 1 < len(calls) else None}
+            if rescale > 0.0:
+                rec["rescale"] = rescale
+            recs = [dict(rec, noise=None if noise is None or s == 0.0 else noise[k, j if noise.shape[1] > 1 else 0])
+                    for j in range(n_img)]
+            ops.cfg_staged_step_rows(x, mid, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, tadd=st["tadd"])
+
     def _denoise_fused(self, latents, sigmas, text, region_state, weight_func, guidance_scale, n_img,
                        cross_attention_kwargs, start_time, timeout, slot=0, sampler=None, sampler_args=None, step_noise=None,
-                       guidance_rescale=0.0, extra=None):
-        """sampler: None (DPM++ 2M) or one of sampling.LINEAR_FAMILY's functions.  DPM++ 2M on an eps-prediction model is one
+                       guidance_rescale=0.0, extra=None, two_call=False):
+        """sampler: None (DPM++ 2M) or one of sampling.LINEAR_FAMILY's functions - with two_call=True also one of
+        sampling.TWO_CALL_FAMILY's: one model call and one dsc_cfg_staged_step_rows launch per entry of sampling.call_plan, the
+        step's intermediate point kept in `mid` beside `old`; step_noise then has one row per model call
+        (sampling.call_noise_table); not with `extra`.  DPM++ 2M on an eps-prediction model is one
         dsc_cfg_dpmpp2m_step per step; every other member, and every v-prediction model, one dsc_cfg_linear_step_rows with a
         record per image.  step_noise: the noise table [steps, 1 or n_img, c, h, w] (default: sampling.step_noise_table).
         guidance_rescale (phi, arXiv 2305.08891 sec. 3.4) > 0: every family member, DPM++ 2M on an eps model included, takes the
@@ -1460,10 +1498,16 @@ class StableDiffusionPipeline:
         if not 0.0 <= guidance_rescale <= 1.0:
             raise ValueError(f"fused=True: guidance_rescale must be in [0, 1], got {guidance_rescale}")
         family = "dpmpp_2m" if sampler is None else sampling.linear_family(sampler)
+        staged = family is None and two_call and sampling.two_call_family(sampler) is not None
+        if staged:
+            family = sampling.two_call_family(sampler)
+            if extra is not None:
+                raise NotImplementedError(f"fused=True: the two-call sampler {family!r} has no step for a UNet with extra input "
+                                          "channels (dsc_cfg_staged_step_rows takes no CAT form); run it with fused=False")
         if family is None:
             raise NotImplementedError(f"fused=True: sampler {getattr(sampler, '__name__', sampler)!r} has no fused step "
                                       f"(supported: {', '.join(sampling.LINEAR_FAMILY)}); run it with fused=False")
-        rows_path = family != "dpmpp_2m" or self.v_prediction or guidance_rescale > 0.0 or extra is not None
+        rows_path = staged or family != "dpmpp_2m" or self.v_prediction or guidance_rescale > 0.0 or extra is not None
         if rows_path and n_img > ops.ROW_STEP_MAX_SLOTS:
             raise NotImplementedError(f"fused=True: the per-row sampler step takes at most {ops.ROW_STEP_MAX_SLOTS} images per "
                                       f"batch, got {n_img}; run it with fused=False")
@@ -1492,11 +1536,17 @@ class StableDiffusionPipeline:
             sig = sigmas.detach().float().cpu().tolist()             # one device->host transfer before the loop
         sargs = dict(sampler_args or {})
         noise_sampler = sargs.pop("noise_sampler", None)
-        if family not in ("euler_ancestral", "dpmpp_2m_sde"):
+        if family not in ("euler_ancestral", "dpmpp_2m_sde", "dpm_2_ancestral", "dpmpp_2s_ancestral", "dpmpp_sde"):
             sargs.pop("eta", None)
         if family != "dpmpp_2m_sde":
             sargs.pop("solver_type", None)
-        coeffs = sampling.linear_step_coefficients(family, sig, **sargs) if rows_path else sampling.dpmpp_2m_coefficients(sig)
+        if staged:
+            # the sigma a model call runs at is rounded to the latents' dtype, as protocol mode's `sigma * s_in` does (the schedule's
+            # own sigmas already are); the update's scalars keep the unrounded value, as the samplers' host arithmetic does
+            plan = sampling.call_plan(family, sig, **sargs)
+            coeffs = [(float(torch.tensor(call.sigma, dtype=torch.float64).to(latents.dtype)), call) for call in plan]
+        else:
+            coeffs = sampling.linear_step_coefficients(family, sig, **sargs) if rows_path else sampling.dpmpp_2m_coefficients(sig)
         ack = getattr(self, "_added_cond_kwargs", None)
         ip_key = None if ack is None else (tuple(tuple(e.shape) for e in ack["image_embeds"]),
                                            id(getattr(self.unet, "encoder_hid_proj", None)))
@@ -1520,6 +1570,7 @@ class StableDiffusionPipeline:
         st = self._static_step(key, n_img, in_shape, text, region_state, weight_func, cross_attention_kwargs)
         x = latents.contiguous().clone()
         old = torch.zeros_like(x)
+        call_sig = [s_ for s_, _ in coeffs] if staged else sig[:len(coeffs)]      # the sigma of every model call
         if prof:
             torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -1527,9 +1578,9 @@ class StableDiffusionPipeline:
         tab = None
         if st["tadd"] is not None:
             # the schedule's timesteps are known here: every step's embedding rows in one table (kept while the schedule repeats)
-            tkey = (tuple(sig[:len(coeffs)]), self.unet.temb_signature())     # the schedule AND the weights the table bakes in
+            tkey = (tuple(call_sig), self.unet.temb_signature())              # the schedule AND the weights the table bakes in
             if st["temb_key"] != tkey:
-                ts = [float(kdm.step_scalars(s_)[2]) for s_ in sig[:len(coeffs)]]
+                ts = [float(kdm.step_scalars(s_)[2]) for s_ in call_sig]
                 st["temb_tab"] = self.unet.temb_add_table(torch.tensor(ts, dtype=torch.float32, device=x.device))
                 st["temb_key"] = tkey
             tab = st["temb_tab"]
@@ -1539,7 +1590,16 @@ class StableDiffusionPipeline:
             ops.cfg_linear_step_rows_cat(x, None, old, 0, st["x_in"], st["t"], st["sigma_rows"], [join] * n_img, extras, tadd=st["tadd"])
         else:
             ops.prepare_unet_input(x, c_in, t, sig[0], st["x_in"], st["t"], st["sigma"], row=None if tab is None else (tab[0], st["tadd"]))
-        if rows_path:
+        if staged:
+            noise = None
+            if any(call.coeffs[4] != 0.0 for _, call in coeffs):
+                noise = step_noise if step_noise is not None else \
+                    sampling.call_noise_table(family, x, sigmas, eta=sargs.get("eta", 1.0), noise_sampler=noise_sampler)
+                noise = self._check_step_noise(noise, len(coeffs), x)
+            self._staged_fused_loop(st, x, old, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout,
+                                    rescale=guidance_rescale)
+            coeffs = []
+        elif rows_path:
             noise = None
             if any(c4[3] != 0.0 for c4 in coeffs):
                 noise = step_noise if step_noise is not None else \

@@ -20,6 +20,7 @@ step (dsc_dpmpp2m_step) instead of the 3-5 elementwise launches of the torch ver
 host in fp64 from the (already fp16-rounded, model_k_diffusion.py:1027-1029) sigmas, so there is no device->host
 sync inside the loop (the reference's sampler tests `sigmas[i + 1] == 0` on a device tensor every step).
 """
+import collections
 import math
 
 import torch
@@ -545,4 +546,129 @@ def step_noise_table(name, x, sigmas, eta=1.0, noise_sampler=None):
             rows.append(noise_sampler(sig[i], sig[i + 1]).to(x.dtype))
         else:
             rows.append(noise_sampler(sigmas[i], sigmas[i + 1]).to(x.dtype))
+    return torch.stack(rows)
+
+
+# ----------------------------------------------------------------------------------------------- the two-call family
+# The samplers above that make TWO model calls per step and whose new x is a linear combination of x, the intermediate point, the
+# two denoised estimates and a noise row: two consecutive transitions of the staged per-row step kernel
+# (dsc_cfg_staged_step_rows) - PREDICT writes the intermediate point beside x and leaves x alone, CORRECT reads it back as a third
+# state row.  Every transition is  x_out = a x + m x_mid + b D + c D_old + s xi  with D the estimate of the call that just ran
+# and D_old that of the call before.  sample_heunpp2 (three calls), sample_lms and sample_dpmpp_3m_sde (longer histories) do not fit.
+TWO_CALL_FAMILY = ("heun", "dpm_2", "dpm_2_ancestral", "dpmpp_2s_ancestral", "dpmpp_sde")
+STAGE_FULL, STAGE_PREDICT, STAGE_CORRECT = 0, 1, 2      # (dsc_row_stage.stage, include/dsc_hip.h)
+
+
+def two_call_family(sampler):
+    """linear_family's rule for TWO_CALL_FAMILY: the family name of a sampler given as a callable of this module or as a name
+    ("sample_heun" / "heun"); None for anything else, and for a functools.partial (app.py binds s_churn that way: churn is not
+    part of the plan)"""
+    name = sampler if isinstance(sampler, str) else getattr(sampler, "__name__", "")
+    if not isinstance(sampler, str) and (getattr(sampler, "__module__", "") or "") != __name__:
+        return None
+    if name.startswith("sample_"):
+        name = name[len("sample_"):]
+    return name if name in TWO_CALL_FAMILY else None
+
+
+class Call(collections.namedtuple("Call", "stage sigma coeffs query step ends_step")):
+    """one model call of a two-call sampler and the transition that follows it: `stage` (STAGE_*), `sigma` the call's model ran
+    at, `coeffs` = (a, m, b, c, s), `query` = the (sigma_from, sigma_to) the sampler hands its noise sampler here or None,
+    `step` the sampler step the call belongs to, `ends_step` whether x is the step's result afterwards"""
+    __slots__ = ()
+
+
+def call_plan(name, sigmas, eta=1.0, s_noise=1.0, r=0.5):
+    """One Call per model call of sampler `name` (a TWO_CALL_FAMILY name or the callable) over `sigmas`, in order, host fp64
+    scalars read off sample_heun (without churn), sample_dpm_2 (without churn), sample_dpm_2_ancestral,
+    sample_dpmpp_2s_ancestral and sample_dpmpp_sde.  A step whose target sigma is 0 is one FULL call (Euler to 0); every other
+    step is a PREDICT call (x_mid = a x + b D [+ s xi]; x stays) and a CORRECT call (the model ran on x_mid at `sigma`;
+    x = a x + m x_mid + b D + c D_old [+ s xi]).  The model call after entry k runs at entry k + 1's sigma."""
+    fam = two_call_family(name)
+    if fam is None:
+        raise NotImplementedError(f"no two-call plan for sampler {getattr(name, '__name__', name)!r} "
+                                  f"(supported: {', '.join(TWO_CALL_FAMILY)})")
+    sig = [float(s) for s in sigmas]
+    plan = []
+
+    def full(i, target, s=0.0, query=None):                      # x + (x - D) * ((target - sigma) / sigma)
+        k = (target - sig[i]) / sig[i]
+        plan.append(Call(STAGE_FULL, sig[i], (1.0 + k, 0.0, -k, 0.0, s), query, i, True))
+
+    def pair(i, predict, sigma_call, correct, q1=None, q2=None):
+        plan.append(Call(STAGE_PREDICT, sig[i], predict, q1, i, False))
+        plan.append(Call(STAGE_CORRECT, sigma_call, correct, q2, i, True))
+
+    for i in range(len(sig) - 1):
+        s0, s1 = sig[i], sig[i + 1]
+        if fam == "heun":
+            dt = s1 - s0
+            if s1 == 0:
+                full(i, s1)
+            else:
+                pair(i, (1.0 + dt / s0, 0.0, -dt / s0, 0.0, 0.0), s1,
+                     (1.0 + dt / (2 * s0), dt / (2 * s1), -dt / (2 * s1), -dt / (2 * s0), 0.0))
+        elif fam in ("dpm_2", "dpm_2_ancestral"):
+            anc = fam == "dpm_2_ancestral"
+            sd, su = get_ancestral_step(s0, s1, eta=eta) if anc else (s1, 0.0)
+            if sd == 0:
+                full(i, sd)
+            else:
+                sm = math.exp(0.5 * (math.log(s0) + math.log(sd)))
+                k = (sd - s0) / sm
+                pair(i, (sm / s0, 0.0, 1.0 - sm / s0, 0.0, 0.0), sm, (1.0, k, -k, 0.0, s_noise * su),
+                     q2=(s0, s1) if anc else None)
+        elif fam == "dpmpp_2s_ancestral":
+            sd, su = get_ancestral_step(s0, s1, eta=eta)
+            s, q = (s_noise * su, (s0, s1)) if s1 > 0 else (0.0, None)
+            if sd == 0:
+                full(i, sd, s, q)
+            else:
+                t = -math.log(s0)
+                h = -math.log(sd) - t
+                sm = math.exp(-(t + 0.5 * h))
+                pair(i, (sm / s0, 0.0, -math.expm1(-0.5 * h), 0.0, 0.0), sm, (sd / s0, 0.0, -math.expm1(-h), 0.0, s), q2=q)
+        elif s1 == 0:                                             # dpmpp_sde
+            full(i, s1)
+        else:
+            t, t_next = -math.log(s0), -math.log(s1)
+            h = t_next - t
+            ss = t + h * r
+            fac = 1 / (2 * r)
+            sd, su = get_ancestral_step(math.exp(-t), math.exp(-ss), eta)
+            s_ = -math.log(sd)
+            predict = (math.exp(-s_) / math.exp(-t), 0.0, -math.expm1(t - s_), 0.0, s_noise * su)
+            q1 = (math.exp(-t), math.exp(-ss))
+            sd, su = get_ancestral_step(math.exp(-t), math.exp(-t_next), eta)
+            t_next_ = -math.log(sd)
+            e = -math.expm1(t - t_next_)
+            pair(i, predict, math.exp(-ss), (math.exp(-t_next_) / math.exp(-t), 0.0, e * fac, e * (1 - fac), s_noise * su),
+                 q1=q1, q2=(math.exp(-t), math.exp(-t_next)))
+    return plan
+
+
+def call_noise_table(name, x, sigmas, eta=1.0, noise_sampler=None, r=0.5):
+    """step_noise_table for TWO_CALL_FAMILY: one row per model call of call_plan, [n_calls, *x.shape] of x's dtype on x's device -
+    the unit noise the sampler itself would draw there (the plan's `query`, in the plan's order: default_noise_sampler for the
+    two ancestral samplers, the BrownianTreeNoiseSampler with its default seed for sample_dpmpp_sde), zeros for a call that
+    draws none.  None for the samplers without a noise term (heun, dpm_2).  The ancestral samplers are handed the schedule's
+    own tensor entries when `sigmas` is a tensor, as they do it themselves."""
+    fam = two_call_family(name)
+    if fam is None:
+        raise NotImplementedError(f"no two-call plan for sampler {getattr(name, '__name__', name)!r} "
+                                  f"(supported: {', '.join(TWO_CALL_FAMILY)})")
+    if fam in ("heun", "dpm_2"):
+        return None
+    sig = _steps(sigmas) if torch.is_tensor(sigmas) else [float(s) for s in sigmas]
+    if noise_sampler is None:
+        noise_sampler = BrownianTreeNoiseSampler(x, min(v for v in sig if v > 0), max(sig)) if fam == "dpmpp_sde" \
+            else default_noise_sampler(x)
+    rows = []
+    for call in call_plan(fam, sig, eta=eta, r=r):
+        if call.query is None:
+            rows.append(torch.zeros_like(x))
+        elif fam == "dpmpp_sde" or not torch.is_tensor(sigmas):
+            rows.append(noise_sampler(*call.query).to(x.dtype))
+        else:
+            rows.append(noise_sampler(sigmas[call.step], sigmas[call.step + 1]).to(x.dtype))
     return torch.stack(rows)

@@ -11,6 +11,15 @@ with `pass_kwargs = False`, zero region tables: the reference's v-prediction pat
 known-region launch of inpainting carries DPM++ 2M records only, so an inpainting request and a request of another sampler never
 share a batch: the later one waits in the queue until the others have left.
 
+Two-call samplers.  On a batcher built with `two_call=True` a request may also name a sampler of sampling.TWO_CALL_FAMILY (Heun,
+DPM2, DPM2 a, DPM++ 2S a, DPM++ SDE): two model calls per sampler step.  Its per-step lists (sig, coeffs, snoise, scal, skipout)
+then hold one entry per MODEL CALL of sampling.call_plan, `r.i` stays the index of the model call that runs now, and every
+transition applies one call: PREDICT writes the step's intermediate point into the slot's row of `exec.mid` and leaves x alone,
+CORRECT reads it back (dsc_cfg_staged_step_rows).  A transition in which some slot carries such a stage launches that entry for
+all slots - the one-call members ride in it as FULL records with the bits they have otherwise - and any other transition the
+launch it had.  Not with ControlNet / T2I-Adapter requests (their windows count one model call per step), inpainting or
+`inpaint_unet`.
+
 Guidance rescale.  A request may carry `guidance_rescale` (phi in [0, 1], arXiv 2305.08891 sec. 3.4; the usual companion of
 v-prediction models).  Its STEP records carry `rescale` and, DPM++ 2M on an eps-prediction model included, (c_skip, c_out); a
 transition in which such a slot steps launches dsc_cfg_linear_step_rows_rescale for all slots (ops.cfg_linear_step_rows picks it
@@ -56,7 +65,8 @@ class ServingBatcher:
 
     def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
                  t2i_adapter=False, controlnet=False, control_slots=None, decode=False, decode_batch=2, previews=False,
-                 preview_scale=8, preview_coef=None, preview_ring=8, inpaint_unet=False, freeu=False, encode=False, encode_batch=2):
+                 preview_scale=8, preview_coef=None, preview_ring=8, inpaint_unet=False, freeu=False, encode=False, encode_batch=2,
+                 two_call=False):
         requests.check_freeu_off(pipe)
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
@@ -88,8 +98,16 @@ class ServingBatcher:
         # a 9-channel inpainting UNet: every request is an inpainting request, and every transition writes each member's mask and
         # masked-image latents behind its latent row (dsc_cfg_linear_step_rows_cat; package docstring)
         self.inpaint = bool(inpaint_unet)
+        if self.inpaint and two_call:
+            raise ValueError("serve: `two_call=True` and `inpaint_unet=True` are not served together (the staged step has no "
+                             "form with extra input channels)")
         if self.inpaint:
             self._inpaint_setup(controlnet, t2i_adapter)
+        # requests may name a sampler of sampling.TWO_CALL_FAMILY: two transitions per sampler step, the intermediate point in a
+        # third state row (dsc_cfg_staged_step_rows)
+        self.two_call = bool(two_call)
+        if self.two_call:
+            self._stats["staged_transitions"] = 0
         # requests may ask for images ("pil" / "np" / "uint8"): a decode lane beside the step finishes them (decode_lane.py)
         self.decode = bool(decode)
         self.decode_batch = 0
@@ -350,7 +368,11 @@ class ServingBatcher:
         On a batcher built with `encode=True`: `image` / `mask_image` given as pixels (a PIL image, a numpy array or a tensor, of
         this batcher's size) are encoded on the encode lane (encode_lane.py): submit normalises them on the host and makes the
         request's draws, and the request joins the batch once its encode has completed; its result has the bits the inline path
-        gives at the same encode batch size.  Returns a Future of the final output."""
+        gives at the same encode batch size.
+        On a batcher built with `two_call=True`: `sampler_name` may be one of sampling.TWO_CALL_FAMILY (sample_heun, sample_dpm_2,
+        sample_dpm_2_ancestral, sample_dpmpp_2s_ancestral, sample_dpmpp_sde) with `eta` / `s_noise` / `seed` / `generator`;
+        `step_noise` then has one row per MODEL CALL (sampling.call_noise_table) and `preview_every` counts sampler steps; not
+        with `control_img` / `image_t2i_adapter` / `mask_image`.  Returns a Future of the final output."""
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -436,6 +458,8 @@ class ServingBatcher:
         more = {}
         if self.freeu:                                                   # (one more field, `freeu`)
             record, more = (_InpaintFreeuRequest if self.inpaint else _FreeuRequest), {"freeu": freeu}
+        if self.two_call:                                                # (four more: `stage`, `m`, `call_step`, `ends_step`)
+            record = requests._TWO_CALL_RECORD[record]
         if self.encode:                                                  # (one more field, `enc`)
             record = requests._ENCODE_RECORD[record]
         r = record(req=request, future=concurrent.futures.Future(), steps=steps, second=second, ip_embeds=ip_embeds,
@@ -470,13 +494,22 @@ class ServingBatcher:
             if all(g == 0.0 for call in r.cgates for g in call):
                 r.control, r.cgates = None, None                     # no model call carries it: no lane, no embedding
         args = {}
-        if family in ("euler_ancestral", "dpmpp_2m_sde"):
+        if family in ("euler_ancestral", "dpmpp_2m_sde") or family in sampling.TWO_CALL_FAMILY:
             args.update(eta=r.eta, s_noise=float(request.get("s_noise", 1.0)))
         if family == "dpmpp_2m_sde":
             args["solver_type"] = request.get("solver_type") or "midpoint"
             if args["solver_type"] not in ("midpoint", "heun"):
                 raise ValueError(f"serve: `solver_type` must be 'midpoint' or 'heun', got {args['solver_type']!r}")
-        abcs = sampling.linear_step_coefficients(family, r.sig, **args)
+        if family in sampling.TWO_CALL_FAMILY:
+            # one entry per MODEL CALL from here on (r.i: the index of the model call that runs now).  The sigma a call's model
+            # runs at is rounded to the model dtype, as the fused loop and protocol mode's `sigma * s_in` do
+            plan = sampling.call_plan(family, r.sig, **args)
+            r.sig = [float(torch.tensor(call.sigma, dtype=torch.float64).to(dt)) for call in plan] + [0.0]
+            abcs = [(a, b, c, s) for a, _, b, c, s in (call.coeffs for call in plan)]
+            r.stage, r.m = [call.stage for call in plan], [call.coeffs[1] for call in plan]
+            r.call_step, r.ends_step = [call.step for call in plan], [call.ends_step for call in plan]
+        else:
+            abcs = sampling.linear_step_coefficients(family, r.sig, **args)
         r.coeffs = [c4[:3] for c4 in abcs]
         r.snoise = [c4[3] for c4 in abcs]
         kdm = pipe.k_diffusion_model
@@ -735,6 +768,8 @@ class ServingBatcher:
                                noise=self.exec.noise_row(r, r.i) if r.snoise[r.i] != 0.0 else None)
                     if r.rescale > 0.0:
                         rec["rescale"] = r.rescale
+                    if requests.staged(r):
+                        rec.update(stage=r.stage[r.i], m=r.m[r.i])
                 if r in leaving:
                     rec.update(c_in_next=0.0, t_next=0.0, sigma_next=1.0, temb_row=None, req=r, step=r.i, next_step=None)
                 else:
@@ -768,7 +803,7 @@ class ServingBatcher:
     def _transition(self, n_src, n_dst, recs, known):
         """the ONE launch of this step; executor.step_launch names it from the records"""
         kind = step_launch(recs, known)
-        if kind == "known" and step_launch(recs) == "linear":
+        if kind == "known" and step_launch(recs) in ("linear", "staged"):
             raise RuntimeError("serve: an inpainting slot and a slot of another sampler step together (admission check bypassed)")
         if kind == "known":
             self.exec.transition(n_src, n_dst, recs, known)
@@ -776,6 +811,8 @@ class ServingBatcher:
             self.exec.transition(n_src, n_dst, recs)
         if kind == "linear":                         # a slot steps another sampler / a v-prediction model / with a rescale
             self._stats["linear_transitions"] += 1
+        if kind == "staged":                         # a slot is inside a two-call sampler's step
+            self._stats["staged_transitions"] += 1
 
     def _transition_cat(self, n_src, n_dst, recs):
         """the ONE launch of a step on a batcher built with `inpaint_unet=True`: always dsc_cfg_linear_step_rows_cat, with one
@@ -788,7 +825,13 @@ class ServingBatcher:
         """the slots whose request is due a preview after the step just applied (every preview_every-th of its steps, never its
         last) go to ONE launch; with no free ring entry it is skipped and counted - the step does not wait"""
         asked = self._preview_of
-        due = [r for r in stepping if r in asked and (r.i + 1) % asked[r].every == 0 and r not in leaving]
+
+        def done(r):                                 # sampler steps applied once this transition has run, or None inside a step
+            if not requests.staged(r):
+                return r.i + 1
+            return r.call_step[r.i] + 1 if r.ends_step[r.i] else None
+
+        due = [r for r in stepping if r in asked and done(r) and done(r) % asked[r].every == 0 and r not in leaving]
         if not due:
             return
         self.exec.ensure_preview()
@@ -798,7 +841,8 @@ class ServingBatcher:
             return
         for r in due:
             asked[r].out += 1
-        self._preview_queue.append((h, [(asked[r], r.i + 1, len(r.coeffs)) for r in due]))
+        self._preview_queue.append((h, [(asked[r], done(r), r.call_step[-1] + 1 if requests.staged(r) else len(r.coeffs))
+                                        for r in due]))
         self._stats["previews"] += 1
         self._stats["preview_rows"] += len(due)
 

@@ -53,7 +53,7 @@ from .preview_lane import _PreviewLane
 
 _EMBED_LOCK = threading.Lock()       # around the process-wide deterministic switch in _GraphExecutor._control_embedding
 _STEP_ROWS = {"rows": "cfg_dpmpp2m_step_rows", "linear": "cfg_linear_step_rows", "known": "cfg_dpmpp2m_step_rows_known",
-              "cat": "cfg_linear_step_rows_cat"}     # in ops
+              "cat": "cfg_linear_step_rows_cat", "staged": "cfg_staged_step_rows"}     # in ops
 
 
 def step_launch(recs, known=None, extras=None):
@@ -62,6 +62,9 @@ def step_launch(recs, known=None, extras=None):
                batcher built with `inpaint_unet=True`): dsc_cfg_linear_step_rows_cat, which carries every sampler, both
                parameterisations and the rescale, and writes the extra input channels behind each latent row;
     "known"  - an inpainting slot steps (some entry of `known` is a record): dsc_cfg_dpmpp2m_step_rows_known;
+    "staged" - a slot is inside a step of a two-call sampler (a STEP record carries a `stage` other than FULL; a batcher built
+               with `two_call=True`): dsc_cfg_staged_step_rows, which takes the intermediate-point buffer; every other slot rides in
+               it as a FULL record with the bits of "linear" (the rescale included);
     "linear" - a slot steps another sampler, a v-prediction model or with a guidance rescale (a STEP record carries c_skip /
                c_out): dsc_cfg_linear_step_rows, whose wrapper picks the rescale entry from the records (records without
                c_skip / c_out are DPM++ 2M's: same bits);
@@ -71,6 +74,8 @@ def step_launch(recs, known=None, extras=None):
         return "cat"
     if known is not None and any(k is not None for k in known):
         return "known"
+    if any(rec["mode"] == ops.ROW_STEP and rec.get("stage", ops.ROW_STAGE_FULL) != ops.ROW_STAGE_FULL for rec in recs):
+        return "staged"
     if any(rec["mode"] == ops.ROW_STEP and "c_skip" in rec for rec in recs):
         return "linear"
     return "rows"
@@ -141,6 +146,8 @@ class _GraphExecutor:
         with torch.cuda.stream(self.stream):
             self.x = torch.zeros((mb,) + self.lat_shape, device=self.device, dtype=self.dtype)
             self.old = torch.zeros_like(self.x)
+            # (two_call) the intermediate point of a two-call sampler's step, a row per slot beside x / old
+            self.mid = torch.zeros_like(self.x) if getattr(batcher, "two_call", False) else None
         self.st = {}
         self._inflight = collections.deque()
         # IP-Adapters: per adapter the layout of one flat row [sum over layers of (k_ip | v_ip), T * C_layer halfs each]
@@ -449,7 +456,13 @@ class _GraphExecutor:
                 elif req.get("generator") is not None:
                     gen = req["generator"]
                     ns = lambda *_: torch.randn(like.shape, generator=gen, device=gen.device, dtype=dt).to(dev)   # noqa: E731
-                table = sampling.step_noise_table(r.family, like, r.sig_dev, eta=eta, noise_sampler=ns)
+                if getattr(r, "stage", None) is not None:            # a two-call sampler: one row per model call
+                    if r.family == "dpmpp_sde":
+                        ns = None if req.get("seed") is None else \
+                            self.pipe.create_noise_sampler(like, r.sig_dev, r.steps, int(req["seed"]))
+                    table = sampling.call_noise_table(r.family, like, r.sig_dev, eta=eta, noise_sampler=ns)
+                else:
+                    table = sampling.step_noise_table(r.family, like, r.sig_dev, eta=eta, noise_sampler=ns)
             r.noise = table.to(device=dev, dtype=dt).contiguous()
 
     def prepare_hires(self, r):
@@ -735,7 +748,8 @@ class _GraphExecutor:
             self.ensure(n_dst)
             st_d = self.st[n_dst]
         eps = self.st[n_src]["eps"] if n_src else None
-        args = (self.x, eps, self.old, n_src, st_d["x_in"], st_d["t"], st_d["sigma"], recs) + \
+        args = (self.x,) + ((self.mid,) if kind == "staged" else ()) + \
+            (eps, self.old, n_src, st_d["x_in"], st_d["t"], st_d["sigma"], recs) + \
             ((known,) if kind == "known" else (extras,) if kind == "cat" else ())
         with torch.cuda.stream(self.stream):
             getattr(ops, _STEP_ROWS[kind])(*args, tadd=st_d["tadd"])

@@ -96,8 +96,35 @@ class _InpaintFreeuEncodeRequest(_InpaintFreeuRequest):
     __slots__ = ("enc",)
 
 
+# a request of a batcher built with `two_call=True` (never together with `inpaint_unet`): the record of its kind plus four lists.
+# When it names a sampler of sampling.TWO_CALL_FAMILY, sig / coeffs / snoise / scal / skipout hold one entry per MODEL CALL of
+# sampling.call_plan, and beside them stand each call's `stage`, `m` (the weight of the intermediate point), `call_step` (its
+# sampler step) and `ends_step`; all four None for a request of the linear family
+class _TwoCallRequest(_Request):
+    __slots__ = ("stage", "m", "call_step", "ends_step")
+
+
+class _FreeuTwoCallRequest(_FreeuRequest):
+    __slots__ = ("stage", "m", "call_step", "ends_step")
+
+
+class _TwoCallEncodeRequest(_TwoCallRequest):
+    __slots__ = ("enc",)
+
+
+class _FreeuTwoCallEncodeRequest(_FreeuTwoCallRequest):
+    __slots__ = ("enc",)
+
+
+_TWO_CALL_RECORD = {_Request: _TwoCallRequest, _FreeuRequest: _FreeuTwoCallRequest}
 _ENCODE_RECORD = {_Request: _EncodeRequest, _InpaintRequest: _InpaintEncodeRequest, _FreeuRequest: _FreeuEncodeRequest,
-                  _InpaintFreeuRequest: _InpaintFreeuEncodeRequest}
+                  _InpaintFreeuRequest: _InpaintFreeuEncodeRequest, _TwoCallRequest: _TwoCallEncodeRequest,
+                  _FreeuTwoCallRequest: _FreeuTwoCallEncodeRequest}
+
+
+def staged(r):
+    """the request runs a two-call sampler: its lists are per model call (only on a batcher built with `two_call=True`)"""
+    return getattr(r, "stage", None) is not None
 
 
 # ---------------------------------------------------------------------- one copy of each small check
@@ -195,6 +222,13 @@ def common_request(b, request):
                          "scalars (setup_unet builds both from the scheduler's prediction_type; do not set the flag alone)")
     sampler = request.get("sampler_name") or "dpmpp_2m"
     family = sampling.linear_family(sampler)
+    if family is None and getattr(b, "two_call", False):
+        family = sampling.two_call_family(sampler)
+        for k in _UNSUPPORTED_KEYS:
+            # (their windows count distinct sigmas seen, which is one per model call only for the one-call samplers)
+            if family is not None and request.get(k) is not None:
+                raise ValueError(f"serve: `{k}` is not served together with the two-call sampler `sampler_name` {family!r} "
+                                 f"(its guidance window counts one model call per step); use txt2img")
     if family is None:
         raise ValueError(f"serve: `sampler_name` {getattr(sampler, '__name__', sampler)!r} has no per-row step (supported: "
                          f"{', '.join(sampling.LINEAR_FAMILY)}; use txt2img)")

@@ -1384,6 +1384,42 @@ def cfg_linear_step_rows_cat(x, eps, old, n_src, x_in, t_buf, sigma_groups, rows
     _step_rows_call(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, tadd, n_dst, n_slots, chw, recs, phi, ex, extra_halfs)
 
 
+ROW_STAGE_FULL, ROW_STAGE_PREDICT, ROW_STAGE_CORRECT = 0, 1, 2
+
+
+class RowStage(ctypes.Structure):
+    """dsc_row_stage (include/dsc_hip.h)"""
+    _fields_ = [("stage", ctypes.c_int), ("m", ctypes.c_float)]
+
+
+def cfg_staged_step_rows(x, mid, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd=None):
+    """cfg_linear_step_rows for the two-call samplers of sampling.TWO_CALL_FAMILY (dsc_cfg_staged_step_rows).  rows:
+    cfg_linear_step_rows' dicts plus `stage` (ROW_STAGE_FULL, the default: the linear step; ROW_STAGE_PREDICT: the update goes to
+    the slot's row of `mid` and into x_in, x stays; ROW_STAGE_CORRECT: the model ran on `mid` - D is taken from it and `m` * mid
+    joins the update of x) and `m` (default 0).  mid: a dense fp16 tensor of x's shape (None only when every STEP record is FULL).
+    A STEP record's `rescale` is applied inside the same launch, whatever the stage."""
+    what = "cfg_staged_step_rows"
+    phis = _row_rescales(what, rows)
+    n_dst, n_slots, chw, recs = _step_rows_args(what, x, eps, old, n_src, x_in, t_buf, sigma_groups, rows, tadd, linear=True)
+    if mid is not None:
+        _require_gpu(mid)
+        if mid.dtype != torch.float16 or not mid.is_contiguous() or mid.device != x.device or mid.shape != x.shape:
+            raise ValueError(f"{what}: mid must be dense fp16 of x's shape {tuple(x.shape)} on {x.device}")
+        _drop_gn_partials(mid)
+    stages = (RowStage * n_slots)()
+    for i, r in enumerate(rows):
+        stage = r.get("stage", ROW_STAGE_FULL)
+        if isinstance(stage, bool) or not isinstance(stage, int):
+            raise ValueError(f"{what}: rows[{i}]['stage'] must be ROW_STAGE_FULL / _PREDICT / _CORRECT, got {stage!r}")
+        stages[i] = RowStage(stage, float(r.get("m", 0.0)))
+    phi = (ctypes.c_float * n_slots)(*phis) if any(p > 0.0 for p in phis) else None
+    rc = _lib.load_library().dsc_cfg_staged_step_rows(
+        _p(x), _p(mid), _p(eps), _p(old), n_src, _p(x_in), _p(t_buf), _p(sigma_groups), _p(tadd),
+        0 if tadd is None else tadd.shape[1], n_dst, ctypes.cast(recs, ctypes.c_void_p), ctypes.cast(stages, ctypes.c_void_p),
+        None if phi is None else ctypes.cast(phi, ctypes.c_void_p), n_slots, chw, 0, _stream_ptr(x))
+    _lib.check(rc, "dsc_" + what)
+
+
 class RowKnown(ctypes.Structure):
     """dsc_row_known (include/dsc_hip.h)"""
     _fields_ = [("image", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("mask", ctypes.c_void_p),

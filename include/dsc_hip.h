@@ -320,6 +320,43 @@ int dsc_cfg_linear_step_rows_cat(void* x, const void* eps, void* old, int n_src,
                                  const dsc_row_linear* rows /* host */, const float* rescale /* host, n_slots, or NULL */,
                                  const dsc_row_extra* extras /* host, n_slots */, int extra_halfs, int n_slots,
                                  int chw, int dtype, void* stream);
+/*
+ * dsc_cfg_linear_step_rows for the samplers that make TWO model calls per step (modules/sampling.py TWO_CALL_FAMILY: sample_heun,
+ * sample_dpm_2, sample_dpm_2_ancestral, sample_dpmpp_2s_ancestral, sample_dpmpp_sde; host scalars: call_plan).  Their step is two
+ * consecutive transitions of the per-row step: the first leaves x alone and writes the intermediate point the second model call
+ * runs on, the second reads that point back as a third state row.  Same launch contract as dsc_cfg_linear_step_rows, with one more
+ * state buffer - mid: fp16 [slots, chw], 16-byte aligned, the row stride of x - and one more record per slot, passed by value
+ * (8 bytes each; with the 64-byte dsc_row_linear and the phi that is 16 x (64 + 8 + 4) bytes plus the buffers, far below the 4 KB
+ * of kernel arguments).  For a DSC_ROW_STEP slot, all fp32, every intermediate rounded to fp32 before the next operation, fp16
+ * rounding where marked; [K]: the rescale factor of a slot with phi > 0, as in dsc_cfg_linear_step_rows_rescale:
+ *   e = fma(guidance, m_c - m_u, m_u)
+ *   DSC_ROW_STAGE_FULL:    exactly dsc_cfg_linear_step_rows (with phi > 0: _rescale); mid is neither read nor written
+ *   DSC_ROW_STAGE_PREDICT: D  = fp16([K] fma(c_out, e, c_skip * x))                        old = D
+ *                          xm = fp16(noise ? fma(s, noise, fma(a, x, b * D)) : fma(a, x, b * D))
+ *                          mid = xm; x is NOT written; x_in rows {i, n_dst + i} = fp16(xm * c_in_next)
+ *   DSC_ROW_STAGE_CORRECT: xm = mid; D = fp16([K] fma(c_out, e, c_skip * xm))   (the model saw xm: D and the rescale's sums read
+ *                          mid, not x)
+ *                          t3 = fma(m, xm, fma(c, old, fma(a, x, b * D)));  x' = fp16(noise ? fma(s, noise, t3) : t3)
+ *                          x = x'; old = D; x_in rows {i, n_dst + i} = fp16(x' * c_in_next)
+ * JOIN / IDLE slots, t_buf, sigma_groups, tadd and slots i >= n_dst are dsc_cfg_linear_step_rows'.  rescale: NULL or one phi per
+ * slot, dsc_cfg_linear_step_rows_cat's meaning: with some phi > 0 the launch has the rescale entry's single-workgroup fixed-order
+ * fp64 sums (over mid in CORRECT), so a linear-family slot with a rescale and a two-call slot share one launch.  No KNOWN and no
+ * CAT form.  Plain vector stores, no atomics, nothing crosses workgroups.
+ * Status: what dsc_cfg_linear_step_rows checks (chw % 8 != 0: DSC_ERR_UNSUPPORTED) and the phi range; stages == NULL, a STEP slot
+ * whose stage is none of the three, or mid == NULL while a STEP slot is PREDICT / CORRECT: DSC_ERR_BAD_ARG; a misaligned mid there:
+ * DSC_ERR_UNSUPPORTED.  All checks run before the launch: nothing is written on failure.
+ */
+#define DSC_ROW_STAGE_FULL 0
+#define DSC_ROW_STAGE_PREDICT 1
+#define DSC_ROW_STAGE_CORRECT 2
+typedef struct {
+    int   stage;            /* DSC_ROW_STAGE_FULL, _PREDICT, _CORRECT (read for STEP slots) */
+    float m;                /* CORRECT: the weight of mid in x' */
+} dsc_row_stage;
+int dsc_cfg_staged_step_rows(void* x, void* mid, const void* eps, void* old, int n_src, void* x_in, float* t_buf,
+                             float* sigma_groups, void* tadd, int tadd_halfs, int n_dst,
+                             const dsc_row_linear* rows /* host */, const dsc_row_stage* stages /* host, n_slots */,
+                             const float* rescale /* host, n_slots, or NULL */, int n_slots, int chw, int dtype, void* stream);
 /* out = a*x + b*denoised + c*old  (old may be NULL when c == 0): the sampler update alone, for callers that keep
  * the reference's `sampler(model_fn, x, sigmas=...)` control flow.  n elements, n % 4 == 0 (8-byte accesses unless n % 8 == 0). */
 int dsc_dpmpp2m_update(const void* x, const void* denoised, const void* old, float a, float b, float c,

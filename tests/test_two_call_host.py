@@ -1,0 +1,279 @@
+"""The two-call sampler family on the host: `sampling.call_plan` run by a small fp64 interpreter of the three stages against
+the tree's own `sample_*` functions (analytic denoiser, replayed noise), the plan's noise-sampler queries and noise table against
+what the samplers ask and draw, and the serving scheduler on a fake executor: stages per transition, the launch choice, previews
+counted in sampler steps, and every refusal."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from inputs import FakeTokenizer
+from serving_fakes import RecordingExec
+
+from diffusionspatialcontrol_amd import ops
+from diffusionspatialcontrol_amd.modules import sampling
+from diffusionspatialcontrol_amd.modules.serving import ServingBatcher, step_launch
+
+FUNCS = {"heun": sampling.sample_heun, "dpm_2": sampling.sample_dpm_2, "dpm_2_ancestral": sampling.sample_dpm_2_ancestral,
+         "dpmpp_2s_ancestral": sampling.sample_dpmpp_2s_ancestral, "dpmpp_sde": sampling.sample_dpmpp_sde}
+NOISY = ("dpm_2_ancestral", "dpmpp_2s_ancestral", "dpmpp_sde")
+VARIANTS = [("heun", {}), ("dpm_2", {})] + \
+    [(name, {"eta": eta, "s_noise": 0.9}) for name in NOISY for eta in (0.0, 0.7, 1.0)] + \
+    [("dpmpp_sde", {"eta": 1.0, "s_noise": 0.9, "r": 0.3})]
+F, P, C = sampling.STAGE_FULL, sampling.STAGE_PREDICT, sampling.STAGE_CORRECT
+
+
+def _sigmas(kind, steps):
+    fn = sampling.get_sigmas_karras if kind == "karras" else sampling.get_sigmas_exponential
+    return fn(steps, 0.0292, 14.6146).double()
+
+
+def _denoiser(x, sigma):
+    """D(x, sigma) = x / (1 + sigma^2): the posterior mean of unit-variance data"""
+    return x / (1 + sigma.reshape(-1, 1, 1, 1) ** 2)
+
+
+def _interpret(x, plan, noise):
+    """the three stages as the kernel runs them: FULL and CORRECT write x, PREDICT writes mid; the model sees mid in CORRECT"""
+    mid, old = torch.zeros_like(x), torch.zeros_like(x)
+    for k, call in enumerate(plan):
+        a, m, b, c, s = call.coeffs
+        seen = mid if call.stage == C else x
+        d = _denoiser(seen, torch.tensor([call.sigma], dtype=torch.float64))
+        out = a * x + m * mid + b * d + c * old + (s * noise[k] if s != 0.0 else 0.0)
+        if call.stage == P:
+            mid = out
+        else:
+            x = out
+        old = d
+    return x
+
+
+@pytest.mark.parametrize("steps", [2, 3, 9])
+@pytest.mark.parametrize("kind", ["karras", "exponential"])
+@pytest.mark.parametrize("name, kw", VARIANTS)
+def test_plan_reproduces_the_samplers(name, kw, kind, steps):
+    sigmas = _sigmas(kind, steps)
+    g = torch.Generator().manual_seed(steps)
+    x0 = torch.randn(2, 4, 8, 8, generator=g, dtype=torch.float64) * sigmas[0]
+    plan = sampling.call_plan(name, sigmas.tolist(), **kw)
+    noise = torch.randn(len(plan), 2, 4, 8, 8, generator=g, dtype=torch.float64)
+    # the sampler's j-th query gets the row of the j-th plan entry that names a query
+    rows = iter([k for k, call in enumerate(plan) if call.query is not None])
+    asked = []
+
+    def replay(s0, s1):
+        asked.append((float(s0), float(s1)))
+        return noise[next(rows)]
+
+    args = dict(kw)
+    if name in NOISY:
+        args["noise_sampler"] = replay
+    else:
+        assert not kw
+    ref = FUNCS[name](_denoiser, x0.clone(), sigmas, **args)
+    got = _interpret(x0.clone(), plan, noise)
+    err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
+    assert err <= 1e-12 * scale, (name, kw, kind, steps, err, scale)
+    # the queries the plan names are the ones the sampler made, in order
+    assert asked == [call.query for call in plan if call.query is not None]
+    assert next(rows, None) is None
+    # shape of the plan: (PREDICT, CORRECT) per step, one FULL entry for the step to sigma = 0, steps in order
+    assert [call.stage for call in plan] == [P, C] * (steps - 1) + [F]
+    assert [call.step for call in plan] == [i // 2 for i in range(2 * steps - 1)]
+    assert [call.ends_step for call in plan] == [call.stage != P for call in plan]
+    last = plan[-1]
+    assert last.coeffs == (0.0, 0.0, 1.0, 0.0, 0.0) and last.query is None and last.sigma == sigmas[-2].item()
+    assert all(call.coeffs[1] == 0.0 and call.coeffs[3] == 0.0 for call in plan if call.stage == P)
+    for k, call in enumerate(plan[:-1]):                             # PREDICT runs at the step's sigma, CORRECT strictly below it
+        if call.stage == P:
+            assert call.sigma == sigmas[call.step].item() and 0.0 < plan[k + 1].sigma < call.sigma
+    if name in NOISY and kw["eta"] == 0.0:
+        assert all(call.coeffs[4] == 0.0 for call in plan)
+
+
+def test_eta_zero_reductions_and_names():
+    sig = _sigmas("karras", 9).tolist()
+    plain = sampling.call_plan("dpm_2", sig)
+    anc = sampling.call_plan("dpm_2_ancestral", sig, eta=0.0)
+    assert [(c.stage, c.sigma, c.coeffs, c.step, c.ends_step) for c in anc] == \
+        [(c.stage, c.sigma, c.coeffs, c.step, c.ends_step) for c in plain]
+    assert all(c.query is None for c in plain) and sum(c.query is not None for c in anc) == 8   # (it still asks, and multiplies by 0)
+    assert sampling.TWO_CALL_FAMILY == ("heun", "dpm_2", "dpm_2_ancestral", "dpmpp_2s_ancestral", "dpmpp_sde")
+    for fam, fn in FUNCS.items():
+        assert sampling.two_call_family(fn) == fam == sampling.two_call_family(fam) == sampling.two_call_family("sample_" + fam)
+        assert sampling.linear_family(fn) is None                    # the linear family's own rule is unchanged
+    for other in (sampling.sample_euler, sampling.sample_lms, sampling.sample_dpmpp_3m_sde, "sample_heunpp2", "nonsense",
+                  functools.partial(sampling.sample_heun, s_churn=1.0), lambda *a, **k: None):
+        assert sampling.two_call_family(other) is None
+    for name in ("sample_euler", "sample_lms", "sample_heunpp2", "sample_dpmpp_3m_sde"):
+        with pytest.raises(NotImplementedError, match=name):
+            sampling.call_plan(name, [2.0, 1.0, 0.0])
+        with pytest.raises(NotImplementedError, match=name):
+            sampling.call_noise_table(name, torch.zeros(1, 4, 2, 2), [2.0, 1.0, 0.0])
+
+
+def test_noise_table_is_what_the_samplers_draw():
+    """seeded CPU generator: the table's non-zero rows are the draws the sampler itself makes in protocol mode, in its order
+    (default noise sampler for the ancestral samplers, the Brownian tree for DPM++ SDE); the ODE samplers have no table"""
+    sigmas = _sigmas("karras", 6).float()
+    x = torch.zeros(2, 4, 4, 4)
+    for name in NOISY:
+        seen = []
+
+        def spy(inner):
+            def call(s0, s1):
+                seen.append(inner(s0, s1))
+                return seen[-1]
+            return call
+        torch.manual_seed(11)
+        inner = sampling.BrownianTreeNoiseSampler(x, sigmas[-2], sigmas[0]) if name == "dpmpp_sde" \
+            else sampling.default_noise_sampler(x)
+        FUNCS[name](lambda v, s: v * 0.5, x.clone(), sigmas, noise_sampler=spy(inner))
+        torch.manual_seed(11)
+        tab = sampling.call_noise_table(name, x, sigmas)
+        plan = sampling.call_plan(name, sigmas.double().tolist())
+        drawn = [k for k, call in enumerate(plan) if call.query is not None]
+        assert tuple(tab.shape) == (11, 2, 4, 4, 4) and len(seen) == len(drawn) == (10 if name == "dpmpp_sde" else 5)
+        assert torch.equal(tab[drawn], torch.stack(seen))
+        assert not tab[[k for k in range(11) if k not in drawn]].any()
+    assert sampling.call_noise_table("heun", x, sigmas) is None and sampling.call_noise_table("dpm_2", x, sigmas) is None
+    # a seeded Brownian sampler (sampler_opt brownian_noise) rides in the same way
+    ns = sampling.BrownianTreeNoiseSampler(x, sigmas[-2], sigmas[0], seed=5)
+    ref = sampling.BrownianTreeNoiseSampler(x, sigmas[-2], sigmas[0], seed=5)
+    tab = sampling.call_noise_table("dpmpp_2s_ancestral", x, sigmas, noise_sampler=ns)
+    assert torch.equal(tab[5], [ref(sigmas[i], sigmas[i + 1]) for i in range(3)][2])
+
+
+# ----------------------------------------------------------------------------- serving host logic
+S = 77
+
+
+class PreviewExec(RecordingExec):
+    """RecordingExec plus the preview interface: a handle is ready at once, a thumbnail is a 2 x 2 image of its slot number"""
+
+    def __init__(self):
+        super().__init__()
+        self.preview_calls = []
+
+    def ensure_preview(self):
+        pass
+
+    def preview(self, slots):
+        self.preview_calls.append(list(slots))
+        return {"slots": list(slots)}
+
+    def preview_ready(self, h):
+        return True
+
+    def preview_image(self, h, j):
+        return np.full((2, 2, 3), h["slots"][j], dtype=np.uint8)
+
+
+@pytest.fixture(scope="module")
+def pipe():
+    from diffusionspatialcontrol_amd.modules.model_k_diffusion import SD15Scheduler, StableDiffusionPipeline
+    from diffusionspatialcontrol_amd.modules.u_net_condition_modify import UNet2DConditionModel, UNetConfig
+    torch.manual_seed(0)
+    unet = UNet2DConditionModel(UNetConfig.tiny()).half()
+    return StableDiffusionPipeline(None, None, FakeTokenizer(), unet, SD15Scheduler())
+
+
+def _req(name, steps=4, **kw):
+    emb = torch.randn(2, S, 64, generator=torch.Generator().manual_seed(len(name)))
+    r = {"name": name, "prompt_embeds": emb[1:2].half(), "negative_prompt_embeds": emb[0:1].half(),
+         "num_inference_steps": steps, "guidance_scale": 7.5, "sampler_opt": {"scheduler": "karras"},
+         "latents": torch.zeros(1, 4, 16, 16).half()}
+    r.update(kw)
+    return r
+
+
+def _stages(call):
+    """{request name: stage} of the STEP records of one recorded transition"""
+    return {rec["req"].req["name"]: rec.get("stage") for rec in call[3] if rec["mode"] == ops.ROW_STEP}
+
+
+def test_heun_takes_two_transitions_per_step_beside_dpmpp_2m(pipe):
+    ex = PreviewExec()
+    b = ServingBatcher(pipe, 128, 128, executor=ex, max_batch=2, buckets=(1, 2), previews=True, two_call=True)
+    log = []
+    fh = b.submit(_req("H", steps=3, sampler_name="sample_heun", preview_every=1,
+                       on_preview=lambda step, steps, image: log.append((step, steps))))
+    fm = b.submit(_req("M", steps=7))
+    b.step()                                                          # both join
+    assert ex.calls[0][0] == "rows" and b.stats()["staged_transitions"] == 0
+    h = b._slots[0]
+    assert h.stage == [sampling.STAGE_PREDICT, sampling.STAGE_CORRECT] * 2 + [sampling.STAGE_FULL] and len(h.coeffs) == 5
+    assert h.call_step == [0, 0, 1, 1, 2] and h.ends_step == [False, True, False, True, True] and len(h.sig) == 6
+    for _ in range(5):
+        assert b.step()
+    assert fh.done() and not fm.done() and b._slots[0] is None
+    # five transitions with H's stages P, C, P, C, F; M advances once per transition and carries no stage
+    calls = ex.calls[1:6]
+    assert [_stages(c) for c in calls] == [{"H": st, "M": None} for st in (P, C, P, C, F)]
+    assert [c[0] for c in calls] == ["staged"] * 4 + ["linear"]       # (a FULL record is the linear launch's)
+    assert [rec["step"] for c in calls for rec in c[3] if rec["mode"] == ops.ROW_STEP and rec["req"].req["name"] == "M"] == [0, 1, 2, 3, 4]
+    sched = pipe._schedule(3, {"scheduler": "karras"}, torch.device("cpu"), torch.float16)
+    plan = sampling.call_plan("heun", getattr(sched, "_dsc_host", None) or sched.float().tolist())
+    for c, call in zip(calls, plan):
+        rec = next(rec for rec in c[3] if rec["mode"] == ops.ROW_STEP and rec["req"].req["name"] == "H")
+        a, m, bb, cc, s = call.coeffs
+        assert (rec["a"], rec["m"], rec["b"], rec["c"], rec["s"]) == (a, m, bb, cc, s) and rec["noise"] is None
+        assert rec["c_skip"] == 1.0 and rec["c_out"] == -rec["sigma"]
+        assert rec["sigma"] == float(torch.tensor(call.sigma, dtype=torch.float64).half())  # the sigma the call's model ran at, in the model dtype
+    # the coming call's scalars: the CORRECT call's sigma after a PREDICT, the next step's after a CORRECT
+    first = next(rec for rec in calls[0][3] if rec["mode"] == ops.ROW_STEP and rec["req"].req["name"] == "H")
+    assert first["sigma_next"] == h.sig[1] and first["temb_row"] == ("temb", "H", 1)
+    assert step_launch(calls[0][3]) == "staged" and step_launch(calls[4][3]) == "linear"
+    b.run_until_idle()
+    s = b.stats()
+    assert fm.done() and s["staged_transitions"] == 4 and s["leaves"] == 2 and s["steps"] == 7
+    assert log == [(1, 3), (2, 3)] and ex.preview_calls == [[0], [0]]  # after the calls that end steps 1 and 2, not the last
+
+
+def test_noise_rows_follow_the_calls(pipe):
+    b = ServingBatcher(pipe, 128, 128, executor=RecordingExec(), max_batch=2, buckets=(1, 2), two_call=True)
+    ex = b.exec
+    f = b.submit(_req("S", steps=2, sampler_name="sample_dpmpp_sde", eta=1.0, s_noise=0.9, seed=3))
+    assert ex.noise_tables == {"S": 1.0}
+    b.run_until_idle()
+    assert f.done()
+    recs = [rec for c in ex.calls for rec in c[3] if rec["mode"] == ops.ROW_STEP]
+    assert [rec["stage"] for rec in recs] == [P, C, F]
+    assert [rec["noise"] for rec in recs] == [("noise", "S", 0), ("noise", "S", 1), None] and recs[0]["s"] > 0 and recs[1]["s"] > 0
+    # img2img: the plan is made from the truncated schedule
+    g = b.submit(_req("I", steps=4, sampler_name="dpm_2_ancestral", image=torch.zeros(1, 4, 16, 16), strength=0.5))
+    b.run_until_idle()
+    assert g.done() and len(g.result(timeout=0)[1]) == 1 + 3          # the join, then P, C, F of 2 steps
+    # a step_noise table has one row per model call
+    with pytest.raises(ValueError, match="step_noise"):
+        b.submit(_req("T", steps=2, sampler_name="sample_dpmpp_sde", step_noise=torch.zeros(2, 1, 4, 16, 16)))
+    b.submit(_req("T", steps=2, sampler_name="sample_dpmpp_sde", step_noise=torch.zeros(3, 1, 4, 16, 16)))
+
+
+def test_refusals_and_the_unflagged_batcher(pipe):
+    plain = ServingBatcher(pipe, 128, 128, executor=RecordingExec())
+    assert not plain.two_call and "staged_transitions" not in plain.stats()
+    for name in ("sample_heun", "dpm_2", "sample_dpm_2_ancestral", "sample_dpmpp_2s_ancestral", "sample_dpmpp_sde"):
+        with pytest.raises(ValueError, match="sampler_name.*no per-row step"):
+            plain.submit(_req("A", sampler_name=name))
+    b = ServingBatcher(pipe, 128, 128, executor=RecordingExec(), two_call=True)
+    assert b.two_call and b.stats()["staged_transitions"] == 0
+    for name in ("sample_lms", "sample_heunpp2", "sample_dpmpp_3m_sde", functools.partial(sampling.sample_heun, s_churn=1.0)):
+        with pytest.raises(ValueError, match="sampler_name"):
+            b.submit(_req("A", sampler_name=name))
+    with pytest.raises(ValueError, match="control_img"):
+        b.submit(_req("A", sampler_name="sample_heun", control_img=torch.zeros(1, 3, 128, 128)))
+    with pytest.raises(ValueError, match="image_t2i_adapter"):
+        b.submit(_req("A", sampler_name="sample_heun", image_t2i_adapter=torch.zeros(1, 3, 128, 128)))
+    with pytest.raises(ValueError, match="mask_image"):
+        b.submit(_req("A", sampler_name="sample_heun", image=torch.zeros(1, 4, 16, 16), mask_image=torch.zeros(1, 1, 128, 128)))
+    with pytest.raises(ValueError, match="two_call.*inpaint_unet"):
+        ServingBatcher(pipe, 128, 128, executor=RecordingExec(), two_call=True, inpaint_unet=True)
+    with pytest.raises(ValueError, match="two_call"):
+        pipe.serve_hires(128, 128, 1.5, two_call=True)
+    # the linear family is served as ever by the flagged batcher, on the launches it had
+    f = b.submit(_req("B", steps=2))
+    b.run_until_idle()
+    assert f.done() and b.stats()["staged_transitions"] == 0 and {c[0] for c in b.exec.calls} == {"rows"}

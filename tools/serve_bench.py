@@ -19,7 +19,11 @@ latents, as tests/test_full_size_parity_gpu.py::_requests builds them):
               images/s and sampler steps/s beside the same figures of the all-txt2img batch in the same process
   sampler     (--sampler NAME, one of sampling.LINEAR_FAMILY: this leg only) 8 slots kept full, every other request running NAME
               (its step goes through dsc_cfg_linear_step_rows, with a noise table per request) beside the all-DPM++ 2M batch in
-              the same process, three alternating runs; then one-at-a-time txt2img with NAME, fused against protocol mode
+              the same process, three alternating runs; then one-at-a-time txt2img with NAME, fused against protocol mode.
+              NAME of sampling.TWO_CALL_FAMILY (sample_heun, sample_dpm_2, sample_dpm_2_ancestral, sample_dpmpp_2s_ancestral,
+              sample_dpmpp_sde) builds the batcher with two_call=True (its steps go through dsc_cfg_staged_step_rows, two model
+              calls each: the leg also prints model calls/s); --two-call alone is that batcher with no such request, and
+              --two-call --kernels only the device time of the per-row sampler entries, the staged one included
   rescale     (--guidance-rescale PHI, alone or with --sampler: this leg only) the same leg with `guidance_rescale` = PHI on
               every other request (its step goes through dsc_cfg_linear_step_rows_rescale; DPM++ 2M unless --sampler names
               another), and one-at-a-time txt2img with PHI, fused against protocol mode
@@ -182,9 +186,10 @@ def graph_launch_us(fn, launches=100, replays=3):
 
 
 def step_rows_kernel_us(rounds=3):
-    """device microseconds per launch of the five per-row sampler entries on 8 STEP slots of a 4 x 64 x 64 latent, `rounds`
+    """device microseconds per launch of the per-row sampler entries on 8 STEP slots of a 4 x 64 x 64 latent, `rounds`
     alternating figures each -> (slots, extra_halfs, {entry: [us, ...]}).  One slot of the rescale entry has phi > 0 (its row
-    belongs to one workgroup), one slot of the known entry a known region with both blends on"""
+    belongs to one workgroup), one slot of the known entry a known region with both blends on; the staged entry runs once with
+    every slot PREDICT and once with every slot CORRECT"""
     from diffusionspatialcontrol_amd import ops
     n, chw, eh = 8, 4 * 64 * 64, 5 * 64 * 64
     h = lambda *shape: torch.randn(*shape, device="cuda").half()      # noqa: E731
@@ -197,11 +202,16 @@ def step_rows_kernel_us(rounds=3):
     resc = [dict(recs[0], rescale=0.7)] + recs[1:]
     known = [{"image": h(chw), "noise": h(chw), "mask": (torch.rand(chw, device="cuda") < 0.5).half(), "blend_now": True,
               "blend_next": True}] + [None] * (n - 1)
+    mid = h(n, chw)
+    pred = [dict(r, stage=ops.ROW_STAGE_PREDICT) for r in recs]
+    corr = [dict(r, stage=ops.ROW_STAGE_CORRECT, m=0.0) for r in recs]
     entries = {"cfg_dpmpp2m_step_rows": lambda: ops.cfg_dpmpp2m_step_rows(x, eps, old, n, x4, t, sg, recs),
                "cfg_dpmpp2m_step_rows_known": lambda: ops.cfg_dpmpp2m_step_rows_known(x, eps, old, n, x4, t, sg, recs, known),
                "cfg_linear_step_rows": lambda: ops.cfg_linear_step_rows(x, eps, old, n, x4, t, sg, recs),
                "cfg_linear_step_rows_rescale": lambda: ops.cfg_linear_step_rows_rescale(x, eps, old, n, x4, t, sg, resc),
-               "cfg_linear_step_rows_cat": lambda: ops.cfg_linear_step_rows_cat(x, eps, old, n, x9, t, sg, recs, ex)}
+               "cfg_linear_step_rows_cat": lambda: ops.cfg_linear_step_rows_cat(x, eps, old, n, x9, t, sg, recs, ex),
+               "cfg_staged_step_rows_predict": lambda: ops.cfg_staged_step_rows(x, mid, eps, old, n, x4, t, sg, pred),
+               "cfg_staged_step_rows_correct": lambda: ops.cfg_staged_step_rows(x, mid, eps, old, n, x4, t, sg, corr)}
     us = {name: [] for name in entries}
     for _ in range(rounds):
         for name, fn in entries.items():
@@ -310,7 +320,13 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--mix", action="store_true", help="only the mixed txt2img / img2img / inpainting leg")
     ap.add_argument("--sampler", default=None, help="only the saturated leg with every other request on this sampler "
-                                                    "(sample_euler, sample_euler_ancestral, sample_dpmpp_2m_sde, sample_lcm)")
+                                                    "(sample_euler, sample_euler_ancestral, sample_dpmpp_2m_sde, sample_lcm; a "
+                                                    "two-call sampler - sample_heun, sample_dpm_2, sample_dpm_2_ancestral, "
+                                                    "sample_dpmpp_2s_ancestral, sample_dpmpp_sde - builds the batcher with two_call=True)")
+    ap.add_argument("--two-call", action="store_true",
+                    help="the saturated sampler leg on a batcher built with two_call=True (alone: no request names a two-call "
+                         "sampler); --kernels: only the device time of the per-row sampler entries, the staged one included")
+    ap.add_argument("--kernels", action="store_true", help="with --two-call: only the per-row sampler entries' device time")
     ap.add_argument("--guidance-rescale", type=float, default=None, metavar="PHI",
                     help="only the saturated leg with guidance_rescale = PHI (in (0, 1]) on every other request")
     ap.add_argument("--hires", type=float, default=None, metavar="X",
@@ -779,8 +795,17 @@ def main():
         emit(leg="stats", **pair.stats())
         return
 
-    if a.sampler or a.guidance_rescale is not None:
-        b = pipe.serve(512, 512, max_batch=8, slot=0).warm()
+    if a.two_call and a.kernels:
+        n, eh, us = step_rows_kernel_us()
+        emit(leg="step_rows_kernels", slots=n, latent="4x64x64", device_us_per_launch=us,
+             note="a captured graph of 100 launches per figure, alternating")
+        return
+
+    if a.sampler or a.guidance_rescale is not None or a.two_call:
+        from diffusionspatialcontrol_amd.modules import sampling
+        staged = a.sampler is not None and sampling.two_call_family(a.sampler) is not None
+        flag = {"two_call": True} if staged or a.two_call else {}
+        b = pipe.serve(512, 512, max_batch=8, slot=0, **flag).warm()
         keys = {} if a.guidance_rescale is None else {"guidance_rescale": a.guidance_rescale}
         if a.sampler:
             keys["sampler_name"] = a.sampler
@@ -794,8 +819,10 @@ def main():
         emit(leg="sampler" if a.guidance_rescale is None else "rescale", sampler=a.sampler, guidance_rescale=a.guidance_rescale,
              requests=len(reqs), steps=25, mix="every other request on the named sampler / with the rescale",
              dpmpp_2m_img_s=[round(t[0], 2) for t, _ in runs], mixed_img_s=[round(m[0], 2) for _, m in runs],
+             dpmpp_2m_calls_s=[round(t[1], 2) for t, _ in runs], mixed_calls_s=[round(m[1], 2) for _, m in runs],
+             two_call=bool(flag), staged_transitions=b.stats().get("staged_transitions"),
              linear_transitions=b.stats()["linear_transitions"], captures_after_warm=b.stats()["captures_after_warm"])
-        from diffusionspatialcontrol_amd.modules import sampling, samplers_extra_k_diffusion as sx
+        from diffusionspatialcontrol_amd.modules import samplers_extra_k_diffusion as sx
         fn = sx.sample_lcm if a.sampler.endswith("lcm") else getattr(sampling, a.sampler)
         r = reqs[0]
         one = dict(height=512, width=512, sampler_name=fn, latents=r["latents"], region_map_state=r["region_map_state"],
@@ -803,6 +830,8 @@ def main():
                    text_input_ids=r["text_input_ids"], output_type="latent", **kw25)
         if a.guidance_rescale is not None:
             one["guidance_rescale"] = a.guidance_rescale
+        if staged:
+            one["two_call"] = True
         rate = {}
         for mode in (True, False):
             pipe.txt2img(None, fused=mode, **one)
