@@ -146,6 +146,8 @@ _SIGNATURES = {
                            [ctypes.POINTER(ctypes.c_float), ctypes.c_int, _vp, _vp]),
     "dsc_image_prepare": (ctypes.c_int, [ctypes.POINTER(ImagePrepareRow)] + [ctypes.c_int] * 3 + [_vp]),
     "dsc_latent_start_rows": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(LatentStartRow)] + [ctypes.c_int] * 3 + [_vp]),
+    "dsc_causal_attn_f16": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 4 + [_i64p] * 4 + [ctypes.c_float, ctypes.c_int, _vp]),
+    "dsc_act_f16": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
 }
 
 

@@ -155,11 +155,19 @@ def pad_tokens_and_weights(tokens, weights, max_length, bos, eos, pad, no_boseos
     return tokens, weights
 
 
+def final_layer_norm_of(enc):
+    """the text encoder's final LayerNorm for the `clip_skip` branches: `enc.text_model.final_layer_norm` where the encoder has
+    a `text_model` (transformers 4.x, diffusers-era wrappers, modules/clip_text.py), else `enc.final_layer_norm` (transformers 5.x,
+    whose CLIPTextModel holds `embeddings`, `encoder` and `final_layer_norm` itself)"""
+    inner = getattr(enc, "text_model", None)
+    return (enc if inner is None else inner).final_layer_norm
+
+
 def clip_skip_prompt(pipe, text_input, clip_skip=None):
     """reference :186-210: last hidden state, or the hidden state `clip_skip` layers from the end + the final LayerNorm"""
     if clip_skip is not None and clip_skip > 1:
         hidden = pipe.text_encoder(text_input, attention_mask=None, output_hidden_states=True)[-1][-clip_skip]
-        return pipe.text_encoder.text_model.final_layer_norm(hidden)
+        return final_layer_norm_of(pipe.text_encoder)(hidden)
     return pipe.text_encoder(text_input, attention_mask=None)[0]
 
 
@@ -279,7 +287,7 @@ def encode_short_prompt(pipe, prompt, device, num_images_per_prompt, do_classifi
     def encode(ids):
         if clip_skip is not None and clip_skip > 1:
             hidden = pipe.text_encoder(ids.to(device), attention_mask=None, output_hidden_states=True)[-1][-clip_skip]
-            return pipe.text_encoder.text_model.final_layer_norm(hidden)
+            return final_layer_norm_of(pipe.text_encoder)(hidden)
         return pipe.text_encoder(ids.to(device), attention_mask=None)[0]
 
     if prompt_embeds is None:

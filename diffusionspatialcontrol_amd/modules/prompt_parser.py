@@ -244,5 +244,6 @@ class FrozenCLIPEmbedderWithCustomWords(FrozenCLIPEmbedderWithCustomWordsBase):
         out = self.text_encoder(tokens.to(self.text_encoder.device), output_hidden_states=True)
         skip = self.CLIP_stop_at_last_layers
         if skip is not None and skip > 1:
-            return self.text_encoder.text_model.final_layer_norm(out.hidden_states[-skip])
+            from .encoder_prompt_modify import final_layer_norm_of      # (that module imports this one)
+            return final_layer_norm_of(self.text_encoder)(out.hidden_states[-skip])
         return out.last_hidden_state

@@ -341,6 +341,54 @@ def self_attention(q, k, v, scale=None, out=None):
     return out
 
 
+CAUSAL_ATTN_HEAD_DIM = 64      # DSC_CAUSAL_ATTN_HEAD_DIM (include/dsc_hip.h): CLIP-L, OpenCLIP-H and bigG
+CAUSAL_ATTN_MAX_TOKENS = 80    # DSC_CAUSAL_ATTN_MAX_TOKENS: five 16-row MFMA tiles (one 77-token chunk)
+ACT_KINDS = {"quick_gelu": 0, "gelu": 1}    # DSC_ACT_QUICK_GELU / DSC_ACT_GELU_ERF
+
+
+def causal_attn_takes(dtype, S, d):
+    """dsc_causal_attn_f16's limits (stated in include/dsc_hip.h): fp16, head dim 64, 1..80 tokens"""
+    return dtype == torch.float16 and d == CAUSAL_ATTN_HEAD_DIM and 1 <= S <= CAUSAL_ATTN_MAX_TOKENS
+
+
+def causal_attn(q, k, v, scale=None, into=None):
+    """softmax_{j <= i}(q_i.k_j * scale) . v for q / k / v [B, S, H, d] (strided views allowed, e.g. of one fused QKV
+    projection) -> [B, S, H, d] (dsc_causal_attn_f16: the CLIP text encoder's attention).  `into`: the destination, a
+    [B, S, H, d] fp16 tensor or strided view (unit inner stride, strides in 8s); a new contiguous tensor by default.  (Not
+    `out`: tests/test_output_paths.py keeps a closed table of the ops with that parameter; the contract it checks - sums a
+    producer attached to the destination are dropped - holds here and is checked in tests/test_clip_text_gpu.py.)"""
+    _require_gpu(q, k, v)
+    if q.dtype != torch.float16 or k.dtype != torch.float16 or v.dtype != torch.float16:
+        raise TypeError("causal_attn: fp16 only")
+    qs, (B, H, S, d) = _blhd_strides(q, "blc")
+    ks, kshape = _blhd_strides(k, "blc")
+    vs, vshape = _blhd_strides(v, "blc")
+    if kshape != (B, H, S, d) or vshape != (B, H, S, d):
+        raise ValueError(f"causal_attn: q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} must have one shape")
+    if into is None:
+        into = torch.empty((B, S, H, d), dtype=q.dtype, device=q.device)
+    _check_out(into, (B, S, H, d), q, "causal_attn")
+    _drop_gn_partials(into)
+    os_, _ = _blhd_strides(into, "blc")
+    rc = _lib.load_library().dsc_causal_attn_f16(_p(q), _p(k), _p(v), _p(into), B, H, S, d, _i64x3(*qs), _i64x3(*ks), _i64x3(*vs),
+                                                 _i64x3(*os_), float(scale) if scale else 0.0, 0, _stream_ptr(q))
+    _lib.check(rc, "dsc_causal_attn_f16")
+    return into
+
+
+def act_(x, kind):
+    """x <- quick_gelu(x) / gelu(x) in place (dsc_act_f16); x fp16 contiguous with numel % 8 == 0; kind: a key of ACT_KINDS"""
+    _require_gpu(x)
+    if kind not in ACT_KINDS:
+        raise ValueError(f"act_: kind must be one of {sorted(ACT_KINDS)}")
+    if x.dtype != torch.float16 or not x.is_contiguous():
+        raise TypeError("act_: a contiguous fp16 tensor")
+    _drop_gn_partials(x)
+    rc = _lib.load_library().dsc_act_f16(_p(x), x.numel(), ACT_KINDS[kind], 0, _stream_ptr(x))
+    _lib.check(rc, "dsc_act_f16")
+    return x
+
+
 IP_MAX_TOKENS = 16         # DSC_IP_MAX_TOKENS (include/dsc_hip.h): the image tokens of one adapter are one MFMA tile
 
 

@@ -948,6 +948,40 @@ typedef struct {
 } dsc_latent_start_row;
 int dsc_latent_start_rows(const void* moments, int m, const dsc_latent_start_row* rows, int n, int h, int w, void* stream);
 
+/*
+ * The CLIP text encoder's two own kernels (modules/clip_text.py; the encoder the reference loads from transformers and calls
+ * from modules/encoder_prompt_modify.py and modules/prompt_parser.py).  Its GEMMs and LayerNorms are dsc_linear_f16 and
+ * dsc_add_layernorm.
+ *
+ * dsc_causal_attn_f16: causal self-attention over one text chunk,
+ *   out[b,i,h,:] = softmax_{j<=i}(scale * q[b,i,h,:].k[b,j,h,:]) . v[b,j,h,:]        (transformers CLIPAttention with the causal mask)
+ * Addressing as dsc_self_attn_fwd: q / k / v / out are [B, S, H, d] through {sb, ss, sh} element strides, so q, k and v may be
+ * views of one fused [B, S, 3 H d] projection and out a view of a wider buffer.  scale <= 0 means 1/sqrt(d).
+ * One workgroup per (b, h) keeps the head's K and V in LDS; scores stay in MFMA accumulators; maximum and sum in fp32 over the
+ * whole row; probabilities round to fp16 for the second product and are normalised by the sum of the ROUNDED values (a row with
+ * one key is exactly v).  Rows >= S of any operand are never read, rows >= S of out never written.  No workspace.
+ * Limits - stated here once, mirrored by ops.causal_attn_takes: fp16, d == DSC_CAUSAL_ATTN_HEAD_DIM (CLIP-L, OpenCLIP-H and bigG),
+ * 1 <= S <= DSC_CAUSAL_ATTN_MAX_TOKENS (five 16-row MFMA tiles), strides % 8 == 0, 16-byte aligned pointers, B * H < 2^31:
+ * otherwise DSC_ERR_UNSUPPORTED.  A null pointer or a non-positive B / H / S / d: DSC_ERR_BAD_ARG.  All checks before the launch.
+ */
+#define DSC_CAUSAL_ATTN_HEAD_DIM   64
+#define DSC_CAUSAL_ATTN_MAX_TOKENS 80
+int dsc_causal_attn_f16(const void* q, const void* k, const void* v, void* out, int B, int H, int S, int d,
+                        const int64_t q_strides[3], const int64_t k_strides[3],
+                        const int64_t v_strides[3], const int64_t o_strides[3],
+                        float scale, int dtype, void* stream);
+/*
+ * dsc_act_f16: x <- act(x) in place over a contiguous fp16 buffer of n elements (between fc1 and fc2 of the encoder's MLP); fp32
+ * arithmetic, one fp16 rounding, 16-byte accesses.
+ *   DSC_ACT_QUICK_GELU: x * sigmoid(1.702 x)                 (hidden_act "quick_gelu": SD1.5's CLIP-L)
+ *   DSC_ACT_GELU_ERF:   x/2 (1 + erf(x / sqrt 2))            (hidden_act "gelu": the OpenCLIP encoders of SD2 and SDXL)
+ * NaN and +-inf come out as the fp32 formula gives them (-inf -> NaN in both).  n % 8 == 0, 16-byte aligned x, fp16, fewer than
+ * 2^31 workgroups of 2048 elements: otherwise DSC_ERR_UNSUPPORTED.  NULL x, n <= 0 or an unknown kind: DSC_ERR_BAD_ARG.
+ */
+#define DSC_ACT_QUICK_GELU 0
+#define DSC_ACT_GELU_ERF   1
+int dsc_act_f16(void* x, int64_t n, int kind, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
