@@ -8,7 +8,15 @@
  *   - every entry is asynchronous on the `stream` it is given (a hipStream_t passed as void*), re-entrant for
  *     distinct streams/workspaces, and safe to capture into a hipGraph (no sync, no malloc, no memcpy);
  *   - the return value is a status: DSC_OK (0) or a negative DSC_ERR_* code; no exception crosses the ABI;
- *   - strides are in ELEMENTS; the innermost (head-dim / channel) stride is always 1.
+ *   - strides are in ELEMENTS; the innermost (head-dim / channel) stride is always 1;
+ *   - a destination with a row / pixel stride (ldo, ldq, ld_probs, o_strides) is written inside [rows] x [row length] only, at any
+ *     stride: the ld - row length elements between rows, and everything before the first and behind the last row, are never
+ *     touched, whatever tile overhangs the last row; dense destinations (partial sums, statistics, head-major K / V,
+ *     channel-major images) are written inside their stated shape only;
+ *   - a strided operand (ldx, ldr, ld_scores, add_ld, ...) is read inside [rows] x [row length] only;
+ *   - a *_workspace_bytes() answer is exact: the entry touches those bytes of `workspace` and no others, at the alignment it
+ *     states; fewer bytes are refused with DSC_ERR_WORKSPACE before any launch (tests/test_guard_bands_gpu.py holds every
+ *     entry of the UNet step to these four).
  *
  * Each entry replaces torch-op sequences issued by the reference's Python; the reference has no FFI of its
  * own (it is pure Python), so the "interface each one replaces" is the Python function cited beside it.
@@ -367,7 +375,8 @@ int dsc_dpmpp2m_update(const void* x, const void* denoised, const void* old, flo
  * (u_net_condition_modify.py:465-470,1304-1306 and diffusers ResnetBlock2D / Transformer2DModel norms; SURVEY.md 2b
  * row 12).  y[b,c,:,:] = act((x - mean_bg) * rstd_bg * gamma[c] + beta[c]), statistics in fp32/fp64 over the
  * (C/groups) * hw elements of group g of row b (biased variance, as torch).  Two launches (partial sums, apply);
- * workspace from dsc_groupnorm_workspace_bytes(), no initialisation needed.  gamma/beta fp16 [C].
+ * workspace from dsc_groupnorm_workspace_bytes() (8-byte aligned; exactly those bytes are touched), no initialisation needed.
+ * gamma/beta fp16 [C].
  * Requirements: C % groups == 0, 16-byte aligned x / y (hw % 8 != 0 takes a scalar-load path).
  */
 size_t dsc_groupnorm_workspace_bytes(int B, int C, int hw, int groups);
@@ -383,6 +392,9 @@ int dsc_groupnorm_silu(const void* x, void* y, const void* gamma, const void* be
  *           `hidden + time_emb_proj(silu(temb))[:, :, None, None]` (diffusers ResnetBlock2D) into the norm that follows
  *   y[b,p,c] = act(((x[b,p,c] + add[b,c]) - mean_bg) * rstd_bg * gamma[c] + beta[c])
  * Every access is a coalesced 16-byte vector; two launches (per-chunk partial sums, apply); bit-reproducible.
+ * Workspace: dsc_groupnorm_nhwc_workspace_bytes(), 8-byte aligned, no initialisation needed.  It is sized by the apply pass's row
+ * chunks; the statistics pass writes at most as many chunk rows (fewer in the slab form), the apply pass reads only what was written,
+ * and nothing outside the returned bytes is touched in any launch form of dsc_debug_set_gn_mode.  y is written inside [B, hw, C] only.
  */
 size_t dsc_groupnorm_nhwc_workspace_bytes(int B, int C, int hw, int groups);
 /* diagnostics: 0 = choose the kernel from the shape, 2 = never a single-launch kernel (statistics + apply), 3 = also allow the
@@ -421,6 +433,9 @@ int dsc_add_bias_residual(const void* a, const void* b, const void* bias, void* 
  * added to a result that has a row per classifier-free-guidance branch (the reference repeats nothing there: its batch is
  * already doubled) - is passed as  ldr = row stride | (R << 32)  with R = its row count: row m adds residual row m % R.
  * R % 128 == 0, M % R == 0; same encoding in dsc_linear_ln_f16 and dsc_linear_gn_f16.  High bits 0: a residual of M rows.
+ * Rows >= M of the last row tile (and the workgroups that pad an XCD-ordered grid) load clamped rows and store nothing: out is
+ * written inside [M] x [N] (GEGLU: [M] x [N/2]) at any ldo >= the row length, x and the residual are read inside [M] x [K] and
+ * [M or R] x [N] at any ldx / ldr.
  */
 int dsc_linear_f16(const void* x, const void* w, const void* bias, const void* residual, void* out,
                    int64_t M, int N, int K, int64_t ldx, int64_t ldr, int64_t ldo, int geglu, int dtype, void* stream);
@@ -451,6 +466,11 @@ int dsc_linear_f16(const void* x, const void* w, const void* bias, const void* r
  * Supported (dsc_conv3x3_supported): Cin % 64 == 0, strides % 8 == 0 (when Cout % 8 == 0), 16-byte aligned pointers; any
  * H, W >= 1 (sides that are not multiples of the 8 x 16 / 8 x 8 pixel tile - 12 x 12, the lowest level of a 768 x 768 generation -
  * cost the overhang's MFMAs, nothing else); anything else returns DSC_ERR_UNSUPPORTED and the caller keeps the library convolution.
+ * Overhanging pixels and the channel padding of a ragged last tile are never stored: out is written inside [stored pixels] x [Cout]
+ * at any ldo >= Cout (channel-major: inside [B, Cout, H W]), x and the residual are read inside [pixels] x [Cin] / [Cout] at any ldx /
+ * ldr.  Cout % 8 != 0 takes any ldo / ldr >= Cout (the rows are then 8-byte aligned at best, as with ldo = Cout).
+ * dsc_conv3x3_workspace_bytes() takes no resample code: it sizes the partial sums by the H x W pixels the taps run over, which covers
+ * the fewer pixels a stride-2 launch stores; a launch touches at most those bytes, and its reduce pass reads only what the split pass wrote.
  */
 /* the resample codes (0: none of them); ops.py mirrors them as CONV_*, tests/test_conv_dispatch_host.py compares the two */
 #define DSC_CONV_UPSAMPLE2X 1
@@ -626,7 +646,9 @@ int dsc_geglu(const void* x, void* y, int64_t rows, int n, int dtype, void* stre
  * gn_part is fp32 [B][rows][groups][2][2] with rows = dsc_*_gn_rows(...) pixel tiles per image (0 = shape not covered: 16-wide
  * convolution tiles without split-K, Cout % 64 == 0, groups of <= 64 channels, <= 128 tiles per image); slot [g][1] holds the
  * part of a group that lies beyond a 64-channel tile boundary.  Fixed summation orders: bit-reproducible.  No workgroup waits
- * for another - the partial sums cross the kernel boundary.
+ * for another - the partial sums cross the kernel boundary.  Nothing outside that shape is written; every slot the consumer reads
+ * is ([g][0] of every group, [g][1] of the groups that cross a boundary), a [g][1] no group needs is left as it was.  A shape
+ * dsc_*_gn_rows() answers 0 for is refused with DSC_ERR_UNSUPPORTED before any launch.
  */
 int dsc_conv3x3_gn_rows(int B, int H, int W, int Cin, int Cout, int groups, int resample);
 int dsc_conv3x3_gn_nhwc_f16(const void* x, const void* w, const void* bias, const void* add, int64_t add_ld,
@@ -649,6 +671,9 @@ int dsc_groupnorm_apply_nhwc(const void* x, void* y, const void* gamma, const vo
  * dsc_linear_splitk_workspace_bytes; 16-byte aligned) and a second launch adds the splits IN ORDER, then bias and residual, with
  * one fp16 rounding: bit-reproducible, no atomics, no workgroup waits on another.  Same operand constraints as dsc_linear_f16
  * (K % 64 == 0, N % 64 == 0, 16-byte aligned rows); splits == 1 after clamping runs dsc_linear_f16 itself.
+ * dsc_linear_splitk_workspace_bytes() is the [splits][M][N] fp32 of the split count actually run (uneven last split included;
+ * 0: no split, no workspace); exactly those bytes are written, every one of them, and then read.  out, x and the residual as in
+ * dsc_linear_f16, at any ldo / ldx / ldr.
  */
 size_t dsc_linear_splitk_workspace_bytes(int64_t M, int N, int K, int splits);
 int dsc_linear_splitk_f16(const void* x, const void* w, const void* bias, const void* residual, void* out,
@@ -661,6 +686,7 @@ int dsc_linear_splitk_f16(const void* x, const void* w, const void* bias, const 
  * `Attention`, reached from modules/model_k_diffusion.py:291-299 `decode_latents` and :600-606 `vae.encode`): too wide for
  * the flash kernel's registers, so it runs scores = q.k^T (dsc_linear_f16) -> this -> out = probs.v (dsc_linear_f16).
  * rows x n fp16, row strides ld_* in elements (% 8 == 0); n % 8 == 0, n <= 16384.  One workgroup per row, one launch.
+ * Reads scores[r][0 .. n) and writes probs[r][0 .. n) only, at any ld_scores / ld_probs >= n.
  */
 int dsc_softmax_rows_f16(const void* scores, void* probs, int64_t rows, int n, int64_t ld_scores, int64_t ld_probs,
                          float scale, int dtype, void* stream);
