@@ -16,13 +16,13 @@ def within(out, ref, rel, floor):
     return bool(torch.all((out.detach().cpu().to(ref.dtype) - ref).abs() <= rel * ref.abs() + floor))
 
 
-def linear(x, w, bias=None, residual=None):
-    """x @ w.T (+ bias) (+ residual row m % R) in fp32"""
-    y = x.float() @ w.float().t()
+def linear(x, w, bias=None, residual=None, dtype=torch.float32):
+    """x @ w.T (+ bias) (+ residual row m % R) in fp32 (or `dtype`)"""
+    y = x.to(dtype) @ w.to(dtype).t()
     if bias is not None:
-        y = y + bias.float()
+        y = y + bias.to(dtype)
     if residual is not None:
-        y = y + residual.float().repeat(x.shape[0] // residual.shape[0], 1)
+        y = y + residual.to(dtype).repeat(x.shape[0] // residual.shape[0], 1)
     return y
 
 
@@ -76,10 +76,10 @@ def conv_geometry(mode, h, w):
     return (h, w), (h, w)
 
 
-def conv3x3(x, w, bias=None, residual=None, mode=PLAIN, size=None, add=None):
-    """the 3x3 convolution of x [B, Cin, h, w] in the given resample mode (+ bias) (+ add[b, c]) (+ residual), fp32, NCHW"""
-    xf, wf = x.float(), w.float()
-    bf = None if bias is None else bias.float()
+def conv3x3(x, w, bias=None, residual=None, mode=PLAIN, size=None, add=None, dtype=torch.float32):
+    """the 3x3 convolution of x [B, Cin, h, w] in the given resample mode (+ bias) (+ add[b, c]) (+ residual), fp32 (or `dtype`), NCHW"""
+    xf, wf = x.to(dtype), w.to(dtype)
+    bf = None if bias is None else bias.to(dtype)
     if mode == UPSAMPLE2X:
         y = F.conv2d(F.interpolate(xf, scale_factor=2.0, mode="nearest"), wf, bf, padding=1)
     elif mode == UPSAMPLE_CEIL:
@@ -91,9 +91,9 @@ def conv3x3(x, w, bias=None, residual=None, mode=PLAIN, size=None, add=None):
     else:
         y = F.conv2d(xf, wf, bf, padding=1)
     if add is not None:
-        y = y + add.float()[:, :, None, None]
+        y = y + add.to(dtype)[:, :, None, None]
     if residual is not None:
-        y = y + residual.float()
+        y = y + residual.to(dtype)
     return y
 
 
