@@ -43,6 +43,11 @@ class LatentStartRow(ctypes.Structure):
                 ("coef", ctypes.c_float), ("start", _vp), ("keep", _vp), ("keep_noise", _vp)]
 
 
+class PromptWeightGroup(ctypes.Structure):
+    """dsc_prompt_weight_group (include/dsc_hip.h)"""
+    _fields_ = [("z_row", ctypes.c_int * 2), ("mult", _vp), ("out", _vp * 2)]
+
+
 _SIGNATURES = {
     "dsc_abi_version": (ctypes.c_int, []),
     "dsc_target_arch": (ctypes.c_char_p, []),
@@ -148,6 +153,9 @@ _SIGNATURES = {
     "dsc_latent_start_rows": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(LatentStartRow)] + [ctypes.c_int] * 3 + [_vp]),
     "dsc_causal_attn_f16": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 4 + [_i64p] * 4 + [ctypes.c_float, ctypes.c_int, _vp]),
     "dsc_act_f16": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
+    "dsc_prompt_weight_rows_f16": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [ctypes.POINTER(PromptWeightGroup), ctypes.c_int,
+                                                  ctypes.c_longlong, _vp]),
+    "dsc_debug_set_prompt_weight_slices": (None, [ctypes.c_int]),
 }
 
 

@@ -310,6 +310,27 @@ class CLIPTextModel(nn.Module):
         fin = self.final_layer_norm
         return ops.add_layernorm(h, None, fin.weight, fin.bias, fin.eps)[1], hidden
 
+    def encode_rows(self, ids, clip_skip=None):
+        """What the emphasis parser reads of a call (prompt_parser.py `encode_with_transformers`), for a caller that captures the
+        encoder into a graph of its own (modules/serving/text_lane.py): ids [n, S] int64 on the GPU -> fp16 [n, S, C], the last
+        hidden state or, with clip_skip > 1, the final LayerNorm of hidden_states[-clip_skip] (the layers behind it do not run).
+        Kernel route only, always eager launches on the current stream whatever `enable_graphs` says, no clones: the same launches
+        and bits as `forward` on these ids."""
+        n, S = ids.shape
+        layers = self.encoder.layers
+        skip = clip_skip if clip_skip is not None and clip_skip > 1 else 1
+        if not self.kernel_route(n, S) or ids.device != self.device:
+            raise NotImplementedError(f"CLIPTextModel.encode_rows: [{n}, {S}] ids on {ids.device} do not run on the package's kernels")
+        if skip > len(layers) + 1:
+            raise ValueError(f"CLIPTextModel.encode_rows: clip_skip {clip_skip} reaches behind {len(layers)} layers")
+        self._refresh_qkv()
+        with torch.no_grad():
+            h = self.embeddings(ids)
+            for layer in layers[:len(layers) + 1 - skip]:
+                h = self._layer_kernels(layer, h)
+            fin = self.final_layer_norm
+            return ops.add_layernorm(h, None, fin.weight, fin.bias, fin.eps)[1]
+
     def _forward_graph(self, ids, want_hidden):
         key = (ids.shape[0], ids.shape[1], want_hidden)
         entry = self._graphs.get(key)

@@ -491,7 +491,7 @@ class StableDiffusionPipeline:
               ip_masks: bool = False, t2i_adapter: bool = False, controlnet: bool = False, control_slots=None,
               decode: bool = False, decode_batch: int = 2, previews: bool = False, preview_scale: int = 8, preview_coef=None,
               preview_ring: int = 8, inpaint_unet: bool = False, freeu: bool = False, encode: bool = False, encode_batch: int = 2,
-              two_call: bool = False):
+              two_call: bool = False, text: bool = False, text_batch: int = 2, clip_skip=None):
         """Continuous-batching server (modules/serving/): requests join a running batch at any step boundary, each at its own
         point of its own schedule, and leave when done.  Returns a `ServingBatcher` (submit / step / run_until_idle / start / stop /
         stats / warm).  `ip_masks=True` (IP-Adapters loaded): requests may carry the reference's
@@ -523,7 +523,12 @@ class StableDiffusionPipeline:
         `inpaint_unet`): requests may name a sampler of sampling.TWO_CALL_FAMILY (Heun, DPM2, DPM2 a, DPM++ 2S a, DPM++ SDE) with
         `eta` / `s_noise` / `seed` / `step_noise` (one row per model call, sampling.call_noise_table); such a request advances by
         one model call per transition, two per sampler step (dsc_cfg_staged_step_rows), beside requests of the one-call samplers;
-        not with `control_img` / `image_t2i_adapter`.  Any batcher is refused while the
+        not with `control_img` / `image_t2i_adapter`.  `text=True` (pipe.text_encoder is modules.clip_text.CLIPTextModel in fp16
+        on the GPU, `text_len` a multiple of 77): requests may carry `prompt` / `negative_prompt` strings in place of the
+        embeddings and ids; a text lane - a stream with one captured encoder per bucket, up to `text_batch` (request, chunk)
+        groups per encode, and one dsc_prompt_weight_rows_f16 launch behind it - serves encode_prompt_function's default branch
+        beside the step (`clip_skip`: the batcher's, fixed at construction), `submit` does host work only, and
+        `batcher.encode_text(prompt, negative_prompt)` returns the embeddings synchronously.  Any batcher is refused while the
         UNet-level setting (unet.enable_freeu) is on."""
         from .serving import ServingBatcher
         kw = dict(previews=True, preview_scale=preview_scale, preview_coef=preview_coef, preview_ring=preview_ring) if previews else {}
@@ -535,6 +540,8 @@ class StableDiffusionPipeline:
             kw.update(encode=True, encode_batch=encode_batch)
         if two_call:
             kw["two_call"] = True
+        if text:
+            kw.update(text=True, text_batch=text_batch, clip_skip=clip_skip)
         return ServingBatcher(self, height, width, max_batch=max_batch, slot=slot, buckets=buckets, text_len=text_len,
                               ip_masks=ip_masks, t2i_adapter=t2i_adapter, controlnet=controlnet, control_slots=control_slots,
                               decode=decode, decode_batch=decode_batch, **kw)
@@ -543,7 +550,7 @@ class StableDiffusionPipeline:
                     text_len: int = 77, slots=(0, 1), ip_masks: bool = False, decode: bool = False, decode_batch: int = 2,
                     previews: bool = False, preview_scale: int = 8, preview_coef=None, preview_ring: int = 8,
                     inpaint_unet: bool = False, freeu: bool = False, encode: bool = False, encode_batch: int = 2,
-                    two_call: bool = False):
+                    two_call: bool = False, text: bool = False, text_batch: int = 2, clip_skip=None):
         """Continuous-batching server for requests with a hires pass (reference :1176-1228): a batcher at `height` x `width`
         chained to one at the target size of `upscale_x` (_hires_pass's expression), on two workspace slots.  A request with
         `upscale=True` runs its first pass on the one, is enlarged and re-noised on the device (dsc_latent_resample_noise) and
@@ -554,7 +561,9 @@ class StableDiffusionPipeline:
         `previews=True` gives both batchers the preview path (see `serve`): each pass of a request with `upscale` counts its own
         steps, and the second pass previews at its own size.  `freeu=True` builds both batchers for per-request FreeU (see
         `serve`): both passes of a request get its values.  `encode=True` gives the encode lane (see `serve`) to the base-size batcher
-        only: the second pass starts from the hand-off's latent, never from pixels."""
+        only: the second pass starts from the hand-off's latent, never from pixels.  `text=True` gives the text lane (see `serve`)
+        to the base-size batcher only: a request with `prompt` and `upscale` is encoded once, and its second pass shares the
+        first's text rows and ids (which also serve `region_map_state_hires`)."""
         from .latent_resample import hires_target_size
         from .serving import HiresPair, ServingBatcher
         if two_call:
@@ -588,6 +597,8 @@ class StableDiffusionPipeline:
         if freeu:
             kw["freeu"] = True
         base_kw = dict(kw, encode=True, encode_batch=encode_batch) if encode else kw
+        if text:
+            base_kw = dict(base_kw, text=True, text_batch=text_batch, clip_skip=clip_skip)
         return HiresPair(ServingBatcher(self, height, width, slot=slots[0], **base_kw), ServingBatcher(self, th, tw, slot=slots[1], **kw))
 
     def txt2img_coalesced(self, requests, height: int = 512, width: int = 512, num_inference_steps: int = 50,

@@ -26,6 +26,7 @@ The seam is host scheduling against a replaceable device executor:
   decode_lane.py  the decode lane that finishes images beside the step
   encode_lane.py  the encode lane that encodes pixel inputs beside the step
   preview_lane.py the preview path: thumbnails of running requests' denoised estimates, beside the step
+  text_lane.py    the text lane that encodes prompt strings beside the step
 """
 # every name that is imported from `modules.serving`
 from .batcher import HiresPair, ServingBatcher

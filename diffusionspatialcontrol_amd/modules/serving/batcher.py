@@ -48,7 +48,7 @@ import torch
 from ... import ops
 from .. import sampling
 from ..encode_region_map_function import encode_region_map
-from . import requests
+from . import requests, text_lane
 from .encode_lane import _EncodeHandle, encode_roles
 from .executor import _GraphExecutor, step_launch
 from .requests import MAX_TEXT_KEYS, _FreeuRequest, _InpaintFreeuRequest, _InpaintRequest, _Request, _ip_layers
@@ -66,7 +66,7 @@ class ServingBatcher:
     def __init__(self, pipe, height, width, max_batch=8, slot=0, buckets=(1, 2, 4, 8), text_len=77, executor=None, ip_masks=False,
                  t2i_adapter=False, controlnet=False, control_slots=None, decode=False, decode_batch=2, previews=False,
                  preview_scale=8, preview_coef=None, preview_ring=8, inpaint_unet=False, freeu=False, encode=False, encode_batch=2,
-                 two_call=False):
+                 two_call=False, text=False, text_batch=2, clip_skip=None):
         requests.check_freeu_off(pipe)
         buckets = tuple(sorted(set(int(b) for b in buckets)))
         if not buckets or buckets[0] < 1 or buckets[-1] < max_batch:
@@ -130,6 +130,16 @@ class ServingBatcher:
                 raise ValueError(f"serve: `encode_batch` must be an integer in [1, max_batch = {self.max_batch}], got {encode_batch!r}")
             self.encode_batch = encode_batch
             self._stats["encodes"] = self._stats["encode_rows"] = 0
+        # requests may carry `prompt` / `negative_prompt` strings: a text lane beside the step encodes them (text_lane.py)
+        self.text_on = bool(text)
+        self.text_batch, self.clip_skip, self._parser = 0, None, None
+        if self.text_on:
+            if isinstance(text_batch, bool) or not isinstance(text_batch, int) or not 1 <= text_batch <= ops.PROMPT_WEIGHT_MAX_GROUPS:
+                raise ValueError(f"serve: `text_batch` must be an integer in [1, {ops.PROMPT_WEIGHT_MAX_GROUPS}] (the groups of one "
+                                 f"dsc_prompt_weight_rows_f16 launch), got {text_batch!r}")
+            self._parser = text_lane.check_pipeline(pipe, pipe.unet.config.cross_attention_dim, self.text_len, clip_skip)
+            self.text_batch, self.clip_skip = text_batch, clip_skip
+            self._stats["text_encodes"] = self._stats["text_groups"] = 0
         # requests may carry `preview_every` / `on_preview`: thumbnails of the denoised estimate leave beside the step
         # (preview_lane.py)
         self.previews = bool(previews)
@@ -311,6 +321,8 @@ class ServingBatcher:
                 self._ensure_encode()                # the encode lane's stream, static buffers, graphs, staging and pinned ring
             if self.previews:
                 self.exec.ensure_preview()           # the preview stream and its ring of device / pinned buffers
+            if self.text_on:
+                self._ensure_text()                  # the text lane's stream, static buffers, graphs and the empty chunk's rows
             self._warm_captures = self._stats["captures"]
         return self
 
@@ -330,6 +342,9 @@ class ServingBatcher:
         if hi.height < self.height or hi.width < self.width:
             raise ValueError(f"serve: the hires batcher runs {hi.height}x{hi.width}, smaller than this one's "
                              f"{self.height}x{self.width} (only enlarging is served)")
+        if self.text_on and hi.text_len != self.text_len:
+            raise ValueError(f"serve: `text=True` on a hires pair: the second pass shares the first's text rows, but the batchers "
+                             f"run {self.text_len} and {hi.text_len} text keys")
         with self._lock:
             self._hires = hi
         return self
@@ -372,7 +387,13 @@ class ServingBatcher:
         On a batcher built with `two_call=True`: `sampler_name` may be one of sampling.TWO_CALL_FAMILY (sample_heun, sample_dpm_2,
         sample_dpm_2_ancestral, sample_dpmpp_2s_ancestral, sample_dpmpp_sde) with `eta` / `s_noise` / `seed` / `generator`;
         `step_noise` then has one row per MODEL CALL (sampling.call_noise_table) and `preview_every` counts sampler steps; not
-        with `control_img` / `image_t2i_adapter` / `mask_image`.  Returns a Future of the final output."""
+        with `control_img` / `image_t2i_adapter` / `mask_image`.
+        On a batcher built with `text=True`: `prompt` (a string) and optionally `negative_prompt` (absent / None: "") in place of
+        `prompt_embeds` / `negative_prompt_embeds` / `text_input_ids` - the default branch of encode_prompt_function (emphasis
+        syntax, 77-token chunks up to this batcher's text_len, `BREAK`) runs on the text lane (text_lane.py): submit parses and
+        chunks on the host, and the request joins the batch once its encode has completed; `region_map_state` needs nothing else
+        (the lane makes the ids); `long_encode` other than 0 and a `clip_skip` other than the batcher's are refused.
+        Returns a Future of the final output."""
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -429,10 +450,30 @@ class ServingBatcher:
             return s
 
     # ------------------------------------------------------------------ request preparation (caller's thread)
-    def _prepare(self, request, second=False, device=True):
+    def encode_text(self, prompt, negative_prompt=None):
+        """(a batcher built with `text=True`) the embeddings a request with these strings would run with, synchronously, through
+        the lane's own path at bucket 1 -> {"prompt_embeds", "negative_prompt_embeds": fp16 [1, S, C] on the GPU, "text_input_ids":
+        [negative, positive] id arrays [1, S]}: what `submit` takes in place of the strings, for clients that cache embeddings"""
+        if not self.text_on:
+            raise ValueError("serve: encode_text needs a batcher built with `text=True` (pipe.serve(..., text=True))")
+        holder = requests.text_record(_Request)(req={"prompt": prompt, "negative_prompt": negative_prompt})
+        holder.txt = requests.prompt_request(self, holder.req)
+        if holder.txt is None:
+            raise ValueError("serve: encode_text takes `prompt` as a string")
+        with self._lock:
+            self.exec.bind_thread()
+            self._ensure_text()
+            self.exec.prepare_text(holder)
+            encodes, groups = self.exec.dispatch_texts([holder], batch=1)
+            self._stats["text_encodes"] += encodes
+            self._stats["text_groups"] += groups
+            self.exec.text_wait(holder)
+        return {"prompt_embeds": holder.text[1], "negative_prompt_embeds": holder.text[0], "text_input_ids": holder.txt.np_ids}
+
+    def _prepare(self, request, second=False, device=True, text_from=None):
         """validate a request (requests.py) and build its record; `second`: the record of a hires request's second pass on
         this batcher (its start latent comes from the hand-off); `device=False` leaves the device half (_prepare_device) to the
-        caller"""
+        caller; `text_from`: the first-pass record of a hires pair whose text rows and ids this second pass shares (text lane)"""
         pipe = self.pipe
         if not isinstance(request, dict):
             raise TypeError("serve: a request is a dict (txt2img_coalesced's request + num_inference_steps / sampler_opt / "
@@ -449,7 +490,11 @@ class ServingBatcher:
         ip_embeds, ip_scale = requests.ip_request(self, request)
         # masks without an image prompt (or with every scale 0) have nothing to weigh: accepted and ignored
         ip_weights = requests.ip_mask_weights(self, ip_masks) if ip_embeds is not None and ip_masks is not None else None
-        text = requests.text_request(self, request)
+        txt, shared = None, getattr(text_from, "txt", None)
+        if shared is None and self.text_on:
+            txt = requests.prompt_request(self, request)
+        # (a prompt request's rows are allocated by the device half; a shared second pass receives its first pass's)
+        text = requests.text_request(self, request) if txt is None and shared is None else None
         every, on_preview = requests.preview_request(self, request)
         steps = int(request.get("num_inference_steps", 25))
         if steps < 1:
@@ -462,6 +507,8 @@ class ServingBatcher:
             record = requests._TWO_CALL_RECORD[record]
         if self.encode:                                                  # (one more field, `enc`)
             record = requests._ENCODE_RECORD[record]
+        if self.text_on:                                                 # (one more field, `txt`)
+            record, more = requests.text_record(record), dict(more, txt=txt)
         r = record(req=request, future=concurrent.futures.Future(), steps=steps, second=second, ip_embeds=ip_embeds,
                    ip_scale=ip_scale, ip_weights=ip_weights, adapter=adapter, control=control, guidance=g, output_type=out_type,
                    family=family, rescale=phi, eta=float(request.get("eta", 1.0)), text=text, **more)
@@ -529,6 +576,8 @@ class ServingBatcher:
                 raise ValueError(f"serve: `step_noise` must be a {list(want)} tensor (one unit-noise row per step), got "
                                  f"{list(table.shape) if torch.is_tensor(table) else type(table).__name__}")
         ids = request.get("text_input_ids") or [None, None]
+        if txt is not None or shared is not None:    # a prompt request: the lane's parser made the ids of both texts
+            ids = (txt or shared).np_ids
         tabs = encode_region_map(pipe, request.get("region_map_state"), width=self.width, height=self.height,
                                  num_images_per_prompt=1, text_ids=ids)
         r.tables = self._request_tables(tabs)
@@ -616,10 +665,12 @@ class ServingBatcher:
         r = self._prepare(first, device=False)
         r2 = None
         try:
-            r2 = hi._prepare(second, second=True, device=False)
+            r2 = hi._prepare(second, second=True, device=False, text_from=r)
             r2.future, r2.t_submit = r.future, r.t_submit
             r.hires = r2
             self._prepare_device(r)
+            if getattr(r, "txt", None) is not None:
+                r2.text = r.text                     # one encode serves both passes
             hi._prepare_device(r2)
         except BaseException:                        # (a refused request leaves no preview state behind)
             self._preview_of.pop(r, None)
@@ -682,11 +733,20 @@ class ServingBatcher:
         stepping = [r for r in slots if r is not None and r.i < len(r.coeffs) and self._n is not None]
         if self.encode:
             self._dispatch_encodes()
+        if self.text_on:
+            self._dispatch_texts()
         joins = self._admit()
-        if self.encode and not stepping and not joins and self._queue and self._queue[0].enc is not None:
-            # nothing steps and the head is still encoding: wait for its event instead of reporting idle with a request queued
-            self.exec.encode_wait(self._queue[0])
-            joins = self._admit()
+        if not stepping and not joins and self._queue and (self.encode or self.text_on):
+            # nothing steps and the head is still encoding: wait for its event(s) instead of reporting idle with a request queued
+            head = self._queue[0]
+            on_encode = self.encode and head.enc is not None
+            on_text = self.text_on and head.txt is not None
+            if on_encode:
+                self.exec.encode_wait(head)
+            if on_text:
+                self.exec.text_wait(head)
+            if on_encode or on_text:
+                joins = self._admit()
         if not stepping and not joins:
             return False
         # who leaves after this transition: a request whose last step is the one being applied now
@@ -731,6 +791,8 @@ class ServingBatcher:
                 break
             if self.encode and head.enc is not None and not self.exec.encode_ready(head):
                 break                                # still encoding: it waits although a slot is free, and nobody overtakes it
+            if self.text_on and head.txt is not None and not self.exec.text_ready(head):
+                break                                # its prompt is still on the text lane: the same rule
             if head.control is not None:
                 # a ControlNet lane, the lowest free one, kept until the request leaves; with none free the request waits at the
                 # head of the queue although a slot is free (FIFO, the rule of _launch_compatible)
@@ -753,6 +815,15 @@ class ServingBatcher:
             encodes, rows = self.exec.dispatch_encodes(todo)
             self._stats["encodes"] += encodes
             self._stats["encode_rows"] += rows
+
+    def _dispatch_texts(self):
+        """queued prompt requests whose groups have not been sent to the text lane go there now, in FIFO order"""
+        todo = [r for r in self._queue if r.txt is not None and r.txt.sent < r.txt.real]
+        if todo:
+            self._ensure_text()
+            encodes, groups = self.exec.dispatch_texts(todo)
+            self._stats["text_encodes"] += encodes
+            self._stats["text_groups"] += groups
 
     def _records(self, n_slots, stepping, joins, leaving):
         """the per-slot records of this transition's launch and, per slot, the known-region record of an inpainting slot that
@@ -876,6 +947,8 @@ class ServingBatcher:
             r.noise = None                           # ... and its noise table
             if self.encode:
                 r.enc = None                         # ... and its draws and host pixels (encode)
+            if self.text_on:
+                r.txt = None                         # ... and its pinned ids and multipliers (text)
             r.adapter_feats = None                   # ... and its adapter features
             if r.lane is not None:                   # ... and its ControlNet lane goes to whoever waits for one
                 self._lanes[r.lane] = None
@@ -957,6 +1030,9 @@ class ServingBatcher:
 
     def _ensure_encode(self):
         self._stats["captures"] += self.exec.ensure_encode()
+
+    def _ensure_text(self):
+        self._stats["captures"] += self.exec.ensure_text()
 
     def _poll(self, wait=False):
         """resolve the futures of requests whose final row copy has completed (in completion order); on a previews batcher the

@@ -50,6 +50,7 @@ from ..latent_resample import MODES as _RESAMPLE_MODES, device_taps
 from .decode_lane import _DecodeLane, _LaneHandle
 from .encode_lane import _EncodeLane
 from .preview_lane import _PreviewLane
+from .text_lane import _TextLane
 
 _EMBED_LOCK = threading.Lock()       # around the process-wide deterministic switch in _GraphExecutor._control_embedding
 _STEP_ROWS = {"rows": "cfg_dpmpp2m_step_rows", "linear": "cfg_linear_step_rows", "known": "cfg_dpmpp2m_step_rows_known",
@@ -168,6 +169,8 @@ class _GraphExecutor:
         self.lane = _DecodeLane(self, batcher.decode_batch) if getattr(batcher, "decode", False) else None
         # (encode) the lane that encodes pixel inputs beside the step; its stream and buffers are built by ensure_encode
         self.enc_lane = _EncodeLane(self, batcher.encode_batch) if getattr(batcher, "encode", False) else None
+        # (text) the lane that encodes prompt strings beside the step; its stream and buffers are built by ensure_text
+        self.text_lane = _TextLane(self, batcher.text_batch, batcher.clip_skip) if getattr(batcher, "text_on", False) else None
         # (previews) the path that turns rows of `old` into thumbnails beside the step; its stream and ring are built by ensure_preview
         self.previews = _PreviewLane(self, batcher.preview_scale, batcher.preview_coef, batcher.preview_ring) \
             if getattr(batcher, "previews", False) else None
@@ -199,8 +202,11 @@ class _GraphExecutor:
         dev, dt = self.device, self.dtype
         ts = [t for _, t in r.scal]
         r.temb = self.pipe.unet.temb_add_table(torch.tensor(ts, dtype=torch.float32, device=dev))
-        neg, pos = r.text
-        r.text = (neg.to(device=dev, dtype=dt), pos.to(device=dev, dtype=dt))
+        if r.text is None:                               # a prompt request: the text lane writes its rows beside the step
+            self.text_lane.prepare(r)
+        else:
+            neg, pos = r.text
+            r.text = (neg.to(device=dev, dtype=dt), pos.to(device=dev, dtype=dt))
         if r.ip_embeds is not None:
             self._ip_request_rows(r)
             if r.ip_weights is not None:                 # on the device, in memory of this stream, until the request leaves
@@ -515,6 +521,8 @@ class _GraphExecutor:
                 self.stream.wait_event(r.ready)
             if self.enc_lane is not None and r.enc is not None:      # a pixel input: its rows are written on the lane's stream
                 self.stream.wait_event(r.enc.ev)
+            if self.text_lane is not None and r.txt is not None:     # a prompt: its text rows are written on the lane's stream
+                self.stream.wait_event(r.txt.ev)
             self.x[r.slot].copy_(r.lat[0])
 
     def finish(self, r):
@@ -559,6 +567,27 @@ class _GraphExecutor:
 
     def encode_wait(self, r):
         self.enc_lane.wait(r)
+
+    def prepare_text(self, r):
+        """the device half of a holder of prompt strings outside a request (batcher.encode_text): its rows and pinned ids"""
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            self.text_lane.prepare(r)
+
+    def ensure_text(self):
+        """the text lane's stream, per-bucket static buffers and graphs, the empty chunk's rows -> how many graphs this call
+        captured"""
+        return self.text_lane.ensure()
+
+    def dispatch_texts(self, requests, batch=None):
+        """these queued requests' groups to the lane, up to text_batch (`batch`) per encode -> (encodes queued, groups in them)"""
+        return self.text_lane.dispatch(requests, batch)
+
+    def text_ready(self, r):
+        return self.text_lane.ready(r)
+
+    def text_wait(self, r):
+        self.text_lane.wait(r)
 
     def ensure_preview(self):
         """the preview path's stream and its ring of device / pinned buffers (preview_lane.py)"""

@@ -122,6 +122,17 @@ _ENCODE_RECORD = {_Request: _EncodeRequest, _InpaintRequest: _InpaintEncodeReque
                   _FreeuTwoCallRequest: _FreeuTwoCallEncodeRequest}
 
 
+_TEXT_RECORD = {}
+
+
+def text_record(record):
+    """a request of a batcher built with `text=True`: the record of its kind plus `txt`, its handle on the text lane
+    (text_lane._TextHandle) from submit until it leaves, or None when it brings its embeddings"""
+    if record not in _TEXT_RECORD:
+        _TEXT_RECORD[record] = type(record.__name__.replace("Request", "TextRequest"), (record,), {"__slots__": ("txt",)})
+    return _TEXT_RECORD[record]
+
+
 def staged(r):
     """the request runs a two-call sampler: its lists are per model call (only on a batcher built with `two_call=True`)"""
     return getattr(r, "stage", None) is not None
@@ -316,6 +327,33 @@ def text_request(b, request):
     if pos.shape[1] != b.text_len:
         raise ValueError(f"serve: this batcher runs {b.text_len} text keys, the request has {pos.shape[1]}")
     return neg, pos
+
+
+def prompt_request(b, request):
+    """submit-time checks of `prompt` / `negative_prompt` on a batcher built with `text=True` -> the request's handle on the text
+    lane (host work only: parsing, chunking, padding to the batcher's chunk count), or None when it carries no `prompt` (it then
+    brings its embeddings: text_request)"""
+    from . import text_lane
+    prompt = request.get("prompt")
+    if prompt is None:
+        return None
+    for key in ("prompt_embeds", "negative_prompt_embeds", "text_input_ids"):
+        if request.get(key) is not None:
+            raise ValueError(f"serve: `prompt` and `{key}` are given together; a request brings its prompt as strings (the text "
+                             f"lane encodes them and makes the ids) or as embeddings, not both")
+    negative = request.get("negative_prompt")
+    negative = "" if negative is None else negative
+    if not isinstance(prompt, str) or not isinstance(negative, str):
+        raise ValueError(f"serve: `prompt` / `negative_prompt` are one string each (one image per request), got "
+                         f"{type(prompt).__name__} / {type(negative).__name__}")
+    long_encode = request.get("long_encode", 0)
+    if long_encode != 0:                                         # (encode_prompt_function's own test: False is 0)
+        raise ValueError(f"serve: `long_encode` {long_encode!r} is not served: the text lane runs the default branch of "
+                         f"encode_prompt_function (long_encode = 0); encode in the client and pass the embeddings")
+    if "clip_skip" in request and text_lane.effective_skip(request["clip_skip"]) != text_lane.effective_skip(b.clip_skip):
+        raise ValueError(f"serve: `clip_skip` {request['clip_skip']!r} differs from this batcher's ({b.clip_skip!r}): the lane's "
+                         f"captured encoder ends at one layer (build a batcher with pipe.serve(..., text=True, clip_skip=...))")
+    return text_lane.prompt_chunks(b._parser, negative, prompt, b.text_len // text_lane.CHUNK, b.text_len)
 
 
 def adapter_request(b, request):

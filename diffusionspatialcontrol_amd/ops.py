@@ -1541,3 +1541,8 @@ from .freeu import FREEU_MAX_SIDE, fourier_filter_eager, freeu_covers, freeu_eag
 # latent mask; dsc_latent_start_rows: the encoder's moments -> latents and start latents, per row): wrappers beside their kernels'
 # names, reached as ops.image_prepare / ops.latent_start; the *_torch functions are the literal eager chains they replace
 from .image_prepare import image_prepare, image_prepare_torch, latent_start, latent_start_torch, start_form  # noqa: E402,F401
+
+# prompt emphasis behind the text encoder on the text lane of the continuous batcher (dsc_prompt_weight_rows_f16: multipliers and
+# mean restoration of every (request, chunk) group in one launch): wrapper beside its kernel's name, reached as
+# ops.prompt_weight_rows; prompt_weight_numpy restates the contract with exact sums, prompt_weight_torch is the eager chain
+from .prompt_weight import MAX_GROUPS as PROMPT_WEIGHT_MAX_GROUPS, prompt_weight_numpy, prompt_weight_rows, prompt_weight_torch  # noqa: E402,F401

@@ -1008,6 +1008,40 @@ int dsc_causal_attn_f16(const void* q, const void* k, const void* v, void* out, 
 #define DSC_ACT_GELU_ERF   1
 int dsc_act_f16(void* x, int64_t n, int kind, int dtype, void* stream);
 
+/*
+ * dsc_prompt_weight_rows_f16: prompt emphasis after the text encoder on the text lane of the continuous batcher
+ * (modules/serving/text_lane.py), for up to DSC_PROMPT_WEIGHT_MAX_GROUPS (request, chunk) groups in one launch.  Replaces the tail
+ * of FrozenCLIPEmbedderWithCustomWordsBase.process_tokens (reference modules/prompt_parser.py:196-221: `z * multipliers` with the
+ * tensor mean restored), the hstack over chunks in its forward and the cast of encode_prompt_automatic1111.  Per group, with
+ * N = 2 T C the elements of its two rows of z and m the fp32 multiplier of a token:
+ *     before = fp16(sum z / N);   p = fp32(z) * m, every product rounded to fp32;   after = fp32(sum p / N)
+ *     ratio  = fp32(before) / after   (an IEEE fp32 division);   out = fp16(fp32(p * ratio))
+ * Both sums are fp64 sums over BOTH rows in a fixed order, each divided by N in fp64 and rounded once.  No guard on after == 0:
+ * inf and NaN follow IEEE, as in the eager chain (all-zero multipliers give NaN everywhere).  The product, the scaling and the
+ * conversion to fp16 are three separate roundings.
+ * z: fp16 [m, T, C] dense (the encoder's output).  groups: a HOST array of n records, read at the call and passed to the kernel by
+ * value (the caller may reuse it at once).  Per group: z_row[2], its negative and positive row of z, each in [0, m), in any order
+ * and not necessarily adjacent; mult, DEVICE fp32 [2][T]; out[2], fp16 [T, C] destinations with row stride ldo (elements) - chunk
+ * k's place inside a request's negative / positive [S, C] row.  A group whose two destinations are NULL is neither read nor
+ * written; with no live group nothing is launched.
+ * C % 8 == 0, ldo % 8 == 0, z and every destination 16-byte aligned, mult 4-byte aligned, any T >= 1.  No workspace, no atomics, no
+ * allocation; deterministic, and the bits do not depend on the grid: every workgroup of a group redoes the group's sums in the
+ * order its 1024 lanes define and stores one slice.  Safe beside captured graphs.
+ * DSC_ERR_BAD_ARG (before any GPU call): NULL z / groups; m, T, C < 1; n < 1 or > 16; ldo < C; a group with one NULL destination,
+ * a NULL mult, a z_row outside [0, m), out[0] == out[1] (or two dense destinations that overlap), a destination that overlaps z
+ * or the group's mult.  DSC_ERR_UNSUPPORTED: C % 8 or ldo % 8, alignment, 2^30 elements and more per row of z.
+ * dsc_debug_set_prompt_weight_slices: workgroups per group for A/B runs (tools/mb_prompt_weight.py); 0 = the launch rule.
+ */
+#define DSC_PROMPT_WEIGHT_MAX_GROUPS 16
+typedef struct {
+    int z_row[2];
+    const void* mult;
+    void* out[2];
+} dsc_prompt_weight_group;
+int dsc_prompt_weight_rows_f16(const void* z, int m, int T, int C, const dsc_prompt_weight_group* groups, int n, long long ldo,
+                               void* stream);
+void dsc_debug_set_prompt_weight_slices(int slices);
+
 #ifdef __cplusplus
 }
 #endif
