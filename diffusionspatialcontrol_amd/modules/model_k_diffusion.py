@@ -39,6 +39,7 @@ import torch
 from .. import _lib, ops
 from . import sampling
 from .encode_region_map_function import encode_region_map
+from .step_plan import step_plan, step_record
 from .attention_modify import weight_func_fused
 from .external_k_diffusion import CompVisDenoiser, CompVisVDenoiser
 
@@ -1444,50 +1445,30 @@ class StableDiffusionPipeline:
                              f"got {tuple(noise.shape) if torch.is_tensor(noise) else type(noise).__name__}")
         return noise.to(device=x.device, dtype=x.dtype).contiguous()
 
-    def _linear_fused_loop(self, st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout, rescale=0.0,
-                           extras=None):
-        """the fused loop's steps through the per-row kernel: one record per image, all on the same step of the same schedule;
-        rescale > 0: every record carries it (ops.cfg_linear_step_rows then issues the rescale launch); extras: the images' extra
-        input channels of a 9-channel UNet (ops.cfg_linear_step_rows_cat writes them behind each latent row)"""
-        kdm = self.k_diffusion_model
-        for i, (a, b, c, s) in enumerate(coeffs):
+    def _rows_fused_loop(self, st, x, old, plan, noise, tab, guidance_scale, n_img, start_time, timeout, rescale=0.0, extras=None):
+        """the fused loop's steps through the per-row kernels: one model call and one launch per entry of `plan`, one record per
+        image, all on the same call of the same plan.  A two-call plan launches dsc_cfg_staged_step_rows (the step's intermediate
+        point in `mid`), any other dsc_cfg_linear_step_rows; rescale > 0: every record carries it (the wrappers then issue the
+        rescale launch); extras: the images' extra input channels of a 9-channel UNet (ops.cfg_linear_step_rows_cat writes them
+        behind each latent row)"""
+        mid = torch.zeros_like(x) if plan.two_call else None
+        for k, call in enumerate(plan):
             self._check_timeout(start_time, timeout)
             st["run"]()
-            nxt = sig[i + 1]
-            c_in_n, _, t_n = kdm.step_scalars(nxt) if nxt > 0 else (1.0, 0.0, 0.0)
-            rec = {"mode": ops.ROW_STEP, "sigma": sig[i], "guidance": guidance_scale, "a": a, "b": b, "c": c, "s": s,
-                   "c_skip": kdm.step_skip(sig[i]), "c_out": kdm.step_scalars(sig[i])[1], "c_in_next": c_in_n, "t_next": t_n,
-                   "sigma_next": max(nxt, 1e-10), "temb_row": tab[i + 1] if tab is not None and i + 1 < len(coeffs) else None}
-            if rescale > 0.0:
-                rec["rescale"] = rescale
-            recs = [dict(rec, noise=None if noise is None or s == 0.0 else noise[i, j if noise.shape[1] > 1 else 0])
+            after = (1.0, 0.0, 1e-10, None)                          # (c_in, t, sigma, time-embedding row) of the coming call
+            if k + 1 < len(plan):
+                nxt = plan[k + 1]
+                after = (nxt.c_in, nxt.t, max(nxt.sigma, 1e-10), None if tab is None else tab[k + 1])
+            recs = [step_record(plan, call, guidance_scale, rescale,
+                                None if noise is None or call.s == 0.0 else noise[k, j if noise.shape[1] > 1 else 0], *after)
                     for j in range(n_img)]
-            if extras is not None:
+            if plan.two_call:
+                ops.cfg_staged_step_rows(x, mid, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, tadd=st["tadd"])
+            elif extras is not None:
                 ops.cfg_linear_step_rows_cat(x, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, extras,
                                              tadd=st["tadd"])
             else:
                 ops.cfg_linear_step_rows(x, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, tadd=st["tadd"])
-
-    def _staged_fused_loop(self, st, x, old, calls, noise, tab, guidance_scale, n_img, start_time, timeout, rescale=0.0):
-        """_linear_fused_loop for a two-call sampler: one model call and one dsc_cfg_staged_step_rows launch per entry of `calls`,
-        [(the sigma the call's model runs at, its sampling.Call)]; every image is on the same call of the same plan"""
-        kdm = self.k_diffusion_model
-        mid = torch.zeros_like(x)
-        for k, (sigma, call) in enumerate(calls):
-            self._check_timeout(start_time, timeout)
-            st["run"]()
-            nxt = calls[k + 1][0] if k + 1 < len(calls) else 0.0
-            c_in_n, _, t_n = kdm.step_scalars(nxt) if nxt > 0 else (1.0, 0.0, 0.0)
-            a, m, b, c, s = call.coeffs
-            rec = {"mode": ops.ROW_STEP, "stage": call.stage, "sigma": sigma, "guidance": guidance_scale, "a": a, "m": m, "b": b,
-                   "c": c, "s": s, "c_skip": kdm.step_skip(sigma), "c_out": kdm.step_scalars(sigma)[1], "c_in_next": c_in_n,
-                   "t_next": t_n, "sigma_next": max(nxt, 1e-10),
-                   "temb_row": tab[k + 1] if tab is not None and k + 1 < len(calls) else None}
-            if rescale > 0.0:
-                rec["rescale"] = rescale
-            recs = [dict(rec, noise=None if noise is None or s == 0.0 else noise[k, j if noise.shape[1] > 1 else 0])
-                    for j in range(n_img)]
-            ops.cfg_staged_step_rows(x, mid, st["eps"], old, n_img, st["x_in"], st["t"], st["sigma_rows"], recs, tadd=st["tadd"])
 
     def _denoise_fused(self, latents, sigmas, text, region_state, weight_func, guidance_scale, n_img,
                        cross_attention_kwargs, start_time, timeout, slot=0, sampler=None, sampler_args=None, step_noise=None,
@@ -1547,17 +1528,9 @@ class StableDiffusionPipeline:
             sig = sigmas.detach().float().cpu().tolist()             # one device->host transfer before the loop
         sargs = dict(sampler_args or {})
         noise_sampler = sargs.pop("noise_sampler", None)
-        if family not in ("euler_ancestral", "dpmpp_2m_sde", "dpm_2_ancestral", "dpmpp_2s_ancestral", "dpmpp_sde"):
-            sargs.pop("eta", None)
-        if family != "dpmpp_2m_sde":
-            sargs.pop("solver_type", None)
-        if staged:
-            # the sigma a model call runs at is rounded to the latents' dtype, as protocol mode's `sigma * s_in` does (the schedule's
-            # own sigmas already are); the update's scalars keep the unrounded value, as the samplers' host arithmetic does
-            plan = sampling.call_plan(family, sig, **sargs)
-            coeffs = [(float(torch.tensor(call.sigma, dtype=torch.float64).to(latents.dtype)), call) for call in plan]
-        else:
-            coeffs = sampling.linear_step_coefficients(family, sig, **sargs) if rows_path else sampling.dpmpp_2m_coefficients(sig)
+        # one entry per model call; on the lockstep path (DPM++ 2M's own kernel) only its sigma, (a, b, c) and model scalars are read
+        plan = step_plan(kdm, family, sig, latents.dtype, eta=sargs.get("eta"), s_noise=sargs.get("s_noise"),
+                         solver_type=sargs.get("solver_type"), needs_linear=rows_path)
         ack = getattr(self, "_added_cond_kwargs", None)
         ip_key = None if ack is None else (tuple(tuple(e.shape) for e in ack["image_embeds"]),
                                            id(getattr(self.unet, "encoder_hid_proj", None)))
@@ -1581,18 +1554,16 @@ class StableDiffusionPipeline:
         st = self._static_step(key, n_img, in_shape, text, region_state, weight_func, cross_attention_kwargs)
         x = latents.contiguous().clone()
         old = torch.zeros_like(x)
-        call_sig = [s_ for s_, _ in coeffs] if staged else sig[:len(coeffs)]      # the sigma of every model call
         if prof:
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-        c_in, _, t = kdm.step_scalars(sig[0])
+        c_in, t = plan[0].c_in, plan[0].t
         tab = None
         if st["tadd"] is not None:
             # the schedule's timesteps are known here: every step's embedding rows in one table (kept while the schedule repeats)
-            tkey = (tuple(call_sig), self.unet.temb_signature())              # the schedule AND the weights the table bakes in
+            tkey = (tuple(call.sigma for call in plan), self.unet.temb_signature())   # the schedule AND the weights the table bakes in
             if st["temb_key"] != tkey:
-                ts = [float(kdm.step_scalars(s_)[2]) for s_ in call_sig]
-                st["temb_tab"] = self.unet.temb_add_table(torch.tensor(ts, dtype=torch.float32, device=x.device))
+                st["temb_tab"] = self.unet.temb_add_table(torch.tensor([call.t for call in plan], dtype=torch.float32, device=x.device))
                 st["temb_key"] = tkey
             tab = st["temb_tab"]
         if extras is not None:
@@ -1601,38 +1572,29 @@ class StableDiffusionPipeline:
             ops.cfg_linear_step_rows_cat(x, None, old, 0, st["x_in"], st["t"], st["sigma_rows"], [join] * n_img, extras, tadd=st["tadd"])
         else:
             ops.prepare_unet_input(x, c_in, t, sig[0], st["x_in"], st["t"], st["sigma"], row=None if tab is None else (tab[0], st["tadd"]))
-        if staged:
+        if rows_path:
             noise = None
-            if any(call.coeffs[4] != 0.0 for _, call in coeffs):
-                noise = step_noise if step_noise is not None else \
-                    sampling.call_noise_table(family, x, sigmas, eta=sargs.get("eta", 1.0), noise_sampler=noise_sampler)
-                noise = self._check_step_noise(noise, len(coeffs), x)
-            self._staged_fused_loop(st, x, old, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout,
-                                    rescale=guidance_rescale)
-            coeffs = []
-        elif rows_path:
-            noise = None
-            if any(c4[3] != 0.0 for c4 in coeffs):
-                noise = step_noise if step_noise is not None else \
-                    sampling.step_noise_table(family, x, sigmas, eta=sargs.get("eta", 1.0), noise_sampler=noise_sampler)
-                noise = self._check_step_noise(noise, len(coeffs), x)
-            self._linear_fused_loop(st, x, old, sig, coeffs, noise, tab, guidance_scale, n_img, start_time, timeout,
-                                    rescale=guidance_rescale, extras=extras)
-            coeffs = []
-        for i, (a, b, c) in enumerate(coeffs):
+            if plan.noisy:
+                noise = step_noise
+                if noise is None:
+                    table = sampling.call_noise_table if plan.two_call else sampling.step_noise_table
+                    noise = table(family, x, sigmas, eta=sargs.get("eta", 1.0), noise_sampler=noise_sampler)
+                noise = self._check_step_noise(noise, len(plan), x)
+            self._rows_fused_loop(st, x, old, plan, noise, tab, guidance_scale, n_img, start_time, timeout,
+                                  rescale=guidance_rescale, extras=extras)
+        for i, call in enumerate(() if rows_path else plan):        # DPM++ 2M's own lockstep kernel (sampling.dpmpp_2m_coefficients)
             self._check_timeout(start_time, timeout)
             st["run"]()
-            nxt = sig[i + 1]
-            c_in_n, _, t_n = kdm.step_scalars(nxt) if nxt > 0 else (1.0, 0.0, 0.0)
+            c_in_n, t_n, nxt = (plan[i + 1].c_in, plan[i + 1].t, plan[i + 1].sigma) if i + 1 < len(plan) else (1.0, 0.0, 0.0)
             # x <- a*x + b*D + c*D_old with D = x - sigma*(eps_u + g*(eps_c - eps_u)); also writes next x_in/t/sigma
-            ops.cfg_dpmpp2m_step(x, st["eps"], old, sig[i], guidance_scale, a, b, c, c_in_n, t_n, max(nxt, 1e-10),
+            ops.cfg_dpmpp2m_step(x, st["eps"], old, call.sigma, guidance_scale, call.a, call.b, call.c, c_in_n, t_n, max(nxt, 1e-10),
                                  st["x_in"], st["t"], st["sigma"],
-                                 row=(tab[i + 1], st["tadd"]) if tab is not None and i + 1 < len(coeffs) else None)
+                                 row=(tab[i + 1], st["tadd"]) if tab is not None and i + 1 < len(plan) else None)
         if x.is_cuda:
             self._record_done(st, x.device)
         if prof:
             torch.cuda.synchronize()
             t2 = time.perf_counter()
             print(f"[dsc host profile] setup (tables, text K/V, graph) {1e3 * (t1 - t0):.1f} ms, "
-                  f"{len(coeffs)}-step loop {1e3 * (t2 - t1):.1f} ms", flush=True)
+                  f"{len(plan)}-call loop {1e3 * (t2 - t1):.1f} ms", flush=True)
         return x

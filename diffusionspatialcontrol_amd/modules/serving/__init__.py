@@ -19,8 +19,10 @@ the copy of its final latent row, and futures resolve when those events are seen
 The seam is host scheduling against a replaceable device executor:
   batcher.py      ServingBatcher (construction, the public interface, the phases of a step) and HiresPair; samplers, guidance
                   rescale, hires pairs, the region-table budget
-  requests.py     the request record and the submit-time validation of every request key; image-conditioned requests, region
-                  masks of image prompts
+  requests.py     the request record (one class, `_Request`, on every batcher: a feature's fields stay None where it is off) and
+                  the submit-time validation of every request key; image-conditioned requests, region masks of image prompts
+  ../step_plan.py a request's `plan`, one entry per model call, and the STEP record of an entry - shared with the pipeline's
+                  fused loop, so a served request's records are those of its own fused txt2img
   executor.py     _GraphExecutor, the capture sequence, step_launch (which launch serves a transition); image prompts,
                   T2I-Adapter, ControlNet
   decode_lane.py  the decode lane that finishes images beside the step

@@ -12,10 +12,10 @@ known-region launch of inpainting carries DPM++ 2M records only, so an inpaintin
 share a batch: the later one waits in the queue until the others have left.
 
 Two-call samplers.  On a batcher built with `two_call=True` a request may also name a sampler of sampling.TWO_CALL_FAMILY (Heun,
-DPM2, DPM2 a, DPM++ 2S a, DPM++ SDE): two model calls per sampler step.  Its per-step lists (sig, coeffs, snoise, scal, skipout)
-then hold one entry per MODEL CALL of sampling.call_plan, `r.i` stays the index of the model call that runs now, and every
-transition applies one call: PREDICT writes the step's intermediate point into the slot's row of `exec.mid` and leaves x alone,
-CORRECT reads it back (dsc_cfg_staged_step_rows).  A transition in which some slot carries such a stage launches that entry for
+DPM2, DPM2 a, DPM++ 2S a, DPM++ SDE): two model calls per sampler step.  A request's `plan` (step_plan.py, the fused loop's too)
+holds one entry per MODEL CALL whatever its sampler - here sampling.call_plan's - `r.i` is the index of the model call that runs
+now, and every transition applies one call: PREDICT writes the step's intermediate point into the slot's row of `exec.mid` and
+leaves x alone, CORRECT reads it back (dsc_cfg_staged_step_rows).  A transition in which some slot carries such a stage launches that entry for
 all slots - the one-call members ride in it as FULL records with the bits they have otherwise - and any other transition the
 launch it had.  Not with ControlNet / T2I-Adapter requests (their windows count one model call per step), inpainting or
 `inpaint_unet`.
@@ -48,10 +48,11 @@ import torch
 from ... import ops
 from .. import sampling
 from ..encode_region_map_function import encode_region_map
+from ..step_plan import step_plan, step_record
 from . import requests, text_lane
 from .encode_lane import _EncodeHandle, encode_roles
 from .executor import _GraphExecutor, step_launch
-from .requests import MAX_TEXT_KEYS, _FreeuRequest, _InpaintFreeuRequest, _InpaintRequest, _Request, _ip_layers
+from .requests import MAX_TEXT_KEYS, _Request, _ip_layers
 
 
 def _conv_out_hw(conv, h, w):
@@ -456,7 +457,7 @@ class ServingBatcher:
         [negative, positive] id arrays [1, S]}: what `submit` takes in place of the strings, for clients that cache embeddings"""
         if not self.text_on:
             raise ValueError("serve: encode_text needs a batcher built with `text=True` (pipe.serve(..., text=True))")
-        holder = requests.text_record(_Request)(req={"prompt": prompt, "negative_prompt": negative_prompt})
+        holder = _Request(req={"prompt": prompt, "negative_prompt": negative_prompt})
         holder.txt = requests.prompt_request(self, holder.req)
         if holder.txt is None:
             raise ValueError("serve: encode_text takes `prompt` as a string")
@@ -490,7 +491,7 @@ class ServingBatcher:
         ip_embeds, ip_scale = requests.ip_request(self, request)
         # masks without an image prompt (or with every scale 0) have nothing to weigh: accepted and ignored
         ip_weights = requests.ip_mask_weights(self, ip_masks) if ip_embeds is not None and ip_masks is not None else None
-        txt, shared = None, getattr(text_from, "txt", None)
+        txt, shared = None, None if text_from is None else text_from.txt
         if shared is None and self.text_on:
             txt = requests.prompt_request(self, request)
         # (a prompt request's rows are allocated by the device half; a shared second pass receives its first pass's)
@@ -499,19 +500,9 @@ class ServingBatcher:
         steps = int(request.get("num_inference_steps", 25))
         if steps < 1:
             raise ValueError("serve: num_inference_steps must be >= 1")
-        record = _InpaintRequest if self.inpaint else _Request           # (the former: one more field, `extra`)
-        more = {}
-        if self.freeu:                                                   # (one more field, `freeu`)
-            record, more = (_InpaintFreeuRequest if self.inpaint else _FreeuRequest), {"freeu": freeu}
-        if self.two_call:                                                # (four more: `stage`, `m`, `call_step`, `ends_step`)
-            record = requests._TWO_CALL_RECORD[record]
-        if self.encode:                                                  # (one more field, `enc`)
-            record = requests._ENCODE_RECORD[record]
-        if self.text_on:                                                 # (one more field, `txt`)
-            record, more = requests.text_record(record), dict(more, txt=txt)
-        r = record(req=request, future=concurrent.futures.Future(), steps=steps, second=second, ip_embeds=ip_embeds,
-                   ip_scale=ip_scale, ip_weights=ip_weights, adapter=adapter, control=control, guidance=g, output_type=out_type,
-                   family=family, rescale=phi, eta=float(request.get("eta", 1.0)), text=text, **more)
+        r = _Request(req=request, future=concurrent.futures.Future(), steps=steps, second=second, ip_embeds=ip_embeds,
+                     ip_scale=ip_scale, ip_weights=ip_weights, adapter=adapter, control=control, guidance=g, output_type=out_type,
+                     family=family, rescale=phi, eta=float(request.get("eta", 1.0)), text=text, freeu=freeu, txt=txt)
         t_start = requests.image_request(self, r)
         if self.encode:                              # its rows on the encode lane; None: the request does not touch it
             roles = encode_roles(self, r)
@@ -540,38 +531,17 @@ class ServingBatcher:
             r.cgates = self.control_gates(n_keep, len(r.sig) - 1, r.control["scale"], r.control["start"], r.control["end"])
             if all(g == 0.0 for call in r.cgates for g in call):
                 r.control, r.cgates = None, None                     # no model call carries it: no lane, no embedding
-        args = {}
-        if family in ("euler_ancestral", "dpmpp_2m_sde") or family in sampling.TWO_CALL_FAMILY:
-            args.update(eta=r.eta, s_noise=float(request.get("s_noise", 1.0)))
-        if family == "dpmpp_2m_sde":
-            args["solver_type"] = request.get("solver_type") or "midpoint"
-            if args["solver_type"] not in ("midpoint", "heun"):
-                raise ValueError(f"serve: `solver_type` must be 'midpoint' or 'heun', got {args['solver_type']!r}")
-        if family in sampling.TWO_CALL_FAMILY:
-            # one entry per MODEL CALL from here on (r.i: the index of the model call that runs now).  The sigma a call's model
-            # runs at is rounded to the model dtype, as the fused loop and protocol mode's `sigma * s_in` do
-            plan = sampling.call_plan(family, r.sig, **args)
-            r.sig = [float(torch.tensor(call.sigma, dtype=torch.float64).to(dt)) for call in plan] + [0.0]
-            abcs = [(a, b, c, s) for a, _, b, c, s in (call.coeffs for call in plan)]
-            r.stage, r.m = [call.stage for call in plan], [call.coeffs[1] for call in plan]
-            r.call_step, r.ends_step = [call.step for call in plan], [call.ends_step for call in plan]
-        else:
-            abcs = sampling.linear_step_coefficients(family, r.sig, **args)
-        r.coeffs = [c4[:3] for c4 in abcs]
-        r.snoise = [c4[3] for c4 in abcs]
-        kdm = pipe.k_diffusion_model
-        r.scal = []
-        # None: DPM++ 2M's own launch serves the request (c_skip = 1, c_out = -sigma); with a rescale it needs the linear family's
-        # launch, so its (1, -sigma) are spelled out like any other member's
-        r.skipout = [] if family != "dpmpp_2m" or v_pred or phi > 0.0 else None
-        for s_ in r.sig[:len(r.coeffs)]:
-            c_in, c_out, t = kdm.step_scalars(s_)
-            r.scal.append((c_in, float(t)))
-            if r.skipout is not None:
-                r.skipout.append((kdm.step_skip(s_), c_out))
+        # one entry per MODEL CALL from here on (r.i: the index of the model call that runs now).  needs_linear: with a rescale (or
+        # a v-prediction model) DPM++ 2M needs the linear family's launch, its (1, -sigma) spelled out like any other member's
+        try:
+            r.plan = step_plan(pipe.k_diffusion_model, family, r.sig, dt, eta=r.eta, s_noise=float(request.get("s_noise", 1.0)),
+                               solver_type=request.get("solver_type"), needs_linear=v_pred or phi > 0.0)
+        except ValueError as e:
+            raise ValueError(f"serve: {e}") from None
+        r.sig = [call.sigma for call in r.plan] + [0.0]
         table = request.get("step_noise")
         if table is not None:
-            want = (len(r.coeffs), 1, 4, self.height // 8, self.width // 8)
+            want = (len(r.plan), 1, 4, self.height // 8, self.width // 8)
             if not torch.is_tensor(table) or tuple(table.shape) != want:
                 raise ValueError(f"serve: `step_noise` must be a {list(want)} tensor (one unit-noise row per step), got "
                                  f"{list(table.shape) if torch.is_tensor(table) else type(table).__name__}")
@@ -654,7 +624,7 @@ class ServingBatcher:
             self.exec.prepare_encode(r)              # host pixels and draws only: the lane encodes it beside the step
         else:
             self.exec.prepare_image(r)
-        if any(v != 0.0 for v in r.snoise):
+        if r.plan.noisy:
             self.exec.prepare_noise(r, r.eta)
 
     def _prepare_hires_pair(self, request):
@@ -669,7 +639,7 @@ class ServingBatcher:
             r2.future, r2.t_submit = r.future, r.t_submit
             r.hires = r2
             self._prepare_device(r)
-            if getattr(r, "txt", None) is not None:
+            if r.txt is not None:
                 r2.text = r.text                     # one encode serves both passes
             hi._prepare_device(r2)
         except BaseException:                        # (a refused request leaves no preview state behind)
@@ -720,8 +690,8 @@ class ServingBatcher:
         eps-prediction records only: it has no c_skip / c_out / noise fields.  So an inpainting request and a request of another
         sampler never share a batch - whichever comes second waits at the head of the queue (FIFO) until the others have left."""
         if head.kind == "inpaint":
-            return all(r.skipout is None for r in members)
-        if head.skipout is not None:
+            return not any(r.plan.linear for r in members)
+        if head.plan.linear:
             return all(r.kind != "inpaint" for r in members)
         return True
 
@@ -730,7 +700,7 @@ class ServingBatcher:
         records, ensure the next bucket and load the joins, ONE transition launch, (previews) the launch for the slots that are
         due, let the finished leave, advance, refresh / upload / run the next bucket, flush decodes"""
         slots = self._slots
-        stepping = [r for r in slots if r is not None and r.i < len(r.coeffs) and self._n is not None]
+        stepping = [r for r in slots if r is not None and r.i < len(r.plan) and self._n is not None]
         if self.encode:
             self._dispatch_encodes()
         if self.text_on:
@@ -750,7 +720,7 @@ class ServingBatcher:
         if not stepping and not joins:
             return False
         # who leaves after this transition: a request whose last step is the one being applied now
-        leaving = [r for r in stepping if r.i + 1 == len(r.coeffs)]
+        leaving = [r for r in stepping if r.i + 1 == len(r.plan)]
         staying = [r for r in slots if r is not None and r not in leaving]
         n_src = self._n or 0
         n_dst = self._bucket_for(max(r.slot for r in staying)) if staying else None
@@ -832,23 +802,17 @@ class ServingBatcher:
         for i in range(n_slots):
             r = slots[i] if i < len(slots) else None
             if r is not None and r in stepping:
-                a, b, c = r.coeffs[r.i]
-                rec = {"mode": ops.ROW_STEP, "sigma": r.sig[r.i], "guidance": r.guidance, "a": a, "b": b, "c": c}
-                if r.skipout is not None:
-                    rec.update(c_skip=r.skipout[r.i][0], c_out=r.skipout[r.i][1], s=r.snoise[r.i],
-                               noise=self.exec.noise_row(r, r.i) if r.snoise[r.i] != 0.0 else None)
-                    if r.rescale > 0.0:
-                        rec["rescale"] = r.rescale
-                    if requests.staged(r):
-                        rec.update(stage=r.stage[r.i], m=r.m[r.i])
+                call = r.plan[r.i]
+                noise = self.exec.noise_row(r, r.i) if r.plan.linear and call.s != 0.0 else None
                 if r in leaving:
-                    rec.update(c_in_next=0.0, t_next=0.0, sigma_next=1.0, temb_row=None, req=r, step=r.i, next_step=None)
+                    j, after = None, (0.0, 0.0, 1.0, None)
                 else:
                     j = r.i + 1
-                    rec.update(c_in_next=r.scal[j][0], t_next=r.scal[j][1], sigma_next=max(r.sig[j], 1e-10),
-                               temb_row=self.exec.temb_row(r, j), req=r, step=r.i, next_step=j)
+                    after = (r.plan[j].c_in, r.plan[j].t, max(r.plan[j].sigma, 1e-10), self.exec.temb_row(r, j))
+                rec = step_record(r.plan, call, r.guidance, r.rescale, noise, *after)
+                rec.update(req=r, step=r.i, next_step=j)
             elif r is not None and r in joins:
-                rec = {"mode": ops.ROW_JOIN, "c_in_next": r.scal[0][0], "t_next": r.scal[0][1], "sigma_next": r.sig[0],
+                rec = {"mode": ops.ROW_JOIN, "c_in_next": r.plan[0].c_in, "t_next": r.plan[0].t, "sigma_next": r.sig[0],
                        "temb_row": self.exec.temb_row(r, 0), "req": r, "step": None, "next_step": 0}
             else:
                 rec = {"mode": ops.ROW_IDLE, "t_next": 0.0, "sigma_next": 1.0, "temb_row": None, "req": None}
@@ -898,9 +862,7 @@ class ServingBatcher:
         asked = self._preview_of
 
         def done(r):                                 # sampler steps applied once this transition has run, or None inside a step
-            if not requests.staged(r):
-                return r.i + 1
-            return r.call_step[r.i] + 1 if r.ends_step[r.i] else None
+            return r.plan[r.i].step + 1 if r.plan[r.i].ends_step else None
 
         due = [r for r in stepping if r in asked and done(r) and done(r) % asked[r].every == 0 and r not in leaving]
         if not due:
@@ -912,8 +874,7 @@ class ServingBatcher:
             return
         for r in due:
             asked[r].out += 1
-        self._preview_queue.append((h, [(asked[r], done(r), r.call_step[-1] + 1 if requests.staged(r) else len(r.coeffs))
-                                        for r in due]))
+        self._preview_queue.append((h, [(asked[r], done(r), r.plan[-1].step + 1) for r in due]))
         self._stats["previews"] += 1
         self._stats["preview_rows"] += len(due)
 
@@ -942,13 +903,10 @@ class ServingBatcher:
                 self._done.append((r, self.exec.finish(r)))
             r.hnoise = None                          # (a second-pass record: its start noise was read before it joined)
             r.known = None                           # its image / noise / mask rows go back to the allocator (stream-ordered)
-            if self.inpaint:
-                r.extra = None                       # ... and its mask + masked-image latents row (inpaint_unet)
+            r.extra = None                           # ... and its mask + masked-image latents row (inpaint_unet)
             r.noise = None                           # ... and its noise table
-            if self.encode:
-                r.enc = None                         # ... and its draws and host pixels (encode)
-            if self.text_on:
-                r.txt = None                         # ... and its pinned ids and multipliers (text)
+            r.enc = None                             # ... and its draws and host pixels (encode)
+            r.txt = None                             # ... and its pinned ids and multipliers (text)
             r.adapter_feats = None                   # ... and its adapter features
             if r.lane is not None:                   # ... and its ControlNet lane goes to whoever waits for one
                 self._lanes[r.lane] = None

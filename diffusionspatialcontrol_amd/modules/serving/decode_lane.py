@@ -24,7 +24,7 @@ _DECODE_RING = 4                     # pinned host slots of the decode lane: dec
 
 
 def decode_buckets(decode_batch):
-    """the batch sizes the decode lane captures: 1, decode_batch and the powers of two between"""
+    """the batch sizes a lane captures: 1, its batch size and the powers of two between"""
     out, m = {1, int(decode_batch)}, 2
     while m < decode_batch:
         out.add(m)

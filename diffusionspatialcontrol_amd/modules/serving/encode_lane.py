@@ -31,17 +31,9 @@ import collections
 import torch
 
 from ... import ops
+from .decode_lane import decode_buckets as encode_buckets    # (the encode and text lanes capture the same batch sizes)
 
 _ENCODE_RING = 4                     # pinned host slots of the encode lane: encodes whose uploads may still be in flight
-
-
-def encode_buckets(encode_batch):
-    """the batch sizes the encode lane captures: 1, encode_batch and the powers of two between"""
-    out, m = {1, int(encode_batch)}, 2
-    while m < encode_batch:
-        out.add(m)
-        m *= 2
-    return tuple(sorted(out))
 
 
 def encode_roles(batcher, r):

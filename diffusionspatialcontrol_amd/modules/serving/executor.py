@@ -200,7 +200,7 @@ class _GraphExecutor:
 
     def _tables_and_text(self, r):
         dev, dt = self.device, self.dtype
-        ts = [t for _, t in r.scal]
+        ts = [call.t for call in r.plan]
         r.temb = self.pipe.unet.temb_add_table(torch.tensor(ts, dtype=torch.float32, device=dev))
         if r.text is None:                               # a prompt request: the text lane writes its rows beside the step
             self.text_lane.prepare(r)
@@ -458,11 +458,11 @@ class _GraphExecutor:
                 ns = None
                 if r.family == "dpmpp_2m_sde":
                     if req.get("seed") is not None:              # protocol mode's `brownian_noise` sampler, seeded per request
-                        ns = self.pipe.create_noise_sampler(like, r.sig_dev, len(r.coeffs), int(req["seed"]))
+                        ns = self.pipe.create_noise_sampler(like, r.sig_dev, len(r.plan), int(req["seed"]))
                 elif req.get("generator") is not None:
                     gen = req["generator"]
                     ns = lambda *_: torch.randn(like.shape, generator=gen, device=gen.device, dtype=dt).to(dev)   # noqa: E731
-                if getattr(r, "stage", None) is not None:            # a two-call sampler: one row per model call
+                if r.plan.two_call:                                  # a two-call sampler: one row per model call
                     if r.family == "dpmpp_sde":
                         ns = None if req.get("seed") is None else \
                             self.pipe.create_noise_sampler(like, r.sig_dev, r.steps, int(req["seed"]))
@@ -519,9 +519,9 @@ class _GraphExecutor:
         with torch.cuda.stream(self.stream):
             if r.ready is not None:                  # a hires second pass: its start latent is written on another stream
                 self.stream.wait_event(r.ready)
-            if self.enc_lane is not None and r.enc is not None:      # a pixel input: its rows are written on the lane's stream
+            if r.enc is not None:                    # a pixel input: its rows are written on the lane's stream
                 self.stream.wait_event(r.enc.ev)
-            if self.text_lane is not None and r.txt is not None:     # a prompt: its text rows are written on the lane's stream
+            if r.txt is not None:                    # a prompt: its text rows are written on the lane's stream
                 self.stream.wait_event(r.txt.ev)
             self.x[r.slot].copy_(r.lat[0])
 

@@ -1,5 +1,5 @@
-"""A request's record and the submit-time validation of its keys (caller's thread, host only): functions of
-(batcher, request, ...) that ServingBatcher._prepare calls in order, on top of one copy of each small check.
+"""A request's record (`_Request`, the one class of every batcher) and the submit-time validation of its keys (caller's thread,
+host only): functions of (batcher, request, ...) that ServingBatcher._prepare calls in order, on top of one copy of each small check.
 
 Image-conditioned requests.  A request with `image` is img2img (the last `strength` fraction of its schedule, started from
 `image_latents + noise * sqrt(sigma_0^2 + 1)`, the pipeline method's line); with `mask_image` too it is inpainting on the 4-channel
@@ -43,99 +43,27 @@ _FLAG_HINT = {"image_t2i_adapter": "; a batcher built with `t2i_adapter=True` (p
 
 
 class _Request:
-    """one request from submit until its future resolves: every field starts at its default here (None unless listed), and
-    _prepare assigns only what it computes"""
-    __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "coeffs", "scal", "guidance", "tables",
+    """one request from submit until its future resolves, the same record on every batcher: every field starts at its default here
+    (None unless listed), and _prepare assigns only what it computes.  `plan`: its step_plan.StepPlan, one entry per MODEL CALL
+    (`i`: the index of the call that runs now); `sig`: the plan's sigmas and the final 0.0.  Fields of a feature stay None on a
+    batcher built without it: `extra` (`inpaint_unet=True`: the fp16 [5, h, w] row cat([nearest-downsampled mask, masked-image
+    latents]) on the device from admission until it leaves), `freeu` (its (s1, s2, b1, b2)), `enc` / `txt` (its handle on the
+    encode / text lane, encode_lane._EncodeHandle / text_lane._TextHandle, from submit until it leaves; None: it does not touch
+    the lane - it brings latents / embeddings)"""
+    __slots__ = ("rid", "req", "future", "steps", "sig", "sig_dev", "plan", "guidance", "tables",
                  "slot", "i", "lat", "temb", "text", "output_type", "t_submit", "t_done", "kind", "strength", "known",
-                 "family", "snoise", "skipout", "noise", "rescale", "eta", "hires", "second", "ready", "hnoise", "t_handoff",
+                 "family", "noise", "rescale", "eta", "hires", "second", "ready", "hnoise", "t_handoff",
                  "ip_embeds", "ip_scale", "ip_rows", "ip_weights", "adapter", "adapter_limit", "adapter_feats",
-                 "control", "cgates", "lane", "cemb")
+                 "control", "cgates", "lane", "cemb", "extra", "freeu", "enc", "txt")
     _DEFAULTS = {"steps": 0, "i": 0, "output_type": "latent", "kind": "txt2img", "strength": 1.0, "rescale": 0.0, "eta": 1.0,
                  "second": False, "adapter_limit": 0}
 
     def __init__(self, **given):
-        fields = [name for cls in type(self).__mro__ for name in getattr(cls, "__slots__", ())]
-        unknown = set(given) - set(fields)
+        unknown = set(given) - set(self.__slots__)
         if unknown:
             raise TypeError(f"_Request has no field {sorted(unknown)}")
-        for name in fields:
+        for name in self.__slots__:
             setattr(self, name, given.get(name, self._DEFAULTS.get(name)))
-
-
-class _InpaintRequest(_Request):
-    """a request of a batcher built with `inpaint_unet=True`: the record plus `extra`, its fp16 [5, h, w] row
-    cat([nearest-downsampled mask, masked-image latents]) on the device from admission until it leaves"""
-    __slots__ = ("extra",)
-
-
-class _FreeuRequest(_Request):
-    """a request of a batcher built with `freeu=True`: the record plus `freeu`, its (s1, s2, b1, b2) or None"""
-    __slots__ = ("freeu",)
-
-
-class _InpaintFreeuRequest(_InpaintRequest):
-    """... of a batcher built with `inpaint_unet=True` and `freeu=True`"""
-    __slots__ = ("freeu",)
-
-
-# a request of a batcher built with `encode=True`: the record of its kind plus `enc`, its handle on the encode lane
-# (encode_lane._EncodeHandle) from submit until it leaves, or None when it does not touch the lane
-class _EncodeRequest(_Request):
-    __slots__ = ("enc",)
-
-
-class _InpaintEncodeRequest(_InpaintRequest):
-    __slots__ = ("enc",)
-
-
-class _FreeuEncodeRequest(_FreeuRequest):
-    __slots__ = ("enc",)
-
-
-class _InpaintFreeuEncodeRequest(_InpaintFreeuRequest):
-    __slots__ = ("enc",)
-
-
-# a request of a batcher built with `two_call=True` (never together with `inpaint_unet`): the record of its kind plus four lists.
-# When it names a sampler of sampling.TWO_CALL_FAMILY, sig / coeffs / snoise / scal / skipout hold one entry per MODEL CALL of
-# sampling.call_plan, and beside them stand each call's `stage`, `m` (the weight of the intermediate point), `call_step` (its
-# sampler step) and `ends_step`; all four None for a request of the linear family
-class _TwoCallRequest(_Request):
-    __slots__ = ("stage", "m", "call_step", "ends_step")
-
-
-class _FreeuTwoCallRequest(_FreeuRequest):
-    __slots__ = ("stage", "m", "call_step", "ends_step")
-
-
-class _TwoCallEncodeRequest(_TwoCallRequest):
-    __slots__ = ("enc",)
-
-
-class _FreeuTwoCallEncodeRequest(_FreeuTwoCallRequest):
-    __slots__ = ("enc",)
-
-
-_TWO_CALL_RECORD = {_Request: _TwoCallRequest, _FreeuRequest: _FreeuTwoCallRequest}
-_ENCODE_RECORD = {_Request: _EncodeRequest, _InpaintRequest: _InpaintEncodeRequest, _FreeuRequest: _FreeuEncodeRequest,
-                  _InpaintFreeuRequest: _InpaintFreeuEncodeRequest, _TwoCallRequest: _TwoCallEncodeRequest,
-                  _FreeuTwoCallRequest: _FreeuTwoCallEncodeRequest}
-
-
-_TEXT_RECORD = {}
-
-
-def text_record(record):
-    """a request of a batcher built with `text=True`: the record of its kind plus `txt`, its handle on the text lane
-    (text_lane._TextHandle) from submit until it leaves, or None when it brings its embeddings"""
-    if record not in _TEXT_RECORD:
-        _TEXT_RECORD[record] = type(record.__name__.replace("Request", "TextRequest"), (record,), {"__slots__": ("txt",)})
-    return _TEXT_RECORD[record]
-
-
-def staged(r):
-    """the request runs a two-call sampler: its lists are per model call (only on a batcher built with `two_call=True`)"""
-    return getattr(r, "stage", None) is not None
 
 
 # ---------------------------------------------------------------------- one copy of each small check

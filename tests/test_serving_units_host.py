@@ -127,7 +127,7 @@ def test_control_images(image, multi, cins, size, ok):
 def test_a_fresh_request_has_every_field_readable():
     r = requests._Request()
     fields = list(r.__slots__)
-    assert len(fields) == 43 == len(set(fields)) and not hasattr(r, "__dict__")
+    assert len(fields) == 44 == len(set(fields)) and not hasattr(r, "__dict__")
     for name in fields:
         getattr(r, name)
     assert (r.i, r.kind, r.strength, r.second, r.adapter_limit, r.rescale, r.output_type) == (0, "txt2img", 1.0, False, 0, 0.0, "latent")

@@ -329,7 +329,7 @@ def test_hires_pair_shares_one_encode(pipe, monkeypatch):
     pair = HiresPair(base, hi)
     fut = pair.submit(_req("H", prompt="a (cat:1.3)", upscale=True, upscale_x=1.5))
     first = base._queue[0]
-    assert first.hires.text is first.text and first.text == ("text", "H") and not hasattr(first.hires, "txt")
+    assert first.hires.text is first.text and first.text == ("text", "H") and first.hires.txt is None
     pair.run_until_idle()
     assert fut.done() and base.exec.encodes == [[("H", 0)]] and not hi.exec.encodes
     assert base.stats()["text_encodes"] == 1 and "text_encodes" not in hi.stats()

@@ -204,8 +204,8 @@ def test_heun_takes_two_transitions_per_step_beside_dpmpp_2m(pipe):
     b.step()                                                          # both join
     assert ex.calls[0][0] == "rows" and b.stats()["staged_transitions"] == 0
     h = b._slots[0]
-    assert h.stage == [sampling.STAGE_PREDICT, sampling.STAGE_CORRECT] * 2 + [sampling.STAGE_FULL] and len(h.coeffs) == 5
-    assert h.call_step == [0, 0, 1, 1, 2] and h.ends_step == [False, True, False, True, True] and len(h.sig) == 6
+    assert [c.stage for c in h.plan] == [sampling.STAGE_PREDICT, sampling.STAGE_CORRECT] * 2 + [sampling.STAGE_FULL] and len(h.plan) == 5
+    assert [c.step for c in h.plan] == [0, 0, 1, 1, 2] and [c.ends_step for c in h.plan] == [False, True, False, True, True] and len(h.sig) == 6
     for _ in range(5):
         assert b.step()
     assert fh.done() and not fm.done() and b._slots[0] is None
