@@ -221,7 +221,9 @@ __device__ __forceinline__ float group_std_reduce(const XattnParams& p, const do
     // sequences and this runs in every wave of every workgroup), the cancellation-prone subtraction still in fp64; the square
     // root in fp32 (the oracle's std is an fp32 tensor: one more rounding at 6e-8)
     double var = (t2 - t1 * t1 * p.inv_n) * p.inv_nm1;
-    var = var > 0.0 ? var : 0.0;
+    // clamp rounding's negative variances, not a NaN: `var > 0 ? var : 0` alone turns the std of a diverged group (NaN or inf
+    // scores) into 0, and its region bias silently vanishes (tests/test_isolation_gpu.py: region_xattn_std)
+    var = (var > 0.0 || var != var) ? var : 0.0;
     float sd = sqrtf((float)var);
     if (ref16) sd = round_f16(sd);                           // std of an fp16 tensor is a 0-dim fp16 tensor
     return sd;
