@@ -48,6 +48,12 @@ class PromptWeightGroup(ctypes.Structure):
     _fields_ = [("z_row", ctypes.c_int * 2), ("mult", _vp), ("out", _vp * 2)]
 
 
+class LoraJob(ctypes.Structure):
+    """dsc_lora_job (include/dsc_hip.h)"""
+    _fields_ = [("base", _vp), ("dst", _vp), ("up", _vp), ("down", _vp), ("gain", _vp), ("N", ctypes.c_int), ("K", ctypes.c_int),
+                ("R", ctypes.c_int), ("tile0", ctypes.c_int), ("ld_dst", ctypes.c_longlong)]
+
+
 _SIGNATURES = {
     "dsc_abi_version": (ctypes.c_int, []),
     "dsc_target_arch": (ctypes.c_char_p, []),
@@ -156,6 +162,8 @@ _SIGNATURES = {
     "dsc_prompt_weight_rows_f16": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [ctypes.POINTER(PromptWeightGroup), ctypes.c_int,
                                                   ctypes.c_longlong, _vp]),
     "dsc_debug_set_prompt_weight_slices": (None, [ctypes.c_int]),
+    "dsc_lora_merge_plan": (ctypes.c_longlong, [ctypes.POINTER(LoraJob), ctypes.c_int]),
+    "dsc_lora_merge_f16": (ctypes.c_int, [ctypes.POINTER(LoraJob), _vp, ctypes.c_int, ctypes.c_int, _vp]),
 }
 
 

@@ -20,7 +20,8 @@ the module's dtype, with a -inf upper-triangular mask.
 branches, a static ids buffer in, clones out.
 
 Not here: padding masks (`attention_mask` must be None - no caller passes one), the projection head of
-CLIPTextModelWithProjection, a tokenizer, textual inversion, LoRA on the encoder."""
+CLIPTextModelWithProjection, a tokenizer, textual inversion.  LoRA on the encoder is modules/lora.py's: merged weights, which the
+fused QKV copies follow through the version counter."""
 import os
 
 import torch

@@ -32,6 +32,7 @@ import inspect
 import os
 import threading
 import time
+import weakref
 from typing import List, Optional, Union
 
 import torch
@@ -107,6 +108,9 @@ class StableDiffusionPipeline:
         self._do_classifier_free_guidance = True
         self._graphs = {}
         self._added_cond_kwargs = None
+        self.weights_epoch = 0                               # counts the LoRA changes; a serving batcher serves the epoch it was built at
+        self._batchers = weakref.WeakSet()                   # the ServingBatchers built on this pipeline (modules/serving/batcher.py)
+        self._lora = None                                    # modules.lora.LoraManager, from the first load_lora_weights on
         self.setup_unet(self.unet)
 
     # ------------------------------------------------------------------ reference surface
@@ -401,6 +405,34 @@ class StableDiffusionPipeline:
         self.unet.config["encoder_hid_dim_type"] = None
         self.unet.set_attn_processor(AttnProcessor())
         self._graphs = {}
+
+    # ---- LoRA surface (reference app.py:532-597 `load_lora_control_pipeline`; modules/lora.py)
+    def load_lora_weights(self, state_dict_or_safetensors_path, scale=1.0, name=None, use_alpha=False):
+        """Merge a kohya-format LoRA (a state dict or a .safetensors path) into the UNet and the text encoder at `scale`, the
+        reference's `lora_scale`; `use_alpha=False` skips the file's `.alpha` keys as the reference does, True multiplies by
+        alpha / rank.  Several adapters may be loaded (`name`: default the file's stem / "lora<n>").  Captured steps are dropped
+        and `weights_epoch` advances; a ServingBatcher built before the call refuses to go on.  -> the adapter's name"""
+        from .lora import LoraManager
+        if self._lora is None:
+            self._lora = LoraManager(self)
+        return self._lora.load(state_dict_or_safetensors_path, scale=scale, name=name, use_alpha=use_alpha)
+
+    def set_lora_scale(self, scale):
+        """a float for every loaded adapter, or {name: scale}: all touched weights are recomputed from their pristine copies"""
+        if self._lora is None:
+            raise ValueError("set_lora_scale: no LoRA is loaded")
+        self._lora.set_scale(scale)
+
+    def unload_lora_weights(self, name=None):
+        """drop one adapter, or all: weights no adapter touches any more get their original bits back; after the last adapter
+        the pristine copies and the packed operands are freed"""
+        if self._lora is not None:
+            self._lora.unload(name)
+
+    def lora_state(self):
+        """{"adapters": {name: {scale, use_alpha, layers, rank}}, "targets", "kernel_targets", "base_bytes", "weights_epoch"}"""
+        from .lora import LoraManager
+        return (self._lora or LoraManager(self)).state()
 
     def encode_image(self, image, device, num_images_per_prompt, output_hidden_states=None):
         """reference :148-170: CLIP image embeddings (or penultimate hidden states) of the IP-Adapter image and their

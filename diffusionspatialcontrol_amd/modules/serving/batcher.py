@@ -152,6 +152,10 @@ class ServingBatcher:
         self._warm_captures = None
         self._thread = None
         self._stop = False
+        # the weights this batcher's captured steps hold (derived copies included): a LoRA change on the pipeline retires it
+        self._weights_epoch = getattr(pipe, "weights_epoch", 0)
+        if hasattr(pipe, "_batchers"):
+            pipe._batchers.add(self)                    # load / set / unload refuse while one of these runs its own thread
         # the IP-Adapters this batcher's step is built for (load_ip_adapter): the processors, the image projection, tokens per adapter
         self._ip = _ip_layers(pipe)
         self._ip_proj = getattr(pipe.unet, "encoder_hid_proj", None) if self._ip else None
@@ -306,8 +310,16 @@ class ServingBatcher:
         return want
 
     # ------------------------------------------------------------------ public interface
+    def _check_weights(self):
+        now = getattr(self.pipe, "weights_epoch", 0)
+        if now != self._weights_epoch:
+            raise RuntimeError(f"serve: the pipeline's weights changed since this batcher was built (LoRA load / set_lora_scale / "
+                               f"unload: weights_epoch {self._weights_epoch} -> {now}); its captured steps hold the old weights - "
+                               f"build a new batcher")
+
     def warm(self):
         """capture every bucket's step now (otherwise each is captured on first use)"""
+        self._check_weights()
         with self._lock:
             if self.t2i:
                 self.exec.warm_adapter()             # the adapter's convolutions pay their first-call cost here, not at a join
@@ -395,6 +407,7 @@ class ServingBatcher:
         chunks on the host, and the request joins the batch once its encode has completed; `region_map_state` needs nothing else
         (the lane makes the ids); `long_encode` other than 0 and a `clip_skip` other than the batcher's are refused.
         Returns a Future of the final output."""
+        self._check_weights()
         r = self._prepare(request)
         with self._lock:
             r.rid = self._next_id
@@ -405,6 +418,7 @@ class ServingBatcher:
 
     def step(self):
         """advance every active request by one sigma (admitting queued requests into free slots first); False when idle"""
+        self._check_weights()
         with self._lock:
             self.exec.bind_thread()
             self._poll()

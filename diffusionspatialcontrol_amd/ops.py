@@ -1546,3 +1546,9 @@ from .image_prepare import image_prepare, image_prepare_torch, latent_start, lat
 # mean restoration of every (request, chunk) group in one launch): wrapper beside its kernel's name, reached as
 # ops.prompt_weight_rows; prompt_weight_numpy restates the contract with exact sums, prompt_weight_torch is the eager chain
 from .prompt_weight import MAX_GROUPS as PROMPT_WEIGHT_MAX_GROUPS, prompt_weight_numpy, prompt_weight_rows, prompt_weight_torch  # noqa: E402,F401
+
+# LoRA adapters merged into every touched weight in one launch (dsc_lora_merge_f16: base + sum of gain-scaled low-rank products,
+# rounded once): wrapper beside its kernel's name, reached as ops.lora_merge_ / ops.lora_merge_takes; lora_merge_eager is the
+# reference's arithmetic in torch (CPU, fp32 / fp64, shapes outside the limits, DSC_LORA=0)
+from .lora_merge import (MAX_RANK as LORA_MAX_RANK, SEGMENT as LORA_SEGMENT, LoraMergeTable, lora_merge_, lora_merge_eager,  # noqa: E402,F401
+                         lora_merge_takes, pack_adapters as lora_pack_adapters, padded_rank as lora_padded_rank)

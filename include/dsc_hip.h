@@ -1042,6 +1042,44 @@ int dsc_prompt_weight_rows_f16(const void* z, int m, int T, int C, const dsc_pro
                                void* stream);
 void dsc_debug_set_prompt_weight_slices(int slices);
 
+/*
+ * dsc_lora_merge_f16: LoRA adapters merged into a table of weights in one launch (modules/lora.py; the reference merges in
+ * load_lora_control_pipeline, app.py:532-597, with four to five eager launches per layer).  Per job, one nn.Linear or 1x1-conv
+ * weight [N, K] (a [N, K, 1, 1] weight has the same bytes):
+ *     dst[n,k] = fp16( fp32(base[n,k]) + sum_seg gain[seg] * ( sum_{r in seg} up[n,r] * down[r,k] ) )
+ * base: fp16 [N, K] dense, the pristine copy, never written.  dst: fp16 [N, K] with row stride ld_dst (elements), the live
+ * parameter.  up: fp16 [N, R] dense, down: fp16 [R, K] dense: all adapters of the job concatenated along the rank, each padded
+ * with zero columns / rows to a multiple of DSC_LORA_SEGMENT.  A segment is DSC_LORA_SEGMENT consecutive rank columns of one
+ * adapter; gain: DEVICE fp32 [R / DSC_LORA_SEGMENT], read by the kernel (a rescale uploads gains and launches again).
+ * Arithmetic: a segment's sum is one v_mfma_f32_16x16x32_f16 from a zero accumulator; the gain multiplies that fp32 sum (a
+ * rounding of its own); segments are added in ascending order in fp32; base is added last; one rounding to fp16, to nearest
+ * even.  A segment whose gain is 0 is skipped - its up / down values are not read, NaN and inf included - so all gains 0 gives
+ * dst == base bit for bit.  The order is fixed per 64 x 64 tile: the bits do not depend on the grid or on the other jobs.
+ * dsc_lora_merge_plan(jobs, n) checks a HOST table and writes each job's tile0 (the prefix sum of tile counts a workgroup
+ * bisects to find its job) -> the launch's tile count (> 0), or a negative status.  dsc_lora_merge_f16 takes that host table
+ * (checked again, nothing else is read from it) and a DEVICE copy of the same bytes, which is what the kernel reads.
+ * Limits - stated here once, mirrored by ops.lora_merge_takes: fp16; K % 8 == 0 and ld_dst % 8 == 0 (16-byte rows); any N >= 1
+ * (the last row tile is masked); R % DSC_LORA_SEGMENT == 0, R <= DSC_LORA_MAX_RANK; base / dst / up / down 16-byte aligned, gain
+ * 4-byte, the device table 8-byte; fewer than 2^31 tiles: otherwise DSC_ERR_UNSUPPORTED.
+ * DSC_ERR_BAD_ARG: NULL tables, n < 1, a NULL pointer in a job, N / K / R < 1, ld_dst < K, dst overlapping the job's base, up,
+ * down or gain, a tile0 that is not the plan's.  All checks run on the host before the launch.  No workspace, no atomics, no
+ * allocation, no synchronisation.
+ */
+#define DSC_LORA_SEGMENT  32
+#define DSC_LORA_MAX_RANK 256
+typedef struct {
+    const void* base;
+    void* dst;
+    const void* up;
+    const void* down;
+    const float* gain;
+    int N, K, R;
+    int tile0;
+    long long ld_dst;
+} dsc_lora_job;
+long long dsc_lora_merge_plan(dsc_lora_job* jobs, int n_jobs);
+int dsc_lora_merge_f16(const dsc_lora_job* jobs, const void* jobs_dev, int n_jobs, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
